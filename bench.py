@@ -6,9 +6,11 @@ basisu_frontend::init + compress() (SURVEY.md 8a rows a6-a15: per-block ETC1S fi
 TSVQ + codebook + assignment) -- nothing is skipped or cached between steps. With --gpus N every rank encodes its own image
 (independent objects, like the reference's basis_parallel_compress): weak scaling, no data-path collective.
 
-Prints ONE JSON line (rank 0). Extra objects: "roofline" for the dominant kernel (HIP events on the launch stream, live),
+Prints ONE JSON line (rank 0). A plain run does only what the headline needs: set-up, warm-up, the timed steps (uninstrumented) and the line.
+With --full the line also carries: "roofline" for the dominant kernel (HIP events on the launch stream, live, inside the timed steps),
 "cpu_baseline" (the real reference frontend from oracle/_ref when present, else the C oracle, on a bounded sample),
-"stages" (host wall seconds per frontend stage) and "kernels" (device ms per kernel).
+"stages" (host wall seconds per frontend stage), "kernels" (device ms per kernel), the check against the reference's digests and the
+secondary workloads. --dump-outputs DIR writes what the last timed step computed (dump_outputs) as .npy files.
 """
 import argparse
 import json
@@ -86,6 +88,9 @@ def main():
                     "rank: what the driver runs) or gloo (ranks may share a GPU: the path tests/test_gpu_bench_distributed.py drives on a one-GPU box)")
     ap.add_argument("--no-big", action="store_true", help="skip the secondary 8192x8192 -q255 measurement (BASELINE config #4's single-GPU form)")
     ap.add_argument("--no-fast", action="store_true", help="skip the secondary measurement of the codebook builders' fast mode (SURVEY 8f row f3, not bit-identical)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: per-kernel profile, roofline, reference check, PSNR, backend, CPU baseline, "
+                    "throughput modes and the secondary workloads (the --no-* options above apply to it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the arrays the last timed step produced to DIR/<name>.npy (float32, at most 64 MB)")
     args = ap.parse_args()
 
     import torch
@@ -203,8 +208,10 @@ def main():
     # The timed steps carry HIP events around the kernels that are ONE launch each (profile level 2: the per-block / per-cluster kernels, among them the dominant
     # one whose roofline is reported): the step then runs as it does uninstrumented. Timing every region -- an event pair around each round of the codebook builders,
     # which also keeps a round's two kinds of nodes from sharing the device -- costs the step 0.5-0.7 ms (tools/headline_ab.py), so the full per-region breakdown
-    # (kernels_ms_per_step, dominant_stage, host_gap_ms) comes from a second, separately timed pass of the same steps below.
-    ctx.profile_enable(2)
+    # (kernels_ms_per_step, dominant_stage, host_gap_ms) comes from a second, separately timed pass of the same steps below. A plain run (no --full) times the
+    # steps without any event.
+    if args.full:
+        ctx.profile_enable(2)
     stage_acc = {}
     last = None
     cpu0 = time.process_time()
@@ -215,8 +222,9 @@ def main():
             if last is not None:
                 last.close()
             last = step()
-            for name, s in last.stage_times():
-                stage_acc[name] = stage_acc.get(name, 0.0) + s
+            if args.full:
+                for name, s in last.stage_times():
+                    stage_acc[name] = stage_acc.get(name, 0.0) + s
         barrier()
         elapsed = time.perf_counter() - t0
     else:
@@ -228,21 +236,22 @@ def main():
         for fe in finished[:-1]:
             fe.close()
     host_cpu_s = (time.process_time() - cpu0) / args.steps  # all host threads of this rank (spin-waits on the stream included)
-    kernels_headline = ctx.profile_read()
-    # second pass: every region timed (instrumented: slower than the headline steps by what the events cost)
-    instrumented_steps = max(1, min(args.steps, 10))
-    ctx.profile_enable(1)
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(instrumented_steps):
-        step().close()
-    barrier()
-    instrumented_elapsed = time.perf_counter() - t0
-    kernels = ctx.profile_read()
-    ctx.profile_enable(False)
+    if args.full:
+        kernels_headline = ctx.profile_read()
+        # second pass: every region timed (instrumented: slower than the headline steps by what the events cost)
+        instrumented_steps = max(1, min(args.steps, 10))
+        ctx.profile_enable(1)
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(instrumented_steps):
+            step().close()
+        barrier()
+        instrumented_elapsed = time.perf_counter() - t0
+        kernels = ctx.profile_read()
+        ctx.profile_enable(False)
 
     pipelined = None
-    if args.streams <= 1 and not sharded and not args.no_pipelined:
+    if args.full and args.streams <= 1 and not sharded and not args.no_pipelined:
         pipelined = pipelined_bench(local_rank, d_blocks, n_blocks, w, h, max_ep, max_sel, args, barrier)
         if world > 1:
             t = torch.tensor([pipelined.pop("_seconds")], device=red_dev, dtype=torch.float64)
@@ -265,7 +274,7 @@ def main():
         pipelined["thread_per_image"] = {"images_in_flight_per_gpu": 6, "value": round(12 * (w * h) / 1e6 / dt, 3), "unit": "Mpixels/s (this rank)",
                                          "host_cpu_s_per_image": round(cpu / 12, 5)}
     whole_encoder = None
-    if args.streams <= 1 and not sharded and not args.no_pipelined and world == 1:
+    if args.full and args.streams <= 1 and not sharded and not args.no_pipelined and world == 1:
         nf = max(1, args.backend_in_flight)
         fes, dt = run_in_flight(nf, 2 * nf, with_backend=True)
         for fe in fes:
@@ -313,7 +322,7 @@ def main():
     #      here with the same steps / barrier / max-over-ranks rule, the sharded one with its per-stage split, so that DESIGN.md section 7's estimates are checked by the
     #      first run on a multi-GPU node.
     both_modes = None
-    if world > 1 and args.streams <= 1:
+    if args.full and world > 1 and args.streams <= 1:
         def mode_leg(shard):
             if shard:
                 c, seen, kind = (comm, comm_check.get("sharding_communicator_ranks_seen"), comm_check.get("sharding_communicator")) if comm is not None else make_comm()
@@ -368,6 +377,25 @@ def main():
     if rank == 0:
         mpix = (1 if sharded else world) * args.steps * (w * h) / 1e6
         value = mpix / elapsed
+        final_ep = int(last.get("endpoint_clusters", np.uint32)[0])
+        final_sel = int(last.get("selector_cluster_block_indices", np.uint32)[0])
+        out = {
+            "metric": "encoder Mpixels/s (ETC1S frontend hot path)", "value": round(value, 3), "unit": "Mpixels/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 2), "higher_is_better": True,
+            "scaling": "strong" if sharded else "weak", "vs_baseline": None, "dtype": "u8/int32", "data": "synthetic",
+            "config": {"workload": f"{w}x{h} synthetic RGBA (SURVEY 8d recipe, seed 1234), ETC1S -q{args.quality} comp_level {args.level}, "
+                                   f"basisu_frontend init+compress with tiles resident in HBM",
+                       "blocks": n_blocks, "max_endpoint_clusters": max_ep, "max_selector_clusters": max_sel,
+                       "final_endpoint_clusters": final_ep, "final_selector_clusters": final_sel,
+                       "images_in_flight_per_gpu": args.streams, "host_threads_per_rank": int(os.environ.get("BU_HOST_THREADS", "8")), "host_cpus": host_cpus(),
+                       "parallelism": (f"one image sharded over {world} GPUs: block-row slabs + cluster shares, RCCL all_gather / all_reduce between stages, TSVQ replicated"
+                                       if sharded else f"{world} x one image per GPU (no collective)")},
+            "comm": comm_check,
+            "both_modes": both_modes,
+        }
+        if args.dump_outputs:   # before the backend below, which changes the frontend's state above level 1
+            dump_outputs(last, n_blocks, args.dump_outputs)
+    if rank == 0 and args.full:
         # ---- roofline of the dominant KERNEL: the profile labels that are one kernel launch each (the tsvq_* / unique_* / map_* labels cover many launches
         #      of several kernels -- a codebook build is reported as a stage below, not as a kernel)
         single = {k: v for k, v in kernels_headline.items() if k in KERNEL_SYMBOL}   # measured inside the timed steps
@@ -393,21 +421,7 @@ def main():
             k, (ms, launches) = max(stages_multi.items(), key=lambda kv: kv[1][0])
             dom_stage = {"label": k, "ms_per_step": round(ms / instrumented_steps, 3), "timed_regions_per_step": round(launches / instrumented_steps, 1),
                          "note": "a profile label over many kernel launches (not a kernel): device time between the HIP events around the region (instrumented pass)"}
-        final_ep = int(last.get("endpoint_clusters", np.uint32)[0])
-        final_sel = int(last.get("selector_cluster_block_indices", np.uint32)[0])
-        out = {
-            "metric": "encoder Mpixels/s (ETC1S frontend hot path)", "value": round(value, 3), "unit": "Mpixels/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 2), "higher_is_better": True,
-            "scaling": "strong" if sharded else "weak", "vs_baseline": None, "dtype": "u8/int32", "data": "synthetic",
-            "config": {"workload": f"{w}x{h} synthetic RGBA (SURVEY 8d recipe, seed 1234), ETC1S -q{args.quality} comp_level {args.level}, "
-                                   f"basisu_frontend init+compress with tiles resident in HBM",
-                       "blocks": n_blocks, "max_endpoint_clusters": max_ep, "max_selector_clusters": max_sel,
-                       "final_endpoint_clusters": final_ep, "final_selector_clusters": final_sel,
-                       "images_in_flight_per_gpu": args.streams, "host_threads_per_rank": int(os.environ.get("BU_HOST_THREADS", "8")), "host_cpus": host_cpus(),
-                       "parallelism": (f"one image sharded over {world} GPUs: block-row slabs + cluster shares, RCCL all_gather / all_reduce between stages, TSVQ replicated"
-                                       if sharded else f"{world} x one image per GPU (no collective)")},
-            "comm": comm_check,
-            "both_modes": both_modes,
+        out.update({
             "roofline": roofline,
             "step_roofline": step_roofline,
             "dominant_stage": dom_stage,
@@ -420,7 +434,7 @@ def main():
             "instrumented_pass": {"steps": instrumented_steps, "ms_per_step": round(instrumented_elapsed / instrumented_steps * 1e3, 2),
                                   "what": "the same steps with HIP events around EVERY region (kernels_ms_per_step, dominant_stage and host_gap_ms come from here); the timed "
                                           "steps above carry events around the single-launch kernels only"},
-        }
+        })
         # the state the LAST timed step left (every per-block and per-cluster result the reference's getters serve) against the digests of the reference's
         # own run on this image (tests/golden/: tools/gen_golden_big.py / gen_golden_etc1s.py ran oracle/_ref; nothing under oracle/ is touched here)
         out["identical_to_reference"] = headline_identical(last, w, h, args)
@@ -581,6 +595,31 @@ def headline_identical(last, w, h, args):
     import test_gpu_etc1s_frontend as T      # the canonical byte form of each state array (tests/: checker code, outside the timed region)
     got = T._digest({k: last.get(k) for k in want})
     return got == want
+
+
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: all files together
+
+
+def dump_outputs(fe, n_blocks, out_dir):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the arrays the ETC1S backend is built from
+    (backend.Etc1sBackend.from_arrays) -- as float32 .npy files, exact (bytes, and cluster indices below 2^24). The selector codebook keeps its
+    selector bytes only: the colour bytes of its entries carry nothing. Where the per-block arrays would exceed DUMP_BYTES, they hold a fixed
+    sample of the blocks (seed 0), whose indices are written beside them as block_sample.npy (float64)."""
+    per_block = {"encoded_blocks": fe.get("encoded_blocks").reshape(n_blocks, 8),
+                 "block_endpoint_index": fe.get("block_endpoint_clusters_indices", np.uint32),
+                 "block_selector_index": fe.get("block_selector_cluster_index", np.uint32)}
+    codebooks = {"endpoint_color5_inten": fe.get("endpoint_cluster_etc_params").reshape(-1, 16)[:, :4],
+                 "selector_bits": fe.get("optimized_cluster_selectors").reshape(-1, 8)[:, 4:]}
+    room = DUMP_BYTES - 4096 - 4 * sum(a.size for a in codebooks.values())   # 4 KiB for the .npy headers
+    row = 4 * sum(a.size for a in per_block.values()) // n_blocks
+    if n_blocks * row > room:
+        pick = np.sort(np.random.default_rng(0).choice(n_blocks, room // (row + 8), replace=False))
+        per_block = {k: v[pick] for k, v in per_block.items()}
+        per_block["block_sample"] = pick.astype(np.float64)
+    out_dir = pathlib.Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in {**per_block, **codebooks}.items():
+        np.save(out_dir / f"{name}.npy", a if a.dtype == np.float64 else a.astype(np.float32))
 
 
 def etc1s_8192_bench(ctx, helpers, args):

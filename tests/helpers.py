@@ -338,11 +338,7 @@ def uastc_test_blocks():
     """~1.2k source blocks covering every class encode_uastc distinguishes (uastc_enc.cpp:3135-3152) plus degenerate cases."""
     rng = np.random.default_rng(77)
     parts = [to_pixel_blocks(synth(64, 64, 1234)), to_pixel_blocks(uniform_random(32, 32, 42))]
-    kod = REF_DIR / "test_files" / "kodim03.png"
-    if kod.exists():
-        parts.append(to_pixel_blocks(load_png(kod)[200:264, 300:364]))
-    else:
-        parts.append(to_pixel_blocks(synth(64, 64, 99)))
+    parts.append(to_pixel_blocks(np.load(ROOT / "tests" / "golden" / "kodim03.npz")["rgba"][200:264, 300:364]))   # the reference's test_files/kodim03.png
     g = synth(48, 48, 5).copy(); g[..., 1] = g[..., 0]; g[..., 2] = g[..., 0]
     parts.append(to_pixel_blocks(g))
     yy, xx = np.mgrid[0:48, 0:48]

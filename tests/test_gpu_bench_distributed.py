@@ -10,11 +10,12 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = pathlib.Path(__file__).resolve().parent.parent
-COMMON = ["--steps", "2", "--warmup", "1", "--size", "512", "--no-cpu-baseline", "--no-pipelined", "--no-uastc", "--no-fast", "--no-big"]
+COMMON = ["--steps", "2", "--warmup", "1", "--size", "512", "--full", "--no-cpu-baseline", "--no-pipelined", "--no-uastc", "--no-fast", "--no-big"]
 
 
 def _free_port():
@@ -25,13 +26,13 @@ def _free_port():
     return p
 
 
-def _run(n, extra):
+def _run(n, extra, common=COMMON):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     if n == 1:
-        cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", *COMMON, *extra]
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", *common, *extra]
     else:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-               str(ROOT / "bench.py"), "--gpus", str(n), "--dist-backend", "gloo", *COMMON, *extra]
+               str(ROOT / "bench.py"), "--gpus", str(n), "--dist-backend", "gloo", *common, *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -69,6 +70,33 @@ def _contract(d, n):
 
 def test_single_gpu_line_has_no_multi_gpu_objects(single):
     assert single["comm"] is None and single["both_modes"] is None
+
+
+def test_plain_line_and_dumped_outputs(tmp_path, hip_ctx):
+    """Without --full the line holds the headline and nothing measured beside it; --dump-outputs holds what the last timed step computed: the arrays
+    a frontend run of the same image in this process returns."""
+    d = _run(1, ["--dump-outputs", str(tmp_path)], common=["--steps", "3", "--warmup", "1", "--size", "512"])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "Mpixels/s" and d["higher_is_better"] is True and d["dtype"] == "u8/int32"
+    assert d["value"] > 0 and abs(512 * 512 / 1e6 / d["value"] * 1e3 - d["ms_per_step"]) <= 0.006
+    assert not {"roofline", "kernels_ms_per_step", "identical_to_reference", "psnr", "backend", "cpu_baseline", "pipelined", "uastc"} & d.keys()
+    files = sorted(tmp_path.glob("*.npy"))
+    got = {f.stem: np.load(f) for f in files}
+    assert set(got) == {"encoded_blocks", "block_endpoint_index", "block_selector_index", "endpoint_color5_inten", "selector_bits"}
+    assert all(a.dtype == np.float32 for a in got.values()) and sum(f.stat().st_size for f in files) <= 64 * 10 ** 6
+    import helpers
+    from basis_universal_amd.etc1s import Etc1sFrontend, quality_to_clusters
+    blocks = helpers.to_pixel_blocks(helpers.synth(512, 512, 1234))
+    fe = Etc1sFrontend(hip_ctx)
+    fe.init(blocks, *quality_to_clusters(128, blocks.shape[0]), 1, True)
+    fe.compress()
+    want = {"encoded_blocks": fe.get("encoded_blocks").reshape(-1, 8), "block_endpoint_index": fe.get("block_endpoint_clusters_indices", np.uint32),
+            "block_selector_index": fe.get("block_selector_cluster_index", np.uint32),
+            "endpoint_color5_inten": fe.get("endpoint_cluster_etc_params").reshape(-1, 16)[:, :4],
+            "selector_bits": fe.get("optimized_cluster_selectors").reshape(-1, 8)[:, 4:]}
+    fe.close()
+    for k, v in want.items():
+        assert got[k].shape == v.shape and (got[k] == v).all(), k
+    assert got["block_endpoint_index"].max() < d["config"]["final_endpoint_clusters"] == got["endpoint_color5_inten"].shape[0]
 
 
 def test_native_rccl_communicator_two_processes():

@@ -6,17 +6,14 @@ import numpy as np
 import pytest
 
 from helpers import (oracle, ref, have_ref, RefFrontend, ptr, u32p, u64p, f32p, synth, uniform_random, to_pixel_blocks,
-                     load_png, REF_DIR, csr_from_lists)
+                     csr_from_lists, ROOT)
 
 pytestmark = pytest.mark.skipif(not have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 
 
 def _inputs():
-    out = {"synth": to_pixel_blocks(synth(256, 192, 1234)), "noise": to_pixel_blocks(uniform_random(96, 64, 42))}
-    k = REF_DIR / "test_files" / "kodim03.png"
-    if k.exists():
-        out["kodim03"] = to_pixel_blocks(load_png(k))
-    return out
+    return {"synth": to_pixel_blocks(synth(256, 192, 1234)), "noise": to_pixel_blocks(uniform_random(96, 64, 42)),
+            "kodim03": to_pixel_blocks(np.load(ROOT / "tests" / "golden" / "kodim03.npz")["rgba"])}   # the reference's test_files/kodim03.png
 
 
 INPUTS = _inputs()

@@ -1,14 +1,15 @@
 # round 6: everything profiles/ needs at one commit -- parity suite, smoke, the bench line, rocprofv3 kernel stats + one step's time line, PMC passes, TSVQ round log,
 # and the concurrency of the pipelined leg.   usage (on the GPU box): bash tools/scratch/r06_final.sh [tag]
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out; R=$GRAFT_REPO_ROOT; tag=${1:-r06}
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"   # where the bench line goes
 if [[ " $* " != *" notests "* ]]; then
   timeout 1500 python -m pytest tests -m gpu -x -q --durations=6 2>&1 | tail -12 > gpurun_out/${tag}_tests.txt; tail -2 gpurun_out/${tag}_tests.txt
   timeout 120 python __graft_entry__.py smoke 2>&1 | tail -1
 fi
-timeout 600 python bench.py --steps 20 --warmup 3 > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err; tail -c 300 gpurun_out/bench_$tag.err
+timeout 600 python bench.py --full --steps 20 --warmup 3 > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err"; tail -c 300 "$OUT/bench_$tag.err"
 python - <<PY
 import json
-d=json.load(open("gpurun_out/bench_$tag.json"))
+d=json.load(open("$OUT/bench_$tag.json"))
 print({k:d.get(k) for k in ("value","ms_per_step","identical_to_reference","host_gap_ms","host_cpu_s_per_step")}, d["roofline"]["frac"], d["roofline"]["avg_launch_ms"])
 p=d.get("pipelined") or {}; print({k:p.get(k) for k in ("value","host_cpu_s_per_image","driver_thread_cpu_s_per_image","identical_to_reference","thread_per_image")})
 print("with backend", (d.get("pipelined_with_backend") or {}).get("value"))
