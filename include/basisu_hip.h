@@ -195,7 +195,8 @@ BU_HIP_API int bu_hip_k_cluster_colour_means(bu_hip_context*, const void* d_pixe
  *     etc1_optimizer with the selectors of d_encoded_blocks held fixed (m_pForce_selectors). Lists are CSR over training-vector indices
  *     like a9 and MAY contain duplicates (the reference's m_subblocks lists grow from iteration to iteration). Outputs per cluster:
  *     the refitted {r5,g5,b5,inten}, its error, a validity flag, and the CURRENT error of the listed sub-blocks under their blocks'
- *     present colours -- the caller applies the refit only where new error < current error (:2822). */
+ *     present colours -- the caller applies the refit only where new error < current error (:2822). An EMPTY list is allowed (a cluster
+ *     no block uses any more): no texel is read for it and its four output entries are unspecified -- callers skip them. */
 BU_HIP_API int bu_hip_k_refit_endpoints_given_selectors(bu_hip_context*, const void* d_pixel_blocks, const void* d_encoded_blocks, uint32_t n_clusters,
     const uint32_t* h_offsets, const uint32_t* d_offsets, const uint32_t* d_indices, int perceptual,
     uint8_t* d_params, uint64_t* d_err, uint8_t* d_valid, uint64_t* d_current_err);

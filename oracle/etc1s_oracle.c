@@ -98,6 +98,8 @@ typedef struct {
     uint8_t *best_sel, *trial_sel, *tmp_sel;
     /* fast path */
     uint16_t* luma;
+    /* m_pForce_selectors (etc.cpp:780-784): one selector per pixel, NULL = nearest colour */
+    const uint8_t* force;
 } opt_t;
 
 /* check_for_redundant_solution (etc.cpp:1072-1089): 1024-bit Bloom filter, k=2. Returns 1 if definitely new. */
@@ -127,8 +129,14 @@ static int evaluate(opt_t* o, int r5, int g5, int b5) {
             uint64_t total = 0;
             for (uint32_t i = 0; i < o->n; i++) {
                 const uint8_t* p = o->px + 4 * i;
-                uint32_t be = orc_color_distance(o->perceptual, p, bc[0]); uint32_t bs = 0;
-                for (uint32_t s = 1; s < 4; s++) { uint32_t e = orc_color_distance(o->perceptual, p, bc[s]); if (e < be) { be = e; bs = s; } }
+                uint32_t be, bs = 0;
+                if (o->force) { /* etc.cpp:1137-1160: the given selector, whatever its distance */
+                    bs = o->force[i];
+                    be = orc_color_distance(o->perceptual, p, bc[bs]);
+                } else {
+                    be = orc_color_distance(o->perceptual, p, bc[0]);
+                    for (uint32_t s = 1; s < 4; s++) { uint32_t e = orc_color_distance(o->perceptual, p, bc[s]); if (e < be) { be = e; bs = s; } }
+                }
                 o->tmp_sel[i] = (uint8_t)bs;
                 total += be;
             }
@@ -177,10 +185,10 @@ static int evaluate(opt_t* o, int r5, int g5, int b5) {
     return 0;
 }
 
-int orc_etc1_optimize(const uint8_t* rgba, uint32_t n, int quality, int perceptual,
-                      uint8_t out_color5[3], uint32_t* out_inten, uint64_t* out_err, uint8_t* out_selectors) {
+static int optimize(const uint8_t* rgba, uint32_t n, int quality, int perceptual, const uint8_t* force,
+                    uint8_t out_color5[3], uint32_t* out_inten, uint64_t* out_err, uint8_t* out_selectors) {
     opt_t o; memset(&o, 0, sizeof(o));
-    o.px = rgba; o.n = n; o.quality = quality; o.perceptual = perceptual;
+    o.px = rgba; o.n = n; o.quality = quality; o.perceptual = perceptual; o.force = force;
     uint8_t* selbuf = (uint8_t*)malloc((size_t)n * 3 + 3);
     o.best_sel = selbuf; o.trial_sel = selbuf + n + 1; o.tmp_sel = selbuf + 2 * (size_t)n + 2;
     o.luma = (quality == ORC_QUALITY_FAST) ? (uint16_t*)malloc(sizeof(uint16_t) * (n ? n : 1)) : NULL;
@@ -230,6 +238,17 @@ int orc_etc1_optimize(const uint8_t* rgba, uint32_t n, int quality, int perceptu
     }
     free(selbuf); free(o.luma);
     return ok;
+}
+
+int orc_etc1_optimize(const uint8_t* rgba, uint32_t n, int quality, int perceptual,
+                      uint8_t out_color5[3], uint32_t* out_inten, uint64_t* out_err, uint8_t* out_selectors) {
+    return optimize(rgba, n, quality, perceptual, NULL, out_color5, out_inten, out_err, out_selectors);
+}
+
+int orc_etc1_optimize_forced(const uint8_t* rgba, uint32_t n, int quality, int perceptual, const uint8_t* force_selectors,
+                             uint8_t out_color5[3], uint32_t* out_inten, uint64_t* out_err) {
+    if (quality < ORC_QUALITY_SLOW || !force_selectors) return 0; /* etc.cpp:780-784 */
+    return optimize(rgba, n, quality, perceptual, force_selectors, out_color5, out_inten, out_err, NULL);
 }
 
 static int level_to_block_quality(int level) { return level == 0 ? ORC_QUALITY_FAST : level == 1 ? ORC_QUALITY_MEDIUM : level == 6 ? ORC_QUALITY_UBER : ORC_QUALITY_SLOW; }
@@ -403,4 +422,96 @@ void orc_selector_training_vectors(const uint8_t* encoded_blocks, uint32_t n_blo
         uint32_t w = orc_color_distance(perceptual, bc[0], bc[3]) / 300u;
         out_weight[i] = w < 1 ? 1 : (w > 4096 ? 4096 : w);
     }
+}
+
+/* ---- refine_block_endpoints_given_selectors (frontend.cpp:2718-2976), the part before the caller's "only if better" test */
+void orc_refit_endpoints_given_selectors(const uint8_t* pixel_blocks, const uint8_t* encoded_blocks, uint32_t n_clusters, const uint32_t* offsets,
+                                         const uint32_t* indices, int quality, int perceptual, uint8_t* params, uint64_t* err, uint8_t* valid, uint64_t* cur_err) {
+    for (uint32_t ci = 0; ci < n_clusters; ci++) {
+        const uint32_t cnt = offsets[ci + 1] - offsets[ci];
+        if (!cnt) continue; /* nothing to fit: the four entries are left alone */
+        uint8_t* px = (uint8_t*)malloc(32ull * cnt);
+        uint8_t* force = (uint8_t*)malloc(8ull * cnt);
+        gather_cluster_pixels(pixel_blocks, indices + offsets[ci], cnt, px);
+        uint64_t cur = 0;
+        for (uint32_t k = 0; k < cnt; k++) {
+            const uint32_t tv = indices[offsets[ci] + k], block = tv >> 1, sub = tv & 1;
+            int r5, g5, b5, inten; uint8_t sel[16], bc[4][3];
+            unpack_etc1s(encoded_blocks + 8ull * block, &r5, &g5, &b5, &inten, sel);
+            block_colors5(bc, r5, g5, b5, inten);
+            for (uint32_t i = 0; i < 8; i++) {
+                /* flipped layout: texel i of sub-block `sub` is raster texel 8 * sub + i of the block (rows 2 * sub, 2 * sub + 1) */
+                const uint32_t p = 8 * sub + i;
+                force[8ull * k + i] = sel[p];
+                cur += orc_color_distance(perceptual, pixel_blocks + 64ull * block + 4 * p, bc[sel[p]]);
+            }
+        }
+        uint8_t c[3]; uint32_t inten = 0; uint64_t e = 0;
+        const int ok = orc_etc1_optimize_forced(px, cnt * 8, quality, perceptual, force, c, &inten, &e);
+        valid[ci] = (uint8_t)(ok ? 1 : 0);
+        if (ok) { params[4 * ci] = c[0]; params[4 * ci + 1] = c[1]; params[4 * ci + 2] = c[2]; params[4 * ci + 3] = (uint8_t)inten; err[ci] = e; }
+        cur_err[ci] = cur;
+        free(px); free(force);
+    }
+}
+
+/* ---- compute_endpoint_subblock_error_vec (frontend.cpp:1006-1091). The reference hands the 5-bit colour to get_block_colors5 with
+   scaled = true, so the four colours are built from the UNSCALED 0..31 values plus the intensity modifiers; reproduced as is. */
+void orc_subblock_errors(const uint8_t* pixel_blocks, uint32_t n_blocks, const uint32_t* block_cluster, const uint8_t* cluster_params,
+                         int perceptual, uint64_t* out_err) {
+    for (uint32_t tv = 0; tv < 2 * n_blocks; tv++) {
+        const uint8_t* cp = cluster_params + 4ull * block_cluster[tv >> 1];
+        uint8_t bc[4][3];
+        for (int s = 0; s < 4; s++) {
+            const int yd = k_inten[cp[3]][s];
+            for (int c = 0; c < 3; c++) bc[s][c] = (uint8_t)clampi((int)cp[c] + yd, 0, 255);
+        }
+        uint64_t tot = 0;
+        for (uint32_t i = 0; i < 8; i++) {
+            const uint8_t* px = pixel_blocks + 32ull * tv + 4 * i;
+            uint32_t be = orc_color_distance(perceptual, px, bc[0]);
+            for (int s = 1; s < 4; s++) { uint32_t d = orc_color_distance(perceptual, px, bc[s]); if (d < be) be = d; }
+            tot += be;
+        }
+        out_err[tv] = tot;
+    }
+}
+
+/* ---- the stateless part of basisu_backend::create_encoder_blocks (backend.cpp:406-617) as include/basisu_hip.h states it for
+   bu_hip_k_backend_block_errors. Outputs are indexed by ABSOLUTE block; entries outside the slice are not touched. */
+static uint32_t block_error_under(const uint8_t* px64, const uint8_t sel[16], int r5, int g5, int b5, int inten, int perceptual) {
+    uint8_t bc[4][3];
+    block_colors5(bc, r5, g5, b5, inten);
+    uint64_t e = 0;
+    for (int p = 0; p < 16; p++) e += orc_color_distance(perceptual, px64 + 4 * p, bc[sel[p]]);
+    return (uint32_t)e; /* 16 texels: fits 32 bits for both metrics */
+}
+
+void orc_backend_block_errors(const uint8_t* pixel_blocks, const uint8_t* etc_blocks, const uint32_t* block_cluster, const uint8_t* cluster_params,
+                              uint32_t first_block, uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t n_clusters, int perceptual, int with_neighbours,
+                              uint32_t* own_err, uint32_t* neighbour_err) {
+    static const int pred_dx[3] = {-1, 0, -1}, pred_dy[3] = {0, -1, -1}; /* g_endpoint_preds (backend.cpp:120-128) */
+    for (uint32_t by = 0; by < num_blocks_y; by++)
+        for (uint32_t bx = 0; bx < num_blocks_x; bx++) {
+            const uint32_t b = first_block + by * num_blocks_x + bx;
+            int r5, g5, b5, inten; uint8_t sel[16];
+            unpack_etc1s(etc_blocks + 8ull * b, &r5, &g5, &b5, &inten, sel);
+            const uint32_t mine_err = block_error_under(pixel_blocks + 64ull * b, sel, r5, g5, b5, inten, perceptual);
+            own_err[b] = mine_err;
+            if (!with_neighbours) continue;
+            int have[3]; uint32_t nb[3] = {0, 0, 0}; int any_equal = 0;
+            for (int p = 0; p < 3; p++) {
+                const int x = (int)bx + pred_dx[p], y = (int)by + pred_dy[p];
+                have[p] = x >= 0 && y >= 0;
+                if (have[p]) { nb[p] = block_cluster[first_block + (uint32_t)y * num_blocks_x + (uint32_t)x]; if (nb[p] == block_cluster[b]) any_equal = 1; }
+            }
+            for (int p = 0; p < 3; p++) {
+                uint32_t e = 0xFFFFFFFFu;
+                if (mine_err != 0 && !any_equal && have[p] && nb[p] < n_clusters) {
+                    const uint8_t* cp = cluster_params + 4ull * nb[p];
+                    e = block_error_under(pixel_blocks + 64ull * b, sel, cp[0], cp[1], cp[2], cp[3], perceptual);
+                }
+                neighbour_err[3ull * b + p] = e;
+            }
+        }
 }

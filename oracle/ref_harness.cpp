@@ -115,6 +115,35 @@ REF_API int ref_etc1_optimize(const uint8_t* rgba, uint32_t n, int quality, int 
 	return 1;
 }
 
+// What this build of the harness offers, for tests that need more than an older build carried over in oracle/_ref/ has:
+// 2 = ref_etc1_optimize_forced, the frontend call "compute_endpoint_subblock_error_vec" and the getter "subblock_endpoint_quant_err".
+REF_API int ref_harness_version() { return 2; }
+
+// The same with m_pForce_selectors (etc.cpp:780-784): one selector (0..3) per pixel; the reference refuses qualities below slow.
+REF_API int ref_etc1_optimize_forced(const uint8_t* rgba, uint32_t n, int quality, int perceptual, const uint8_t* force_selectors,
+	uint8_t* out_color5, uint32_t* out_inten, uint64_t* out_err) {
+	etc1_optimizer opt;
+	etc1_optimizer::params prm;
+	etc1_optimizer::results res;
+	prm.m_quality = (basis_etc_quality)quality;
+	prm.m_num_src_pixels = n;
+	prm.m_pSrc_pixels = reinterpret_cast<const color_rgba*>(rgba);
+	prm.m_use_color4 = false;
+	prm.m_perceptual = perceptual != 0;
+	prm.m_pForce_selectors = force_selectors;
+	std::vector<uint8_t> sels(n ? n : 1);
+	res.m_pSelectors = sels.data();
+	res.m_n = n;
+	opt.init(prm, res);
+	if (!opt.compute()) return 0;
+	out_color5[0] = res.m_block_color_unscaled.r;
+	out_color5[1] = res.m_block_color_unscaled.g;
+	out_color5[2] = res.m_block_color_unscaled.b;
+	*out_inten = res.m_block_inten_table;
+	*out_err = res.m_error;
+	return 1;
+}
+
 // init_etc1_images' CPU branch (frontend.cpp:765-818) over a bare array of pixel blocks.
 REF_API void ref_encode_etc1s_blocks(const uint8_t* pixel_blocks, uint32_t n_blocks, int comp_level, int perceptual, uint8_t* out_blocks) {
 	const pixel_block* src = reinterpret_cast<const pixel_block*>(pixel_blocks);
@@ -207,6 +236,7 @@ REF_API int64_t ref_frontend_call(void* hv, const char* name, uint32_t arg) {
 	if (n == "init_etc1_images") { fe.init_etc1_images(); return 1; }
 	if (n == "init_endpoint_training_vectors") { fe.init_endpoint_training_vectors(); return 1; }
 	if (n == "generate_endpoint_clusters") { fe.generate_endpoint_clusters(); return 1; }
+	if (n == "compute_endpoint_subblock_error_vec") { fe.compute_endpoint_subblock_error_vec(); return 1; }
 	if (n == "introduce_new_endpoint_clusters") { fe.introduce_new_endpoint_clusters(); return 1; }
 	if (n == "generate_endpoint_codebook") { fe.generate_endpoint_codebook(arg); return 1; }
 	if (n == "refine_endpoint_clusterization") return fe.refine_endpoint_clusterization();
@@ -266,6 +296,17 @@ REF_API uint64_t ref_frontend_get(void* hv, const char* name, void* buf, uint64_
 			v[i * 16 + 3] = (uint8_t)e.m_inten_table[0];
 			v[i * 16 + 4] = e.m_valid ? 1 : 0;
 			memcpy(&v[i * 16 + 8], &e.m_color_error[0], 8);
+		}
+		return emit(v, buf, cap);
+	}
+	if (n == "subblock_endpoint_quant_err") {
+		// what compute_endpoint_subblock_error_vec left (sorted by error): per entry u64 total error, u32 block, u32 sub-block
+		std::vector<uint8_t> v(fe.m_subblock_endpoint_quant_err_vec.size() * 16);
+		for (size_t i = 0; i < fe.m_subblock_endpoint_quant_err_vec.size(); i++) {
+			const auto& e = fe.m_subblock_endpoint_quant_err_vec[(uint32_t)i];
+			memcpy(&v[i * 16], &e.m_total_err, 8);
+			memcpy(&v[i * 16 + 8], &e.m_block_index, 4);
+			memcpy(&v[i * 16 + 12], &e.m_subblock_index, 4);
 		}
 		return emit(v, buf, cap);
 	}

@@ -141,6 +141,11 @@ def oracle():
         L.orc_hash_hsieh3.argtypes = [C.c_uint8] * 3
         L.orc_etc1_optimize.restype = C.c_int
         L.orc_etc1_optimize.argtypes = [u8p, C.c_uint32, C.c_int, C.c_int, u8p, u32p, u64p, u8p]
+        L.orc_etc1_optimize_forced.restype = C.c_int
+        L.orc_etc1_optimize_forced.argtypes = [u8p, C.c_uint32, C.c_int, C.c_int, u8p, u8p, u32p, u64p]
+        L.orc_refit_endpoints_given_selectors.argtypes = [u8p, u8p, C.c_uint32, u32p, u32p, C.c_int, C.c_int, u8p, u64p, u8p, u64p]
+        L.orc_subblock_errors.argtypes = [u8p, C.c_uint32, u32p, u8p, C.c_int, u64p]
+        L.orc_backend_block_errors.argtypes = [u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, u32p, u32p]
         L.orc_encode_etc1s_blocks.argtypes = [u8p, C.c_uint32, C.c_int, C.c_int, u8p]
         L.orc_determine_selectors.argtypes = [u8p, C.c_uint32, u8p, C.c_int, u8p]
         L.orc_generate_endpoint_codebook.argtypes = [u8p, C.c_uint32, u32p, u32p, C.c_int, C.c_int, C.c_uint32, u8p, u64p, u8p]
@@ -169,6 +174,18 @@ def have_ref():
     return (ORACLE_DIR / "_ref" / "libref_harness.so").exists()
 
 
+def ref_harness_version():
+    """ref_harness_version() of oracle/_ref/libref_harness.so: 0 = no harness, 1 = a build from before the function existed (an oracle/_ref/ carried over from an
+    earlier revision where the reference is not there to rebuild it: oracle/Makefile rebuilds it wherever it is), else what the harness says (oracle/ref_harness.cpp)."""
+    if not have_ref():
+        return 0
+    L = ref()
+    if not hasattr(L, "ref_harness_version"):
+        return 1
+    L.ref_harness_version.restype = C.c_int
+    return int(L.ref_harness_version())
+
+
 def ref():
     global _ref
     if _ref is None:
@@ -176,6 +193,9 @@ def ref():
         L.ref_init.restype = C.c_int
         L.ref_etc1_optimize.restype = C.c_int
         L.ref_etc1_optimize.argtypes = [u8p, C.c_uint32, C.c_int, C.c_int, u8p, u32p, u64p, u8p]
+        if hasattr(L, "ref_etc1_optimize_forced"):   # harness version 2 (ref_harness_version)
+            L.ref_etc1_optimize_forced.restype = C.c_int
+            L.ref_etc1_optimize_forced.argtypes = [u8p, C.c_uint32, C.c_int, C.c_int, u8p, u8p, u32p, u64p]
         L.ref_encode_etc1s_blocks.argtypes = [u8p, C.c_uint32, C.c_int, C.c_int, u8p]
         L.ref_determine_selectors.argtypes = [u8p, C.c_uint32, u8p, C.c_int, u8p]
         L.ref_color_distance.restype = C.c_uint32

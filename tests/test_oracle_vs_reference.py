@@ -5,7 +5,7 @@ reproduce the reference's next state bit for bit. CPU only; skipped where the re
 import numpy as np
 import pytest
 
-from helpers import (oracle, ref, have_ref, RefFrontend, ptr, u32p, u64p, f32p, synth, uniform_random, to_pixel_blocks,
+from helpers import (oracle, ref, have_ref, ref_harness_version, RefFrontend, ptr, u32p, u64p, f32p, synth, uniform_random, to_pixel_blocks,
                      csr_from_lists, ROOT)
 
 pytestmark = pytest.mark.skipif(not have_ref(), reason="oracle/_ref not built (needs /root/reference)")
@@ -63,6 +63,87 @@ def test_cluster_optimizer(n, quality):
         assert oracle().orc_etc1_optimize(ptr(rgba), n, quality, perceptual, ptr(ca), ptr(ia, u32p), ptr(ea, u64p), ptr(sa)) == 1
         assert ref().ref_etc1_optimize(ptr(rgba), n, quality, perceptual, ptr(cb), ptr(ib, u32p), ptr(eb, u64p), ptr(sb)) == 1
         assert (ca == cb).all() and ia[0] == ib[0] and ea[0] == eb[0] and (sa == sb).all()
+
+
+# the pins below need entry points an oracle/_ref/ built from an earlier revision's harness does not have; where the reference lies, build() rebuilds the harness
+needs_harness_2 = pytest.mark.skipif(ref_harness_version() < 2, reason="oracle/_ref/libref_harness.so was built from an older oracle/ref_harness.cpp and the reference "
+                                                                       "is not there to rebuild it")
+
+
+def _nearest_selectors(rgba, color5, inten, perceptual):
+    """the selector (0..3) of the nearest of the four colours of (color5, inten) per pixel, first minimum (etc.cpp:1162-1186)"""
+    table = np.array([[-8, -2, 2, 8], [-17, -5, 5, 17], [-29, -9, 9, 29], [-42, -13, 13, 42], [-60, -18, 18, 60], [-80, -24, 24, 80], [-106, -33, 33, 106],
+                      [-183, -47, 47, 183]], np.int64)
+    base = (color5.astype(np.int64) << 3) | (color5.astype(np.int64) >> 2)
+    cols = np.clip(base[None, :] + table[inten][:, None], 0, 255).astype(np.uint8)
+    sel = np.zeros(rgba.shape[0], np.uint8)
+    for i in range(rgba.shape[0]):
+        p = np.ascontiguousarray(rgba[i, :3])
+        d = [oracle().orc_color_distance(perceptual, ptr(p), ptr(np.ascontiguousarray(cols[s]))) for s in range(4)]
+        sel[i] = int(np.argmin(d))
+    return sel
+
+
+@pytest.mark.ref
+@needs_harness_2
+@pytest.mark.parametrize("quality", [2, 3])
+@pytest.mark.parametrize("selectors", ["nearest", "random"])
+@pytest.mark.parametrize("n", [8, 16, 24, 8 * 1023, 8 * 1024, 8 * 1025])
+def test_forced_cluster_optimizer(n, selectors, quality):
+    """etc1_optimizer with m_pForce_selectors (etc.cpp:780-784, 1137-1160), the fit of refine_block_endpoints_given_selectors: the oracle's forced optimizer against
+    the reference's on seeded pixel lists, the forced selectors once those of the unforced fit's nearest colours, once uniformly random (where the forced error is
+    far from the nearest-colour one); sizes on either side of 8192 texels."""
+    rng = np.random.default_rng(1000 * quality + n + (7 if selectors == "random" else 0))
+    base = rng.integers(0, 256, 3)
+    px = np.clip(base[None, :] + rng.normal(0, 30, (n, 3)), 0, 255).astype(np.uint8)
+    rgba = np.ascontiguousarray(np.concatenate([px, np.full((n, 1), 255, np.uint8)], axis=1))
+    for perceptual in (1, 0):
+        if selectors == "nearest":
+            c = np.zeros(3, np.uint8); it = np.zeros(1, np.uint32); e = np.zeros(1, np.uint64)
+            assert oracle().orc_etc1_optimize(ptr(rgba), n, quality, perceptual, ptr(c), ptr(it, u32p), ptr(e, u64p), None) == 1
+            # one table up: the nearest selectors of a neighbouring solution, so that the forced fit has something to move
+            force = _nearest_selectors(rgba, c, min(int(it[0]) + 1, 7), perceptual)
+        else:
+            force = rng.integers(0, 4, n).astype(np.uint8)
+        ca = np.zeros(3, np.uint8); cb = np.zeros(3, np.uint8)
+        ia = np.zeros(1, np.uint32); ib = np.zeros(1, np.uint32)
+        ea = np.zeros(1, np.uint64); eb = np.zeros(1, np.uint64)
+        assert oracle().orc_etc1_optimize_forced(ptr(rgba), n, quality, perceptual, ptr(force), ptr(ca), ptr(ia, u32p), ptr(ea, u64p)) == 1
+        assert ref().ref_etc1_optimize_forced(ptr(rgba), n, quality, perceptual, ptr(force), ptr(cb), ptr(ib, u32p), ptr(eb, u64p)) == 1
+        assert (ca == cb).all() and ia[0] == ib[0] and ea[0] == eb[0], (n, selectors, quality, perceptual, ca, cb, ia, ib, ea, eb)
+    # the reference refuses forced selectors below slow quality, and so does the oracle
+    assert oracle().orc_etc1_optimize_forced(ptr(rgba), n, 1, 1, ptr(force), ptr(ca), ptr(ia, u32p), ptr(ea, u64p)) == 0
+
+
+@pytest.mark.ref
+@needs_harness_2
+@pytest.mark.parametrize("perceptual", [1, 0])
+def test_subblock_errors_of_a_level4_frontend(perceptual):
+    """compute_endpoint_subblock_error_vec (frontend.cpp:1006-1091) of the reference's level-4 frontend after its first endpoint codebook, against orc_subblock_errors
+    fed the same clusters and endpoints: every sub-block's error, the unscaled-colour quirk included."""
+    blocks = INPUTS["synth"]
+    n = blocks.shape[0]
+    fe = RefFrontend(blocks, 300, 400, 4, perceptual)
+    for stage in ("init_etc1_images", "init_endpoint_training_vectors", "generate_endpoint_clusters"):
+        fe.call(stage)
+    fe.call("generate_endpoint_codebook", 0)
+    offs, idx = fe.get_csr("endpoint_clusters")
+    k = len(offs) - 1
+    prm = np.ascontiguousarray(fe.get("endpoint_cluster_etc_params").reshape(k, 16)[:, :4])
+    tv_cluster = np.full(2 * n, 0xFFFFFFFF, np.uint32)
+    for ci, l in enumerate(_lists(offs, idx)):
+        tv_cluster[l] = ci
+    assert (tv_cluster[0::2] == tv_cluster[1::2]).all() and (tv_cluster != 0xFFFFFFFF).all()   # both halves of a block share a cluster here
+    block_cluster = np.ascontiguousarray(tv_cluster[0::2])
+    fe.call("compute_endpoint_subblock_error_vec")
+    rec = fe.get("subblock_endpoint_quant_err").reshape(-1, 16)
+    assert rec.shape[0] == 2 * n
+    want = np.full(2 * n, 2 ** 64 - 1, np.uint64)
+    want[rec[:, 8:12].copy().view(np.uint32).reshape(-1) * 2 + rec[:, 12:16].copy().view(np.uint32).reshape(-1)] = rec[:, :8].copy().view(np.uint64).reshape(-1)
+    got = np.zeros(2 * n, np.uint64)
+    oracle().orc_subblock_errors(ptr(blocks), n, ptr(block_cluster, u32p), ptr(prm), perceptual, ptr(got, u64p))
+    assert (got == want).all()
+    fe.close()
 
 
 def _lists(offs, idx):
