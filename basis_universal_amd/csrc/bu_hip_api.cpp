@@ -25,6 +25,7 @@
 #include "tsvq_kernels.h"
 #include "tsvq_bufs.h"
 #include "uastc_kernels.h"
+#include "uastc_transcode_kernels.h"
 #include "mipmap_kernels.h"
 #include "unique_kernels.h"
 #include "bookkeeping_kernels.h"
@@ -1918,6 +1919,40 @@ int bu_hip_encode_uastc_blocks(bu_hip_context* ctx, bu_uastc_block* out, uint32_
     BU_TRY(ctx, o.reserve((size_t)n * 16));
     if (!bu_hip_k_encode_uastc_blocks(ctx, ctx->d_pixel_blocks, n, flags, o.p)) return 0;
     if (!fetch(ctx, out, o.p, (size_t)n * 16)) return 0;
+    return 1;
+}
+
+// ---------------------------------------------------------------- UASTC transcode (uastc_transcode_kernels.hip)
+
+size_t bu_hip_transcode_output_bytes(uint32_t nbx, uint32_t nby, uint32_t orig_width, uint32_t orig_height, uint32_t target) {
+    return bu::transcode_output_bytes(nbx, nby, orig_width, orig_height, target);
+}
+
+int bu_hip_k_transcode_uastc(bu_hip_context* ctx, const void* d_blocks, uint32_t nbx, uint32_t nby, uint32_t orig_width, uint32_t orig_height, uint32_t target,
+                             uint32_t decode_flags, int32_t channel0, int32_t channel1, void* d_out, uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels,
+                             uint32_t* out_invalid_blocks) {
+    if (!ctx) return 0;
+    if (out_invalid_blocks) *out_invalid_blocks = 0;
+    if (!bu::transcode_output_bytes(1, 1, 0, 0, target)) { set_error(ctx, "transcode_uastc: target %u is not supported (RGBA32, ASTC 4x4, BC1, BC3, BC4, BC5, BC7 are)", target); return 0; }
+    if (!d_blocks || !d_out) { set_error(ctx, "transcode_uastc: null device pointer"); return 0; }
+    if ((uint64_t)nbx * nby > 0x7FFFFFFFull) { set_error(ctx, "transcode_uastc: %u x %u blocks is too many", nbx, nby); return 0; }
+    const uint32_t width = orig_width ? orig_width : nbx * 4, height = orig_height ? orig_height : nby * 4;
+    if (width > nbx * 4 || height > nby * 4) { set_error(ctx, "transcode_uastc: %u x %u pixels do not fit %u x %u blocks", width, height, nbx, nby); return 0; }
+    const uint32_t pitch = out_row_pitch_pixels ? out_row_pitch_pixels : width, rows = out_rows_pixels ? out_rows_pixels : height;
+    if (pitch < width) { set_error(ctx, "transcode_uastc: row pitch %u is less than the width %u", pitch, width); return 0; }
+    if (channel0 > 3 || channel1 > 3) { set_error(ctx, "transcode_uastc: channel out of range"); return 0; }
+    device_guard g(ctx->device);
+    arena& counter = ctx->scratch[4];
+    BU_TRY(ctx, counter.reserve(sizeof(uint32_t)));
+    {
+        prof_scope ps(ctx, "uastc_transcode");
+        BU_TRY(ctx, bu::launch_transcode_uastc(ctx->stream, d_blocks, nbx, nby, width, height, target, (decode_flags & 32u) != 0 /* cDecodeFlagsHighQuality */,
+                                               channel0 < 0 ? 0u : (uint32_t)channel0, channel1 < 0 ? 3u : (uint32_t)channel1, d_out, pitch, rows, static_cast<uint32_t*>(counter.p)));
+    }
+    uint32_t invalid = 0;
+    BU_TRY(ctx, d2h_pageable(ctx, &invalid, counter.p, sizeof(invalid)));
+    BU_TRY(ctx, stream_wait(ctx, ctx->stream));
+    if (out_invalid_blocks) *out_invalid_blocks = invalid;
     return 1;
 }
 

@@ -1484,8 +1484,9 @@ BU_FN bc1_blk bc1_solid(uint32_t r, uint32_t g, uint32_t b) {  // encode_bc1_sol
     return out;
 }
 
-// basist::encode_bc1 (transcoder.cpp:18047-18283) with flags 0 (use_given false) or cEncodeBC1UseSelectors (the selectors in `given`, 2 bits per texel)
-BU_FN bc1_blk bc1_encode(const uint32_t* px, bool use_given, uint32_t given) {
+// basist::encode_bc1 (transcoder.cpp:18047-18283) with flags 0 (use_given false) or cEncodeBC1UseSelectors (the selectors in `given`, 2 bits per texel);
+// ls_passes 2 = cEncodeBC1HighQuality (the transcoder's high-quality BC1 / BC3), the encoder's hint search always runs one
+BU_FN bc1_blk bc1_encode(const uint32_t* px, bool use_given, uint32_t given, uint32_t ls_passes = 1) {
     int avg[3] = { -1, 0, 0 };
     int l[3] = { 0, 0, 0 }, h[3] = { 0, 0, 0 };
     uint32_t sels = given;
@@ -1539,7 +1540,7 @@ BU_FN bc1_blk bc1_encode(const uint32_t* px, bool use_given, uint32_t given) {
         }
         sels = bc1_pick_selectors(px, l, h);
     }
-    {
+    for (uint32_t pass = 0; pass < ls_passes; pass++) {
         // one least-squares pass (compute_least_squares_endpoints_rgb, transcoder.cpp:17922-17997)
         uint32_t q00[3] = { 0, 0, 0 }, wacc = 0;
         BU_UNROLL
@@ -1622,41 +1623,50 @@ BU_FN uint32_t pack565_scaled(uint32_t r, uint32_t g, uint32_t b) {  // dxt1_blo
     return (r << 11) | (g << 5) | b;
 }
 
+// the first plane's weights translated to BC1's four levels, 2 bits per texel
+BU_FN uint32_t bc1_translated_weights(const cand& norm) {
+    const uint32_t wbits = ku_mode_weight_bits[norm.mode], planes = ku_mode_planes[norm.mode];
+    uint32_t tw = 0;
+    BU_UNROLL
+    for (int i = 0; i < 16; i++) tw |= bc1_weight_translate(wbits, planes == 2 ? norm.weights[i * 2] : norm.weights[i]) << (2 * i);
+    return tw;
+}
+// transcode_uastc_to_bc1_hint1, transcoder.cpp:18700-18728: BC1 code -> linear selector {0, 3, 1, 2}, all sixteen at once: (low bit, high ^ low)
+BU_FN uint32_t bc1_hint1_selectors(uint32_t tw) {
+    const uint32_t hi = (tw >> 1) & 0x55555555u, lo = tw & 0x55555555u;
+    return (lo << 1) | (hi ^ lo);
+}
+// transcode_uastc_to_bc1_hint0, :18602-18697: the first subset's endpoints scaled to 5:6:5, the translated weights as selectors
+BU_FN bc1_blk bc1_hint0_block(const cand& norm, uint32_t tw) {
+    const uint8_t* UQ = ku_unquant + ku_mode_endpoint_ranges[norm.mode] * 256;
+    uint32_t lc, hc;
+    if (ku_mode_comps[norm.mode] == 2) { lc = pack565_scaled(UQ[norm.endpoints[0]], UQ[norm.endpoints[0]], UQ[norm.endpoints[0]]); hc = pack565_scaled(UQ[norm.endpoints[1]], UQ[norm.endpoints[1]], UQ[norm.endpoints[1]]); }
+    else { lc = pack565_scaled(UQ[norm.endpoints[0]], UQ[norm.endpoints[2]], UQ[norm.endpoints[4]]); hc = pack565_scaled(UQ[norm.endpoints[1]], UQ[norm.endpoints[3]], UQ[norm.endpoints[5]]); }
+    bc1_blk b;
+    if (lc == hc) {
+        uint32_t mask = 0;
+        if (hc > 0) hc--;
+        else { hc = 0; lc = 1; mask = 0x55; }
+        b.c0 = (uint16_t)lc; b.c1 = (uint16_t)hc; b.sel = mask * 0x01010101u;
+    } else {
+        uint32_t sels = tw;
+        if (lc < hc) { const uint32_t t = lc; lc = hc; hc = t; sels ^= 0x55555555u; }
+        b.c0 = (uint16_t)lc; b.c1 = (uint16_t)hc; b.sel = sels;
+    }
+    return b;
+}
+
 // compute_bc1_hints (uastc_enc.cpp:2535-2629); `norm` is the anchor-normalised winner, `decoded` its UASTC decode, `px` the source texels (both packed dwords)
 BU_FN void bc1_hints(const cand& norm, const uint32_t* px, const uint32_t* decoded, bool& hint0, bool& hint1) {
     hint0 = hint1 = false;
     const uint32_t mode = norm.mode;
     const bool has0 = ku_mode_has_bc1_hint0[mode] != 0, has1 = ku_mode_has_bc1_hint1[mode] != 0;
     if (!has0 && !has1) return;
-    const uint32_t wbits = ku_mode_weight_bits[mode], planes = ku_mode_planes[mode], comps = ku_mode_comps[mode];
-    // the first plane's weights translated to BC1's four levels, 2 bits per texel
-    uint32_t tw = 0;
-    BU_UNROLL
-    for (int i = 0; i < 16; i++) tw |= bc1_weight_translate(wbits, planes == 2 ? norm.weights[i * 2] : norm.weights[i]) << (2 * i);
+    const uint32_t tw = bc1_translated_weights(norm);
     const uint32_t et = bc1_error(bc1_encode(decoded, false, 0), px);
     uint32_t e0 = 0, e1 = 0;
-    if (has1) {  // transcode_uastc_to_bc1_hint1, transcoder.cpp:18700-18728: BC1 code -> linear selector {0, 3, 1, 2}, all sixteen at once: (low bit, high ^ low)
-        const uint32_t hi = (tw >> 1) & 0x55555555u, lo = tw & 0x55555555u;
-        e1 = bc1_error(bc1_encode(decoded, true, (lo << 1) | (hi ^ lo)), px);
-    }
-    if (has0) {  // transcode_uastc_to_bc1_hint0, :18602-18697
-        const uint8_t* UQ = ku_unquant + ku_mode_endpoint_ranges[mode] * 256;
-        uint32_t lc, hc;
-        if (comps == 2) { lc = pack565_scaled(UQ[norm.endpoints[0]], UQ[norm.endpoints[0]], UQ[norm.endpoints[0]]); hc = pack565_scaled(UQ[norm.endpoints[1]], UQ[norm.endpoints[1]], UQ[norm.endpoints[1]]); }
-        else { lc = pack565_scaled(UQ[norm.endpoints[0]], UQ[norm.endpoints[2]], UQ[norm.endpoints[4]]); hc = pack565_scaled(UQ[norm.endpoints[1]], UQ[norm.endpoints[3]], UQ[norm.endpoints[5]]); }
-        bc1_blk b;
-        if (lc == hc) {
-            uint32_t mask = 0;
-            if (hc > 0) hc--;
-            else { hc = 0; lc = 1; mask = 0x55; }
-            b.c0 = (uint16_t)lc; b.c1 = (uint16_t)hc; b.sel = mask * 0x01010101u;
-        } else {
-            uint32_t sels = tw;
-            if (lc < hc) { const uint32_t t = lc; lc = hc; hc = t; sels ^= 0x55555555u; }
-            b.c0 = (uint16_t)lc; b.c1 = (uint16_t)hc; b.sel = sels;
-        }
-        e0 = bc1_error(b, px);
-    }
+    if (has1) e1 = bc1_error(bc1_encode(decoded, true, bc1_hint1_selectors(tw)), px);
+    if (has0) e0 = bc1_error(bc1_hint0_block(norm, tw), px);
     const float t_err = sqrtf((float)et), t0 = sqrtf((float)e0), t1 = sqrtf((float)e1);
     if (has0 && t0 <= t_err * 1.075f) hint0 = true;
     if (has1 && t1 <= t_err * 1.075f) hint1 = true;

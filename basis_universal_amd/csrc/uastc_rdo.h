@@ -57,6 +57,15 @@ BU_FN void parse_weights(cand& r, uint64_t lo, uint64_t hi) {
     }
 }
 
+// the two BC1 hint bits of a non-solid block of `mode` (m_bc1_hint0 / m_bc1_hint1 of unpack_uastc with read_hints, transcoder.cpp:15342-15352): they follow the
+// mode code, each present only in the modes that have it
+BU_FN void read_bc1_hints(const uint8_t* blk, uint32_t mode, bool& hint0, bool& hint1) {
+    uint32_t ofs = ku_mode_code_len[mode];
+    hint0 = hint1 = false;
+    if (ku_mode_has_bc1_hint0[mode]) { hint0 = block_bits(blk, ofs, 1) != 0; ofs++; }
+    if (ku_mode_has_bc1_hint1[mode]) hint1 = block_bits(blk, ofs, 1) != 0;
+}
+
 // unpack_uastc(blk, unpacked, blue_contract_check = false, read_hints = *): everything but the hints. Returns false where the reference
 // does (invalid mode code, pattern index out of range). A solid block comes back as mode 8 with its colour in endpoints[0..3].
 BU_FN bool unpack_block(const uint8_t* blk, cand& r) {

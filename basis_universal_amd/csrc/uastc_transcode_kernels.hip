@@ -1,0 +1,98 @@
+// uastc_transcode_kernels.hip -- basisu_lowlevel_uastc_ldr_4x4_transcoder::transcode_slice (transcoder/basisu_transcoder.cpp:10078-10339) over resident UASTC
+// blocks: one lane per 16-byte block, the target a template parameter so that each instance carries only its own path (uastc_transcode.h). A block
+// is loaded as one uint4 and its result stored as whole uint2 / uint4 words, consecutive lanes on consecutive blocks; RGBA32 writes the four 16-byte
+// rows of its tile into the caller's raster, cropped to the image. A block the core refuses (mode code that matches nothing, pattern index out of
+// range) gets zeros and is counted with a vector atomic; it never stops the others.
+#include <hip/hip_runtime.h>
+#include "uastc_transcode.h"
+#include "uastc_transcode_kernels.h"
+
+namespace bu {
+using namespace bu_uastc;
+
+struct transcode_args {
+    const uint4* blocks;
+    void* out;
+    uint32_t* invalid;
+    uint32_t nbx, nby, width, height, pitch, rows, chan0, chan1;
+};
+
+template <uint32_t TARGET, bool HQ>
+__global__ __launch_bounds__(256) void transcode_uastc_kernel(transcode_args a) {
+    const uint32_t n = a.nbx * a.nby, i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint4 in = a.blocks[i];
+    uint8_t blk[16];
+    const uint32_t words[4] = { in.x, in.y, in.z, in.w };
+    BU_UNROLL
+    for (int k = 0; k < 16; k++) blk[k] = (uint8_t)(words[k >> 2] >> (8 * (k & 3)));
+    bool ok;
+    if (TARGET == TF_RGBA32) {
+        rgba8 px[16];
+        ok = transcode_rgba32(blk, px);
+        const uint32_t bx = i % a.nbx, by = i / a.nbx;
+        BU_UNROLL
+        for (uint32_t y = 0; y < 4; y++) {
+            const uint32_t row = by * 4 + y;
+            if (row >= a.height || row >= a.rows) break;
+            uint32_t* dst = (uint32_t*)a.out + (size_t)row * a.pitch + bx * 4;
+            uint32_t v[4];
+            BU_UNROLL
+            for (uint32_t x = 0; x < 4; x++) v[x] = ok ? pack_px(px[y * 4 + x].c) : 0u;
+            if (bx * 4 + 4 <= a.width && ((a.pitch & 3u) == 0)) *(uint4*)dst = make_uint4(v[0], v[1], v[2], v[3]);   // rows of a tile are 16-byte aligned when the pitch is
+            else {
+                BU_UNROLL
+                for (uint32_t x = 0; x < 4; x++) if (bx * 4 + x < a.width) dst[x] = v[x];
+            }
+        }
+    } else if (TARGET == TF_ASTC_4x4_RGBA || TARGET == TF_BC7_RGBA) {
+        uint8_t o[16];
+        ok = TARGET == TF_BC7_RGBA ? transcode_bc7(blk, o) : transcode_astc(blk, o);
+        uint32_t w[4] = { 0, 0, 0, 0 };
+        if (ok) {
+            BU_UNROLL
+            for (int k = 0; k < 16; k++) w[k >> 2] |= (uint32_t)o[k] << (8 * (k & 3));
+        }
+        ((uint4*)a.out)[i] = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+        uint64_t w[2] = { 0, 0 };
+        ok = transcode_bcn(blk, TARGET, HQ, a.chan0, a.chan1, w);
+        if (!ok) w[0] = w[1] = 0;
+        if (TARGET == TF_BC1_RGB || TARGET == TF_BC4_R) ((uint2*)a.out)[i] = make_uint2((uint32_t)w[0], (uint32_t)(w[0] >> 32));
+        else ((uint4*)a.out)[i] = make_uint4((uint32_t)w[0], (uint32_t)(w[0] >> 32), (uint32_t)w[1], (uint32_t)(w[1] >> 32));
+    }
+    if (!ok) atomicAdd(a.invalid, 1u);
+}
+
+template <uint32_t TARGET, bool HQ>
+static hipError_t launch(hipStream_t st, const transcode_args& a) {
+    const uint32_t n = a.nbx * a.nby;
+    hipLaunchKernelGGL((transcode_uastc_kernel<TARGET, HQ>), dim3((n + 255) / 256), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+size_t transcode_output_bytes(uint32_t nbx, uint32_t nby, uint32_t width, uint32_t height, uint32_t target) {
+    const uint32_t bpb = transcode_bytes_per_block(target);
+    if (!bpb) return 0;
+    if (target == TF_RGBA32) return (size_t)(width ? width : nbx * 4) * (height ? height : nby * 4) * 4;
+    return (size_t)nbx * nby * bpb;
+}
+
+hipError_t launch_transcode_uastc(hipStream_t st, const void* d_blocks, uint32_t nbx, uint32_t nby, uint32_t width, uint32_t height, uint32_t target, bool high_quality,
+                                  uint32_t chan0, uint32_t chan1, void* d_out, uint32_t pitch, uint32_t rows, uint32_t* d_invalid) {
+    transcode_args a = { (const uint4*)d_blocks, d_out, d_invalid, nbx, nby, width, height, pitch, rows, chan0, chan1 };
+    hipError_t e = hipMemsetAsync(d_invalid, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess || !nbx || !nby) return e;
+    switch (target) {
+    case TF_RGBA32: return launch<TF_RGBA32, false>(st, a);
+    case TF_ASTC_4x4_RGBA: return launch<TF_ASTC_4x4_RGBA, false>(st, a);
+    case TF_BC7_RGBA: return launch<TF_BC7_RGBA, false>(st, a);
+    case TF_BC1_RGB: return high_quality ? launch<TF_BC1_RGB, true>(st, a) : launch<TF_BC1_RGB, false>(st, a);
+    case TF_BC3_RGBA: return high_quality ? launch<TF_BC3_RGBA, true>(st, a) : launch<TF_BC3_RGBA, false>(st, a);
+    case TF_BC4_R: return launch<TF_BC4_R, false>(st, a);
+    case TF_BC5_RG: return launch<TF_BC5_RG, false>(st, a);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+} // namespace bu

@@ -1,0 +1,173 @@
+"""UASTC LDR 4x4 -> GPU texture formats on the GPU: the host-side mirror of basist::basisu_lowlevel_uastc_ldr_4x4_transcoder::transcode_slice
+(transcoder/basisu_transcoder.cpp:10078) as a batch op, a reader for the two UASTC containers this package writes, and `transcode_file` on top of both.
+
+Targets are the reference's transcoder_texture_format values; only the ones below exist here. ETC1 / ETC2 / EAC / PVRTC1, the 16-bit pixel formats, ETC1S files,
+UASTC HDR / ASTC LDR / XUASTC and Zstandard-supercompressed KTX2 levels are out of scope and are refused with an error. There is no CPU implementation:
+without the HIP library and a GPU `transcode_uastc_blocks` raises.
+"""
+import ctypes as C
+import struct
+
+import numpy as np
+
+BC1_RGB, BC3_RGBA, BC4_R, BC5_RG, BC7_RGBA, ASTC_4x4_RGBA, RGBA32 = 2, 3, 4, 5, 6, 10, 13
+BYTES_PER_BLOCK = {BC1_RGB: 8, BC3_RGBA: 16, BC4_R: 8, BC5_RG: 16, BC7_RGBA: 16, ASTC_4x4_RGBA: 16, RGBA32: 64}
+DECODE_FLAGS_HIGH_QUALITY = 32   # cDecodeFlagsHighQuality
+
+
+class InvalidBlocksError(ValueError):
+    """Some blocks did not unpack as UASTC (their output was zero-filled). `count` is how many."""
+
+    def __init__(self, count, total):
+        super().__init__(f"{count} of {total} blocks are not valid UASTC LDR 4x4 blocks")
+        self.count = count
+
+
+def transcode_uastc_blocks(ctx, blocks, nbx, nby, target, *, width=None, height=None, high_quality=False, channels=None, out_device=None,
+                           out_row_pitch=0, out_rows=0):
+    """blocks: (nby * nbx, 16) uint8 array in raster order (uploaded once) or a device pointer (int) to that many resident blocks.
+    Returns (nby * nbx, bytes_per_block) uint8, for RGBA32 the (height, width, 4) raster, or None when out_device (a device pointer with room for
+    bu_hip_transcode_output_bytes, or for out_rows x out_row_pitch pixels when those are given) receives the output. width / height default to the padded size;
+    channels: BC4's (c,) or BC5's (c0, c1), default (0,) / (0, 3). Raises InvalidBlocksError when a block does not unpack."""
+    nbx, nby, target = int(nbx), int(nby), int(target)
+    if target not in BYTES_PER_BLOCK:
+        raise ValueError(f"transcode target {target} is not supported (supported: {sorted(BYTES_PER_BLOCK)})")
+    n = nbx * nby
+    width, height = int(width or nbx * 4), int(height or nby * 4)
+    if not (0 < width <= nbx * 4 and 0 < height <= nby * 4) and n:
+        raise ValueError(f"{width} x {height} pixels do not fit {nbx} x {nby} blocks")
+    ch = tuple(channels) if channels is not None else ()
+    if len(ch) > 2 or any(not 0 <= int(c) <= 3 for c in ch):
+        raise ValueError("channels: up to two values in 0..3")
+    c0, c1 = (int(ch[0]) if len(ch) > 0 else -1), (int(ch[1]) if len(ch) > 1 else -1)
+    own = None
+    if isinstance(blocks, np.ndarray):
+        blocks = np.ascontiguousarray(blocks, np.uint8)
+        if blocks.size != n * 16:
+            raise ValueError(f"{nbx} x {nby} blocks need {n * 16} bytes, got {blocks.size}")
+        d_blk = own = ctx.upload(blocks) if n else 0
+    else:
+        d_blk = blocks
+    if out_device is None and (out_row_pitch or out_rows):
+        raise ValueError("out_row_pitch / out_rows describe a caller-owned raster: give out_device")
+    nbytes = ctx.lib.transcode_output_bytes(nbx, nby, width, height, target)
+    d_out = out_device if out_device is not None else ctx.alloc(max(nbytes, 1))
+    try:
+        invalid = C.c_uint32(0)
+        if n:
+            ctx.check(ctx.lib.k_transcode_uastc(ctx.h, C.c_void_p(d_blk), nbx, nby, width, height, target, DECODE_FLAGS_HIGH_QUALITY if high_quality else 0, c0, c1,
+                                                C.c_void_p(d_out), int(out_row_pitch), int(out_rows), C.byref(invalid)), "transcode_uastc")
+        if invalid.value:
+            raise InvalidBlocksError(invalid.value, n)
+        if out_device is not None:
+            return None
+        if target == RGBA32:
+            return ctx.download(d_out, (height, width, 4), np.uint8) if n else np.zeros((0, 0, 4), np.uint8)
+        return ctx.download(d_out, (n, BYTES_PER_BLOCK[target]), np.uint8) if n else np.zeros((0, BYTES_PER_BLOCK[target]), np.uint8)
+    finally:
+        if own:
+            ctx.free(own)
+        if out_device is None:
+            ctx.free(d_out)
+
+
+# ---------------------------------------------------------------- containers
+
+_KTX2_MAGIC = bytes([0xAB, 0x4B, 0x54, 0x58, 0x20, 0x32, 0x30, 0xBB, 0x0D, 0x0A, 0x1A, 0x0A])
+_BASIS_HEADER, _BASIS_SLICE = 77, 23   # sizeof(basis_file_header), sizeof(basis_slice_desc) (transcoder/basisu_file_headers.h)
+
+
+def _need(data, ofs, size, what):
+    if ofs < 0 or size < 0 or ofs + size > len(data):
+        raise ValueError(f"truncated or corrupt file: {what} needs bytes {ofs}..{ofs + size} of {len(data)}")
+
+
+def _image(level, layer, face, width, height, ofs, what, data):
+    nbx, nby = (width + 3) // 4, (height + 3) // 4
+    _need(data, ofs, nbx * nby * 16, what)
+    return {"level": level, "layer": layer, "face": face, "width": width, "height": height, "num_blocks_x": nbx, "num_blocks_y": nby, "offset": ofs, "length": nbx * nby * 16}
+
+
+def _read_basis(data):
+    _need(data, 0, _BASIS_HEADER, "the .basis header")
+    (sig, ver, hsize, _hcrc, dsize, _dcrc), total_slices, total_images = struct.unpack_from("<HHHHIH", data, 0), int.from_bytes(data[14:17], "little"), int.from_bytes(data[17:20], "little")
+    tex_format, flags, tex_type = data[20], struct.unpack_from("<H", data, 21)[0], data[23]
+    if ver != 0x13 or hsize != _BASIS_HEADER:
+        raise ValueError(f"unsupported .basis version {ver:#x} / header size {hsize}")
+    if tex_format != 1 or flags & 1:
+        raise ValueError("not a UASTC LDR 4x4 .basis file (ETC1S and other texture formats are not transcoded here)")
+    if dsize + _BASIS_HEADER > len(data):
+        raise ValueError(f"truncated .basis file: the header promises {dsize + _BASIS_HEADER} bytes, {len(data)} are here")
+    descs_ofs = struct.unpack_from("<I", data, 65)[0]
+    _need(data, descs_ofs, _BASIS_SLICE * total_slices, "the slice descriptors")
+    if not total_slices:
+        raise ValueError("a .basis file without slices")
+    faces = 6 if tex_type == 2 else 1
+    if total_images % faces:
+        raise ValueError("a cubemap .basis file whose image count is not a multiple of 6")
+    images = []
+    for i in range(total_slices):
+        at = descs_ofs + _BASIS_SLICE * i
+        image, level, sflags = int.from_bytes(data[at:at + 3], "little"), data[at + 3], data[at + 4]
+        ow, oh, nbx, nby, ofs, size, _crc = struct.unpack_from("<HHHHIIH", data, at + 5)
+        if sflags & 1:
+            raise ValueError("an alpha slice in a UASTC .basis file")
+        if image >= total_images or not ow or not oh or nbx != (ow + 3) // 4 or nby != (oh + 3) // 4 or size != nbx * nby * 16:
+            raise ValueError(f"slice {i}: inconsistent descriptor")
+        images.append(_image(level, image // faces, image % faces, ow, oh, ofs, f"slice {i}", data))
+    return {"container": "basis", "format": "UASTC_LDR_4x4", "width": images[0]["width"], "height": images[0]["height"], "has_alpha": bool(flags & 4),
+            "levels": sorted({im["level"] for im in images}), "layers": total_images // faces, "faces": faces, "images": images}
+
+
+def _read_ktx2(data):
+    _need(data, 0, 80, "the KTX2 header")
+    vk_format, _type_size, width, height, depth, layers, faces, levels, scheme, dfd_ofs, dfd_len, _kvo, _kvl = struct.unpack_from("<13I", data, 12)
+    if scheme != 0:
+        raise ValueError(f"KTX2 supercompression scheme {scheme} is not supported (only none: BasisLZ is ETC1S, Zstandard levels are out of scope)")
+    if vk_format != 0 or depth or not width or not height or faces not in (1, 6) or not 1 <= levels <= 16:
+        raise ValueError("not a 2D Basis Universal KTX2 file")
+    _need(data, 80, 24 * levels, "the level index")
+    _need(data, dfd_ofs, dfd_len, "the data format descriptor")
+    if dfd_len < 44 or data[dfd_ofs + 12] != 166:
+        raise ValueError("the KTX2 data format descriptor is not UASTC's (colour model 166)")
+    has_alpha = data[dfd_ofs + 28 + 3] == 3   # first sample's channel id: KTX2_DF_CHANNEL_UASTC_RGBA
+    n_layers = max(layers, 1)
+    images = []
+    for l in range(levels):
+        ofs, length, _ulen = struct.unpack_from("<3Q", data, 80 + 24 * l)
+        _need(data, ofs, length, f"level {l}")
+        w, h = max(width >> l, 1), max(height >> l, 1)
+        per = ((w + 3) // 4) * ((h + 3) // 4) * 16
+        if length != per * n_layers * faces:
+            raise ValueError(f"level {l}: {length} bytes where {per * n_layers * faces} are expected")
+        for layer in range(n_layers):
+            for face in range(faces):
+                images.append(_image(l, layer, face, w, h, ofs + (layer * faces + face) * per, f"level {l}", data))
+    return {"container": "ktx2", "format": "UASTC_LDR_4x4", "width": width, "height": height, "has_alpha": has_alpha, "levels": list(range(levels)), "layers": n_layers,
+            "faces": faces, "images": images}
+
+
+def read_uastc_file(data):
+    """Parse a UASTC .basis (cBASISTexFormatUASTC4x4) or .ktx2 (KTX2_SS_NONE, UASTC data format descriptor) file, the two containers this package writes.
+    -> {"container", "format", "width", "height", "has_alpha", "levels", "layers", "faces", "images": [{"level", "layer", "face", "width", "height", "num_blocks_x",
+    "num_blocks_y", "offset", "length"}]}. Every offset and length is checked against len(data); ETC1S, supercompressed or truncated files raise ValueError."""
+    data = bytes(data) if not isinstance(data, (bytes, bytearray, memoryview)) else data
+    if len(data) >= 12 and bytes(data[:12]) == _KTX2_MAGIC:
+        return _read_ktx2(data)
+    if len(data) >= 2 and bytes(data[:2]) == b"sB":
+        return _read_basis(data)
+    if len(data) < 12:
+        raise ValueError(f"truncated file: {len(data)} bytes hold no container signature")
+    raise ValueError("neither a .basis nor a .ktx2 file")
+
+
+def transcode_file(ctx, data, target, *, level=0, layer=0, face=0, high_quality=False, channels=None):
+    """One image of a UASTC .basis / .ktx2 file (read_uastc_file) transcoded on the GPU: blocks as transcode_uastc_blocks returns them, RGBA32 as the image."""
+    raw = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
+    info = read_uastc_file(raw)
+    for im in info["images"]:
+        if (im["level"], im["layer"], im["face"]) == (level, layer, face):
+            blocks = np.frombuffer(raw, np.uint8, im["length"], im["offset"]).reshape(-1, 16)
+            return transcode_uastc_blocks(ctx, blocks, im["num_blocks_x"], im["num_blocks_y"], target, width=im["width"], height=im["height"], high_quality=high_quality,
+                                          channels=channels)
+    raise ValueError(f"the file has no image at level {level}, layer {layer}, face {face}")

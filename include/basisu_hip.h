@@ -296,6 +296,17 @@ BU_HIP_API int  bu_hip_uastc_pipeline_submit(bu_uastc_pipeline*, const void* d_p
 BU_HIP_API int  bu_hip_uastc_pipeline_wait(bu_uastc_pipeline*, uint64_t ticket, uint32_t out_stats[4]);
 BU_HIP_API void bu_hip_uastc_pipeline_destroy(bu_uastc_pipeline*);
 
+/* basisu_lowlevel_uastc_ldr_4x4_transcoder::transcode_slice over resident blocks. target: the reference's
+ * transcoder_texture_format value; decode_flags: its cDecodeFlags* (only cDecodeFlagsHighQuality is read);
+ * channel0 / channel1: -1 = the reference's defaults (0, 3). row_pitch / rows: RGBA32 only, in pixels, 0 = orig size.
+ * Supported targets: cTFBC1_RGB (2), cTFBC3_RGBA (3), cTFBC4_R (4), cTFBC5_RG (5), cTFBC7_RGBA (6), cTFASTC_4x4_RGBA (10), cTFRGBA32 (13); any other fails.
+ * One launch on the context's stream; the call synchronises only to read the count of blocks that did not unpack, whose output is zero-filled
+ * (the reference stops at the first one). RGBA32 writes exactly orig_width x orig_height pixels (rows cut at `rows`): a padded pitch stays untouched. */
+BU_HIP_API int bu_hip_k_transcode_uastc(bu_hip_context*, const void* d_uastc_blocks, uint32_t num_blocks_x, uint32_t num_blocks_y,
+        uint32_t orig_width, uint32_t orig_height, uint32_t target, uint32_t decode_flags, int32_t channel0, int32_t channel1,
+        void* d_out, uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels, uint32_t* out_invalid_blocks);
+BU_HIP_API size_t bu_hip_transcode_output_bytes(uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height, uint32_t target);
+
 /* a15 + the list handling inside a9 / a10 / a13 / a14: cluster bookkeeping on the device (basis_universal_amd/csrc/bookkeeping_kernels.hip).
  *     A clustering is two resident per-block arrays, cluster index and position inside the cluster's list; these calls turn distinct-vector level
  *     results into them, rebuild them after a reassignment, apply codebook renumberings to them and produce the CSR lists the per-cluster
