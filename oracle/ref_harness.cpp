@@ -117,7 +117,8 @@ REF_API int ref_etc1_optimize(const uint8_t* rgba, uint32_t n, int quality, int 
 
 // What this build of the harness offers, for tests that need more than an older build carried over in oracle/_ref/ has:
 // 2 = ref_etc1_optimize_forced, the frontend call "compute_endpoint_subblock_error_vec" and the getter "subblock_endpoint_quant_err".
-REF_API int ref_harness_version() { return 2; }
+// 3 = ref_transcode_uastc: the per-block UASTC transcoders of every supported target over an array of blocks.
+REF_API int ref_harness_version() { return 3; }
 
 // The same with m_pForce_selectors (etc.cpp:780-784): one selector (0..3) per pixel; the reference refuses qualities below slow.
 REF_API int ref_etc1_optimize_forced(const uint8_t* rgba, uint32_t n, int quality, int perceptual, const uint8_t* force_selectors,
@@ -732,6 +733,37 @@ REF_API int ref_uastc_to_bc7_pixels(const uint8_t* blk16, uint8_t* out_bc7_16, u
 	basist::uastc_block b; memcpy(&b, blk16, 16);
 	if (!basist::transcode_uastc_to_bc7(b, out_bc7_16)) return 0;
 	return unpack_block(texture_format::cBC7, out_bc7_16, (color_rgba*)out_rgba64, false) ? 1 : 0;
+}
+// `n` 16-byte UASTC blocks through the reference's per-block transcoder of `target` (a transcoder_texture_format value: 2 BC1, 3 BC3, 4 BC4, 5 BC5, 6 BC7,
+// 10 ASTC 4x4, 13 RGBA32 = unpack_uastc with srgb off). ok[i] = what the reference returned; the output of a block it refused is left zeroed, whatever it
+// had written before it gave up. chan0 / chan1: BC4's channel, BC5's two. Returns the number of blocks refused, or -1 for a target this entry does not know.
+REF_API int ref_transcode_uastc(const uint8_t* blocks16, uint32_t n, uint32_t target, int high_quality, uint32_t chan0, uint32_t chan1, uint8_t* out, uint8_t* ok) {
+	uint32_t bytes;
+	switch (target) {
+	case 2: case 4: bytes = 8; break;
+	case 3: case 5: case 6: case 10: bytes = 16; break;
+	case 13: bytes = 64; break;
+	default: return -1;
+	}
+	const bool hq = high_quality != 0;
+	int refused = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		basist::uastc_block b; memcpy(&b, blocks16 + (size_t)i * 16, 16);
+		uint8_t tmp[64]; memset(tmp, 0, sizeof(tmp));
+		bool good = false;
+		switch (target) {
+		case 2: good = basist::transcode_uastc_to_bc1(b, tmp, hq); break;
+		case 3: good = basist::transcode_uastc_to_bc3(b, tmp, hq); break;
+		case 4: good = basist::transcode_uastc_to_bc4(b, tmp, hq, chan0); break;
+		case 5: good = basist::transcode_uastc_to_bc5(b, tmp, hq, chan0, chan1); break;
+		case 6: good = basist::transcode_uastc_to_bc7(b, tmp); break;
+		case 10: good = basist::transcode_uastc_to_astc(b, tmp); break;
+		default: good = basist::unpack_uastc(b, (basist::color32*)tmp, false); break;
+		}
+		if (good) memcpy(out + (size_t)i * bytes, tmp, bytes); else { memset(out + (size_t)i * bytes, 0, bytes); refused++; }
+		ok[i] = good ? 1 : 0;
+	}
+	return refused;
 }
 // basist::encode_bc1 (:18047) + unpack
 REF_API void ref_encode_bc1(const uint8_t* rgba64, uint32_t flags, uint8_t* out8, uint8_t* out_rgba64) {

@@ -196,6 +196,9 @@ def ref():
         if hasattr(L, "ref_etc1_optimize_forced"):   # harness version 2 (ref_harness_version)
             L.ref_etc1_optimize_forced.restype = C.c_int
             L.ref_etc1_optimize_forced.argtypes = [u8p, C.c_uint32, C.c_int, C.c_int, u8p, u8p, u32p, u64p]
+        if hasattr(L, "ref_transcode_uastc"):   # harness version 3
+            L.ref_transcode_uastc.restype = C.c_int
+            L.ref_transcode_uastc.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, u8p, u8p]
         L.ref_encode_etc1s_blocks.argtypes = [u8p, C.c_uint32, C.c_int, C.c_int, u8p]
         L.ref_determine_selectors.argtypes = [u8p, C.c_uint32, u8p, C.c_int, u8p]
         L.ref_color_distance.restype = C.c_uint32
@@ -587,6 +590,19 @@ def blocks_to_raster(texels, nbx, nby):
     """(n, 4, 4, C) block-raster texels -> (nby * 4, nbx * 4, C)"""
     c = texels.shape[-1]
     return texels.reshape(nby, nbx, 4, 4, c).transpose(0, 2, 1, 3, 4).reshape(nby * 4, nbx * 4, c)
+
+
+def ref_transcode_uastc(blocks, target, high_quality=False, channels=(0, 3)):
+    """The reference's per-block UASTC transcoder of `target` (a transcoder_texture_format value) over (n, 16) blocks, one call (harness version 3)
+    -> ((n, bytes per block) uint8 with refused blocks zeroed, what the reference returned per block (n,) uint8)"""
+    L = ref()
+    assert hasattr(L, "ref_transcode_uastc"), "oracle/_ref/libref_harness.so is older than harness version 3"
+    blocks = np.ascontiguousarray(blocks, np.uint8).reshape(-1, 16)
+    n = blocks.shape[0]
+    out, ok = np.zeros((n, {2: 8, 3: 16, 4: 8, 5: 16, 6: 16, 10: 16, 13: 64}[target]), np.uint8), np.zeros(n, np.uint8)
+    refused = L.ref_transcode_uastc(ptr(blocks), n, target, int(high_quality), channels[0], channels[1], ptr(out), ptr(ok))
+    assert refused == n - int(ok.sum())
+    return out, ok
 
 
 def ref_decode_uastc(packed):

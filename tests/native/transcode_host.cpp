@@ -64,4 +64,64 @@ uint32_t ht_bc1_hints(const uint8_t* blk) {
 
 uint32_t ht_mode(const uint8_t* blk) { cand c; return unpack_block(blk, c) ? c.mode : 255u; }
 
+// ht_mode / ht_bc1_hints over an array: modes[i] = 255 for a refused block
+void ht_modes_routes(const uint8_t* blocks, uint32_t n, uint8_t* modes, uint8_t* routes) {
+    for (uint32_t i = 0; i < n; i++) {
+        modes[i] = (uint8_t)ht_mode(blocks + (size_t)i * 16);
+        routes[i] = (uint8_t)ht_bc1_hints(blocks + (size_t)i * 16);
+    }
+}
+
+// Where the fields of a block of `mode` lie, from the tables unpack_block walks (bit offsets from bit 0 of byte 0; a width of 0 = the mode has no such field).
+// The test-side block generator (tests/transcode_helpers.py) writes fields through this, so it cannot drift from the unpacker's idea of the format.
+//   out[0] mode code, [1] its length          [2] hint0 present, [3] its offset, [4] hint1 present, [5] its offset
+//   [6] pattern offset, [7] width, [8] first pattern index that is out of range          [9] component selector offset, [10] width
+//   [11] radix of the packed endpoint digits (3 trits, 5 quints, 0 none), [12] number of packed groups, [13] offset of the first, [14..21] their widths
+//   [22] offset of the raw endpoint bits, [23] raw bits per endpoint value, [24] endpoint values, [25] values per packed group
+//   [26] weight field offset, [27] its length          [28] subsets, [29] components, [30] planes, [31] weight bits
+// Mode 8 (solid): [6] is the offset of the four colour bytes; every other field is 0.
+void ht_mode_layout(uint32_t mode, uint32_t* out) {
+    for (uint32_t i = 0; i < 32; i++) out[i] = 0;
+    if (mode >= 19) return;
+    out[0] = ku_mode_code[mode]; out[1] = ku_mode_code_len[mode];
+    uint32_t ofs = ku_mode_code_len[mode];
+    if (mode == 8) { out[6] = ofs; return; }
+    if (ku_mode_has_bc1_hint0[mode]) { out[2] = 1; out[3] = ofs; ofs++; }
+    if (ku_mode_has_bc1_hint1[mode]) { out[4] = 1; out[5] = ofs; }
+    ofs = ku_mode_code_len[mode] + hint_bits(mode);
+    const uint32_t subsets = ku_mode_subsets[mode], planes = ku_mode_planes[mode], comps = ku_mode_comps[mode];
+    if (subsets == 3) { out[6] = ofs; out[7] = 4; out[8] = 11; ofs += 4; }
+    else if (subsets == 2) { out[6] = ofs; out[7] = 5; out[8] = mode == 7 ? 19 : 30; ofs += 5; }
+    if (planes == 2 && mode != 17) { out[9] = ofs; out[10] = 2; ofs += 2; }
+    const uint32_t range = ku_mode_endpoint_ranges[mode], total_values = comps * 2 * subsets;
+    const uint32_t ep_bits = ku_bise[range * 3], ep_trits = ku_bise[range * 3 + 1], ep_quints = ku_bise[range * 3 + 2];
+    uint32_t groups = 0, per_group = 0;
+    if (ep_trits) { groups = (total_values + 4) / 5; per_group = 5; out[11] = 3; }
+    else if (ep_quints) { groups = (total_values + 2) / 3; per_group = 3; out[11] = 5; }
+    out[12] = groups; out[13] = ofs; out[25] = per_group;
+    for (uint32_t g = 0; g < groups; g++) {
+        uint32_t nb = ep_trits ? 8 : 7;
+        if (g == groups - 1) {
+            const uint32_t left = total_values - (groups - 1) * per_group;
+            if (ep_trits) nb = left == 1 ? 2 : (left == 2 ? 4 : (left == 3 ? 5 : (left == 4 ? 7 : 8)));
+            else nb = left == 1 ? 3 : (left == 2 ? 5 : 7);
+        }
+        out[14 + g] = nb;
+        ofs += nb;
+    }
+    out[22] = ofs; out[23] = ep_bits; out[24] = total_values;
+    ofs += ep_bits * total_values;
+    out[26] = ofs; out[27] = ku_sel_len[mode];
+    out[28] = subsets; out[29] = comps; out[30] = planes; out[31] = ku_mode_weight_bits[mode];
+}
+
+// what unpack_block made of a block: endpoints (18), weights (32), pattern, component selector; returns the mode, 255 for a refused block
+uint32_t ht_unpack(const uint8_t* blk, uint8_t* endpoints18, uint8_t* weights32, uint32_t* pattern, uint32_t* ccs) {
+    cand c;
+    if (!unpack_block(blk, c)) return 255u;
+    memcpy(endpoints18, c.endpoints, 18); memcpy(weights32, c.weights, 32);
+    *pattern = c.pattern; *ccs = c.ccs;
+    return c.mode;
+}
+
 }

@@ -1,7 +1,8 @@
 """-m gpu tests of the device-side UASTC LDR 4x4 transcoder (include/basisu_hip.h: bu_hip_k_transcode_uastc; basis_universal_amd/transcode.py) against the reference's
-known answers: tests/golden/uastc_transcode_vectors.npz and uastc_transcode_big_digests.json (tools/gen_golden_uastc_transcode.py ran oracle/_ref on the build
-machine). Where no golden exists (odd sizes, spliced invalid blocks) the expected values come from the g++ build of the same core, which
-tests/test_uastc_transcode_host.py holds to the reference."""
+known answers: on encoder output tests/golden/uastc_transcode_vectors.npz and uastc_transcode_big_digests.json, on arbitrary valid and invalid blocks no encoder
+writes tests/golden/uastc_transcode_fuzz.npz (tools/gen_golden_uastc_transcode.py ran oracle/_ref on the build machine for all three). Where no golden exists (odd
+sizes, spliced invalid blocks, a million random-bit blocks) the expected values come from the g++ build of the same core, which tests/test_uastc_transcode_host.py
+holds to the reference on encoder output, on the fuzz fixture and on fresh random blocks."""
 import hashlib
 import json
 import pathlib
@@ -167,3 +168,107 @@ def test_transcode_file_of_compress_output(hip_ctx, name):
             assert out.shape == ((lh, lw, 4) if target == transcode.RGBA32 else (((lw + 3) // 4) * ((lh + 3) // 4), transcode.BYTES_PER_BLOCK[target]))
     p = helpers.psnr(transcode.transcode_file(hip_ctx, data, transcode.RGBA32), img)
     assert abs(p - digests["uastc_psnr_rgba"]) < 1e-3, p
+
+
+# ---------------------------------------------------------------- blocks no encoder writes
+
+@pytest.fixture(scope="module")
+def fuzz():
+    return np.load(HERE / "golden" / "uastc_transcode_fuzz.npz")
+
+
+def _channels(target, ch):
+    """FUZZ_CASES' channel pair as transcode_uastc_blocks takes it"""
+    return (ch[0],) if target == transcode.BC4_R else (ch if target == transcode.BC5_RG else None)
+
+
+def _c_abi(hip_ctx, blocks, nbx, nby, target, hq, ch, width=0, height=0):
+    """bu_hip_k_transcode_uastc on (nby * nbx, 16) host blocks or a device pointer -> (what it wrote, its `invalid` out-parameter). The call succeeds whatever the blocks are."""
+    import ctypes as C
+    own = hip_ctx.upload(np.ascontiguousarray(blocks, np.uint8)) if isinstance(blocks, np.ndarray) else None
+    nbytes = hip_ctx.lib.transcode_output_bytes(nbx, nby, width, height, target)
+    assert nbytes == ((width or nbx * 4) * (height or nby * 4) * 4 if target == transcode.RGBA32 else nbx * nby * transcode.BYTES_PER_BLOCK[target])
+    d_out = hip_ctx.alloc(nbytes)
+    try:
+        invalid = C.c_uint32(0xFFFFFFFF)
+        c0, c1 = (ch[0], -1) if target == transcode.BC4_R else (ch if target == transcode.BC5_RG else (-1, -1))
+        hip_ctx.check(hip_ctx.lib.k_transcode_uastc(hip_ctx.h, C.c_void_p(own if own is not None else blocks), nbx, nby, width, height, target, 32 if hq else 0, c0, c1,
+                                                    C.c_void_p(d_out), 0, 0, C.byref(invalid)))
+        raw = hip_ctx.download(d_out, (nbytes,), np.uint8)
+    finally:
+        if own is not None:
+            hip_ctx.free(own)
+        hip_ctx.free(d_out)
+    if target == transcode.RGBA32:
+        return raw.reshape(height or nby * 4, width or nbx * 4, 4), invalid.value
+    return raw.reshape(nbx * nby, -1), invalid.value
+
+
+@pytest.mark.parametrize("name", sorted(T.FUZZ_CASES))
+def test_device_equals_reference_on_fuzz_families(hip_ctx, fuzz, name):
+    """Every family of the fuzz fixture, one launch each through the C ABI and one through transcode_uastc_blocks: blocks the reference accepts byte-equal, blocks it
+    refuses zero-filled, and both ways of reporting the invalid count equal to the fixture's."""
+    target, hq, ch = T.FUZZ_CASES[name]
+    for f, family in enumerate(T.FAMILIES):
+        pick = fuzz["family"] == f
+        blocks, exp, valid = np.ascontiguousarray(fuzz["blocks"][pick]), fuzz[name][pick], fuzz["valid"][pick]
+        n, bad = blocks.shape[0], int((valid == 0).sum())
+        assert n > 0
+        got, invalid = _c_abi(hip_ctx, blocks, n, 1, target, hq, ch)
+        T.assert_equals_reference(blocks, exp, valid, _as_blocks(got, target, n, 1), None, f"device, {name}, family {family}", fuzz["family"][pick])
+        assert invalid == bad, (name, family)
+        if bad:
+            with pytest.raises(transcode.InvalidBlocksError) as e:
+                transcode.transcode_uastc_blocks(hip_ctx, blocks, n, 1, target, high_quality=hq, channels=_channels(target, ch))
+            assert e.value.count == bad, (name, family)
+        else:
+            out = _as_blocks(transcode.transcode_uastc_blocks(hip_ctx, blocks, n, 1, target, high_quality=hq, channels=_channels(target, ch)), target, n, 1)
+            assert (out == exp).all(), (name, family)
+
+
+@pytest.mark.parametrize("name", sorted(T.FUZZ_CASES))
+def test_device_fuzz_blocks_on_ragged_grids(hip_ctx, fuzz, name):
+    """The whole fixture (valid and invalid blocks mixed) as grids whose block count is not a multiple of the 256-lane workgroup: one row, one column, a width that leaves a
+    ragged last workgroup, fewer blocks than one workgroup; RGBA32 also cropped so that the last column and row of tiles are cut."""
+    target, hq, ch = T.FUZZ_CASES[name]
+    total = fuzz["blocks"].shape[0]
+    assert total % 256 != 0
+    for nbx, nby in ((total, 1), (1, total), (37, total // 37), (9, 11), (1, 1)):
+        n = nbx * nby
+        assert n == 1 or n % 256 != 0
+        blocks, exp, valid = np.ascontiguousarray(fuzz["blocks"][:n]), fuzz[name][:n], fuzz["valid"][:n]
+        got, invalid = _c_abi(hip_ctx, blocks, nbx, nby, target, hq, ch)
+        T.assert_equals_reference(blocks, exp, valid, _as_blocks(got, target, nbx, nby), None, f"device, {name}, {nbx} x {nby} blocks", fuzz["family"][:n])
+        assert invalid == int((valid == 0).sum()), (name, nbx, nby)
+        if target == transcode.RGBA32:
+            for cut_w, cut_h in ((1, 3), (3, 1), (2, 0), (0, 2)):
+                w, h = nbx * 4 - cut_w, nby * 4 - cut_h
+                got, invalid = _c_abi(hip_ctx, blocks, nbx, nby, target, hq, ch, width=w, height=h)
+                assert got.shape == (h, w, 4) and (got == T.to_raster(exp.reshape(n, 4, 4, 4), nbx, nby, w, h)).all(), (nbx, nby, w, h)
+                assert invalid == int((valid == 0).sum())
+
+
+def test_device_equals_host_core_on_a_million_random_blocks(hip_ctx):
+    """1,048,576 random-bit blocks uploaded once and transcoded to every target from the resident buffer: the one full-size launch of blocks no encoder wrote. Output, zero
+    fill and invalid count against the g++ build of the core; a strided sample of 65,536 blocks also against the reference itself where oracle/_ref is there."""
+    n = 1 << 20
+    blocks = T.random_bit_blocks(n, 20261019)
+    sample = np.arange(0, n, 16)
+    with_ref = helpers.ref_harness_version() >= 3
+    d_blocks = hip_ctx.upload(blocks)
+    try:
+        for name, (target, hq, ch) in T.FUZZ_CASES.items():
+            got, invalid = _c_abi(hip_ctx, d_blocks, 1024, 1024, target, hq, ch)
+            got = _as_blocks(got, target, 1024, 1024)
+            exp, ok = T.host_transcode(blocks, target, hq, ch)
+            assert ok.mean() > 0.9
+            T.assert_equals_reference(blocks, exp, ok, got, None, f"device against the host core, {name}")
+            assert invalid == int((ok == 0).sum()), name
+            if with_ref:
+                ref_out, ref_ok = helpers.ref_transcode_uastc(blocks[sample], target, hq, ch)
+                T.assert_equals_reference(blocks[sample], ref_out, ref_ok, got[sample], None, f"device against the reference, {name}")
+            with pytest.raises(transcode.InvalidBlocksError) as e:
+                transcode.transcode_uastc_blocks(hip_ctx, d_blocks, 1024, 1024, target, high_quality=hq, channels=_channels(target, ch))
+            assert e.value.count == invalid, name
+    finally:
+        hip_ctx.free(d_blocks)

@@ -1,5 +1,8 @@
 """CPU tests of the UASTC LDR 4x4 transcode core (basis_universal_amd/csrc/uastc_transcode.h, compiled by g++ into tests/native/libtranscode_host.so) against the
-reference's known answers (tests/golden/uastc_transcode_vectors.npz, tools/gen_golden_uastc_transcode.py), and of the container reader (transcode.read_uastc_file)."""
+reference's known answers, on encoder output (tests/golden/uastc_transcode_vectors.npz) and on arbitrary valid and invalid blocks no encoder writes
+(tests/golden/uastc_transcode_fuzz.npz: the block families of transcode_helpers.fuzz_families; live, 200,000 random-bit blocks per target where oracle/_ref is built).
+Both fixtures come from tools/gen_golden_uastc_transcode.py. Also the container reader (transcode.read_uastc_file)."""
+import json
 import pathlib
 import struct
 
@@ -79,20 +82,118 @@ def test_channel_plumbing(golden):
         assert (bc5[:, :8] == bc4[1]).all() and (bc5[:, 8:] == bc4[2]).all()
 
 
+# ---------------------------------------------------------------- blocks no encoder writes
+
+needs_harness3 = pytest.mark.skipif(helpers.ref_harness_version() < 3, reason="oracle/_ref/libref_harness.so with ref_transcode_uastc (harness version 3) not present")
+
+
+@pytest.fixture(scope="module")
+def fuzz():
+    return np.load(GOLDEN / "uastc_transcode_fuzz.npz")
+
+
+def test_mode_layout_agrees_with_the_unpacker():
+    """The field layout the generator writes through: the weight field is where the RDO pass's table has it, every field lies inside the block, and endpoint values,
+    pattern and component selector written through the layout are what unpack_block reads back."""
+    first = [65, 69, 73, 89, 89, 68, 66, 89, 0, 97, 65, 66, 81, 94, 92, 62, 98, 61, 49]   # g_uastc_mode_selector_bits' first bit per mode
+    rng = T._Bits(5)
+    for lay in T.layouts():
+        if lay.mode == 8:
+            continue
+        assert lay.weight_ofs == first[lay.mode] and lay.weight_ofs + lay.weight_len <= 128
+        assert lay.ep_ofs + lay.ep_bits * lay.ep_values == lay.weight_ofs
+        for _ in range(16):
+            values = [rng.below(lay.levels) for _ in range(lay.ep_values)]
+            v = T._put_endpoints(T._random_in_mode(rng, lay), lay, values)
+            pattern, ccs = T._get(v, lay.pattern_ofs, lay.pattern_bits), T._get(v, lay.ccs_ofs, lay.ccs_bits)
+            mode, ep, _w, got_pattern, got_ccs = T.unpacked_fields(T._to_blocks([v])[0])
+            assert mode == lay.mode and ep[:lay.ep_values].tolist() == values and got_pattern == pattern
+            assert got_ccs == (3 if lay.mode == 17 else ccs)
+
+
+def test_fuzz_generator_reproduces_the_fixture(fuzz):
+    """The committed blocks are what the generator makes today: a change to it cannot silently detach the tests from the fixture."""
+    fam, cause, _drawn = T.fuzz_families()
+    meta = json.loads(bytes(fuzz["meta"]))
+    assert (meta["seed"], meta["quota"], tuple(meta["families"]), tuple(meta["invalid_causes"])) == (T.FUZZ_SEED, T.FUZZ_QUOTA, T.FAMILIES, T.INVALID_CAUSES)
+    for i, name in enumerate(T.FAMILIES):
+        got, want = fam[name], fuzz["blocks"][fuzz["family"] == i]
+        assert got.shape == want.shape and (got == want).all(), f"family {name}: the generator no longer writes the fixture's blocks (rerun tools/gen_golden_uastc_transcode.py fuzz)"
+    assert (cause == fuzz["invalid_cause"]).all()
+    assert sorted(fuzz.files) == sorted(["blocks", "family", "invalid_cause", "valid", "meta"] + list(T.FUZZ_CASES))
+
+
+def test_fuzz_fixture_coverage(fuzz):
+    """Among the blocks the reference accepts: every mode at least the quota of times, each BC1 route (hint0, hint1 only, neither) at least 100 times among non-solid blocks,
+    a trit / quint group at or past its radix in every mode that has such groups; and the invalid family has blocks of each of its four causes, all refused."""
+    blocks, family, valid = fuzz["blocks"], fuzz["family"], fuzz["valid"]
+    per_mode, routes = T.check_fuzz_coverage(blocks, family, valid, fuzz["invalid_cause"], T.FUZZ_QUOTA)
+    meta = json.loads(bytes(fuzz["meta"]))
+    assert per_mode.tolist() == meta["valid_per_mode"] and list(routes) == meta["bc1_routes_hint0_hint1_neither"]
+    names = np.array(T.FAMILIES)[family]
+    assert not valid[(names == "random_invalid") | (names == "invalid")].any()
+    assert valid[~((names == "random_invalid") | (names == "invalid"))].all()
+    assert all((names == f).any() for f in T.FAMILIES)
+    # the families are what their names say
+    hints = T.layout_hints(blocks[names == "hints"])
+    assert all((hints == h).sum() >= 100 for h in range(4))
+    assert T.bise_overflow_mask(blocks[names == "bise_overflow"]).all()
+    solid = blocks[names == "solid"]
+    assert (T.code_modes(solid) == 8).all() and (solid[:, 5:] != 0).any(axis=1).sum() > solid.shape[0] // 2   # junk after the colour (bits 5..36): in the bytes past it
+    # the mode-8 colours include 0 and 255 in every channel
+    colours = T.host_transcode(solid, T.RGBA32)[0][:, 0, 0, :]
+    assert all((colours[:, c] == 0).any() and (colours[:, c] == 255).any() for c in range(4))
+
+
+@pytest.mark.parametrize("name", sorted(T.FUZZ_CASES))
+def test_host_core_equals_reference_on_fuzz_families(fuzz, name):
+    target, hq, ch = T.FUZZ_CASES[name]
+    out, ok = T.host_transcode(fuzz["blocks"], target, hq, ch)
+    T.assert_equals_reference(fuzz["blocks"], fuzz[name], fuzz["valid"], out, ok, f"host core, {name}", fuzz["family"])
+
+
+LIVE_BLOCKS, LIVE_BATCH = 200000, 50000
+
+
+@pytest.mark.ref
+@needs_harness3
+@pytest.mark.parametrize("name", sorted(T.FUZZ_CASES))
+def test_random_blocks_every_target_against_reference(name):
+    """200,000 fresh random-bit blocks per target, in batches, through the reference's per-block transcoders: validity and bytes equal, refused blocks zero on both
+    sides, no block left out. At least 90 % of the blocks drawn must be valid according to the reference (96.3 % measured with the core)."""
+    target, hq, ch = T.FUZZ_CASES[name]
+    rng = T._Bits(20261018)
+    compared = valid = 0
+    while compared < LIVE_BLOCKS:
+        blocks = rng.blocks(LIVE_BATCH)
+        exp, exp_ok = helpers.ref_transcode_uastc(blocks, target, hq, ch)
+        out, ok = T.host_transcode(blocks, target, hq, ch)
+        T.assert_equals_reference(blocks, exp, exp_ok, out, ok, f"host core against the live reference, {name}, blocks {compared}..")
+        compared += blocks.shape[0]
+        valid += int(exp_ok.sum())
+    print(f"{name}: {compared} random-bit blocks compared with the reference, none excluded; {valid} ({100.0 * valid / compared:.2f} %) valid, {compared - valid} refused by both")
+    assert compared >= 200000 and valid >= 0.9 * compared, (compared, valid)
+
+
 @pytest.mark.ref
 def test_random_blocks_validity_and_bc7_against_reference():
-    """20,000 random-bit blocks that unpack as valid: BC7 bytes equal the reference's; and on every random block drawn the core agrees with the reference on validity."""
+    """20,000 random-bit blocks that unpack as valid: BC7 bytes equal the reference's; and on every random block drawn the core agrees with the reference on validity.
+    Runs on any build of the harness: the batched ref_transcode_uastc where it is there (version 3), the per-block entries of the older builds otherwise."""
     import ctypes as C
     L = helpers.ref()
     L.ref_unpack_uastc.restype = C.c_int
     L.ref_unpack_uastc.argtypes = [helpers.u8p, helpers.u8p]
     L.ref_uastc_to_bc7_pixels.restype = C.c_int
     L.ref_uastc_to_bc7_pixels.argtypes = [helpers.u8p, helpers.u8p, helpers.u8p]
+    batched = hasattr(L, "ref_transcode_uastc")
     rng = np.random.default_rng(20261016)
     valid_seen, invalid_seen, tmp, px = 0, 0, np.zeros(64, np.uint8), np.zeros(64, np.uint8)
     while valid_seen < 20000:
         blocks = rng.integers(0, 256, (8192, 16), dtype=np.uint8)
-        ref_ok = np.array([L.ref_unpack_uastc(helpers.ptr(blocks[i]), helpers.ptr(tmp)) for i in range(blocks.shape[0])], np.uint8)
+        if batched:
+            ref_ok = helpers.ref_transcode_uastc(blocks, T.RGBA32)[1]   # unpack_uastc
+        else:
+            ref_ok = np.array([L.ref_unpack_uastc(helpers.ptr(blocks[i]), helpers.ptr(tmp)) for i in range(blocks.shape[0])], np.uint8)
         bc7, ok = T.host_transcode(blocks, T.BC7)
         assert (ok == ref_ok).all(), "validity differs from unpack_uastc's"
         for t in (T.RGBA32, T.ASTC, T.BC1, T.BC5):
@@ -100,6 +201,9 @@ def test_random_blocks_validity_and_bc7_against_reference():
         exp = np.zeros((blocks.shape[0], 16), np.uint8)
         for i in np.flatnonzero(ref_ok):
             assert L.ref_uastc_to_bc7_pixels(helpers.ptr(blocks[i]), helpers.ptr(exp[i]), helpers.ptr(px)) in (0, 1)   # the BC7 bytes are written before the unpack
+        if batched:   # the batched entry refuses what unpack_uastc refuses and writes what the single-block one does
+            out, out_ok = helpers.ref_transcode_uastc(blocks, T.BC7)
+            assert (out_ok == ref_ok).all() and (out == exp).all()
         assert (bc7 == exp).all()
         assert (bc7[ref_ok == 0] == 0).all()
         valid_seen += int(ref_ok.sum())

@@ -7,7 +7,10 @@
 How: the blocks are wrapped into a .ktx2 with this package's own writer (backend.uastc_ktx2_file, host code), `basisu -unpack -ktx_only` (and again with
 -higher_quality_transcoding) transcodes it, and the raw blocks are read back out of the .ktx files it writes (68 bytes of KTX1 header + imageSize, then the
 blocks in raster order). RGBA32 is not written under -ktx_only: it comes from the harness's unpack_uastc. The tool's BC4 is channel 0 and its BC5 channels 0 and 3.
-usage: gen_golden_uastc_transcode.py [vectors] [big]   (default: both; `big` spends about a minute encoding with the reference)"""
+  tests/golden/uastc_transcode_fuzz.npz         blocks no encoder writes (transcode_helpers.fuzz_families: random bits stratified by mode, every BC1 hint setting,
+                                                trit / quint groups past their radix, degenerate endpoints, solid blocks with junk after the colour, invalid blocks)
+                                                with the reference's validity flag and output for every target, from the harness's ref_transcode_uastc (version 3)
+usage: gen_golden_uastc_transcode.py [vectors] [big] [fuzz]   (default: vectors and big; `big` spends about a minute encoding with the reference)"""
 import hashlib
 import json
 import pathlib
@@ -107,9 +110,44 @@ def gen_big():
     print("wrote", p)
 
 
+def gen_fuzz():
+    assert helpers.ref_harness_version() >= 3, "oracle/_ref/libref_harness.so has no ref_transcode_uastc: rebuild it (make -C oracle ref)"
+    fam, cause, drawn = T.fuzz_families()
+    blocks = np.concatenate([fam[k] for k in T.FAMILIES])
+    family = np.concatenate([np.full(fam[k].shape[0], i, np.uint8) for i, k in enumerate(T.FAMILIES)])
+    arrays = {"blocks": blocks, "family": family, "invalid_cause": cause}
+    for name, (target, hq, ch) in T.FUZZ_CASES.items():
+        out, ok = helpers.ref_transcode_uastc(blocks, target, hq, ch)
+        if "valid" in arrays:
+            assert (ok == arrays["valid"]).all(), f"the reference's {name} transcoder refuses other blocks than its unpack_uastc"
+        else:
+            arrays["valid"] = ok
+        assert (out[ok == 0] == 0).all()
+        arrays[name] = out
+    valid = arrays["valid"]
+    per_mode, routes = T.check_fuzz_coverage(blocks, family, valid, cause, T.FUZZ_QUOTA)
+    # the reference's own view of the uniformly random draw the `random` families come from
+    drawn_blocks = T.random_bit_blocks(((drawn + 1023) // 1024) * 1024, T.FUZZ_SEED)[:drawn]
+    drawn_ok = helpers.ref_transcode_uastc(drawn_blocks, T.RGBA32)[1] != 0
+    drawn_modes = np.bincount(T.code_modes(drawn_blocks)[drawn_ok], minlength=19)[:19]
+    assert int((~drawn_ok).sum()) == fam["random_invalid"].shape[0]
+    meta = {"seed": T.FUZZ_SEED, "quota": T.FUZZ_QUOTA, "families": list(T.FAMILIES), "invalid_causes": list(T.INVALID_CAUSES), "blocks": int(blocks.shape[0]),
+            "valid_by_reference": int(valid.sum()), "valid_per_mode": per_mode.tolist(), "bc1_routes_hint0_hint1_neither": list(routes),
+            "random_drawn": int(drawn), "random_drawn_valid_by_reference": int(drawn_ok.sum()), "random_drawn_valid_per_mode": drawn_modes.tolist()}
+    arrays["meta"] = np.frombuffer(json.dumps(meta, sort_keys=True).encode(), np.uint8)
+    p = GOLDEN / "uastc_transcode_fuzz.npz"
+    helpers_save(p, arrays)
+    assert p.stat().st_size <= 1 << 20, p.stat().st_size
+    print("wrote", p, p.stat().st_size, "bytes")
+    print(json.dumps(meta, indent=1, sort_keys=True))
+    print(f"uniformly random draw: {drawn} blocks, {100.0 * drawn_ok.mean():.2f} % valid according to the reference")
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["vectors", "big"]
     if "vectors" in what:
         gen_vectors()
     if "big" in what:
         gen_big()
+    if "fuzz" in what:
+        gen_fuzz()
