@@ -1,0 +1,320 @@
+// api_uastc.cpp -- UASTC behind the C ABI of libbasisu_hip.so (rows a16-a19): encode (device-resident and blocking), transcode, RDO, the pipeline of images in flight.
+#include "api_internal.h"
+#include "uastc_kernels.h"
+#include "uastc_transcode_kernels.h"
+
+// ---------------------------------------------------------------- UASTC (+ RDO) over a stream of images: several in flight (BASELINE configs[4])
+//
+// uastc_rdo's walk is a serial chain per strip (uastc_enc.cpp:3824-4100): one workgroup per strip, ~3 us per block, so the strips of one batch of images occupy a
+// fraction of the chip for ~20 ms whatever the batch holds (96 strips of the Kodak batch: 96 of 256 CUs). Nothing in one batch can fill the rest -- the next batch can:
+// its encode / prepare kernels (and the previous batch's finish) run on the idle CUs while this batch's strips walk. The pipeline owns `lanes` private contexts (stream +
+// workspaces each); a submission is ENQUEUED on the next lane without any host synchronisation -- the finish kernel is launched for the longest list a strip can have
+// instead of waiting for the walk to learn the real one -- and completes behind an event. Results are those of bu_hip_k_encode_uastc_blocks + bu_hip_k_uastc_rdo.
+struct bu_uastc_pipeline {
+    struct lane { bu_hip_context* ctx = nullptr; hipEvent_t done = nullptr, input = nullptr; uint32_t* stats = nullptr; bool busy = false, with_rdo = false; uint64_t ticket = 0; uint32_t strips = 0; };
+    bu_hip_context* parent = nullptr;
+    std::vector<lane> lanes;
+    uint64_t next_ticket = 1;
+};
+
+extern "C" {
+// ---------------------------------------------------------------- UASTC (rows a16-a19)
+
+size_t bu_hip_uastc_workspace_bytes(uint32_t n_blocks, uint32_t flags) { return bu::uastc_workspace_bytes(n_blocks, flags); }
+
+int bu_hip_k_encode_uastc_blocks(bu_hip_context* ctx, const void* d_px, uint32_t n_blocks, uint32_t flags, void* d_out) {
+    if (!ctx) return 0;
+    if (!d_px || !d_out) { set_error(ctx, "encode_uastc: null device pointer"); return 0; }
+    device_guard g(ctx->device);
+    arena& ws = ctx->scratch[5];
+    BU_TRY(ctx, ws.reserve(bu::uastc_workspace_bytes(n_blocks, flags)));
+    static const char* const names[4] = { "uastc_classify", "uastc_candidates", "uastc_score", "uastc_finish" };
+    for (int phase = 0; phase < 4; phase++) {
+        prof_scope ps(ctx, names[phase]);
+        BU_TRY(ctx, bu::launch_uastc_phase(ctx->stream, phase, d_px, n_blocks, flags, ws.p, d_out));
+    }
+    return 1;
+}
+
+int bu_hip_encode_uastc_blocks(bu_hip_context* ctx, bu_uastc_block* out, uint32_t flags) {
+    if (!ctx || !ctx->d_pixel_blocks) { if (ctx) set_error(ctx, "no pixel blocks set"); return 0; }
+    device_guard g(ctx->device);
+    const uint32_t n = (uint32_t)ctx->total_blocks;
+    arena& o = ctx->scratch[0];
+    BU_TRY(ctx, o.reserve((size_t)n * 16));
+    if (!bu_hip_k_encode_uastc_blocks(ctx, ctx->d_pixel_blocks, n, flags, o.p)) return 0;
+    if (!fetch(ctx, out, o.p, (size_t)n * 16)) return 0;
+    return 1;
+}
+
+// ---------------------------------------------------------------- UASTC transcode (uastc_transcode_kernels.hip)
+
+size_t bu_hip_transcode_output_bytes(uint32_t nbx, uint32_t nby, uint32_t orig_width, uint32_t orig_height, uint32_t target) {
+    return bu::transcode_output_bytes(nbx, nby, orig_width, orig_height, target);
+}
+
+int bu_hip_k_transcode_uastc(bu_hip_context* ctx, const void* d_blocks, uint32_t nbx, uint32_t nby, uint32_t orig_width, uint32_t orig_height, uint32_t target,
+                             uint32_t decode_flags, int32_t channel0, int32_t channel1, void* d_out, uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels,
+                             uint32_t* out_invalid_blocks) {
+    if (!ctx) return 0;
+    if (out_invalid_blocks) *out_invalid_blocks = 0;
+    if (!bu::transcode_output_bytes(1, 1, 0, 0, target)) { set_error(ctx, "transcode_uastc: target %u is not supported (RGBA32, ASTC 4x4, BC1, BC3, BC4, BC5, BC7 are)", target); return 0; }
+    if (!d_blocks || !d_out) { set_error(ctx, "transcode_uastc: null device pointer"); return 0; }
+    if ((uint64_t)nbx * nby > 0x7FFFFFFFull) { set_error(ctx, "transcode_uastc: %u x %u blocks is too many", nbx, nby); return 0; }
+    const uint32_t width = orig_width ? orig_width : nbx * 4, height = orig_height ? orig_height : nby * 4;
+    if (width > nbx * 4 || height > nby * 4) { set_error(ctx, "transcode_uastc: %u x %u pixels do not fit %u x %u blocks", width, height, nbx, nby); return 0; }
+    const uint32_t pitch = out_row_pitch_pixels ? out_row_pitch_pixels : width, rows = out_rows_pixels ? out_rows_pixels : height;
+    if (pitch < width) { set_error(ctx, "transcode_uastc: row pitch %u is less than the width %u", pitch, width); return 0; }
+    if (channel0 > 3 || channel1 > 3) { set_error(ctx, "transcode_uastc: channel out of range"); return 0; }
+    device_guard g(ctx->device);
+    arena& counter = ctx->scratch[4];
+    BU_TRY(ctx, counter.reserve(sizeof(uint32_t)));
+    {
+        prof_scope ps(ctx, "uastc_transcode");
+        BU_TRY(ctx, bu::launch_transcode_uastc(ctx->stream, d_blocks, nbx, nby, width, height, target, (decode_flags & 32u) != 0 /* cDecodeFlagsHighQuality */,
+                                               channel0 < 0 ? 0u : (uint32_t)channel0, channel1 < 0 ? 3u : (uint32_t)channel1, d_out, pitch, rows, static_cast<uint32_t*>(counter.p)));
+    }
+    uint32_t invalid = 0;
+    BU_TRY(ctx, d2h_pageable(ctx, &invalid, counter.p, sizeof(invalid)));
+    BU_TRY(ctx, stream_wait(ctx, ctx->stream));
+    if (out_invalid_blocks) *out_invalid_blocks = invalid;
+    return 1;
+}
+
+void bu_hip_uastc_rdo_default_params(bu_uastc_rdo_params* p) {
+    if (!p) return;
+    p->m_lz_dict_size = 4096; p->m_lambda = 0.5f; p->m_max_allowed_rms_increase_ratio = 10.0f; p->m_skip_block_rms_thresh = 8.0f;
+    p->m_endpoint_refinement = 1; p->m_lz_literal_cost = 100; p->m_max_smooth_block_std_dev = 18.0f; p->m_smooth_block_max_error_scale = 10.0f;
+}
+
+// The strip walks of uastc_rdo behind its prepare pass: the lean build (strips without a block of a sensitive mode: four waves per SIMD) on the context's stream and,
+// when endpoint refinement is on, the build with the refit in it (the flagged strips) on the side stream beside it -- forked and joined with events, nobody waits on
+// the host. Without a side stream the two launches simply follow each other.
+static int uastc_rdo_walks(bu_hip_context* ctx, void* d_blocks, const void* d_px, uint32_t n_blocks, const float* fp, const uint32_t* up, uint32_t flags, uint32_t total_jobs, void* ws) {
+    const bool refit = up[2] != 0;
+    if (ctx->walk_stream) {
+        // a pipeline lane with reserved walk CUs: both builds of the walk on streams of their own whose CU masks are the reserved set, forked off and joined back to the
+        // lane's stream (which may not use those CUs): the walks' waves never wait for a slot behind a chip-filling kernel, and never share a SIMD with one
+        BU_TRY(ctx, hipEventRecord(ctx->side_fork, ctx->stream));
+        BU_TRY(ctx, hipStreamWaitEvent(ctx->walk_stream, ctx->side_fork, 0));
+        BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->walk_stream, 1, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws));
+        BU_TRY(ctx, hipEventRecord(ctx->walk_join, ctx->walk_stream));
+        if (refit) {
+            BU_TRY(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->side_fork, 0));
+            BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->side_stream, 3, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws));
+            BU_TRY(ctx, hipEventRecord(ctx->side_join, ctx->side_stream));
+            BU_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_join, 0));
+        }
+        BU_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->walk_join, 0));
+        return 1;
+    }
+    const bool side = refit && ensure_side_stream(ctx);
+    if (side) {
+        BU_TRY(ctx, hipEventRecord(ctx->side_fork, ctx->stream));
+        BU_TRY(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->side_fork, 0));
+        BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->side_stream, 3, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws));
+        BU_TRY(ctx, hipEventRecord(ctx->side_join, ctx->side_stream));
+    }
+    BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->stream, 1, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws));
+    if (side) BU_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_join, 0));
+    else if (refit) BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->stream, 3, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws));
+    return 1;
+}
+
+int bu_hip_k_uastc_rdo(bu_hip_context* ctx, void* d_blocks, const void* d_px, uint32_t n_blocks, const bu_uastc_rdo_params* params, uint32_t flags,
+                       uint32_t total_jobs, uint32_t out_stats[4]) {
+    if (!ctx) return 0;
+    if (!d_blocks || !d_px || !params) { set_error(ctx, "uastc_rdo: null pointer"); return 0; }
+    // uastc_rdo's asserts (uastc_enc.cpp:4097-4099) as errors
+    if (!(params->m_max_allowed_rms_increase_ratio > 1.0f) || !params->m_lz_dict_size || !(params->m_lambda > 0.0f)) {
+        set_error(ctx, "uastc_rdo: need max_allowed_rms_increase_ratio > 1, lz_dict_size > 0, lambda > 0");
+        return 0;
+    }
+    device_guard g(ctx->device);
+    if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = 0, out_stats[3] = bu::uastc_rdo_strips(n_blocks, total_jobs);
+    if (!n_blocks) return 1;
+    const float fp[5] = { params->m_lambda, params->m_max_allowed_rms_increase_ratio, params->m_skip_block_rms_thresh, params->m_max_smooth_block_std_dev,
+                          params->m_smooth_block_max_error_scale };
+    const uint32_t up[3] = { params->m_lz_dict_size, params->m_lz_literal_cost, params->m_endpoint_refinement };
+    arena& ws = ctx->scratch[5];
+    BU_TRY(ctx, ws.reserve(bu::uastc_rdo_workspace_bytes(n_blocks, total_jobs)));
+    {
+        prof_scope ps(ctx, "uastc_rdo_prepare");
+        BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->stream, 0, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p));
+    }
+    {
+        prof_scope ps(ctx, "uastc_rdo_strips");   // both walks: the scope ends behind the join
+        if (!uastc_rdo_walks(ctx, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p)) return 0;
+    }
+    // how many blocks each strip modified: sizes the finish launch (a 16-byte copy per 4 strips; the walk has to be over anyway)
+    std::vector<uint32_t> per_strip(bu::uastc_rdo_strips(n_blocks, total_jobs));
+    if (!fetch(ctx, per_strip.data(), bu::uastc_rdo_strip_counts(ws.p, n_blocks, total_jobs), per_strip.size() * 4)) return 0;
+    uint32_t longest = 0;
+    for (uint32_t c : per_strip) longest = c > longest ? c : longest;
+    {
+        prof_scope ps(ctx, "uastc_rdo_finish");
+        BU_TRY(ctx, bu::launch_uastc_rdo_finish(ctx->stream, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p, longest));
+    }
+    uint32_t counters[4] = { 0, 0, 0, 0 };
+    if (!fetch(ctx, counters, bu::uastc_rdo_counters(ws.p, n_blocks, total_jobs), sizeof(counters))) return 0;
+#ifdef RDO_PROFILE
+    {
+        unsigned long long prof[16];
+        hipMemcpy(prof, static_cast<const char*>(bu::uastc_rdo_counters(ws.p, n_blocks, total_jobs)) + 64, sizeof(prof), hipMemcpyDeviceToHost);
+        fprintf(stderr, "rdo strip 0 cycles by phase:");
+        for (int k = 0; k < 16; k++) fprintf(stderr, " %llu", prof[k]);
+        fprintf(stderr, "\n");
+    }
+#endif
+    if (counters[1]) { set_error(ctx, "uastc_rdo: a block does not unpack as UASTC"); return 0; }
+    if (out_stats) { out_stats[0] = counters[0]; out_stats[1] = counters[2]; out_stats[2] = counters[3]; }
+    return 1;
+}
+
+static int uastc_rdo_enqueue(bu_hip_context* ctx, void* d_blocks, const void* d_px, uint32_t n_blocks, const bu_uastc_rdo_params* params, uint32_t flags, uint32_t total_jobs,
+                             uint32_t* h_pinned_counters) {
+    if (!(params->m_max_allowed_rms_increase_ratio > 1.0f) || !params->m_lz_dict_size || !(params->m_lambda > 0.0f)) {
+        set_error(ctx, "uastc_rdo: need max_allowed_rms_increase_ratio > 1, lz_dict_size > 0, lambda > 0");
+        return 0;
+    }
+    const float fp[5] = { params->m_lambda, params->m_max_allowed_rms_increase_ratio, params->m_skip_block_rms_thresh, params->m_max_smooth_block_std_dev,
+                          params->m_smooth_block_max_error_scale };
+    const uint32_t up[3] = { params->m_lz_dict_size, params->m_lz_literal_cost, params->m_endpoint_refinement };
+    arena& ws = ctx->scratch[5];
+    BU_TRY(ctx, ws.reserve(bu::uastc_rdo_workspace_bytes(n_blocks, total_jobs)));
+    BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->stream, 0, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p));
+    if (!uastc_rdo_walks(ctx, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p)) return 0;
+    // the longest list a strip can have (every block of it modified): the launch does not wait for the walk to know better, surplus workgroups leave at once
+    const uint32_t strips = bu::uastc_rdo_strips(n_blocks, total_jobs);
+    const uint32_t longest = strips > 1 ? (total_jobs ? n_blocks / total_jobs : n_blocks) : n_blocks;
+    BU_TRY(ctx, bu::launch_uastc_rdo_finish(ctx->stream, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p, longest));
+    BU_TRY(ctx, hipMemcpyAsync(h_pinned_counters, bu::uastc_rdo_counters(ws.p, n_blocks, total_jobs), 16, hipMemcpyDeviceToHost, ctx->stream));
+    return 1;
+}
+
+bu_uastc_pipeline* bu_hip_uastc_pipeline_create(bu_hip_context* ctx, uint32_t lanes, uint32_t max_blocks, uint32_t flags, uint32_t max_total_jobs) {
+    if (!ctx) return nullptr;
+    if (lanes < 1 || lanes > 8 || !max_blocks) { set_error(ctx, "uastc_pipeline_create: 1..8 lanes, max_blocks > 0"); return nullptr; }
+    device_guard g(ctx->device);
+    bu_uastc_pipeline* p = new (std::nothrow) bu_uastc_pipeline();
+    if (!p) return nullptr;
+    p->parent = ctx;
+    p->lanes.resize(lanes);
+    // every workspace at its final size now: growing one later would free it under the kernels of an earlier submission
+    const size_t ws_bytes = std::max(bu::uastc_workspace_bytes(max_blocks, flags), bu::uastc_rdo_workspace_bytes(max_blocks, max_total_jobs));
+    for (auto& l : p->lanes) {
+        l.ctx = create_context_kind(ctx->device, true);
+        if (l.ctx) {
+            l.ctx->tuning = ctx->tuning;   // the lanes take the paths their parent context is set to
+            // The runtime maps ordinary streams onto its few shared hardware queues (GPU_MAX_HW_QUEUES) by how many streams each queue already carries -- history, as far
+            // as a library can tell -- and two lanes whose streams share a queue run one after the other. A stream with a CU mask gets a hardware queue of its OWN: the
+            // lanes' streams are made with one that enables every CU.
+            const uint32_t walk_cus = ctx->tuning.uastc_walk_cus;
+            if (!l.ctx->dedicated_queue || l.ctx->walk_cus != walk_cus) {
+                hipStream_t fresh = make_dedicated_stream(l.ctx->device, walk_cus, false);
+                if (fresh) {
+                    (void)hipStreamSynchronize(l.ctx->own_stream);
+                    const bool own = l.ctx->stream == l.ctx->own_stream;
+                    (void)hipStreamDestroy(l.ctx->own_stream);
+                    l.ctx->own_stream = fresh; l.ctx->dedicated_queue = true;
+                    if (own) l.ctx->stream = fresh;
+                    // the walks' streams: on the reserved CUs (or gone, when nothing is reserved)
+                    if (l.ctx->walk_stream) { (void)hipStreamSynchronize(l.ctx->walk_stream); (void)hipStreamDestroy(l.ctx->walk_stream); l.ctx->walk_stream = nullptr; }
+                    if (l.ctx->side_stream) { (void)hipStreamSynchronize(l.ctx->side_stream); (void)hipStreamDestroy(l.ctx->side_stream); l.ctx->side_stream = nullptr; }
+                    l.ctx->walk_cus = 0;
+                    if (walk_cus) {
+                        l.ctx->walk_stream = make_dedicated_stream(l.ctx->device, walk_cus, true);
+                        l.ctx->side_stream = make_dedicated_stream(l.ctx->device, walk_cus, true);
+                        bool ok = l.ctx->walk_stream && l.ctx->side_stream;
+                        if (ok && !l.ctx->walk_join) ok = hipEventCreateWithFlags(&l.ctx->walk_join, hipEventDisableTiming) == hipSuccess;
+                        if (ok && !l.ctx->side_fork) ok = hipEventCreateWithFlags(&l.ctx->side_fork, hipEventDisableTiming) == hipSuccess;
+                        if (ok && !l.ctx->side_join) ok = hipEventCreateWithFlags(&l.ctx->side_join, hipEventDisableTiming) == hipSuccess;
+                        if (ok) l.ctx->walk_cus = walk_cus;
+                        else {   // fall back to the unreserved form rather than fail: the lane's own stream keeps its (restricted) mask, the walks share it
+                            (void)hipGetLastError();
+                            if (l.ctx->walk_stream) { (void)hipStreamDestroy(l.ctx->walk_stream); l.ctx->walk_stream = nullptr; }
+                            if (l.ctx->side_stream) { (void)hipStreamDestroy(l.ctx->side_stream); l.ctx->side_stream = nullptr; }
+                        }
+                    }
+                }
+            }
+        }
+        if (!l.ctx || hipEventCreateWithFlags(&l.done, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&l.input, hipEventDisableTiming) != hipSuccess ||
+            hipHostMalloc(reinterpret_cast<void**>(&l.stats), 64, hipHostMallocDefault) != hipSuccess || l.ctx->scratch[5].reserve(ws_bytes) != hipSuccess) {
+            set_error(ctx, "uastc_pipeline_create: lane set-up failed (%s)", l.ctx ? bu_hip_last_error(l.ctx) : "no context");
+            bu_hip_uastc_pipeline_destroy(p);
+            return nullptr;
+        }
+    }
+    return p;
+}
+
+static int uastc_pipeline_collect(bu_uastc_pipeline* p, bu_uastc_pipeline::lane& l, uint32_t out_stats[4]) {
+    if (!l.busy) return 1;
+    if (hipEventSynchronize(l.done) != hipSuccess) { set_error(p->parent, "uastc_pipeline: a submission failed on the device"); l.busy = false; return 0; }
+    l.busy = false;
+    if (out_stats) { out_stats[0] = l.with_rdo ? l.stats[0] : 0; out_stats[1] = l.with_rdo ? l.stats[2] : 0; out_stats[2] = l.with_rdo ? l.stats[3] : 0; out_stats[3] = l.strips; }
+    if (l.with_rdo && l.stats[1]) { set_error(p->parent, "uastc_rdo: a block does not unpack as UASTC"); return 0; }
+    return 1;
+}
+
+int bu_hip_uastc_pipeline_submit(bu_uastc_pipeline* p, const void* d_px, uint32_t n_blocks, void* d_out, const bu_uastc_rdo_params* rdo, uint32_t flags, uint32_t total_jobs,
+                                 uint64_t* out_ticket) {
+    if (!p) return 0;
+    bu_hip_context* ctx = p->parent;
+    if (!d_px || !d_out || !n_blocks) { set_error(ctx, "uastc_pipeline_submit: null pointer / no blocks"); return 0; }
+    device_guard g(ctx->device);
+    const uint64_t ticket = p->next_ticket;
+    bu_uastc_pipeline::lane& l = p->lanes[(size_t)(ticket % p->lanes.size())];
+    if (!uastc_pipeline_collect(p, l, nullptr)) return 0;   // the lane's previous submission (its results are complete from here on; nobody asked for its statistics)
+    const size_t need = std::max(bu::uastc_workspace_bytes(n_blocks, flags), rdo ? bu::uastc_rdo_workspace_bytes(n_blocks, total_jobs) : (size_t)0);
+    if (need > l.ctx->scratch[5].cap) { set_error(ctx, "uastc_pipeline_submit: %u blocks / %u jobs exceed what the pipeline was created for", n_blocks, total_jobs); return 0; }
+    // the input tiles may still be being produced on the caller's stream
+    BU_TRY(ctx, hipEventRecord(l.input, ctx->stream));
+    BU_TRY(ctx, hipStreamWaitEvent(l.ctx->stream, l.input, 0));
+    if (!bu_hip_k_encode_uastc_blocks(l.ctx, d_px, n_blocks, flags, d_out)) { set_error(ctx, "uastc_pipeline_submit: %s", bu_hip_last_error(l.ctx)); return 0; }
+    l.with_rdo = rdo != nullptr;
+    l.strips = rdo ? bu::uastc_rdo_strips(n_blocks, total_jobs) : 0;
+    if (rdo && !uastc_rdo_enqueue(l.ctx, d_out, d_px, n_blocks, rdo, flags, total_jobs, l.stats)) { set_error(ctx, "uastc_pipeline_submit: %s", bu_hip_last_error(l.ctx)); return 0; }
+    BU_TRY(ctx, hipEventRecord(l.done, l.ctx->stream));
+    l.busy = true; l.ticket = ticket;
+    p->next_ticket++;
+    if (out_ticket) *out_ticket = ticket;
+    return 1;
+}
+
+int bu_hip_uastc_pipeline_wait(bu_uastc_pipeline* p, uint64_t ticket, uint32_t out_stats[4]) {
+    if (!p) return 0;
+    if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = out_stats[3] = 0;
+    device_guard g(p->parent->device);
+    int ok = 1;
+    for (auto& l : p->lanes)
+        if (l.busy && (ticket == 0 || l.ticket == ticket)) ok &= uastc_pipeline_collect(p, l, ticket ? out_stats : nullptr);
+    return ok;
+}
+
+void bu_hip_uastc_pipeline_destroy(bu_uastc_pipeline* p) {
+    if (!p) return;
+    for (auto& l : p->lanes) {
+        if (l.ctx) { device_guard g(l.ctx->device); (void)hipStreamSynchronize(l.ctx->stream); }
+        if (l.done) (void)hipEventDestroy(l.done);
+        if (l.input) (void)hipEventDestroy(l.input);
+        if (l.stats) (void)hipHostFree(l.stats);
+        if (l.ctx) bu_hip_destroy_context(l.ctx);
+    }
+    delete p;
+}
+
+int bu_hip_uastc_rdo(bu_hip_context* ctx, bu_uastc_block* blocks, const bu_uastc_rdo_params* params, uint32_t flags, uint32_t total_jobs, uint32_t out_stats[4]) {
+    if (!ctx || !ctx->d_pixel_blocks) { if (ctx) set_error(ctx, "no pixel blocks set"); return 0; }
+    if (!blocks) { set_error(ctx, "uastc_rdo: null blocks"); return 0; }
+    device_guard g(ctx->device);
+    const uint32_t n = (uint32_t)ctx->total_blocks;
+    arena& o = ctx->scratch[0];
+    BU_TRY(ctx, o.reserve((size_t)n * 16));
+    BU_TRY(ctx, h2d(ctx, o.p, blocks, (size_t)n * 16));
+    if (!bu_hip_k_uastc_rdo(ctx, o.p, ctx->d_pixel_blocks, n, params, flags, total_jobs, out_stats)) return 0;
+    if (!fetch(ctx, blocks, o.p, (size_t)n * 16)) return 0;
+    return 1;
+}
+} // extern "C"

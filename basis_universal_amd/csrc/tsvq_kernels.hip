@@ -287,7 +287,7 @@ hipError_t launch_tsvq_signal(hipStream_t st, uint32_t* d_flag, uint32_t value) 
     return hipGetLastError();
 }
 
-// Small results into coherent page-locked host memory + (flag != nullptr) a sequence number behind them for the host to look at (bu_hip_api.cpp, mail_fetch): one workgroup;
+// Small results into coherent page-locked host memory + (flag != nullptr) a sequence number behind them for the host to look at (api_context.cpp, mail_fetch): one workgroup;
 // the data is fenced to system scope by every thread that wrote some of it before thread 0 releases the word.
 __global__ __launch_bounds__(256) void k_mail_copy(unsigned char* __restrict__ dst, const unsigned char* __restrict__ src, uint32_t bytes, uint32_t* flag, uint32_t seq) {
     const uint32_t tid = threadIdx.x;

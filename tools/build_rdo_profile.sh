@@ -3,11 +3,14 @@
 # the serial step, strip 0, printed to stderr by bu_hip_k_uastc_rdo). Development aid for tools/rdo_step_profile.py; never loaded by the product.
 set -e
 cd "$(dirname "$0")/../basis_universal_amd/csrc"
-mkdir -p ../../tools/bin/obj
-F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fvisibility=hidden -Wall -Wno-unused-function -DRDO_PROFILE"
-/opt/rocm/bin/hipcc $F -c uastc_rdo_kernels.hip -o ../../tools/bin/obj/uastc_rdo_kernels.o
-/opt/rocm/bin/hipcc $F -c bu_hip_api.cpp -o ../../tools/bin/obj/bu_hip_api.o
-OBJS=""
-for o in etc1s_kernels tsvq_kernels tsvq_wide_kernels uastc_kernels unique_kernels bookkeeping_kernels kmeans_kernels mipmap_kernels; do OBJS="$OBJS ../lib/obj/$o.o"; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/bin/libbasisu_hip_rdoprof.so $OBJS ../../tools/bin/obj/uastc_rdo_kernels.o ../../tools/bin/obj/bu_hip_api.o
+PROF=../../tools/bin
+# The object list, the compile rule and its flags are the Makefile's: the product's objects as they are (built here only where missing or stale), the instrumented
+# ones by the same rule into $PROF/obj with the -D added.
+OBJS=$(make -s print-objs)
+make -j8 $OBJS
+INSTRUMENTED="uastc_rdo_kernels.o api_uastc.o"
+make -j8 OUT=$PROF EXTRA_CXXFLAGS=-DRDO_PROFILE $(for o in $INSTRUMENTED; do echo $PROF/obj/$o; done)
+LINK=""
+for o in $OBJS; do case " $INSTRUMENTED " in *" $(basename $o) "*) LINK="$LINK $PROF/obj/$(basename $o)";; *) LINK="$LINK $o";; esac; done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $PROF/libbasisu_hip_rdoprof.so $LINK
 echo built tools/bin/libbasisu_hip_rdoprof.so
