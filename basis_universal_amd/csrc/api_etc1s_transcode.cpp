@@ -1,0 +1,126 @@
+// api_etc1s_transcode.cpp -- the ETC1S transcoder behind the C ABI of libbasisu_hip.so: palettes + per-block indices (host/etc1s_decode.cpp's output, resident) -> texture.
+#include "api_internal.h"
+#include "etc1s_transcode_kernels.h"
+
+static const char* const kEtc1sTargets = "ETC1_RGB (0), BC1_RGB (2), RGBA32 (13), RGB565 (14), BGR565 (15), RGBA4444 (16)";
+
+static const char* etc1s_target_name(uint32_t target) {   // the reference's transcoder_texture_format names, for the refusal
+    static const char* const names[] = { "ETC1_RGB", "ETC2_RGBA", "BC1_RGB", "BC3_RGBA", "BC4_R", "BC5_RG", "BC7_RGBA", "BC7_ALT", "PVRTC1_4_RGB", "PVRTC1_4_RGBA", "ASTC_4x4_RGBA",
+                                         "ATC_RGB", "ATC_RGBA", "RGBA32", "RGB565", "BGR565", "RGBA4444", "FXT1_RGB", "PVRTC2_4_RGB", "PVRTC2_4_RGBA", "ETC2_EAC_R11", "ETC2_EAC_RG11" };
+    return target < sizeof(names) / sizeof(names[0]) ? names[target] : "unknown";
+}
+
+// the checks both entry points share; fills the launch arguments
+static int etc1s_transcode_args_from(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
+                                     const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, void* d_out,
+                                     uint32_t pitch_px, uint32_t rows_px, bu::etc1s_transcode_args& a) {
+    if (!bu::etc1s_transcode_unit_bytes(target)) {
+        set_error(ctx, "transcode_etc1s: target %u (%s) is not supported (supported: %s)", target, etc1s_target_name(target), kEtc1sTargets);
+        return 0;
+    }
+    if (!d_ep_pal || !d_sel_pal || !d_ep_idx || !d_sel_idx || !d_out) { set_error(ctx, "transcode_etc1s: null device pointer"); return 0; }
+    if ((d_a_ep_idx == nullptr) != (d_a_sel_idx == nullptr)) { set_error(ctx, "transcode_etc1s: an alpha slice needs both of its index arrays"); return 0; }
+    if (!n_ep || !n_sel || n_ep > 65535u || n_sel > 65535u) { set_error(ctx, "transcode_etc1s: palettes of %u endpoints and %u selectors (1..65535 each)", n_ep, n_sel); return 0; }
+    if (nbx > 16384u || nby > 16384u) { set_error(ctx, "transcode_etc1s: %u x %u blocks is too many (16384 each way at the most)", nbx, nby); return 0; }
+    const uint32_t width = orig_w ? orig_w : nbx * 4, height = orig_h ? orig_h : nby * 4;
+    if (width > nbx * 4 || height > nby * 4) { set_error(ctx, "transcode_etc1s: %u x %u pixels do not fit %u x %u blocks", width, height, nbx, nby); return 0; }
+    const uint32_t pitch = pitch_px ? pitch_px : width, rows = rows_px ? rows_px : height;
+    if (pitch < width) { set_error(ctx, "transcode_etc1s: row pitch %u is less than the width %u", pitch, width); return 0; }
+    a = bu::etc1s_transcode_args{ static_cast<const uint32_t*>(d_ep_pal), static_cast<const uint32_t*>(d_sel_pal), static_cast<const uint16_t*>(d_ep_idx),
+                                  static_cast<const uint16_t*>(d_sel_idx), static_cast<const uint16_t*>(d_a_ep_idx), static_cast<const uint16_t*>(d_a_sel_idx), d_out, nullptr, nullptr,
+                                  n_ep, n_sel, nbx, nby, width, height, pitch, rows };
+    return 1;
+}
+
+// the ETC1S -> BC1 endpoint tables of this context: built on its stream by the first BC1 transcode, resident until the context goes
+static int ensure_bc1_tables(bu_hip_context* ctx) {
+    if (ctx->etc1s_bc1_tables.p) return 1;
+    BU_TRY(ctx, ctx->etc1s_bc1_tables.reserve(2 * bu::kBc1TableEntries * sizeof(uint32_t)));
+    hipError_t e = bu::launch_etc1s_build_bc1_tables(ctx->stream, static_cast<uint32_t*>(ctx->etc1s_bc1_tables.p));
+    if (e != hipSuccess) { ctx->etc1s_bc1_tables.release(); set_error(ctx, "etc1s_build_bc1_tables: %s", hipGetErrorString(e)); return 0; }
+    return 1;
+}
+
+static int read_counter(bu_hip_context* ctx, const void* d_counter, uint32_t* out) {
+    BU_TRY(ctx, d2h_pageable(ctx, out, d_counter, sizeof(uint32_t)));
+    BU_TRY(ctx, stream_wait(ctx, ctx->stream));
+    return 1;
+}
+
+extern "C" {
+
+size_t bu_hip_etc1s_transcode_output_bytes(uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, uint32_t pitch_px, uint32_t rows_px) {
+    const size_t unit = bu::etc1s_transcode_unit_bytes(target);
+    if (!unit) return 0;
+    if (!bu::etc1s_transcode_is_pixel_target(target)) return (size_t)nbx * nby * unit;
+    const size_t width = orig_w ? orig_w : nbx * 4, height = orig_h ? orig_h : nby * 4;
+    return (pitch_px ? pitch_px : width) * (rows_px ? rows_px : height) * unit;
+}
+
+int bu_hip_etc1s_bc1_endpoint_tables(bu_hip_context* ctx, uint32_t* h_out5, uint32_t* h_out6) {
+    if (!ctx || !h_out5 || !h_out6) { if (ctx) set_error(ctx, "etc1s_bc1_endpoint_tables: null pointer"); return 0; }
+    device_guard g(ctx->device);
+    if (!ensure_bc1_tables(ctx)) return 0;
+    const uint32_t* d = static_cast<const uint32_t*>(ctx->etc1s_bc1_tables.p);
+    if (!fetch(ctx, h_out5, d, bu::kBc1TableEntries * sizeof(uint32_t)) || !fetch(ctx, h_out6, d + bu::kBc1TableEntries, bu::kBc1TableEntries * sizeof(uint32_t))) return 0;
+    return 1;
+}
+
+int bu_hip_k_transcode_etc1s_counted(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
+                                     const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, void* d_out,
+                                     uint32_t pitch_px, uint32_t rows_px, uint32_t* out_invalid_blocks) {
+    if (!ctx) return 0;
+    if (out_invalid_blocks) *out_invalid_blocks = 0;
+    bu::etc1s_transcode_args a;
+    if (!etc1s_transcode_args_from(ctx, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out, pitch_px, rows_px, a)) return 0;
+    device_guard g(ctx->device);
+    arena& counter = ctx->scratch[4];
+    BU_TRY(ctx, counter.reserve(sizeof(uint32_t)));
+    a.invalid = static_cast<uint32_t*>(counter.p);
+    if (target == bu::ETF_BC1_RGB) {
+        if (!ensure_bc1_tables(ctx)) return 0;
+        a.bc1_endpoints = static_cast<const uint32_t*>(ctx->etc1s_bc1_tables.p);
+    }
+    {
+        prof_scope ps(ctx, "etc1s_transcode");
+        BU_TRY(ctx, bu::launch_transcode_etc1s(ctx->stream, a, target));
+    }
+    uint32_t invalid = 0;
+    if (!read_counter(ctx, counter.p, &invalid)) return 0;
+    if (out_invalid_blocks) *out_invalid_blocks = invalid;
+    return 1;
+}
+
+int bu_hip_k_transcode_etc1s(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
+                             const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, void* d_out,
+                             uint32_t pitch_px, uint32_t rows_px) {
+    if (!ctx) return 0;
+    bu::etc1s_transcode_args a;
+    if (!etc1s_transcode_args_from(ctx, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out, pitch_px, rows_px, a)) return 0;
+    device_guard g(ctx->device);
+    arena& counter = ctx->scratch[4];
+    BU_TRY(ctx, counter.reserve(sizeof(uint32_t)));
+    uint32_t* d_count = static_cast<uint32_t*>(counter.p);
+    const uint32_t n = nbx * nby;
+    // the indices are resident, so the range check that has to come before the launch is a pass over them on the device: 2-4 bytes per block read, one word back
+    {
+        prof_scope ps(ctx, "etc1s_transcode_check");
+        BU_TRY(ctx, bu::launch_etc1s_count_indices_past(ctx->stream, a.endpoint_idx, n, n_ep, d_count, true));
+        BU_TRY(ctx, bu::launch_etc1s_count_indices_past(ctx->stream, a.selector_idx, n, n_sel, d_count, false));
+        const bool alpha_read = a.alpha_endpoint_idx && (target == bu::ETF_RGBA32 || target == bu::ETF_RGBA4444);
+        if (alpha_read) {
+            BU_TRY(ctx, bu::launch_etc1s_count_indices_past(ctx->stream, a.alpha_endpoint_idx, n, n_ep, d_count, false));
+            BU_TRY(ctx, bu::launch_etc1s_count_indices_past(ctx->stream, a.alpha_selector_idx, n, n_sel, d_count, false));
+        }
+    }
+    uint32_t past = 0;
+    if (!read_counter(ctx, d_count, &past)) return 0;
+    if (past) { set_error(ctx, "transcode_etc1s: %u indices are past their palette (%u endpoints, %u selectors): nothing was transcoded", past, n_ep, n_sel); return 0; }
+    uint32_t invalid = 0;
+    if (!bu_hip_k_transcode_etc1s_counted(ctx, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out, pitch_px, rows_px,
+                                          &invalid)) return 0;
+    if (invalid) { set_error(ctx, "transcode_etc1s: %u blocks had an index past its palette", invalid); return 0; }
+    return 1;
+}
+
+} // extern "C"

@@ -46,6 +46,7 @@ struct bu_hip_context {
     // set; own_stream (and with it everything that fills the chip) is masked to the OTHER CUs, side_stream (the walk with the refit in it) to the reserved ones
     hipStream_t walk_stream = nullptr; hipEvent_t walk_join = nullptr; uint32_t walk_cus = 0;
     arena refine_lists;                   // the sorted candidate lists of refine_endpoint_clusterization (etc1s_kernels.hip, k_refine_sort_lists)
+    arena etc1s_bc1_tables;               // the ETC1S -> BC1 endpoint tables (api_etc1s_transcode.cpp), built by the first BC1 transcode of the context
     const void* d_pixel_blocks = nullptr; // resident tiles (a1): 64 B per block
     size_t total_blocks = 0;
     arena pixel_arena;                    // owns the tiles when they were uploaded through bu_hip_set_pixel_blocks

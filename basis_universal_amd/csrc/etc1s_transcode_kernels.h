@@ -1,0 +1,31 @@
+// etc1s_transcode_kernels.h -- launchers of etc1s_transcode_kernels.hip: the device half of reading an ETC1S file (palettes + per-block indices -> texture).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace bu {
+
+enum : uint32_t { kBc1TableEntries = 8 * 32 * 6 * 10 };   // per endpoint width: intensity tables x 5-bit base values x selector ranges x selector mappings
+// the reference's transcoder_texture_format values of the targets that exist here
+enum : uint32_t { ETF_ETC1_RGB = 0, ETF_BC1_RGB = 2, ETF_RGBA32 = 13, ETF_RGB565 = 14, ETF_BGR565 = 15, ETF_RGBA4444 = 16 };
+
+struct etc1s_transcode_args {
+    const uint32_t* endpoint_palette;   // r5 | g5 << 8 | b5 << 16 | intensity table << 24
+    const uint32_t* selector_palette;   // selector of texel (x, y) at bits 2 * (y * 4 + x)
+    const uint16_t *endpoint_idx, *selector_idx, *alpha_endpoint_idx, *alpha_selector_idx;   // alpha: both null = opaque
+    void* out;
+    uint32_t* invalid;                  // device counter
+    const uint32_t* bc1_endpoints;      // BC1 only: 2 * kBc1TableEntries words from launch_etc1s_build_bc1_tables
+    uint32_t n_endpoints, n_selectors, nbx, nby, width, height, pitch, rows;
+};
+
+uint32_t etc1s_transcode_unit_bytes(uint32_t target);   // per block for block targets, per pixel for pixel targets; 0 = the target does not exist here
+bool etc1s_transcode_is_pixel_target(uint32_t target);
+// one launch; d_invalid is cleared first and afterwards holds how many blocks had an index past its palette (their output is zero-filled)
+hipError_t launch_transcode_etc1s(hipStream_t st, const etc1s_transcode_args& a, uint32_t target);
+// fills d_tables[2 * kBc1TableEntries] with the ETC1S -> BC1 endpoint tables (5-bit, then 6-bit)
+hipError_t launch_etc1s_build_bc1_tables(hipStream_t st, uint32_t* d_tables);
+// counts the entries of idx[n] that are >= limit into *d_count (cleared first)
+hipError_t launch_etc1s_count_indices_past(hipStream_t st, const uint16_t* idx, uint32_t n, uint32_t limit, uint32_t* d_count, bool clear);
+
+}  // namespace bu

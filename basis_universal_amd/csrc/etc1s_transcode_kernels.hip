@@ -1,0 +1,272 @@
+// etc1s_transcode_kernels.hip -- the texel half of basisu_lowlevel_etc1s_transcoder::transcode_slice (transcoder/basisu_transcoder.cpp:8858-9345) over the indices
+// host/etc1s_decode.cpp produced: one lane per 4x4 block, one launch per image, the target a template parameter so that each instance carries only its own path.
+// A lane reads its two u16 indices (four with an alpha slice), gathers the palette entries (4 bytes each) and builds its output in registers: block targets store
+// one uint2 per block, consecutive lanes on consecutive blocks; pixel targets store the four rows of the tile into the caller's raster, cropped to the image, as
+// one 16-byte (RGBA32) or 8-byte (16-bit formats) word per row where the row is whole and aligned. An index past its palette never reaches a gather: the block is
+// zero-filled and counted with a vector atomic, and it does not stop the others.
+#include <hip/hip_runtime.h>
+#include "etc1s_device.h"
+#include "etc1s_transcode_kernels.h"
+
+#define BU_TAB static __device__ const
+#include "etc1s_transcode_tables.inc"
+#undef BU_TAB
+
+namespace bu {
+
+struct etc1s_entry { uint32_t r5, g5, b5, table; };
+__device__ __forceinline__ etc1s_entry unpack_entry(uint32_t e) { return etc1s_entry{ e & 31u, (e >> 8) & 31u, (e >> 16) & 31u, (e >> 24) & 7u }; }
+__device__ __forceinline__ uint32_t texel_selector(uint32_t sel, uint32_t x, uint32_t y) { return (sel >> (2u * (y * 4u + x))) & 3u; }
+// mul_8 (transcoder.cpp:269): an 8-bit value scaled to q
+__device__ __forceinline__ uint32_t mul_8(uint32_t v, uint32_t q) { v = v * q + 128u; return ((v + (v >> 8)) >> 8) & 255u; }
+
+// the four colours of an entry, r | g << 8 | b << 16 (get_block_colors5, transcoder.cpp:996-1010)
+__device__ __forceinline__ void block_colors(const etc1s_entry& e, uint32_t out[4]) {
+    const int r = scale5((int)e.r5), g = scale5((int)e.g5), b = scale5((int)e.b5);
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int d = inten_delta((int)e.table, s);
+        out[s] = (uint32_t)clamp255(r + d) | ((uint32_t)clamp255(g + d) << 8) | ((uint32_t)clamp255(b + d) << 16);
+    }
+}
+__device__ __forceinline__ uint32_t pick4(const uint32_t c[4], uint32_t s) {   // c[s] as selects: a dynamic index would put the array in scratch memory
+    const uint32_t lo = (s & 1u) ? c[1] : c[0], hi = (s & 1u) ? c[3] : c[2];
+    return (s & 2u) ? hi : lo;
+}
+
+// cETC1 (transcoder.cpp:8863-8875): a differential block whose two halves have the same colour and table, delta 0, flip bit clear; the block's 64 bits as the big-endian
+// value V (etc1s_device.h), returned as it lies in memory
+__device__ __forceinline__ uint2 to_etc1(const etc1s_entry& e, uint32_t sel) {
+    const uint32_t hi = (e.r5 << 27) | (e.g5 << 19) | (e.b5 << 11) | (e.table << 5) | (e.table << 2) | 2u;
+    uint32_t lo = 0;
+#pragma unroll
+    for (uint32_t y = 0; y < 4; y++)
+#pragma unroll
+        for (uint32_t x = 0; x < 4; x++) lo |= selector_bits(x, y, texel_selector(sel, x, y));
+    return make_uint2(__builtin_bswap32(hi), __builtin_bswap32(lo));
+}
+
+// cBC1 with three-colour blocks allowed, which is how the reference transcodes ETC1S to plain BC1 (convert_etc1s_to_dxt1, transcoder.cpp:2271-2461, called with true
+// at :9567): a block with equal endpoints keeps them, no punch-through guard.
+__device__ __forceinline__ uint2 to_bc1(const etc1s_entry& e, uint32_t sel, const uint32_t* endpoints5, const uint32_t* endpoints6) {
+    uint32_t used = 0;
+#pragma unroll
+    for (uint32_t p = 0; p < 16; p++) used |= 1u << ((sel >> (2u * p)) & 3u);
+    const uint32_t low = (uint32_t)__ffs((int)used) - 1u, high = 31u - (uint32_t)__clz((int)used);
+    uint32_t colors[4];
+    block_colors(e, colors);
+    if (low == high) {   // one colour: the pair whose colour 1 is nearest, selectors all 2 (= colour 1 when low > high)
+        const uint32_t c = pick4(colors, low), r = c & 255u, g = (c >> 8) & 255u, b = c >> 16;
+        uint32_t max16 = ((uint32_t)ke_bc1_solid5[r * 2] << 11) | ((uint32_t)ke_bc1_solid6[g * 2] << 5) | ke_bc1_solid5[b * 2];
+        uint32_t min16 = ((uint32_t)ke_bc1_solid5[r * 2 + 1] << 11) | ((uint32_t)ke_bc1_solid6[g * 2 + 1] << 5) | ke_bc1_solid5[b * 2 + 1];
+        uint32_t mask = 0xAAu;
+        if (max16 < min16) { const uint32_t t = max16; max16 = min16; min16 = t; mask ^= 0x55u; }
+        return make_uint2(max16 | (min16 << 16), mask * 0x01010101u);
+    }
+    if (e.table >= 7 && __popc(used) == 2 && low == 0 && high == 3) {   // the widest table with only its extremes in use: the two colours become the endpoints
+        const uint32_t c0 = colors[0], c3 = colors[3];
+        uint32_t max16 = ((uint32_t)ke_bc1_end5[c0 & 255u] << 11) | ((uint32_t)ke_bc1_end6[(c0 >> 8) & 255u] << 5) | ke_bc1_end5[c0 >> 16];
+        uint32_t min16 = ((uint32_t)ke_bc1_end5[c3 & 255u] << 11) | ((uint32_t)ke_bc1_end6[(c3 >> 8) & 255u] << 5) | ke_bc1_end5[c3 >> 16];
+        uint32_t l = 0, h = 1;
+        if (min16 == max16) {
+            if (min16 > 0) { min16--; l = 0; h = 0; }
+            else { max16 = 1; min16 = 0; l = 1; h = 1; }
+        }
+        if (max16 < min16) { const uint32_t t = max16; max16 = min16; min16 = t; l = 1; h = 0; }
+        uint32_t bits = 0;
+#pragma unroll
+        for (uint32_t p = 0; p < 16; p++) bits |= ((((sel >> (2u * p)) & 3u) == 3u) ? h : l) << (2u * p);
+        return make_uint2(max16 | (min16 << 16), bits);
+    }
+    // per channel the best endpoints for each of the ten selector mappings; the mapping with the least summed error wins, first on ties
+    const uint32_t range = ke_bc1_range_index[low * 4 + high];
+    const uint32_t* tr = &endpoints5[((e.table * 32u + e.r5) * 6u + range) * 10u];
+    const uint32_t* tg = &endpoints6[((e.table * 32u + e.g5) * 6u + range) * 10u];
+    const uint32_t* tb = &endpoints5[((e.table * 32u + e.b5) * 6u + range) * 10u];
+    uint32_t best_err = 0xFFFFFFFFu, best = 0, br = 0, bg = 0, bb = 0;
+#pragma unroll
+    for (uint32_t m = 0; m < 10; m++) {
+        const uint32_t r = tr[m], g = tg[m], b = tb[m], err = (r >> 16) + (g >> 16) + (b >> 16);
+        if (err < best_err) { best_err = err; best = m; br = r; bg = g; bb = b; }
+    }
+    uint32_t l = ((br & 255u) << 11) | ((bg & 255u) << 5) | (bb & 255u);
+    uint32_t h = (((br >> 8) & 255u) << 11) | (((bg >> 8) & 255u) << 5) | ((bb >> 8) & 255u);
+    uint32_t swapped = 0;
+    if (l < h) { const uint32_t t = l; l = h; h = t; swapped = 1; }
+    if (l == h) return make_uint2(l | (h << 16), 0u);
+    const unsigned char* xl = &ke_bc1_selector_xlat[(best * 2u + swapped) * 4u];
+    const uint32_t x0 = xl[0], x1 = xl[1], x2 = xl[2], x3 = xl[3];
+    uint32_t bits = 0;
+#pragma unroll
+    for (uint32_t p = 0; p < 16; p++) {
+        const uint32_t s = (sel >> (2u * p)) & 3u;
+        bits |= ((s & 2u) ? ((s & 1u) ? x3 : x2) : ((s & 1u) ? x1 : x0)) << (2u * p);
+    }
+    return make_uint2(l | (h << 16), bits);
+}
+
+// one pixel of a pixel target from the block colour (r | g << 8 | b << 16) and the alpha value (transcoder.cpp:9155-9332; the 4444 colour pass ORs onto the alpha pass)
+template <uint32_t TARGET>
+__device__ __forceinline__ uint32_t pack_pixel(uint32_t c, uint32_t a) {
+    const uint32_t r = c & 255u, g = (c >> 8) & 255u, b = c >> 16;
+    if (TARGET == ETF_RGBA32) return c | (a << 24);
+    if (TARGET == ETF_RGB565) return (mul_8(r, 31) << 11) | (mul_8(g, 63) << 5) | mul_8(b, 31);
+    if (TARGET == ETF_BGR565) return (mul_8(b, 31) << 11) | (mul_8(g, 63) << 5) | mul_8(r, 31);
+    return (mul_8(r, 15) << 12) | (mul_8(g, 15) << 8) | (mul_8(b, 15) << 4) | mul_8(a, 15);   // RGBA4444
+}
+
+template <uint32_t TARGET>
+__global__ __launch_bounds__(256) void transcode_etc1s_kernel(etc1s_transcode_args a) {
+    const uint32_t n = a.nbx * a.nby, i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    constexpr bool kPixels = TARGET == ETF_RGBA32 || TARGET == ETF_RGB565 || TARGET == ETF_BGR565 || TARGET == ETF_RGBA4444;
+    constexpr bool kAlpha = TARGET == ETF_RGBA32 || TARGET == ETF_RGBA4444;
+    const uint32_t ei = a.endpoint_idx[i], si = a.selector_idx[i];
+    bool ok = ei < a.n_endpoints && si < a.n_selectors;
+    uint32_t aei = 0, asi = 0;
+    const bool has_alpha = kAlpha && a.alpha_endpoint_idx != nullptr;
+    if (has_alpha) {
+        aei = a.alpha_endpoint_idx[i]; asi = a.alpha_selector_idx[i];
+        ok = ok && aei < a.n_endpoints && asi < a.n_selectors;
+    }
+    if (!ok) atomicAdd(a.invalid, 1u);
+    if (!kPixels) {
+        uint2 o = make_uint2(0u, 0u);
+        if (ok) {
+            const etc1s_entry e = unpack_entry(a.endpoint_palette[ei]);
+            const uint32_t sel = a.selector_palette[si];
+            o = TARGET == ETF_ETC1_RGB ? to_etc1(e, sel) : to_bc1(e, sel, a.bc1_endpoints, a.bc1_endpoints + kBc1TableEntries);
+        }
+        ((uint2*)a.out)[i] = o;
+        return;
+    }
+    uint32_t colors[4] = { 0, 0, 0, 0 }, alphas[4] = { 255u, 255u, 255u, 255u }, sel = 0, asel = 0;
+    if (ok) {
+        block_colors(unpack_entry(a.endpoint_palette[ei]), colors);
+        sel = a.selector_palette[si];
+        if (has_alpha) {   // alpha = the green channel of the alpha slice's block colours
+            uint32_t ac[4];
+            block_colors(unpack_entry(a.endpoint_palette[aei]), ac);
+#pragma unroll
+            for (int s = 0; s < 4; s++) alphas[s] = (ac[s] >> 8) & 255u;
+            asel = a.selector_palette[asi];
+        }
+    } else {
+        alphas[0] = alphas[1] = alphas[2] = alphas[3] = 0;
+    }
+    const uint32_t bx = i % a.nbx, by = i / a.nbx;
+    const bool whole = bx * 4u + 4u <= a.width;
+#pragma unroll
+    for (uint32_t y = 0; y < 4; y++) {
+        const uint32_t row = by * 4u + y;
+        if (row >= a.height || row >= a.rows) break;
+        uint32_t v[4];
+#pragma unroll
+        for (uint32_t x = 0; x < 4; x++) {
+            const uint32_t px = pack_pixel<TARGET>(pick4(colors, texel_selector(sel, x, y)), has_alpha ? pick4(alphas, texel_selector(asel, x, y)) : alphas[0]);
+            v[x] = ok ? px : 0u;
+        }
+        const size_t at = (size_t)row * a.pitch + bx * 4u;
+        if (TARGET == ETF_RGBA32) {
+            uint32_t* dst = (uint32_t*)a.out + at;
+            if (whole && (((uintptr_t)dst & 15u) == 0)) *(uint4*)dst = make_uint4(v[0], v[1], v[2], v[3]);
+            else {
+#pragma unroll
+                for (uint32_t x = 0; x < 4; x++) if (bx * 4u + x < a.width) dst[x] = v[x];
+            }
+        } else {
+            uint16_t* dst = (uint16_t*)a.out + at;
+            if (whole && (((uintptr_t)dst & 7u) == 0)) *(uint2*)dst = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
+            else {
+#pragma unroll
+                for (uint32_t x = 0; x < 4; x++) if (bx * 4u + x < a.width) dst[x] = (uint16_t)v[x];
+            }
+        }
+    }
+}
+
+// The two endpoint tables of to_bc1, [intensity table][base5][range][mapping] -> lo | hi << 8 | squared error << 16 for 5-bit (first kBc1TableEntries words) and 6-bit
+// endpoints: one lane per entry searches every endpoint pair, hi outermost, lo innermost, first minimum (tools/gen_etc1s_transcode_tables.py's endpoint_table() is the
+// same search on the host). 30,720 lanes x at most 4,096 pairs x at most 4 selectors: well under a millisecond, once per context.
+__global__ __launch_bounds__(256) void etc1s_build_bc1_tables_kernel(uint32_t* tables) {
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= 2u * kBc1TableEntries) return;
+    const bool six = idx >= kBc1TableEntries;
+    const uint32_t e = six ? idx - kBc1TableEntries : idx, m = e % 10u, r = (e / 10u) % 6u, g = (e / 60u) % 32u, t = e / 1920u;
+    const int base = scale5((int)g);
+    int block[4];
+#pragma unroll
+    for (int s = 0; s < 4; s++) block[s] = clamp255(base + inten_delta((int)t, s));
+    const uint32_t s0 = ke_bc1_ranges[r * 2], s1 = ke_bc1_ranges[r * 2 + 1];
+    const uint32_t m0 = ke_bc1_mappings[m * 4], m1 = ke_bc1_mappings[m * 4 + 1], m2 = ke_bc1_mappings[m * 4 + 2], m3 = ke_bc1_mappings[m * 4 + 3];
+    const uint32_t n = six ? 64u : 32u;
+    uint32_t best_err = 0xFFFFFFFFu, best_lo = 0, best_hi = 0;
+    for (uint32_t hi = 0; hi < n; hi++)
+        for (uint32_t lo = 0; lo < n; lo++) {
+            uint32_t c[4];
+            c[0] = six ? ((lo << 2) | (lo >> 4)) : ((lo << 3) | (lo >> 2));
+            c[3] = six ? ((hi << 2) | (hi >> 4)) : ((hi << 3) | (hi >> 2));
+            c[1] = (c[0] * 2u + c[3]) / 3u;
+            c[2] = (c[3] * 2u + c[0]) / 3u;
+            const uint32_t mapped[4] = { pick4(c, m0), pick4(c, m1), pick4(c, m2), pick4(c, m3) };
+            uint32_t err = 0;
+#pragma unroll
+            for (uint32_t s = 0; s < 4; s++) {
+                const int d = block[s] - (int)mapped[s];
+                if (s >= s0 && s <= s1) err += (uint32_t)(d * d);
+            }
+            if (err < best_err) { best_err = err; best_lo = lo; best_hi = hi; }
+        }
+    tables[idx] = best_lo | (best_hi << 8) | (best_err << 16);
+}
+
+__global__ __launch_bounds__(256) void etc1s_count_indices_past_kernel(const uint16_t* idx, uint32_t n, uint32_t limit, uint32_t* count) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n && idx[i] >= limit) atomicAdd(count, 1u);
+}
+
+template <uint32_t TARGET>
+static hipError_t launch(hipStream_t st, const etc1s_transcode_args& a) {
+    const uint32_t n = a.nbx * a.nby;
+    hipLaunchKernelGGL((transcode_etc1s_kernel<TARGET>), dim3((n + 255) / 256), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+uint32_t etc1s_transcode_unit_bytes(uint32_t target) {
+    switch (target) {
+    case ETF_ETC1_RGB: case ETF_BC1_RGB: return 8;
+    case ETF_RGBA32: return 4;
+    case ETF_RGB565: case ETF_BGR565: case ETF_RGBA4444: return 2;
+    default: return 0;
+    }
+}
+bool etc1s_transcode_is_pixel_target(uint32_t target) { return target == ETF_RGBA32 || target == ETF_RGB565 || target == ETF_BGR565 || target == ETF_RGBA4444; }
+
+hipError_t launch_transcode_etc1s(hipStream_t st, const etc1s_transcode_args& a, uint32_t target) {
+    hipError_t e = hipMemsetAsync(a.invalid, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess || !a.nbx || !a.nby) return e;
+    if (target == ETF_BC1_RGB && !a.bc1_endpoints) return hipErrorInvalidValue;
+    switch (target) {
+    case ETF_ETC1_RGB: return launch<ETF_ETC1_RGB>(st, a);
+    case ETF_BC1_RGB: return launch<ETF_BC1_RGB>(st, a);
+    case ETF_RGBA32: return launch<ETF_RGBA32>(st, a);
+    case ETF_RGB565: return launch<ETF_RGB565>(st, a);
+    case ETF_BGR565: return launch<ETF_BGR565>(st, a);
+    case ETF_RGBA4444: return launch<ETF_RGBA4444>(st, a);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_etc1s_build_bc1_tables(hipStream_t st, uint32_t* d_tables) {
+    hipLaunchKernelGGL(etc1s_build_bc1_tables_kernel, dim3((2u * kBc1TableEntries + 255) / 256), dim3(256), 0, st, d_tables);
+    return hipGetLastError();
+}
+
+hipError_t launch_etc1s_count_indices_past(hipStream_t st, const uint16_t* idx, uint32_t n, uint32_t limit, uint32_t* d_count, bool clear) {
+    if (clear) { hipError_t e = hipMemsetAsync(d_count, 0, sizeof(uint32_t), st); if (e != hipSuccess) return e; }
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(etc1s_count_indices_past_kernel, dim3((n + 255) / 256), dim3(256), 0, st, idx, n, limit, d_count);
+    return hipGetLastError();
+}
+
+}  // namespace bu

@@ -4,6 +4,10 @@
 Targets are the reference's transcoder_texture_format values; only the ones below exist here. ETC1 / ETC2 / EAC / PVRTC1, the 16-bit pixel formats, ETC1S files,
 UASTC HDR / ASTC LDR / XUASTC and Zstandard-supercompressed KTX2 levels are out of scope and are refused with an error. There is no CPU implementation:
 without the HIP library and a GPU `transcode_uastc_blocks` raises.
+
+ETC1S files have their own three functions at the end of this module (`read_etc1s_file`, `decode_etc1s_file`, `transcode_etc1s_file`) and their own target list
+(ETC1S_BYTES_PER_BLOCK / ETC1S_BYTES_PER_PIXEL): the serial half -- containers, Huffman tables, palettes, the per-slice symbol walk -- is host code in
+libbasisu_frontend.so (csrc/host/etc1s_decode.cpp, needs no GPU), the texel half is one HIP kernel launch per image (csrc/etc1s_transcode_kernels.hip).
 """
 import ctypes as C
 import struct
@@ -170,4 +174,154 @@ def transcode_file(ctx, data, target, *, level=0, layer=0, face=0, high_quality=
             blocks = np.frombuffer(raw, np.uint8, im["length"], im["offset"]).reshape(-1, 16)
             return transcode_uastc_blocks(ctx, blocks, im["num_blocks_x"], im["num_blocks_y"], target, width=im["width"], height=im["height"], high_quality=high_quality,
                                           channels=channels)
+    raise ValueError(f"the file has no image at level {level}, layer {layer}, face {face}")
+
+
+# ---------------------------------------------------------------- ETC1S files
+
+ETC1_RGB, RGB565, BGR565, RGBA4444 = 0, 14, 15, 16   # with BC1_RGB and RGBA32 above: the ETC1S transcoder's targets (transcoder_texture_format values)
+ETC1S_BYTES_PER_BLOCK = {ETC1_RGB: 8, BC1_RGB: 8}
+ETC1S_BYTES_PER_PIXEL = {RGBA32: 4, RGB565: 2, BGR565: 2, RGBA4444: 2}
+_TARGET_NAMES = ["ETC1_RGB", "ETC2_RGBA", "BC1_RGB", "BC3_RGBA", "BC4_R", "BC5_RG", "BC7_RGBA", "BC7_ALT", "PVRTC1_4_RGB", "PVRTC1_4_RGBA", "ASTC_4x4_RGBA", "ATC_RGB", "ATC_RGBA",
+                 "RGBA32", "RGB565", "BGR565", "RGBA4444", "FXT1_RGB", "PVRTC2_4_RGB", "PVRTC2_4_RGBA", "ETC2_EAC_R11", "ETC2_EAC_RG11"]
+
+
+class _Etc1sFileInfo(C.Structure):   # = bu_etc1s_file_info, include/basisu_hip_etc1s_decode.h
+    _fields_ = [(n, C.c_uint32) for n in ("container", "tex_type", "width", "height", "levels", "layers", "faces", "has_alpha_slices", "srgb", "num_endpoints", "num_selectors",
+                                          "num_images")] + [("total_blocks", C.c_uint64)]
+
+
+class _Etc1sImage(C.Structure):      # = bu_etc1s_image
+    _fields_ = [(n, C.c_uint32) for n in ("level", "layer", "face", "width", "height", "num_blocks_x", "num_blocks_y", "reserved")] + [("first_block", C.c_uint64),
+                                                                                                                                      ("alpha_first_block", C.c_uint64)]
+
+
+def _etc1s_lib():
+    from .etc1s import load_frontend_library
+    L = load_frontend_library()
+    if not getattr(L, "_etc1s_decode_bound", False):
+        L.bu_etc1s_decode_file.restype = C.c_void_p
+        L.bu_etc1s_decode_file.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_char_p, C.c_uint32]
+        L.bu_etc1s_file_destroy.restype = None
+        L.bu_etc1s_file_destroy.argtypes = [C.c_void_p]
+        L.bu_etc1s_file_get_info.restype = None
+        L.bu_etc1s_file_get_info.argtypes = [C.c_void_p, C.POINTER(_Etc1sFileInfo)]
+        L.bu_etc1s_file_get_images.restype = C.c_uint32
+        L.bu_etc1s_file_get_images.argtypes = [C.c_void_p, C.POINTER(_Etc1sImage), C.c_uint32]
+        for name in ("endpoint_palette", "selector_palette", "endpoint_indices", "selector_indices"):
+            fn = getattr(L, "bu_etc1s_file_" + name)
+            fn.restype = C.c_void_p
+            fn.argtypes = [C.c_void_p]
+        L._etc1s_decode_bound = True
+    return L
+
+
+def _decode_etc1s(data, header_only):
+    raw = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
+    L = _etc1s_lib()
+    err = C.create_string_buffer(512)
+    h = L.bu_etc1s_decode_file(raw, len(raw), 1 if header_only else 0, err, len(err))
+    if not h:
+        raise ValueError(err.value.decode(errors="replace"))
+    try:
+        fi = _Etc1sFileInfo()
+        L.bu_etc1s_file_get_info(h, C.byref(fi))
+        ims = (_Etc1sImage * max(fi.num_images, 1))()
+        L.bu_etc1s_file_get_images(h, ims, fi.num_images)
+        images = []
+        for k in range(fi.num_images):
+            im = ims[k]
+            images.append({"level": im.level, "layer": im.layer, "face": im.face, "width": im.width, "height": im.height, "num_blocks_x": im.num_blocks_x,
+                           "num_blocks_y": im.num_blocks_y, "has_alpha": im.alpha_first_block != 2 ** 64 - 1, "_first": im.first_block, "_alpha_first": im.alpha_first_block})
+        info = {"container": "ktx2" if fi.container else "basis", "format": "ETC1S", "width": fi.width, "height": fi.height, "has_alpha": bool(fi.has_alpha_slices),
+                "has_alpha_slices": bool(fi.has_alpha_slices), "levels": sorted({im["level"] for im in images}), "layers": fi.layers, "faces": fi.faces, "tex_type": fi.tex_type,
+                "srgb": bool(fi.srgb), "num_endpoints": fi.num_endpoints, "num_selectors": fi.num_selectors, "images": images}
+        if header_only:
+            for im in images:
+                del im["_first"], im["_alpha_first"]
+            return info
+
+        def take(name, count, dtype):
+            p = getattr(L, "bu_etc1s_file_" + name)(h)
+            return np.frombuffer(C.string_at(p, count * np.dtype(dtype).itemsize), dtype).copy() if count else np.zeros(0, dtype)
+        info["endpoint_palette"] = take("endpoint_palette", fi.num_endpoints * 4, np.uint8).reshape(-1, 4)
+        info["selector_palette"] = take("selector_palette", fi.num_selectors, np.uint32)
+        ep, sel = take("endpoint_indices", fi.total_blocks, np.uint16), take("selector_indices", fi.total_blocks, np.uint16)
+        for im in images:
+            n, a, b = im["num_blocks_x"] * im["num_blocks_y"], im.pop("_first"), im.pop("_alpha_first")
+            shape = (im["num_blocks_y"], im["num_blocks_x"])
+            im["endpoint_indices"], im["selector_indices"] = ep[a:a + n].reshape(shape), sel[a:a + n].reshape(shape)
+            im["alpha_endpoint_indices"], im["alpha_selector_indices"] = (ep[b:b + n].reshape(shape), sel[b:b + n].reshape(shape)) if im["has_alpha"] else (None, None)
+        return info
+    finally:
+        L.bu_etc1s_file_destroy(h)
+
+
+def read_etc1s_file(data):
+    """Parse an ETC1S .basis (cBASISTexFormatETC1S) or .ktx2 (BasisLZ supercompression, ETC1S data format descriptor) file, the two ETC1S containers this package
+    writes: the dictionary read_uastc_file returns ("format": "ETC1S"; an image has "has_alpha" instead of "offset" / "length", because a slice is a bit stream and
+    not an array of blocks) plus "has_alpha_slices", "num_endpoints", "num_selectors", "tex_type" and "srgb". Host only. UASTC, video, truncated or corrupt files
+    raise ValueError with the reason."""
+    return _decode_etc1s(data, True)
+
+
+def decode_etc1s_file(data):
+    """read_etc1s_file plus everything the slices code (host only, no GPU): "endpoint_palette" (n, 4) u8 -- r5, g5, b5, intensity table --, "selector_palette" (n,)
+    u32 -- the selector of texel (x, y) at bits 2 * (y * 4 + x) --, and per image "endpoint_indices" / "selector_indices" (num_blocks_y, num_blocks_x) u16 and, for
+    images with an alpha slice, "alpha_endpoint_indices" / "alpha_selector_indices" (else None). Every index is checked against its palette."""
+    return _decode_etc1s(data, False)
+
+
+def _check_etc1s_target(target):
+    target = int(target)
+    if target not in ETC1S_BYTES_PER_BLOCK and target not in ETC1S_BYTES_PER_PIXEL:
+        name = _TARGET_NAMES[target] if 0 <= target < len(_TARGET_NAMES) else "unknown"
+        raise ValueError(f"ETC1S transcode target {target} ({name}) is not supported (supported: {sorted(list(ETC1S_BYTES_PER_BLOCK) + list(ETC1S_BYTES_PER_PIXEL))})")
+    return target
+
+
+def transcode_etc1s_image(ctx, decoded, image, target, *, out_device=None, out_row_pitch=0, out_rows=0):
+    """One image of decode_etc1s_file's result on the GPU. Block targets (ETC1S_BYTES_PER_BLOCK) return (num_blocks, 8) u8, pixel targets (ETC1S_BYTES_PER_PIXEL)
+    the (height, width, 4) u8 raster for RGBA32 and the (height, width) u16 raster for the 16-bit formats; with out_device (room for out_rows x out_row_pitch
+    pixels when those are given) the output stays there and None is returned."""
+    target = _check_etc1s_target(target)
+    if out_device is None and (out_row_pitch or out_rows):
+        raise ValueError("out_row_pitch / out_rows describe a caller-owned raster: give out_device")
+    nbx, nby, w, h = image["num_blocks_x"], image["num_blocks_y"], image["width"], image["height"]
+    ep_pal = np.ascontiguousarray(decoded["endpoint_palette"], np.uint8).reshape(-1, 4)
+    sel_pal = np.ascontiguousarray(decoded["selector_palette"], np.uint32).reshape(-1)
+    with_alpha = image["alpha_endpoint_indices"] is not None and target in (RGBA32, RGBA4444)
+    names = ["endpoint_indices", "selector_indices"] + (["alpha_endpoint_indices", "alpha_selector_indices"] if with_alpha else [])
+    held = []
+    try:
+        for a in [ep_pal, sel_pal] + [np.ascontiguousarray(image[k], np.uint16).reshape(-1) for k in names]:
+            held.append(ctx.upload(a))
+        d_alpha = (held[4], held[5]) if with_alpha else (None, None)
+        nbytes = ctx.lib.etc1s_transcode_output_bytes(nbx, nby, w, h, target, 0, 0)
+        d_out = out_device if out_device is not None else ctx.alloc(max(nbytes, 1))
+        if out_device is None:
+            held.append(d_out)
+        invalid = C.c_uint32(0)
+        ctx.check(ctx.lib.k_transcode_etc1s_counted(ctx.h, C.c_void_p(held[0]), ep_pal.shape[0], C.c_void_p(held[1]), sel_pal.size, C.c_void_p(held[2]), C.c_void_p(held[3]),
+                                                    C.c_void_p(d_alpha[0]), C.c_void_p(d_alpha[1]), nbx, nby, w, h, target, C.c_void_p(d_out), int(out_row_pitch), int(out_rows),
+                                                    C.byref(invalid)), "transcode_etc1s")
+        if invalid.value:
+            raise ValueError(f"{invalid.value} of {nbx * nby} blocks have an index past its palette")
+        if out_device is not None:
+            return None
+        if target in ETC1S_BYTES_PER_BLOCK:
+            return ctx.download(d_out, (nbx * nby, 8), np.uint8)
+        return ctx.download(d_out, (h, w, 4), np.uint8) if target == RGBA32 else ctx.download(d_out, (h, w), np.uint16)
+    finally:
+        for p in held:
+            ctx.free(p)
+
+
+def transcode_etc1s_file(ctx, data, target, *, level=0, layer=0, face=0):
+    """One image of an ETC1S .basis / .ktx2 file: decoded on the host (decode_etc1s_file), transcoded on the GPU (transcode_etc1s_image)."""
+    target = _check_etc1s_target(target)
+    decoded = decode_etc1s_file(data)
+    for im in decoded["images"]:
+        if (im["level"], im["layer"], im["face"]) == (level, layer, face):
+            return transcode_etc1s_image(ctx, decoded, im, target)
     raise ValueError(f"the file has no image at level {level}, layer {layer}, face {face}")

@@ -307,6 +307,30 @@ BU_HIP_API int bu_hip_k_transcode_uastc(bu_hip_context*, const void* d_uastc_blo
         void* d_out, uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels, uint32_t* out_invalid_blocks);
 BU_HIP_API size_t bu_hip_transcode_output_bytes(uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height, uint32_t target);
 
+/* The texel half of basisu_lowlevel_etc1s_transcoder::transcode_slice (transcoder/basisu_transcoder.cpp:8858-9345) over resident palettes and per-block indices, which
+ * bu_etc1s_decode_file (basisu_hip_etc1s_decode.h) makes of an ETC1S .basis / .ktx2 file on the host. One lane per block, one launch per image.
+ *   d_endpoint_palette: n_endpoints x 4 bytes (r5, g5, b5, intensity table); d_selector_palette: n_selectors x uint32 (texel (x, y) at bits 2 * (y * 4 + x));
+ *   d_endpoint_idx / d_selector_idx: num_blocks_x * num_blocks_y uint16 each, raster order; d_alpha_*: the alpha slice's, both NULL = opaque (read by RGBA32 and
+ *   RGBA4444 only: alpha is the green channel of the alpha slice's decode).
+ * Supported targets (transcoder_texture_format): cTFETC1_RGB (0), cTFBC1_RGB (2), cTFRGBA32 (13), cTFRGB565 (14), cTFBGR565 (15), cTFRGBA4444 (16); any other fails
+ * with an error that names it. Block targets write 8 bytes per block in raster order; pixel targets write exactly orig_width x orig_height pixels (little-endian
+ * 16-bit words for the 16-bit formats) at out_row_pitch_pixels (0 = orig_width), rows cut at out_rows_pixels (0 = orig_height): a padded pitch stays untouched.
+ * bu_hip_k_transcode_etc1s first counts, on the device, the indices that are past their palette; if there is one it fails and the transcode is not launched.
+ * bu_hip_k_transcode_etc1s_counted skips that pass (for indices the host decoder has already range-checked): a block with an index past its palette is zero-filled
+ * and counted in *out_invalid_blocks, never gathered, and does not stop the others. Both synchronise to read their counter. */
+BU_HIP_API int bu_hip_k_transcode_etc1s(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette, uint32_t n_selectors,
+        const void* d_endpoint_idx, const void* d_selector_idx, const void* d_alpha_endpoint_idx, const void* d_alpha_selector_idx, uint32_t num_blocks_x, uint32_t num_blocks_y,
+        uint32_t orig_width, uint32_t orig_height, uint32_t target, void* d_out, uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
+BU_HIP_API int bu_hip_k_transcode_etc1s_counted(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette, uint32_t n_selectors,
+        const void* d_endpoint_idx, const void* d_selector_idx, const void* d_alpha_endpoint_idx, const void* d_alpha_selector_idx, uint32_t num_blocks_x, uint32_t num_blocks_y,
+        uint32_t orig_width, uint32_t orig_height, uint32_t target, void* d_out, uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels, uint32_t* out_invalid_blocks);
+/* The two ETC1S -> BC1 endpoint tables the BC1 target reads ([intensity table 8][base5 32][selector range 6][mapping 10] -> lo | hi << 8 | squared error << 16; 15,360
+ * words each, 5-bit and 6-bit endpoints), copied to the host. The library computes them on the device the first time a context needs them; tests compare them with
+ * tools/gen_etc1s_transcode_tables.py's host computation. */
+BU_HIP_API int bu_hip_etc1s_bc1_endpoint_tables(bu_hip_context*, uint32_t* h_out5, uint32_t* h_out6);
+BU_HIP_API size_t bu_hip_etc1s_transcode_output_bytes(uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height, uint32_t target,
+        uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
+
 /* a15 + the list handling inside a9 / a10 / a13 / a14: cluster bookkeeping on the device (basis_universal_amd/csrc/bookkeeping_kernels.hip).
  *     A clustering is two resident per-block arrays, cluster index and position inside the cluster's list; these calls turn distinct-vector level
  *     results into them, rebuild them after a reassignment, apply codebook renumberings to them and produce the CSR lists the per-cluster
