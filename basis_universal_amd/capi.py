@@ -61,6 +61,8 @@ _SIGNATURES = {
     "bu_hip_tsvq_exchange_pack": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "bu_hip_tsvq_exchange_unpack": (_int, [_vp, _vp, _vp, _vp, _vp, _u32]),
     "bu_hip_kmeans_codebook": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "bu_hip_k_kmeans_seed": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "bu_hip_k_kmeans_round": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _int, _vp, _vp, _vp]),
     "bu_hip_cancel_on_destroy": (None, [_vp, _vp, _vp]),
     "bu_hip_context_device": (_int, [_vp]),
     "bu_hip_set_stream": (_int, [_vp, _vp]),

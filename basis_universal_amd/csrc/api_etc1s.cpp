@@ -546,6 +546,57 @@ int bu_hip_kmeans_codebook(bu_hip_context* ctx, int kind, const void* d_keys, co
     return 1;
 }
 
+// the steps of the call above one at a time (kernel-level tests): the same functions launch_kmeans is made of, on the same workspace
+int bu_hip_k_kmeans_seed(bu_hip_context* ctx, int kind, const void* d_keys, const uint64_t* d_weights, const uint32_t* d_goffs, uint32_t n, uint32_t k, uint32_t* d_pick,
+                         float* d_centroids) {
+    if (!ctx) return 0;
+    if (!d_keys || !d_pick || !d_centroids || !n || !k || k > n || (kind == 0 && !d_weights) || (kind != 0 && !d_goffs)) {
+        set_error(ctx, "kmeans_seed: bad arguments");
+        return 0;
+    }
+    device_guard g(ctx->device);
+    arena& ws = ctx->scratch[3];
+    BU_TRY(ctx, ws.reserve(bu::kmeans_workspace_bytes(n, k)));
+    const bu::kmeans_buffers b = bu::kmeans_carve(ws.p, n, k);
+    const uint64_t* weights = nullptr;
+    BU_TRY(ctx, bu::kmeans_begin(ctx->stream, kind, d_keys, d_weights, d_goffs, n, b, &weights));
+    bu::kmeans_seed(ctx->stream, n, k, b);
+    BU_TRY(ctx, hipGetLastError());
+    BU_TRY(ctx, hipMemcpyAsync(d_pick, b.pick, (size_t)k * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    BU_TRY(ctx, hipMemcpyAsync(d_centroids, b.cen, (size_t)k * 16 * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    return 1;
+}
+
+int bu_hip_k_kmeans_round(bu_hip_context* ctx, int kind, const void* d_keys, const uint64_t* d_weights, const uint32_t* d_goffs, uint32_t n, uint32_t k, float* d_centroids,
+                          uint64_t* d_live, int update, uint32_t* d_assign, uint64_t* d_sums, uint64_t* d_worst) {
+    if (!ctx) return 0;
+    if (!d_keys || !d_centroids || !d_assign || !d_sums || !n || !k || k > n || (kind == 0 && !d_weights) || (kind != 0 && !d_goffs) || (update && !d_live)) {
+        set_error(ctx, "kmeans_round: bad arguments");
+        return 0;
+    }
+    device_guard g(ctx->device);
+    arena& ws = ctx->scratch[3];
+    BU_TRY(ctx, ws.reserve(bu::kmeans_workspace_bytes(n, k)));
+    const bu::kmeans_buffers b = bu::kmeans_carve(ws.p, n, k);
+    hipStream_t st = ctx->stream;
+    const uint64_t* weights = nullptr;
+    BU_TRY(ctx, bu::kmeans_begin(st, kind, d_keys, d_weights, d_goffs, n, b, &weights));
+    bu::kmeans_flags(st, kind, n, k, b);
+    BU_TRY(ctx, hipMemcpyAsync(b.cen, d_centroids, (size_t)k * 16 * 4, hipMemcpyDeviceToDevice, st));
+    // the live word of cluster c is where the rounds keep it: the weight word of its sums
+    if (d_live) bu::kmeans_set_live(st, d_live, k, b);
+    BU_TRY(ctx, bu::kmeans_assign_round(st, kind, weights, n, k, b, d_live != nullptr, update || d_worst, d_assign, 0));
+    BU_TRY(ctx, hipMemcpyAsync(d_sums, b.sums, (size_t)k * 17 * 8, hipMemcpyDeviceToDevice, st));
+    if (d_worst) BU_TRY(ctx, hipMemcpyAsync(d_worst, bu::kmeans_wg_worst(b), (size_t)bu::kmeans_workgroups(n) * 8, hipMemcpyDeviceToDevice, st));
+    if (update) {
+        BU_TRY(ctx, bu::kmeans_update_round(st, n, k, b));
+        BU_TRY(ctx, hipMemcpyAsync(d_centroids, b.cen, (size_t)k * 16 * 4, hipMemcpyDeviceToDevice, st));
+        bu::kmeans_get_live(st, d_live, k, b);
+    }
+    BU_TRY(ctx, hipGetLastError());
+    return 1;
+}
+
 int bu_hip_k_unique_endpoint_vectors(bu_hip_context* ctx, const void* d_etc1_blocks, uint32_t n_blocks, uint32_t* d_sorted_block_idx, uint64_t* d_unique_keys,
                                      uint32_t* d_group_offsets, uint32_t* out_unique) {
     if (!ctx) return 0;

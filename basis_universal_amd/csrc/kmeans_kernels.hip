@@ -128,7 +128,13 @@ __global__ __launch_bounds__(256) void k_km_reseed(const _Float16* __restrict__ 
     if (d == 0) sums[(size_t)c * 17 + 16] = 1;   // live again for the next assignment
 }
 
-// float centroids -> the GEMM operands: -2c as hi + lo halves, |c|^2 (rows past k and empty clusters get +inf: never the minimum)
+// The norm of a row that must never win (past k, or an empty cluster): far above any real key (< 2^24), yet FINITE. With +inf here the two tag bits of k_km_assign turned
+// the key of a group of four such rows into 0x7f800001..3, a signalling NaN; a v_min3_f32 that meets one in IEEE mode answers NaN (ISA manual), and then the whole
+// half-tile -- its live rows included -- loses every comparison (row 64 of k = 65, say). The compiler quiets the operands of some of these minimums, not of all (seen in
+// the generated code, not on a device): with a finite norm the question does not arise, and nothing else changes.
+constexpr float KM_DEAD_NORM = 1e30f;
+
+// float centroids -> the GEMM operands: -2c as hi + lo halves, |c|^2 (rows past k and empty clusters get KM_DEAD_NORM: never the minimum)
 __global__ __launch_bounds__(256) void k_km_prepare(const float* __restrict__ cen, const uint64_t* __restrict__ sums, uint32_t k, uint32_t k_pad, int have_sums,
                                                     _Float16* __restrict__ hi, _Float16* __restrict__ lo, float* __restrict__ cnorm) {
     const uint32_t c = blockIdx.x * 256 + threadIdx.x;
@@ -144,7 +150,7 @@ __global__ __launch_bounds__(256) void k_km_prepare(const float* __restrict__ ce
         const float cc = -0.5f * ((float)h + (float)l);   // the centroid the GEMM really uses
         nrm += cc * cc;
     }
-    cnorm[c] = live ? nrm : __builtin_inff();
+    cnorm[c] = live ? nrm : KM_DEAD_NORM;
 }
 
 // sums -> float centroids (empty clusters keep their place)
@@ -301,7 +307,7 @@ __global__ __launch_bounds__(256, 2) void k_km_assign(const _Float16* __restrict
 #pragma unroll
             for (uint32_t r = 0; r < 4; r++) {
                 const uint32_t c = first_row + r;
-                const bool live = cnorm[c] < __builtin_inff();   // not a row past k, nor an empty cluster
+                const bool live = cnorm[c] < KM_DEAD_NORM;   // not a row past k, nor an empty cluster
                 const half8 h0 = *reinterpret_cast<const half8*>(hi + (size_t)c * KM_DIM), h1 = *reinterpret_cast<const half8*>(hi + (size_t)c * KM_DIM + 8);
                 const half8 l0 = *reinterpret_cast<const half8*>(lo + (size_t)c * KM_DIM), l1 = *reinterpret_cast<const half8*>(lo + (size_t)c * KM_DIM + 8);
                 float dist = 0.0f;
@@ -372,6 +378,12 @@ __global__ __launch_bounds__(256) void k_km_unpack_sums(uint64_t* __restrict__ s
     sums[(size_t)c * 17 + d + 1] = v >> 32;
 }
 
+// the step entry points keep a cluster's live word where the rounds keep it (the weight word of its sums): a strided copy of k words, either way
+__global__ __launch_bounds__(256) void k_km_copy_words(uint64_t* __restrict__ dst, uint32_t dst_stride, const uint64_t* __restrict__ src, uint32_t src_stride, uint32_t k) {
+    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c < k) dst[(size_t)c * dst_stride] = src[(size_t)c * src_stride];
+}
+
 } // namespace
 
 // temporary storage of the two library calls launch_kmeans makes, sized from THOSE calls: the 64-bit key sort of one (error, index) key per assignment workgroup
@@ -417,48 +429,93 @@ kmeans_buffers kmeans_carve(void* ws, uint32_t n, uint32_t k) {
     return b;
 }
 
-hipError_t launch_kmeans(hipStream_t st, int endpoints, const void* d_keys, const uint64_t* d_weights, const uint32_t* d_goffs, uint32_t n, uint32_t k, uint32_t iterations,
-                         const kmeans_buffers& b, uint32_t* d_assign) {
-    if (!n || !k) return hipErrorInvalidValue;
+// The steps of launch_kmeans, one function each: bu_hip_kmeans_codebook runs them through launch_kmeans, the step entry points of the C ABI
+// (bu_hip_k_kmeans_seed, bu_hip_k_kmeans_round) call the same functions, so the launch sequence exists once.
+namespace {
+inline unsigned long long* km_wg_worst(const kmeans_buffers& b) { return reinterpret_cast<unsigned long long*>(b.err_key); }   // one key per workgroup of k_km_assign (the buffers hold n floats each)
+inline unsigned long long* km_wg_worst_sorted(const kmeans_buffers& b) { return reinterpret_cast<unsigned long long*>(b.err_key_sorted); }
+inline uint32_t* km_packed_ok(const kmeans_buffers& b, uint32_t k) { return b.empty + k + 1; }   // one more word behind the empty-cluster count
+}
+
+hipError_t kmeans_begin(hipStream_t st, int endpoints, const void* d_keys, const uint64_t* d_weights, const uint32_t* d_goffs, uint32_t n, const kmeans_buffers& b,
+                        const uint64_t** out_weights) {
+    if (!n) return hipErrorInvalidValue;
     _Float16* vec = static_cast<_Float16*>(b.vec);
-    _Float16* hi = static_cast<_Float16*>(b.hi);
-    _Float16* lo = static_cast<_Float16*>(b.lo);
     const dim3 gu((n + 255) / 256), blk(256);
     const uint64_t* weights = d_weights;
     if (endpoints) {
         hipLaunchKernelGGL(k_km_unpack_endpoints, gu, blk, 0, st, static_cast<const uint64_t*>(d_keys), d_goffs, n, vec, b.weights);
         weights = b.weights;
     } else hipLaunchKernelGGL(k_km_unpack_selectors, gu, blk, 0, st, static_cast<const uint32_t*>(d_keys), n, vec);
-    const dim3 gk((k * KM_DIM + 255) / 256), gp((b.k_pad + 255) / 256);
+    *out_weights = weights;
     size_t bytes = b.cub_bytes;
-    hipError_t e = hipcub::DeviceScan::InclusiveSum(b.cub, bytes, weights, b.cum, (int)n, st);
-    if (e != hipSuccess) return e;
+    return hipcub::DeviceScan::InclusiveSum(b.cub, bytes, weights, b.cum, (int)n, st);
+}
+
+void kmeans_seed(hipStream_t st, uint32_t n, uint32_t k, const kmeans_buffers& b) {
+    const dim3 gk((k * KM_DIM + 255) / 256), blk(256);
     hipLaunchKernelGGL(k_km_seed_pick, dim3((k + 255) / 256), blk, 0, st, b.cum, n, k, b.pick);
     hipLaunchKernelGGL(k_km_seed_distinct, dim3(1), dim3(1024), 0, st, b.pick, n, k);
-    hipLaunchKernelGGL(k_km_seed, gk, blk, 0, st, vec, b.pick, k, b.cen);
-    const dim3 ga((n + KM_WG_VECS - 1) / KM_WG_VECS);
+    hipLaunchKernelGGL(k_km_seed, gk, blk, 0, st, static_cast<const _Float16*>(b.vec), b.pick, k, b.cen);
+}
+
+void kmeans_flags(hipStream_t st, int endpoints, uint32_t n, uint32_t k, const kmeans_buffers& b) {
+    hipLaunchKernelGGL(k_km_flags, dim3(1), dim3(64), 0, st, b.cum, n, endpoints ? 255u : 3u, km_packed_ok(b, k));
+}
+
+uint32_t kmeans_workgroups(uint32_t n) { return (n + KM_WG_VECS - 1) / KM_WG_VECS; }
+
+hipError_t kmeans_assign_round(hipStream_t st, int endpoints, const uint64_t* weights, uint32_t n, uint32_t k, const kmeans_buffers& b, bool have_live, bool want_worst,
+                               uint32_t* d_assign, uint32_t debug_skip) {
+    _Float16* vec = static_cast<_Float16*>(b.vec);
+    _Float16* hi = static_cast<_Float16*>(b.hi);
+    _Float16* lo = static_cast<_Float16*>(b.lo);
+    const dim3 gp((b.k_pad + 255) / 256), blk(256), ga(kmeans_workgroups(n));
     const int dims = endpoints ? 6 : 16;
-    uint32_t* packed_ok = b.empty + k + 1;   // one more word behind the empty-cluster count
-    unsigned long long* wg_worst = reinterpret_cast<unsigned long long*>(b.err_key);            // one key per workgroup of k_km_assign (the buffers hold n floats each)
-    unsigned long long* wg_worst_sorted = reinterpret_cast<unsigned long long*>(b.err_key_sorted);
+    uint32_t* packed_ok = km_packed_ok(b, k);
+    hipError_t e;
+    hipLaunchKernelGGL(k_km_prepare, gp, blk, 0, st, b.cen, b.sums, k, b.k_pad, have_live ? 1 : 0, hi, lo, b.cnorm);
+    if ((e = hipMemsetAsync(b.sums, 0, (size_t)k * 17 * 8, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_km_assign, ga, blk, 0, st, vec, weights, n, hi, lo, b.cnorm, b.k_pad, d_assign, reinterpret_cast<unsigned long long*>(b.sums), dims,
+                       want_worst ? km_wg_worst(b) : nullptr, packed_ok, debug_skip);
+    hipLaunchKernelGGL(k_km_unpack_sums, dim3((k * 8 + 255) / 256), blk, 0, st, b.sums, k, packed_ok);
+    return hipSuccess;
+}
+
+hipError_t kmeans_update_round(hipStream_t st, uint32_t n, uint32_t k, const kmeans_buffers& b) {
+    const dim3 gk((k * KM_DIM + 255) / 256), blk(256), ga(kmeans_workgroups(n));
+    hipError_t e;
+    hipLaunchKernelGGL(k_km_update, gk, blk, 0, st, b.sums, k, b.cen);
+    // empty clusters move onto the workgroups' worst represented vectors (weighted error descending, index ascending among equals: the key order)
+    size_t bytes = b.cub_bytes;
+    if ((e = hipcub::DeviceRadixSort::SortKeysDescending(b.cub, bytes, km_wg_worst(b), km_wg_worst_sorted(b), (int)ga.x, 0, 64, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_km_list_empty, dim3(1), dim3(1024), 0, st, b.sums, k, b.empty, b.empty + k);
+    hipLaunchKernelGGL(k_km_reseed, gk, blk, 0, st, static_cast<const _Float16*>(b.vec), km_wg_worst_sorted(b), ga.x, b.empty, b.empty + k, b.cen, b.sums);
+    return hipSuccess;
+}
+
+const void* kmeans_wg_worst(const kmeans_buffers& b) { return km_wg_worst(b); }
+void kmeans_set_live(hipStream_t st, const uint64_t* d_live, uint32_t k, const kmeans_buffers& b) {
+    hipLaunchKernelGGL(k_km_copy_words, dim3((k + 255) / 256), dim3(256), 0, st, b.sums + 16, 17u, d_live, 1u, k);
+}
+void kmeans_get_live(hipStream_t st, uint64_t* d_live, uint32_t k, const kmeans_buffers& b) {
+    hipLaunchKernelGGL(k_km_copy_words, dim3((k + 255) / 256), dim3(256), 0, st, d_live, 1u, b.sums + 16, 17u, k);
+}
+
+hipError_t launch_kmeans(hipStream_t st, int endpoints, const void* d_keys, const uint64_t* d_weights, const uint32_t* d_goffs, uint32_t n, uint32_t k, uint32_t iterations,
+                         const kmeans_buffers& b, uint32_t* d_assign) {
+    if (!n || !k) return hipErrorInvalidValue;
+    const uint64_t* weights = nullptr;
+    hipError_t e = kmeans_begin(st, endpoints, d_keys, d_weights, d_goffs, n, b, &weights);
+    if (e != hipSuccess) return e;
+    kmeans_seed(st, n, k, b);
     static const uint32_t debug_skip = [] { const char* e = std::getenv("BU_KM_DEBUG_SKIP"); return e ? (uint32_t)std::atoi(e) : 0u; }();
-    hipLaunchKernelGGL(k_km_flags, dim3(1), dim3(64), 0, st, b.cum, n, endpoints ? 255u : 3u, packed_ok);
+    kmeans_flags(st, endpoints, n, k, b);
     for (uint32_t it = 0; it <= iterations; it++) {
-        hipLaunchKernelGGL(k_km_prepare, gp, blk, 0, st, b.cen, b.sums, k, b.k_pad, it != 0, hi, lo, b.cnorm);
-        if ((e = hipMemsetAsync(b.sums, 0, (size_t)k * 17 * 8, st)) != hipSuccess) return e;
         // the last round only assigns (its sums tell which clusters ended up non-empty)
         const bool more = it < iterations;
-        hipLaunchKernelGGL(k_km_assign, ga, blk, 0, st, vec, weights, n, hi, lo, b.cnorm, b.k_pad, d_assign, reinterpret_cast<unsigned long long*>(b.sums), dims,
-                           more ? wg_worst : nullptr, packed_ok, debug_skip);
-        hipLaunchKernelGGL(k_km_unpack_sums, dim3((k * 8 + 255) / 256), blk, 0, st, b.sums, k, packed_ok);
-        if (more) {
-            hipLaunchKernelGGL(k_km_update, gk, blk, 0, st, b.sums, k, b.cen);
-            // empty clusters move onto the workgroups' worst represented vectors (weighted error descending, index ascending among equals: the key order)
-            bytes = b.cub_bytes;
-            if ((e = hipcub::DeviceRadixSort::SortKeysDescending(b.cub, bytes, wg_worst, wg_worst_sorted, (int)ga.x, 0, 64, st)) != hipSuccess) return e;
-            hipLaunchKernelGGL(k_km_list_empty, dim3(1), dim3(1024), 0, st, b.sums, k, b.empty, b.empty + k);
-            hipLaunchKernelGGL(k_km_reseed, gk, blk, 0, st, vec, wg_worst_sorted, ga.x, b.empty, b.empty + k, b.cen, b.sums);
-        }
+        if ((e = kmeans_assign_round(st, endpoints, weights, n, k, b, it != 0, more, d_assign, debug_skip)) != hipSuccess) return e;
+        if (more && (e = kmeans_update_round(st, n, k, b)) != hipSuccess) return e;
     }
     return hipGetLastError();
 }

@@ -365,6 +365,19 @@ BU_HIP_API int bu_hip_k_map_gather(bu_hip_context*, const uint32_t* d_table, con
 BU_HIP_API int bu_hip_kmeans_codebook(bu_hip_context*, int kind, const void* d_keys, const uint64_t* d_weights, const uint32_t* d_group_offsets, uint32_t n_vectors,
     uint32_t max_clusters, uint32_t n_parents, uint32_t iterations, uint32_t* d_out_cluster_of_vector, uint32_t* d_out_parent_of_vector, uint32_t* out_clusters,
     uint32_t* out_parents);
+/*     The same steps one at a time, for kernel-level tests (tests/test_gpu_kmeans_kernels.py): the functions bu_hip_kmeans_codebook is made of, on the same
+ *     workspace; k <= n_vectors. Stream-ordered; nothing synchronises.
+ *   kmeans_seed: d_out_pick[k] = the distinct vector every centroid starts on (the weight quantiles (c + 1/2) / k, made strictly ascending),
+ *     d_out_centroids[k * 16] = those vectors as floats.
+ *   kmeans_round: one assignment round on the caller's d_centroids[k * 16]: d_out_assign[n] = the centroid of every vector (raw: empty clusters keep
+ *     their index), d_out_sums[k * 17] = per cluster the 16 weighted component sums and the weight, d_out_worst[ceil(n / 512)] (may be NULL) = per group of 512
+ *     vectors (float bits of the largest error x weight) << 32 | ~index of that vector. d_live[k] (NULL: all live): clusters whose word is 0 are dead and
+ *     never assigned. update != 0 (needs d_live): also the centroid update and the re-seeding of empty clusters; d_centroids and d_live are overwritten with
+ *     the next round's (live word = the cluster's weight, 1 for a re-seeded cluster, 0 for one left empty). */
+BU_HIP_API int bu_hip_k_kmeans_seed(bu_hip_context*, int kind, const void* d_keys, const uint64_t* d_weights, const uint32_t* d_group_offsets, uint32_t n_vectors, uint32_t k,
+    uint32_t* d_out_pick, float* d_out_centroids);
+BU_HIP_API int bu_hip_k_kmeans_round(bu_hip_context*, int kind, const void* d_keys, const uint64_t* d_weights, const uint32_t* d_group_offsets, uint32_t n_vectors, uint32_t k,
+    float* d_centroids, uint64_t* d_live, int update, uint32_t* d_out_assign, uint64_t* d_out_sums, uint64_t* d_out_worst);
 
 /* a8  tree_vector_quant (encoder/basisu_enc.h:1546-2078): the order-dependent TSVQ tree build, split by split, bit-exact.
  *     The host keeps the tree, the variance priority queue and the split order (enc.h:1616-1660); the device executes batches of
