@@ -292,7 +292,8 @@ bu_hip_context* create_context_kind(int device, bool want_dedicated) {
     // (a pooled queue, not a dedicated one: with EVERY context on a queue of its own the frontend pipeline lost 15-20 %, measured)
     if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) { set_error(nullptr, "hipStreamCreate failed"); delete ctx; return nullptr; }
     ctx->stream = ctx->own_stream;
-    hipError_t e = bu::upload_etc1s_tables(device);
+    hipError_t e = bu::upload_block_fit_tables();
+    if (e == hipSuccess) e = bu::upload_cluster_fit_tables();
     if (e != hipSuccess) { set_error(nullptr, "constant table upload failed: %s", hipGetErrorString(e)); (void)hipStreamDestroy(ctx->own_stream); delete ctx; return nullptr; }
     g_live_contexts.fetch_add(1);
     return ctx;

@@ -45,7 +45,7 @@ struct bu_hip_context {
     // UASTC pipeline lanes with reserved walk CUs (bu_hip_tuning::uastc_walk_cus): the lean strip walk of uastc_rdo goes to walk_stream, whose CU mask is the reserved
     // set; own_stream (and with it everything that fills the chip) is masked to the OTHER CUs, side_stream (the walk with the refit in it) to the reserved ones
     hipStream_t walk_stream = nullptr; hipEvent_t walk_join = nullptr; uint32_t walk_cus = 0;
-    arena refine_lists;                   // the sorted candidate lists of refine_endpoint_clusterization (etc1s_kernels.hip, k_refine_sort_lists)
+    arena refine_lists;                   // the sorted candidate lists of refine_endpoint_clusterization (etc1s_refine_kernels.hip, k_refine_sort_lists)
     arena etc1s_bc1_tables;               // the ETC1S -> BC1 endpoint tables (api_etc1s_transcode.cpp), built by the first BC1 transcode of the context
     const void* d_pixel_blocks = nullptr; // resident tiles (a1): 64 B per block
     size_t total_blocks = 0;

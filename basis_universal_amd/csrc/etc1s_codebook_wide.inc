@@ -1,5 +1,5 @@
 // etc1s_codebook_wide.inc -- a9 (generate_endpoint_codebook, frontend.cpp:1482-1613) and the cluster fit with forced selectors (frontend.cpp:2718-2976, 2996-3104)
-// for LARGE clusters. Included by etc1s_kernels.hip behind k_generate_endpoint_codebook, whose helpers it uses.
+// for LARGE clusters. Included by etc1s_cluster_fit_kernels.hip behind k_generate_endpoint_codebook, whose helpers it uses.
 //
 // k_generate_endpoint_codebook gives a cluster ONE workgroup. That is right for the synthetic bench image (2,416 clusters of ~7,000 texels) and wrong for
 // photographs: a sky, a flat wall or a constant alpha plane is one cluster of 10^5-10^7 texels, and its workgroup walks it 17 times (the trials depend on each
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void k_cbw_init(const uint32_t* __restrict__ p
             prev += cdist<PERCEPTUAL>(pixel_cvec<PERCEPTUAL>(w), select_cvec(bc, cluster_pixel_selector(enc_blocks, members, j)));
         }
     }
-    sr = wave_sum_u64(sr); sg = wave_sum_u64(sg); sb = wave_sum_u64(sb); prev = wave_sum_u64(prev);
+    sr = wave_allsum_u64(sr); sg = wave_allsum_u64(sg); sb = wave_allsum_u64(sb); prev = wave_allsum_u64(prev);
     mn_r = wave_min_i32(mn_r); mn_g = wave_min_i32(mn_g); mn_b = wave_min_i32(mn_b);
     mx_r = wave_max_i32(mx_r); mx_g = wave_max_i32(mx_g); mx_b = wave_max_i32(mx_b);
     if ((threadIdx.x & 63u) == 0) {
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256) void k_cbw_eval(const uint32_t* __restrict__ p
     }
 #pragma unroll
     for (int t = 0; t < 8; t++) {
-        const uint64_t s = wave_sum_u64(tot[t]);
+        const uint64_t s = wave_allsum_u64(tot[t]);
         if ((threadIdx.x & 63u) == 0 && s) atomicAdd(&st.tot[t], (unsigned long long)s);
     }
 }
@@ -387,11 +387,8 @@ hipError_t launch_codebook_wide(hipStream_t st, const void* d_pixel_blocks, cons
     const uint32_t* pw = static_cast<const uint32_t*>(d_pixel_blocks);
     const uint64_t* enc = static_cast<const uint64_t*>(d_enc_blocks);
     if (quality < BU_Q_MEDIUM) quality = BU_Q_MEDIUM;   // (as the one-workgroup launches)
-#define BU_CBW(P, Q, F) cbw_launch<P, Q, F>(st, pw, d_indices, pl, step, d_params, d_err, d_valid, enc, d_cur_err)
-#define BU_CBW_Q(P, F) do { if (quality == BU_Q_MEDIUM) BU_CBW(P, BU_Q_MEDIUM, F); else if (quality == BU_Q_SLOW) BU_CBW(P, BU_Q_SLOW, F); else BU_CBW(P, BU_Q_UBER, F); } while (0)
-    if (perceptual) { if (forced) BU_CBW_Q(true, true); else BU_CBW_Q(true, false); }
-    else { if (forced) BU_CBW_Q(false, true); else BU_CBW_Q(false, false); }
-#undef BU_CBW_Q
-#undef BU_CBW
+    with_bool(perceptual, [&](auto p) { with_bool(forced, [&](auto f) { with_quality<BU_Q_MEDIUM>(quality, [&](auto q) {
+        cbw_launch<decltype(p)::value, decltype(q)::value, decltype(f)::value>(st, pw, d_indices, pl, step, d_params, d_err, d_valid, enc, d_cur_err);
+    }); }); });
     return hipGetLastError();
 }

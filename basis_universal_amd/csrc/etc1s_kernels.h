@@ -1,4 +1,19 @@
-// etc1s_kernels.h -- host-side launch interface of etc1s_kernels.hip (internal to libbasisu_hip.so).
+// etc1s_kernels.h -- host-side launch interface of the ETC1S frontend's kernels (internal to libbasisu_hip.so). One unit per stage:
+//   etc1s_block_fit_kernels.hip    a6   the per-block etc1_optimizer                          } etc1s_fit_common.h: what the two fits share
+//   etc1s_cluster_fit_kernels.hip  a9   the cluster fit, free and with forced selectors       }   (+ etc1s_codebook_wide.inc: large clusters)
+//   etc1s_refine_kernels.hip       a10  refine_endpoint_clusterization, plain and pre-sorted lists
+//   etc1s_selector_kernels.hip     a11-a14  determine_selectors, selector training vectors, k_cosc_*, k_fosc_*
+//   etc1s_misc_kernels.hip         a7, sub-block errors, the backend's block errors, k_extract_blocks
+//
+// All kernels are integer-ALU bound (hundreds of integer ops per byte of pixel data), so the design rules are:
+//   * wave64 mappings that keep all 64 lanes on the SAME kind of work -- and where a wave's blocks need different NUMBERS of steps (the per-block fit's trials), the
+//     cheap part (finding the next step worth taking) loops per block while the expensive part (evaluating it) runs for all blocks at once;
+//   * the 64-byte pixel tile is read once per kernel with 16-byte loads and kept in registers in the metric's separable
+//     basis (etc1s_device.h: cvec), so a colour distance is 3 subtractions + 3 24-bit multiplies + shifts;
+//   * wavefront reductions (DPP/ds_swizzle via __shfl_xor) pick the best intensity table / candidate, with the
+//     reference's tie rules encoded in the reduction key (lowest index wins on equal error);
+//   * candidate codebooks are read through the scalar/vector caches (they are KB-sized and shared by all lanes).
+// Result parity with the reference CPU encoder is bit-exact; each kernel cites the code it restates.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,7 +23,9 @@ namespace bu {
 
 enum { BU_Q_FAST = 0, BU_Q_MEDIUM = 1, BU_Q_SLOW = 2, BU_Q_UBER = 3 }; // basis_etc_quality, basisu_etc.h:794-801
 
-hipError_t upload_etc1s_tables(int device);
+// the two etc1_optimizer tables of the per-block and of the cluster fit unit, onto the current device (every new context calls both)
+hipError_t upload_block_fit_tables();
+hipError_t upload_cluster_fit_tables();
 
 hipError_t launch_encode_etc1s_blocks(hipStream_t st, const void* d_pixel_blocks, uint32_t n_blocks, int quality, bool perceptual, void* d_out);
 hipError_t launch_endpoint_training_vectors(hipStream_t st, const void* d_etc_blocks, uint32_t n_blocks, float* d_out6);

@@ -12,6 +12,7 @@
 // HBM bound in principle (4 B in, 16 B intermediate, 4 B out per pixel, lists and tables in cache); a mip chain is ~1/3 of one pass over
 // the image, so no tiling through LDS is attempted.
 #include "mipmap_kernels.h"
+#include "launch_dispatch.h"
 
 namespace bu {
 namespace {
@@ -89,8 +90,6 @@ __global__ __launch_bounds__(256) void k_second(const float4* __restrict__ tmp, 
 }
 
 }  // namespace
-
-#define BU_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
 
 hipError_t launch_resample_rgba8(hipStream_t st, const void* d_src, uint32_t src_w, uint32_t src_h, void* d_dst, uint32_t dst_w, uint32_t dst_h,
                                  const uint32_t* d_x_first, const uint16_t* d_x_pixel, const float* d_x_weight,

@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/../basis_universal_amd/csrc"
 echo "# hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage, $(git rev-parse --short HEAD 2>/dev/null)"
 echo "# file | kernel | VGPRs | AGPRs | SGPRs | scratch B/lane | LDS B/workgroup | occupancy waves/SIMD"
-for f in etc1s_kernels tsvq_kernels tsvq_wide_kernels tsvq_wide6_kernels unique_kernels bookkeeping_kernels kmeans_kernels mipmap_kernels uastc_kernels uastc_rdo_kernels; do
+for f in etc1s_block_fit_kernels etc1s_cluster_fit_kernels etc1s_refine_kernels etc1s_selector_kernels etc1s_misc_kernels tsvq_kernels tsvq_wide_kernels tsvq_wide6_kernels unique_kernels bookkeeping_kernels kmeans_kernels mipmap_kernels uastc_kernels uastc_rdo_kernels; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off --cuda-device-only -c -Rpass-analysis=kernel-resource-usage -o /dev/null $f.hip 2>&1 |
   awk -v F=$f '
     /Function Name:/ { name=$0; sub(/.*Function Name: /,"",name); sub(/ \[-Rpass.*/,"",name) }

@@ -34,7 +34,7 @@ from rocprof_summary import short  # noqa: E402
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 CSRC = ROOT / "basis_universal_amd" / "csrc"
-SOURCES = ["etc1s_kernels.hip", "uastc_kernels.hip", "uastc_rdo_kernels.hip"]
+SOURCES = ["etc1s_block_fit_kernels.hip", "etc1s_cluster_fit_kernels.hip", "etc1s_refine_kernels.hip", "etc1s_selector_kernels.hip", "etc1s_misc_kernels.hip", "uastc_kernels.hip", "uastc_rdo_kernels.hip"]
 DEFAULT_CYCLES = 4.1   # opcodes the calibration did not time are priced like the 4-cycle class (every multi-operand / non-trivial opcode measured sits there)
 
 
