@@ -105,6 +105,7 @@ _SIGNATURES = {
     "bu_hip_k_transcode_etc1s_counted": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _u32, _vp]),
     "bu_hip_etc1s_bc1_endpoint_tables": (_int, [_vp, _vp, _vp]),
     "bu_hip_etc1s_transcode_output_bytes": (C.c_size_t, [_u32, _u32, _u32, _u32, _u32, _u32, _u32]),
+    "bu_hip_k_image_metrics": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _u32, _u32, _vp]),
     "bu_hip_tsvq_create_packed16_device": (_vp, [_vp, _vp, _vp, _u32, _vp]),
     "bu_hip_k_unique_endpoint_vectors": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "bu_hip_k_unique_selector_vectors": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),

@@ -45,14 +45,16 @@ def unified_quality_effort(uastc, quality=-1, effort=-1):
 
 
 def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=_uastc.LEVEL_DEFAULT, uastc_rdo_lambda=None, uastc_rdo_jobs=1, mipmaps=False,
-             ktx2=False, srgb=True, key_values=(), max_threads=0):
+             ktx2=False, srgb=True, key_values=(), max_threads=0, stats=None):
     """image: (h, w, 4) uint8 RGBA. Returns the file as a uint8 array.
     ETC1S: quality 1-255 (`-q`), comp_level 0-6 (`-comp_level`). UASTC: uastc_level 0-4, uastc_rdo_lambda (`-uastc_rdo_l`; None = no post-pass, any float
     incl. 0.0 = post-pass on, as m_rdo_uastc_ldr_4x4 + its scalar), uastc_rdo_jobs = the strips of the post-pass (the reference: min(4, pool threads) when
     multithreaded, else 1; comp.cpp:2078). `**unified_quality_effort(...)` gives the settings of `-quality` / `-effort`.
     max_threads: the reference's codebook-thread configuration (0 / 1 = `-no_multithreading`; T > 1 = the T-way partitioned codebook build its
     multi-threaded default takes from 262,144 distinct training vectors up, enc.h:2086-2215: etc1s.reference_max_threads() gives the T a host would use).
-    mipmaps: the compressor's defaults (Kaiser, sRGB-aware, wrapping, down to 1x1). srgb: perceptual metrics + sRGB transfer function flag."""
+    mipmaps: the compressor's defaults (Kaiser, sRGB-aware, wrapping, down to 1x1). srgb: perceptual metrics + sRGB transfer function flag.
+    stats: a list to be filled with the reference's per-slice quality stats of the file (m_compute_stats; stats.file_stats) against the level rasters and split
+    planes that are resident here anyway; None = the stage does not run: the call's launches and bytes are what they are without it."""
     img = np.ascontiguousarray(image, np.uint8)
     if img.ndim != 3 or img.shape[2] != 4:
         raise ValueError("image must be (h, w, 4) uint8")
@@ -76,7 +78,7 @@ def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=
         total_blocks = sum(per_level) * (2 if split_alpha else 1)
         d_all = ctx.alloc(total_blocks * 64)   # one contiguous tile array: the levels (and the alpha slices) share the codebooks
         owned.append(d_all)
-        slices, slice_blocks, first = [], [], 0
+        slices, slice_blocks, first, level_planes = [], [], 0, []
         for mip, ((lw, lh), d_raster) in enumerate(zip(sizes, rasters)):
             nbx, nby = (lw + 3) // 4, (lh + 3) // 4
             if split_alpha:
@@ -87,11 +89,18 @@ def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=
                 owned.extend(planes)
             else:
                 planes = [d_raster]
+            level_planes.append([(d_plane, lw, lh, lw) for d_plane in planes])
             for k, d_plane in enumerate(planes):   # basis_compressor::extract_source_blocks on the resident plane, straight into its place
                 ctx.check(ctx.lib.k_extract_blocks(ctx.h, d_plane, lw, lh, lw * 4, d_all + first * 64), "k_extract_blocks")
                 slices.append((first, nbx, nby, lw, lh, 0, mip, k if split_alpha else int(has_alpha)))
                 slice_blocks.append(nbx * nby)
                 first += nbx * nby
+
+        def finish(data):   # m_compute_stats (comp.cpp:4195-4253) while the sources are still resident
+            if stats is not None:
+                from . import stats as _stats
+                stats.extend(_stats._stats_from_slices(ctx, bytes(data), lambda level, layer, face, n_slices: level_planes[level]))
+            return data
         # ---- encode
         if uastc:
             rdo = uastc_rdo_lambda is not None and uastc_rdo_lambda is not False
@@ -106,10 +115,10 @@ def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=
                     at += n
             packed = ctx.download(d_out, (total_blocks, 16), np.uint8)
             if ktx2:
-                return uastc_ktx2_file(packed, slices, srgb=srgb, has_alpha=has_alpha, key_values=key_values)
+                return finish(uastc_ktx2_file(packed, slices, srgb=srgb, has_alpha=has_alpha, key_values=key_values))
             # encode_slices_to_uastc_4x4_ldr (comp.cpp:1973-1985) never sets basisu_backend_output::m_srgb, which basisu_backend_output::clear() leaves true
             # (backend.h:243): the reference's UASTC .basis files carry the sRGB header flag whatever -linear says (the .ktx2 DFD does follow the option)
-            return uastc_basis_file(packed, slices, srgb=True, key_values=key_values)
+            return finish(uastc_basis_file(packed, slices, srgb=True, key_values=key_values))
         max_ep, max_sel = quality_to_clusters(quality, total_blocks)
         fe = Etc1sFrontend(ctx, max_threads=max_threads)
         try:
@@ -119,7 +128,7 @@ def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=
             be = Etc1sBackend.from_frontend(fe, slices, ept, selt, comp_level)
             try:
                 be.encode()
-                return be.ktx2_file(has_alpha=has_alpha, key_values=key_values) if ktx2 else be.basis_file(key_values=key_values)
+                return finish(be.ktx2_file(has_alpha=has_alpha, key_values=key_values) if ktx2 else be.basis_file(key_values=key_values))
             finally:
                 be.close()
         finally:

@@ -1,0 +1,174 @@
+"""How good is the file: the last stage of basis_compressor::process (m_compute_stats, comp.cpp:4195-4253), the per-slice image_stats `basisu -stats` prints --
+RGB / RGBA / R / G / B / A / 709-luma / 601-luma Max, Mean, RMS and PSNR of what the file decodes to against the source.
+
+image_metrics::calc (encoder/basisu_enc.cpp:2155-2226) is a 256-bin histogram of absolute differences under a thin layer of doubles. The histograms (and the channel
+sums) of all eight lines are counted on the GPU in one pass over two resident RGBA8 rasters (csrc/image_metrics_kernels.hip, bu_hip_k_image_metrics): integer counts,
+hence exactly the reference's, whatever the order of accumulation. The doubles are host code in the reference's own expression order (csrc/image_metrics.h,
+bu_image_metrics_reduce in libbasisu_frontend.so). The decode that is compared is the device transcoders' RGBA32 (transcode.py), resident, never downloaded.
+There is no CPU implementation of the counting: without the HIP library and a GPU `image_metrics` raises. No SSIM: this overload of calc never sets m_ssim."""
+import ctypes as C
+
+import numpy as np
+
+from . import transcode
+
+# name -> (first_chan, total_chans, use_601), in the order the reference prints them (comp.cpp:4213-4252)
+LINES = {"rgb": (0, 3, 0), "rgba": (0, 4, 0), "r": (0, 1, 0), "g": (1, 1, 0), "b": (2, 1, 0), "a": (3, 1, 0), "luma_709": (0, 0, 0), "luma_601": (0, 0, 1)}
+
+
+class Counts(C.Structure):      # = bu_image_metrics_counts, include/basisu_hip.h
+    _fields_ = [("struct_bytes", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("reserved", C.c_uint32), ("hist", C.c_uint32 * 256 * 6),
+                ("sum_a", C.c_uint64 * 4), ("sum_b", C.c_uint64 * 4)]
+
+
+class _Metrics(C.Structure):    # = bu_image_metrics, include/basisu_hip_image_metrics.h
+    _fields_ = [("max", C.c_double), ("mean", C.c_float), ("mean_squared", C.c_float), ("rms", C.c_float), ("psnr", C.c_float)]
+
+
+def _reduce_lib():
+    from .etc1s import load_frontend_library
+    L = load_frontend_library()
+    if not getattr(L, "_image_metrics_bound", False):
+        L.bu_image_metrics_reduce.restype = C.c_int
+        L.bu_image_metrics_reduce.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_Metrics)]
+        L._image_metrics_bound = True
+    return L
+
+
+def reduce_counts(hist, width, height):
+    """hist (6, 256) u32 as bu_hip_k_image_metrics counts it -> {line: {"max", "mean", "rms", "psnr"}} for the eight lines of LINES. Host only."""
+    hist = np.ascontiguousarray(hist, np.uint32)
+    if hist.shape != (6, 256):
+        raise ValueError("hist must be (6, 256)")
+    L, out = _reduce_lib(), {}
+    for name, (first, total, use_601) in LINES.items():
+        m = _Metrics()
+        if not L.bu_image_metrics_reduce(hist.ctypes.data_as(C.c_void_p), total, first, int(width), int(height), use_601, C.byref(m)):
+            raise ValueError(f"bu_image_metrics_reduce refused {name}")
+        out[name] = {"max": float(m.max), "mean": float(m.mean), "rms": float(m.rms), "psnr": float(m.psnr)}
+    return out
+
+
+def _resident(ctx, raster, owned):
+    """a numpy (h, w, 4) u8 image (uploaded; the pointer goes to `owned`) or a (device pointer, w, h, pitch in pixels) tuple -> that tuple"""
+    if isinstance(raster, np.ndarray):
+        img = np.ascontiguousarray(raster, np.uint8)
+        if img.ndim != 3 or img.shape[2] != 4:
+            raise ValueError("an image must be (h, w, 4) uint8")
+        d = ctx.upload(img)
+        owned.append(d)
+        return d, img.shape[1], img.shape[0], img.shape[1]
+    d, w, h, pitch = raster
+    return int(d), int(w), int(h), int(pitch)
+
+
+def image_counts(ctx, a, b):
+    """bu_hip_k_image_metrics: a, b as for image_metrics -> (hist (6, 256) u32, sum_a (4,) u64, sum_b (4,) u64, width, height) of the region both cover."""
+    owned = []
+    try:
+        (da, wa, ha, pa), (db, wb, hb, pb) = _resident(ctx, a, owned), _resident(ctx, b, owned)
+        c = Counts()
+        c.struct_bytes = C.sizeof(Counts)
+        ctx.check(ctx.lib.k_image_metrics(ctx.h, C.c_void_p(da), wa, ha, pa, C.c_void_p(db), wb, hb, pb, C.byref(c)), "image_metrics")
+        return np.ctypeslib.as_array(c.hist).copy(), np.array(list(c.sum_a), np.uint64), np.array(list(c.sum_b), np.uint64), int(c.width), int(c.height)
+    finally:
+        for d in owned:
+            ctx.free(d)
+
+
+def image_metrics(ctx, a, b):
+    """image_metrics::calc of `a` against `b` for every line the reference prints. a, b: (h, w, 4) u8 arrays (uploaded) or (device pointer, width, height, row pitch
+    in pixels, 0 = width) tuples of resident RGBA8 rasters; the region is min(widths) x min(heights), as calc crops.
+    -> {"rgb", "rgba", "r", "g", "b", "a", "luma_709", "luma_601": {"max", "mean", "rms", "psnr"}, "sum_a", "sum_b": per-channel sums (4 ints each), "width", "height"}.
+    avg_comp_error = true throughout, as basis_compressor calls it. An empty region has the reference's 0 / 0 (NaN) means."""
+    hist, sum_a, sum_b, w, h = image_counts(ctx, a, b)
+    out = reduce_counts(hist, w, h)
+    out.update({"sum_a": [int(v) for v in sum_a], "sum_b": [int(v) for v in sum_b], "width": w, "height": h})
+    return out
+
+
+def _is_etc1s(raw):
+    if len(raw) >= 48 and raw[:12] == transcode._KTX2_MAGIC:
+        return int.from_bytes(raw[44:48], "little") == 1     # supercompressionScheme: 1 = BasisLZ (ETC1S), 0 = none (UASTC)
+    if len(raw) >= 21 and raw[:2] == b"sB":
+        return raw[20] == 0                                   # basis_file_header::m_tex_format: 0 = ETC1S, 1 = UASTC 4x4
+    raise ValueError("neither a .basis nor a .ktx2 file")
+
+
+def split_planes(image):
+    """The two source images of an ETC1S image with alpha (comp.cpp:2880-2910): (r, g, b, 255) and (a, a, a, 255)."""
+    img = np.ascontiguousarray(image, np.uint8)
+    colour = img.copy()
+    colour[..., 3] = 255
+    alpha = np.repeat(img[..., 3:4], 4, axis=2)
+    alpha[..., 3] = 255
+    return colour, alpha
+
+
+def _slice_order(images):
+    """the compressor's slice order: source image (layer, face) outermost, then its levels"""
+    return sorted(range(len(images)), key=lambda k: (images[k]["layer"], images[k]["face"], images[k]["level"]))
+
+
+def _stats_from_slices(ctx, raw, slice_sources):
+    """slice_sources(level, layer, face, n_slices) -> one source raster per slice of that image (array or resident tuple). -> the per-slice dicts, slice order."""
+    out = []
+    if _is_etc1s(raw):
+        decoded = transcode.decode_etc1s_file(raw)
+        for k in _slice_order(decoded["images"]):
+            im = decoded["images"][k]
+            w, h = im["width"], im["height"]
+            # the alpha slice is decoded as a colour image from the alpha indices, as the reference unpacks every slice on its own
+            parts = [dict(im, alpha_endpoint_indices=None, alpha_selector_indices=None)]
+            if im["has_alpha"]:
+                parts.append(dict(im, endpoint_indices=im["alpha_endpoint_indices"], selector_indices=im["alpha_selector_indices"], alpha_endpoint_indices=None,
+                                  alpha_selector_indices=None))
+            sources = slice_sources(im["level"], im["layer"], im["face"], len(parts))
+            d_out = ctx.alloc(w * h * 4)
+            try:
+                for part, src in zip(parts, sources):
+                    transcode.transcode_etc1s_image(ctx, decoded, part, transcode.RGBA32, out_device=d_out)
+                    out.append(image_metrics(ctx, src, (d_out, w, h, w)))
+            finally:
+                ctx.free(d_out)
+        return out
+    info = transcode.read_uastc_file(raw)
+    for k in _slice_order(info["images"]):
+        im = info["images"][k]
+        w, h = im["width"], im["height"]
+        blocks = np.frombuffer(raw, np.uint8, im["length"], im["offset"]).reshape(-1, 16)
+        (src,) = slice_sources(im["level"], im["layer"], im["face"], 1)
+        d_out = ctx.alloc(w * h * 4)
+        try:
+            transcode.transcode_uastc_blocks(ctx, blocks, im["num_blocks_x"], im["num_blocks_y"], transcode.RGBA32, width=w, height=h, out_device=d_out)
+            out.append(image_metrics(ctx, src, (d_out, w, h, w)))
+        finally:
+            ctx.free(d_out)
+    return out
+
+
+def file_stats(ctx, data, images):
+    """The reference's m_stats for a .basis / .ktx2 file of this package (UASTC LDR 4x4 or ETC1S): one image_metrics dict per slice, in the compressor's slice order
+    (source image outermost, then its levels; an ETC1S image with alpha has a colour slice and then an alpha slice, each with its own stats).
+    images: the source of every image the file holds -- {(level, layer, face): image} or, for a file of one layer and face, a list by level; an image is an
+    (h, w, 4) u8 array or a resident (device pointer, width, height, pitch) tuple. The file is decoded on the device to RGBA32 (transcode_uastc_blocks /
+    decode_etc1s_file + transcode_etc1s_image), cropped to each slice's original size, and compared there. A colour slice of an ETC1S file with alpha is compared
+    against (r, g, b, 255), its alpha slice -- decoded as a colour image -- against (a, a, a, 255)."""
+    raw = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
+    by_key = images if isinstance(images, dict) else {(level, 0, 0): im for level, im in enumerate(images)}
+
+    def slice_sources(level, layer, face, n_slices):
+        if (level, layer, face) not in by_key:
+            raise ValueError(f"no source image for level {level}, layer {layer}, face {face}")
+        src = by_key[(level, layer, face)]
+        if n_slices == 1:
+            return [src]
+        if not isinstance(src, np.ndarray):
+            d, w, h, pitch = (int(v) for v in src)
+            pitch = pitch or w
+            rows = np.zeros((h, pitch, 4), np.uint8)      # a raster ends with its last pixel, not with its last row's padding
+            if w and h:
+                rows.reshape(-1, 4)[:(h - 1) * pitch + w] = ctx.download(d, ((h - 1) * pitch + w, 4), np.uint8)
+            src = rows[:, :w]
+        return list(split_planes(src))
+    return _stats_from_slices(ctx, raw, slice_sources)

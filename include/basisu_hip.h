@@ -331,6 +331,26 @@ BU_HIP_API int bu_hip_etc1s_bc1_endpoint_tables(bu_hip_context*, uint32_t* h_out
 BU_HIP_API size_t bu_hip_etc1s_transcode_output_bytes(uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height, uint32_t target,
         uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
 
+/* The counting half of image_metrics::calc (encoder/basisu_enc.cpp:2155-2226) for all eight lines basis_compressor's m_compute_stats stage reports per slice
+ * (comp.cpp:4195-4253), in one pass over two resident RGBA8 rasters (4 bytes per pixel, 4-byte aligned; a row pitch in pixels, 0 = the width; each raster reaches
+ * to pixel (height - 1) * pitch + width). The region compared is min(width_a, width_b) x min(height_a, height_b), as calc crops; at most 16384 each way.
+ *   hist[row][d]: how many values of the region differ by d = |a - b|; rows 0-3 = R, G, B, A, 4 = 709 luma, 5 = 601 luma ((13938 r + 46869 g + 4729 b + 32768) >> 16
+ *   and (19595 r + 38470 g + 7471 b + 32768) >> 16, per image, then differenced). sum_a / sum_b: per-channel sums of each image over the region (calc's m_sum_a /
+ *   m_sum_b of a channel set are sums of these). Integer counts: exact and the same on every run. bu_image_metrics_reduce (basisu_hip_image_metrics.h, host code)
+ *   turns them into Max / Mean / RMS / PSNR in the reference's own expression order.
+ * Versioned by size like bu_hip_tuning: the caller sets struct_bytes = sizeof(bu_image_metrics_counts) of its header; at most that many bytes are written (and
+ * struct_bytes itself is left alone). One launch on the context's stream (none for an empty region, whose counts are zero); synchronises to copy the counts out.
+ * Fails -- nothing launched, *h_out untouched -- on a null pointer, a misaligned raster, a pitch below its width or a region beyond 16384. */
+typedef struct bu_image_metrics_counts {
+    uint32_t struct_bytes;
+    uint32_t width, height;       /* the region compared */
+    uint32_t reserved;
+    uint32_t hist[6][256];
+    uint64_t sum_a[4], sum_b[4];
+} bu_image_metrics_counts;
+BU_HIP_API int bu_hip_k_image_metrics(bu_hip_context*, const void* d_a, uint32_t width_a, uint32_t height_a, uint32_t pitch_a_pixels, const void* d_b, uint32_t width_b,
+        uint32_t height_b, uint32_t pitch_b_pixels, bu_image_metrics_counts* h_out);
+
 /* a15 + the list handling inside a9 / a10 / a13 / a14: cluster bookkeeping on the device (basis_universal_amd/csrc/bookkeeping_kernels.hip).
  *     A clustering is two resident per-block arrays, cluster index and position inside the cluster's list; these calls turn distinct-vector level
  *     results into them, rebuild them after a reassignment, apply codebook renumberings to them and produce the CSR lists the per-cluster

@@ -1,0 +1,30 @@
+/* include/basisu_hip_image_metrics.h -- the float half of image_metrics::calc (encoder/basisu_enc.cpp:2205-2225): the counts of bu_hip_k_image_metrics
+ * (basisu_hip.h) -> Max / Mean / RMS / PSNR as `basisu -stats` prints them per slice. Host code, lives in libbasisu_frontend.so
+ * (basis_universal_amd/csrc/host/image_metrics.cpp over csrc/image_metrics.h); needs no GPU.
+ *
+ * The reference's expression order: 256 bins in ascending order, sum += i * h[i] and sum2 += i * (i * h[i]) in double; mean, mean_squared and rms narrowed to float;
+ * psnr = rms ? clamp(log10(255.0 / rms) * 20, 0, 100) : 100; avg_comp_error = true as basis_compressor calls it (the divisor is width * height * channels).
+ * This overload of calc never sets m_ssim, so there is no SSIM here.
+ */
+#ifndef BASISU_HIP_IMAGE_METRICS_H
+#define BASISU_HIP_IMAGE_METRICS_H
+#include "basisu_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct bu_image_metrics {
+    double max;                                /* m_max: the largest difference that occurs */
+    float mean, mean_squared, rms, psnr;
+} bu_image_metrics;
+
+/* hist: bu_image_metrics_counts::hist, 6 x 256. total_chans 1..4: channels first_chan .. first_chan + total_chans - 1 counted into one histogram (RGB Avg = 3 from 0,
+ * RGBA Avg = 4 from 0, a single channel = 1 from its index); total_chans 0: a luma row, 601 when use_601 is set, else 709. Returns 0 (and leaves *out alone) on a null
+ * pointer or a channel range past 4. */
+BU_HIP_API int bu_image_metrics_reduce(const uint32_t* hist, uint32_t total_chans, uint32_t first_chan, uint32_t width, uint32_t height, int use_601, bu_image_metrics* out);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
