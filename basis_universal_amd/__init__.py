@@ -2,6 +2,7 @@
 
 Layers:
   csrc/   hand-written gfx950 HIP kernels + the C ABI (include/basisu_hip.h) -> lib/libbasisu_hip.so
+  _cabi   the ctypes signatures of all three libraries, derived from the headers under include/
   capi    ctypes binding of that C ABI (no torch types cross the boundary)
   etc1s   host-side mirror of the reference's basisu_frontend over the device-resident layer
   transcode  UASTC LDR 4x4 blocks / files -> RGBA32, BC1-BC5, BC7, ASTC 4x4 on the device; ETC1S files -> RGBA32, ETC1, BC1, 16-bit pixels (host decode + device)

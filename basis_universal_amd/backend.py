@@ -36,36 +36,7 @@ class BackendError(RuntimeError):
     pass
 
 
-def _lib():
-    L = load_frontend_library()
-    if not getattr(L, "_backend_bound", False):
-        L.bu_backend_default_params.restype = None
-        L.bu_backend_default_params.argtypes = [C.c_int, C.c_uint32, C.POINTER(BackendParams)]
-        L.bu_backend_create.restype = _vp
-        L.bu_backend_destroy.argtypes = [_vp]
-        L.bu_backend_init.argtypes = [_vp, _vp, C.POINTER(BackendParams), C.POINTER(SliceDesc), C.c_uint32]
-        L.bu_backend_init_arrays.argtypes = [_vp, C.POINTER(BackendArrays), C.POINTER(BackendParams), C.POINTER(SliceDesc), C.c_uint32]
-        L.bu_backend_encode.restype = C.c_uint32
-        L.bu_backend_encode.argtypes = [_vp]
-        L.bu_backend_get.restype = C.c_uint64
-        L.bu_backend_get.argtypes = [_vp, C.c_char_p, C.c_uint32, _vp, C.c_uint64]
-        L.bu_backend_write_basis_file.restype = C.c_uint64
-        L.bu_backend_write_basis_file.argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(KeyValue), C.c_uint32, _vp, C.c_uint64]
-        L.bu_write_basis_file_uastc.restype = C.c_uint64
-        L.bu_write_basis_file_uastc.argtypes = [_vp, C.c_uint64, C.POINTER(SliceDesc), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
-                                                C.POINTER(KeyValue), C.c_uint32, _vp, C.c_uint64]
-        L.bu_backend_write_ktx2_file.restype = C.c_uint64
-        L.bu_backend_write_ktx2_file.argtypes = [_vp, C.c_uint32, C.c_int, C.POINTER(KeyValue), C.c_uint32, _vp, C.c_uint64]
-        L.bu_write_ktx2_file_uastc.restype = C.c_uint64
-        L.bu_write_ktx2_file_uastc.argtypes = [_vp, C.c_uint64, C.POINTER(SliceDesc), C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.POINTER(KeyValue), C.c_uint32, _vp, C.c_uint64]
-        L.bu_backend_set_reoptimize_callback.restype = C.c_int
-        L.bu_backend_set_reoptimize_callback.argtypes = [_vp, _vp, _vp]
-        L.bu_backend_error.restype = C.c_char_p
-        L.bu_backend_error.argtypes = [_vp]
-        L.bu_backend_stage_times.restype = C.c_uint32
-        L.bu_backend_stage_times.argtypes = [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_uint32]
-        L._backend_bound = True
-    return L
+_lib = load_frontend_library
 
 
 def default_params(quality_level=-1, compression_level=1):

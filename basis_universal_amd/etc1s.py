@@ -11,75 +11,18 @@
 n_blocks= (tiles already resident in HBM, e.g. a torch tensor's data_ptr()).
 """
 import ctypes as C
-import pathlib
 
 import numpy as np
 
-from . import capi
+from . import _cabi, capi
 
-FRONTEND_LIB_PATH = capi.LIB_DIR / "libbasisu_frontend.so"
+FRONTEND_LIB_PATH = _cabi.library_path("frontend")
 _vp = C.c_void_p
-_lib = None
 
 
 def load_frontend_library():
-    global _lib
-    if _lib is None:
-        if not FRONTEND_LIB_PATH.exists():
-            raise capi.HipError(f"{FRONTEND_LIB_PATH} is missing: run __graft_entry__.build()")
-        capi.load_library()  # libbasisu_hip.so first (the frontend links against it via $ORIGIN rpath)
-        L = C.CDLL(str(FRONTEND_LIB_PATH))
-        L.bu_frontend_create.restype = _vp
-        L.bu_frontend_destroy.argtypes = [_vp]
-        L.bu_frontend_init.restype = C.c_int
-        L.bu_frontend_init.argtypes = [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
-        L.bu_frontend_set_comm.restype = C.c_int
-        L.bu_frontend_set_comm.argtypes = [_vp, _vp]
-        L.bu_frontend_compress.restype = C.c_int
-        L.bu_frontend_compress.argtypes = [_vp]
-        L.bu_frontend_call.restype = C.c_int
-        L.bu_frontend_call.argtypes = [_vp, C.c_char_p, C.c_uint32]
-        L.bu_frontend_get.restype = C.c_uint64
-        L.bu_frontend_get.argtypes = [_vp, C.c_char_p, _vp, C.c_uint64]
-        L.bu_frontend_error.restype = C.c_char_p
-        L.bu_frontend_error.argtypes = [_vp]
-        L.bu_frontend_stage_times.restype = C.c_uint32
-        L.bu_frontend_stage_times.argtypes = [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_uint32]
-        L.bu_etc1s_quality_to_clusters.argtypes = [C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        L.bu_host_tsvq.restype = C.c_int
-        L.bu_host_tsvq.argtypes = [C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64]
-        L.bu_device_tsvq.restype = C.c_int
-        L.bu_device_tsvq.argtypes = [_vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, _vp]
-        L.bu_host_tsvq_mt.restype = C.c_int
-        L.bu_host_tsvq_mt.argtypes = [C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64]
-        L.bu_device_tsvq_mt.restype = C.c_int
-        L.bu_device_tsvq_mt.argtypes = [_vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, _vp]
-        L.bu_frontend_set_max_threads.restype = C.c_int
-        L.bu_frontend_set_max_threads.argtypes = [_vp, C.c_uint32]
-        L.bu_frontend_reference_max_threads.restype = C.c_uint32
-        L.bu_frontend_reference_max_threads.argtypes = [C.c_int, C.c_uint32, C.c_uint32]
-        L.bu_frontend_pipeline_create.restype = _vp
-        L.bu_frontend_pipeline_create.argtypes = [C.c_int, C.c_uint32]
-        L.bu_frontend_pipeline_create_n.restype = _vp
-        L.bu_frontend_pipeline_create_n.argtypes = [C.c_int, C.c_uint32, C.c_uint32]
-        L.bu_frontend_pipeline_submit.restype = C.c_uint64
-        L.bu_frontend_pipeline_submit.argtypes = [_vp, _vp, C.c_uint32]
-        L.bu_frontend_pipeline_wait.restype = _vp
-        L.bu_frontend_pipeline_wait.argtypes = [_vp, C.c_uint64]
-        L.bu_frontend_pipeline_poll.restype = C.c_int
-        L.bu_frontend_pipeline_poll.argtypes = [_vp, C.c_uint64]
-        L.bu_frontend_pipeline_context.restype = _vp
-        L.bu_frontend_pipeline_context.argtypes = [_vp, _vp]
-        L.bu_frontend_pipeline_release.restype = C.c_int
-        L.bu_frontend_pipeline_release.argtypes = [_vp, _vp]
-        L.bu_frontend_pipeline_destroy.argtypes = [_vp]
-        L.bu_frontend_pipeline_error.restype = C.c_char_p
-        L.bu_frontend_pipeline_error.argtypes = [_vp]
-        L.bu_frontend_pipeline_stats.restype = C.c_uint32
-        L.bu_frontend_pipeline_stats.argtypes = [_vp, C.POINTER(C.c_double), C.c_uint32]
-        L.bu_host_last_exception.restype = C.c_char_p
-        _lib = L
-    return _lib
+    capi.load_library()  # libbasisu_hip.so first (the frontend links against it via $ORIGIN rpath)
+    return _cabi.load("frontend")
 
 
 def reference_max_threads(multithreaded=True, hardware_threads=0, job_pool_threads=0):
@@ -153,28 +96,10 @@ class TorchComm:
         self.struct = _BuComm(self.rank, self.world, None, self._gather, self._reduce, 0, 0)   # blocking convention: torch owns its streams
 
 
-_rccl_lib = None
-
-
 def load_rccl_library():
     """libbasisu_rccl.so (include/basisu_hip_comm.h): bu_comm on RCCL, no Python in the collective path."""
-    global _rccl_lib
-    if _rccl_lib is None:
-        capi.load_library()   # libbasisu_hip.so first: the communicator library links against it
-        path = pathlib.Path(__file__).resolve().parent / "lib" / "libbasisu_rccl.so"
-        if not path.exists():
-            raise capi.HipError(f"{path} not found: build it (make -C basis_universal_amd/csrc)")
-        L = C.CDLL(str(path))
-        L.bu_rccl_get_unique_id.restype = C.c_int
-        L.bu_rccl_get_unique_id.argtypes = [_vp]
-        L.bu_rccl_comm_create.restype = _vp
-        L.bu_rccl_comm_create.argtypes = [_vp, _vp, C.c_uint32, C.c_uint32]
-        L.bu_rccl_comm_destroy.argtypes = [_vp]
-        L.bu_rccl_comm_fill.restype = C.c_int
-        L.bu_rccl_comm_fill.argtypes = [_vp, C.POINTER(_BuComm)]
-        L.bu_rccl_last_error.restype = C.c_char_p
-        _rccl_lib = L
-    return _rccl_lib
+    capi.load_library()   # libbasisu_hip.so first: the communicator library links against it
+    return _cabi.load("rccl")
 
 
 class RcclComm:
@@ -225,15 +150,12 @@ class Etc1sFrontend:
         self._keep = None
         self.comm = comm
         if video:  # cBASISTexTypeVideoFrames: a different order of stages, see include/basisu_hip_frontend.h
-            self.L.bu_frontend_set_video.argtypes = [_vp, C.c_int]
             self._check(self.L.bu_frontend_set_video(self.h, 1), "bu_frontend_set_video")
         if fast_codebooks:
-            self.L.bu_frontend_set_fast_codebooks.argtypes = [_vp, C.c_int, C.c_uint32]
             self._check(self.L.bu_frontend_set_fast_codebooks(self.h, 1, int(fast_iterations)), "bu_frontend_set_fast_codebooks")
         if max_threads:
             self._check(self.L.bu_frontend_set_max_threads(self.h, int(max_threads)), "bu_frontend_set_max_threads")
         if comm is not None:
-            self.L.bu_frontend_set_comm_sized.argtypes = [_vp, _vp, C.c_uint32]
             self._check(self.L.bu_frontend_set_comm_sized(self.h, C.byref(comm.struct), C.sizeof(comm.struct)), "bu_frontend_set_comm_sized")
 
     def _check(self, ok, what):

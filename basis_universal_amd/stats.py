@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import transcode
+from .etc1s import load_frontend_library
 
 # name -> (first_chan, total_chans, use_601), in the order the reference prints them (comp.cpp:4213-4252)
 LINES = {"rgb": (0, 3, 0), "rgba": (0, 4, 0), "r": (0, 1, 0), "g": (1, 1, 0), "b": (2, 1, 0), "a": (3, 1, 0), "luma_709": (0, 0, 0), "luma_601": (0, 0, 1)}
@@ -25,14 +26,7 @@ class _Metrics(C.Structure):    # = bu_image_metrics, include/basisu_hip_image_m
     _fields_ = [("max", C.c_double), ("mean", C.c_float), ("mean_squared", C.c_float), ("rms", C.c_float), ("psnr", C.c_float)]
 
 
-def _reduce_lib():
-    from .etc1s import load_frontend_library
-    L = load_frontend_library()
-    if not getattr(L, "_image_metrics_bound", False):
-        L.bu_image_metrics_reduce.restype = C.c_int
-        L.bu_image_metrics_reduce.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_Metrics)]
-        L._image_metrics_bound = True
-    return L
+_reduce_lib = load_frontend_library   # bu_image_metrics_reduce lives in libbasisu_frontend.so
 
 
 def reduce_counts(hist, width, height):

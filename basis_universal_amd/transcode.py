@@ -14,6 +14,8 @@ import struct
 
 import numpy as np
 
+from .etc1s import load_frontend_library
+
 BC1_RGB, BC3_RGBA, BC4_R, BC5_RG, BC7_RGBA, ASTC_4x4_RGBA, RGBA32 = 2, 3, 4, 5, 6, 10, 13
 BYTES_PER_BLOCK = {BC1_RGB: 8, BC3_RGBA: 16, BC4_R: 8, BC5_RG: 16, BC7_RGBA: 16, ASTC_4x4_RGBA: 16, RGBA32: 64}
 DECODE_FLAGS_HIGH_QUALITY = 32   # cDecodeFlagsHighQuality
@@ -196,29 +198,9 @@ class _Etc1sImage(C.Structure):      # = bu_etc1s_image
                                                                                                                                       ("alpha_first_block", C.c_uint64)]
 
 
-def _etc1s_lib():
-    from .etc1s import load_frontend_library
-    L = load_frontend_library()
-    if not getattr(L, "_etc1s_decode_bound", False):
-        L.bu_etc1s_decode_file.restype = C.c_void_p
-        L.bu_etc1s_decode_file.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_char_p, C.c_uint32]
-        L.bu_etc1s_file_destroy.restype = None
-        L.bu_etc1s_file_destroy.argtypes = [C.c_void_p]
-        L.bu_etc1s_file_get_info.restype = None
-        L.bu_etc1s_file_get_info.argtypes = [C.c_void_p, C.POINTER(_Etc1sFileInfo)]
-        L.bu_etc1s_file_get_images.restype = C.c_uint32
-        L.bu_etc1s_file_get_images.argtypes = [C.c_void_p, C.POINTER(_Etc1sImage), C.c_uint32]
-        for name in ("endpoint_palette", "selector_palette", "endpoint_indices", "selector_indices"):
-            fn = getattr(L, "bu_etc1s_file_" + name)
-            fn.restype = C.c_void_p
-            fn.argtypes = [C.c_void_p]
-        L._etc1s_decode_bound = True
-    return L
-
-
 def _decode_etc1s(data, header_only):
     raw = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
-    L = _etc1s_lib()
+    L = load_frontend_library()
     err = C.create_string_buffer(512)
     h = L.bu_etc1s_decode_file(raw, len(raw), 1 if header_only else 0, err, len(err))
     if not h:

@@ -9,14 +9,72 @@ import pytest
 from helpers import have_ref, ref, ptr, u32p, u64p, f32p, synth, to_pixel_blocks
 
 
-def test_library_exports_every_declared_symbol():
-    from basis_universal_amd import capi
-    lib = capi.load_library()
-    declared = capi.declared_symbols()
-    assert len(declared) >= 30
-    for sym in declared:
-        assert hasattr(lib.dll, sym), sym
-    assert sorted(capi._SIGNATURES) == declared, "ctypes signature table out of sync with include/basisu_hip.h"
+def _exports(path):
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--defined-only", str(path)], stdout=subprocess.PIPE, text=True, check=True).stdout
+    return {line.split()[-1] for line in out.splitlines() if line.strip()}
+
+
+def test_every_header_prototype_is_exported_once_and_bound():
+    """Every BU_*API prototype of every header under include/ is exported by exactly one of the built libraries, and that library's loader has put the signature
+    derived from the header on it (basis_universal_amd/_cabi.py). libbasisu_rccl.so only where it has been built."""
+    from basis_universal_amd import _cabi, capi, etc1s
+    inc = pathlib.Path(__file__).resolve().parent.parent / "include"
+    assert sorted(h for _, headers, _ in _cabi.LIBRARIES.values() for h in headers) == sorted(p.name for p in inc.glob("*.h")), "a header no library is bound from"
+    assert capi.declared_symbols() == sorted(_cabi.PROTOTYPES["hip"]) and len(_cabi.PROTOTYPES["hip"]) >= 96
+    assert sum(len(v) for v in _cabi.PROTOTYPES.values()) >= 166
+    loaders = {"hip": lambda: capi.load_library().dll, "frontend": etc1s.load_frontend_library, "rccl": etc1s.load_rccl_library}
+    built = [lib for lib in _cabi.LIBRARIES if lib != "rccl" or _cabi.library_path(lib).exists()]
+    exports = {lib: _exports(_cabi.library_path(lib)) for lib in built}
+    for lib in built:
+        dll = loaders[lib]()
+        for name, (res, args) in _cabi.PROTOTYPES[lib].items():
+            assert [other for other in built if name in exports[other]] == [lib], name
+            fn = getattr(dll, name)
+            assert fn.restype is res and fn.argtypes is not None and list(fn.argtypes) == args, name
+    hip = capi.load_library()
+    assert all(hasattr(hip, name[len("bu_hip_"):]) for name in _cabi.PROTOTYPES["hip"] if name != "bu_hip_last_error")
+
+
+def test_prototype_parser():
+    """_cabi.parse_prototypes on literal header text: no library needed."""
+    from basis_universal_amd._cabi import parse_prototypes
+    vp, u32 = C.c_void_p, C.c_uint32
+    got = parse_prototypes("""
+        #define BU_HIP_API __attribute__((visibility("default")))
+        typedef int (*bu_gather_fn)(void* user, void* d_buf, uint64_t bytes);
+        /* BU_HIP_API int bu_commented_out(int); */
+        BU_HIP_API int bu_multi_line(bu_hip_context* ctx, const float* rows,
+                                     uint32_t n,
+                                     double scale, float f);
+        BU_HIP_API uint64_t bu_commented(bu_pipeline*, const bu_job* job /* the caller's, (not kept) */, uint32_t struct_bytes); // trailing; int bu_not_this(void);
+        BU_HIP_API const char* bu_no_arguments(void);
+        BU_HIP_API   void   bu_names(const bu_thing*, const char** names, const char* one, char* err, uint32_t cap);
+        BU_OTHER_API void bu_array(uint32_t out_stats[4], const uint64_t in[]);
+        BU_HIP_API int bu_callback(bu_hip_context*, bu_gather_fn fn, void* user);
+        BU_HIP_API size_t bu_bytes(size_t n, int32_t signed_one, uint64_t big);
+        BU_HIP_API int32_t bu_signed(int);
+        BU_HIP_API bu_thing* const* bu_pointer_to_pointer(bu_hip_context* const* ctxs);
+    """)
+    assert got == {
+        "bu_multi_line": (C.c_int, [vp, vp, u32, C.c_double, C.c_float]),
+        "bu_commented": (C.c_uint64, [vp, vp, u32]),
+        "bu_no_arguments": (C.c_char_p, []),
+        "bu_names": (None, [vp, vp, C.c_char_p, vp, u32]),
+        "bu_array": (None, [vp, vp]),
+        "bu_callback": (C.c_int, [vp, vp, vp]),
+        "bu_bytes": (C.c_size_t, [C.c_size_t, C.c_int32, C.c_uint64]),
+        "bu_signed": (C.c_int32, [C.c_int]),
+        "bu_pointer_to_pointer": (vp, [vp]),
+    }
+    for bad, what in [("BU_HIP_API int bu_short(uint16_t x);", "uint16_t x"), ("BU_HIP_API int bu_struct_by_value(bu_thing t);", "bu_thing t"),
+                      ("BU_HIP_API unsigned bu_ret(void);", "unsigned"), ("BU_HIP_API int bu_two_words(unsigned int n);", "unsigned int n"),
+                      ("BU_HIP_API bu_gather_fn bu_returns_callback(void);", "bu_gather_fn")]:
+        with pytest.raises(TypeError, match=what) as e:
+            parse_prototypes(bad)
+        assert "bu_" in str(e.value)       # the function is named too
+    with pytest.raises(TypeError, match="1 BU_\\*API marks but 0 prototypes"):   # a call-back written inline: nothing this parser reads may pass silently
+        parse_prototypes("BU_HIP_API int bu_inline_callback(void (*fn)(void* user));")
 
 
 def test_frontend_library_loads():
@@ -194,13 +252,8 @@ def test_rccl_group_communicators_need_one_thread_each():
     inherited. (No GPU needed: the group here has no RCCL communicator behind it, so a collective the rule lets through fails with "no communicator".)"""
     import ctypes as C
     import threading
-    from basis_universal_amd import capi
-    from basis_universal_amd.etc1s import _BuComm
-    capi.load_library()
-    root = pathlib.Path(__file__).resolve().parent.parent
-    L = C.CDLL(str(root / "basis_universal_amd" / "lib" / "libbasisu_rccl.so"))
-    L.bu_rccl_last_error.restype = C.c_char_p
-    L.bu_rccl_comm_destroy.argtypes = [C.c_void_p]
+    from basis_universal_amd.etc1s import _BuComm, load_rccl_library
+    L = load_rccl_library()
     comms = (C.c_void_p * 3)()
     assert L.bu_rccl_debug_unconnected_group(3, comms) == 1
     views = []
@@ -258,7 +311,6 @@ def test_frontend_pipeline_scheduler_selftest():
     import ctypes as C
     from basis_universal_amd import etc1s
     L = etc1s.load_frontend_library()
-    L.bu_frontend_pipeline_selftest.argtypes = [C.c_uint32] * 4
     for lanes, tasks, yields, failing in [(1, 3, 10, 0), (4, 40, 1000, 3), (16, 200, 50, 10), (3, 7, 0, 1)]:
         assert L.bu_frontend_pipeline_selftest(lanes, tasks, yields, failing) == 1, (lanes, tasks, yields, failing)
     assert C.sizeof(etc1s._FrontendJob) == 48   # = sizeof(bu_frontend_job): two pointers + eight 32-bit fields
@@ -271,7 +323,6 @@ def test_host_block_pool_recycles_large_blocks_and_leaves_the_process_alone():
     import pathlib, subprocess
     from basis_universal_amd import etc1s
     F = etc1s.load_frontend_library()
-    F.bu_host_pool_stats.argtypes = [C.POINTER(C.c_uint64)]
     rng = np.random.default_rng(5)
     v = np.ascontiguousarray(np.unique(rng.integers(0, 4, (120000, 16)).astype(np.float32), axis=0))
     n = v.shape[0]
@@ -287,7 +338,6 @@ def test_host_block_pool_recycles_large_blocks_and_leaves_the_process_alone():
     assert st[2][0] == st[1][0] and st[2][1] > st[1][1], "the second run reuses them"
     assert st[2][2] <= st[2][3]
     # bu_host_pool_trim: what the pool keeps goes back to the kernel on request, and the next run maps afresh
-    F.bu_host_pool_trim.restype = C.c_uint64
     held = st[2][2]
     assert held > 0 and F.bu_host_pool_trim() == held
     F.bu_host_pool_stats(st[0])

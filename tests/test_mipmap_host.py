@@ -16,8 +16,6 @@ def plan(sw, sh, dw, dh, srgb, flt, scale, wrap):
     from basis_universal_amd.etc1s import load_frontend_library
     L = load_frontend_library()
     f = L.bu_mipmap_plan
-    f.restype = C.c_int
-    f.argtypes = [C.c_uint32] * 4 + [C.c_int, C.c_char_p, C.c_float, C.c_int] + [C.c_void_p] * 9
     counts = np.zeros(4, np.uint32)
     assert f(sw, sh, dw, dh, int(srgb), flt.encode(), scale, int(wrap), counts.ctypes.data, *([None] * 8))
     xf, xp, xw = np.zeros(dw + 1, np.uint32), np.zeros(counts[0], np.uint16), np.zeros(counts[0], np.float32)
@@ -126,8 +124,6 @@ def test_both_pass_orders_occur():
 def test_mip_chain_sizes():
     from basis_universal_amd.etc1s import load_frontend_library
     L = load_frontend_library()
-    L.bu_mipmap_level_sizes.restype = C.c_uint32
-    L.bu_mipmap_level_sizes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]
     out = np.zeros(64, np.uint32)
     n = L.bu_mipmap_level_sizes(130, 67, 1, out.ctypes.data, 32)
     assert out[:2 * n].reshape(-1, 2).tolist() == [[65, 33], [32, 16], [16, 8], [8, 4], [4, 2], [2, 1], [1, 1]]

@@ -17,7 +17,7 @@ LABELS = ["prologue (node record, origin)", "covariance pass (pipelined chains)"
 threads = int(sys.argv[1]) if len(sys.argv) > 1 else 0
 ctx = capi.Context(0)
 dll = ctx.lib.dll
-dll.tsvq_profile_read.argtypes = [C.c_void_p]
+dll.tsvq_profile_read.argtypes = [C.c_void_p]   # of the instrumented build only: no public header declares it
 blocks = helpers.to_pixel_blocks(helpers.synth(4096, 4096, 1234))
 ep, sel = quality_to_clusters(128, blocks.shape[0])
 buf = (C.c_ulonglong * 16)()
