@@ -5,7 +5,14 @@ image_metrics::calc (encoder/basisu_enc.cpp:2155-2226) is a 256-bin histogram of
 sums) of all eight lines are counted on the GPU in one pass over two resident RGBA8 rasters (csrc/image_metrics_kernels.hip, bu_hip_k_image_metrics): integer counts,
 hence exactly the reference's, whatever the order of accumulation. The doubles are host code in the reference's own expression order (csrc/image_metrics.h,
 bu_image_metrics_reduce in libbasisu_frontend.so). The decode that is compared is the device transcoders' RGBA32 (transcode.py), resident, never downloaded.
-There is no CPU implementation of the counting: without the HIP library and a GPU `image_metrics` raises. No SSIM: this overload of calc never sets m_ssim."""
+There is no CPU implementation of the counting: without the HIP library and a GPU `image_metrics` raises. No SSIM: this overload of calc never sets m_ssim.
+
+With hvs=True (file_stats) / stats_hvs=True (compress) every slice also carries what the tool prints under "PSNR-HVS and PSNR-HVS-M metrics:" (m_psnr_hvs_m_stats,
+comp.cpp:4265-4276; psnr_hvs_compute_metrics, enc.cpp:2256-2519; `basisu -compare_hvs` for any two images = psnr_hvs below). Per 8x8 block and mode (BT.601 Y rounded
+to 8 bits, BT.601 Y in float, R, G, B, A) two float DCTs, two masking strengths and 128 weighted differences, binary32 in the reference's operation order
+(csrc/psnr_hvs.h), one wave per block and mode (csrc/psnr_hvs_kernels.hip, bu_hip_k_psnr_hvs); the per-block doubles are the reference's bit for bit, their sum over
+the image is added in a fixed order of the kernel's own (deterministic; within 2 (blocks - 1) 2^-53 relative of raster order). mseh and dB are host code
+(bu_psnr_hvs_reduce). Not here: SSIM, the "(BC7)" variant of these lines (there is no BC7 decoder in this package) and the best-ETC1S stats."""
 import ctypes as C
 
 import numpy as np
@@ -25,6 +32,21 @@ class Counts(C.Structure):      # = bu_image_metrics_counts, include/basisu_hip.
 class _Metrics(C.Structure):    # = bu_image_metrics, include/basisu_hip_image_metrics.h
     _fields_ = [("max", C.c_double), ("mean", C.c_float), ("mean_squared", C.c_float), ("rms", C.c_float), ("psnr", C.c_float)]
 
+
+class HvsSums(C.Structure):     # = bu_psnr_hvs_sums, include/basisu_hip.h
+    _fields_ = [("struct_bytes", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("blocks", C.c_uint32), ("sum_hvs", C.c_double * 6), ("sum_hvsm", C.c_double * 6)]
+
+
+class _HvsChan(C.Structure):    # = bu_psnr_hvs_chan, include/basisu_hip_image_metrics.h
+    _fields_ = [("mseh_hvs", C.c_double), ("mseh_hvsm", C.c_double), ("psnr_hvs", C.c_double), ("psnr_hvsm", C.c_double)]
+
+
+class _HvsMetrics(C.Structure):  # = bu_psnr_hvs_metrics
+    _fields_ = [("y_601_8bit", _HvsChan), ("y_601_float", _HvsChan), ("chan", _HvsChan * 4), ("rgb", _HvsChan), ("rgba", _HvsChan)]
+
+
+HVS_MODES = ("y_601_8bit", "y_601_float", "r", "g", "b", "a")   # the index of bu_psnr_hvs_sums::sum_hvs / sum_hvsm
+HVS_ENTRIES = ("y_601_float", "y_601_8bit", "rgb", "rgba", "r", "g", "b", "a")   # in the order the reference prints them (psnr_hvs_print_metrics)
 
 _reduce_lib = load_frontend_library   # bu_image_metrics_reduce lives in libbasisu_frontend.so
 
@@ -81,6 +103,65 @@ def image_metrics(ctx, a, b):
     return out
 
 
+def psnr_hvs_sums(ctx, a, b):
+    """bu_hip_k_psnr_hvs: a, b as for image_metrics -> the filled HvsSums (sum_hvs / sum_hvsm per mode of HVS_MODES, blocks, width, height)."""
+    owned = []
+    try:
+        (da, wa, ha, pa), (db, wb, hb, pb) = _resident(ctx, a, owned), _resident(ctx, b, owned)
+        s = HvsSums()
+        s.struct_bytes = C.sizeof(HvsSums)
+        ctx.check(ctx.lib.k_psnr_hvs(ctx.h, C.c_void_p(da), wa, ha, pa, C.c_void_p(db), wb, hb, pb, C.byref(s)), "psnr_hvs")
+        return s
+    finally:
+        for d in owned:
+            ctx.free(d)
+
+
+def psnr_hvs_block_sums(ctx, a, b, mode):
+    """bu_hip_k_psnr_hvs_blocks (the test hook): -> (blocks, 2) f64, the HVS and the HVS-M double of every 8x8 block of mode HVS_MODES[mode], raster order."""
+    owned = []
+    try:
+        (da, wa, ha, pa), (db, wb, hb, pb) = _resident(ctx, a, owned), _resident(ctx, b, owned)
+        w, h = min(wa, wb), min(ha, hb)
+        cap = ((w + 7) // 8) * ((h + 7) // 8)
+        out, n = np.zeros((max(cap, 1), 2), np.float64), C.c_uint32(0)
+        ctx.check(ctx.lib.k_psnr_hvs_blocks(ctx.h, C.c_void_p(da), wa, ha, pa, C.c_void_p(db), wb, hb, pb, int(mode), out.ctypes.data_as(C.c_void_p), cap, C.byref(n)),
+                  "psnr_hvs_blocks")
+        return out[:n.value]
+    finally:
+        for d in owned:
+            ctx.free(d)
+
+
+def reduce_hvs_sums(sums):
+    """bu_psnr_hvs_reduce: an HvsSums -> {entry of HVS_ENTRIES: {"mseh_hvs", "mseh_hvsm", "psnr_hvs", "psnr_hvsm"}}. Host only."""
+    m = _HvsMetrics()
+    if not _reduce_lib().bu_psnr_hvs_reduce(C.byref(sums), C.byref(m)):
+        raise ValueError("bu_psnr_hvs_reduce refused the sums")
+    chans = {"y_601_float": m.y_601_float, "y_601_8bit": m.y_601_8bit, "rgb": m.rgb, "rgba": m.rgba, "r": m.chan[0], "g": m.chan[1], "b": m.chan[2], "a": m.chan[3]}
+    return {name: {f: float(getattr(chans[name], f)) for f, _ in _HvsChan._fields_} for name in HVS_ENTRIES}
+
+
+def psnr_hvs(ctx, a, b):
+    """psnr_hvs_compute_metrics of `a` against `b` (what `basisu -compare_hvs a b` prints after the image metrics). a, b: (h, w, 4) u8 arrays (uploaded) or (device
+    pointer, width, height, row pitch in pixels, 0 = width) tuples of resident RGBA8 rasters; the region is min(widths) x min(heights) in 8x8 blocks whose pixel
+    coordinates are clamped to each raster's own edge.
+    -> {"y_601_float", "y_601_8bit", "rgb", "rgba", "r", "g", "b", "a": {"mseh_hvs", "mseh_hvsm", "psnr_hvs", "psnr_hvsm"}, "width", "height"}; a psnr of 100000.0
+    means no difference (PSNR_HVS_LOSSLESS_DB). An empty region has the 0 / 0 (NaN) of the division; the reference refuses it."""
+    sums = psnr_hvs_sums(ctx, a, b)
+    out = reduce_hvs_sums(sums)
+    out.update({"width": int(sums.width), "height": int(sums.height)})
+    return out
+
+
+def _slice_stats(ctx, src, decoded, hvs):
+    """the dict of one slice: image_metrics, and under "hvs" psnr_hvs of the same two resident rasters when asked for"""
+    out = image_metrics(ctx, src, decoded)
+    if hvs:
+        out["hvs"] = psnr_hvs(ctx, src, decoded)
+    return out
+
+
 def _is_etc1s(raw):
     if len(raw) >= 48 and raw[:12] == transcode._KTX2_MAGIC:
         return int.from_bytes(raw[44:48], "little") == 1     # supercompressionScheme: 1 = BasisLZ (ETC1S), 0 = none (UASTC)
@@ -104,7 +185,7 @@ def _slice_order(images):
     return sorted(range(len(images)), key=lambda k: (images[k]["layer"], images[k]["face"], images[k]["level"]))
 
 
-def _stats_from_slices(ctx, raw, slice_sources):
+def _stats_from_slices(ctx, raw, slice_sources, hvs=False):
     """slice_sources(level, layer, face, n_slices) -> one source raster per slice of that image (array or resident tuple). -> the per-slice dicts, slice order."""
     out = []
     if _is_etc1s(raw):
@@ -122,7 +203,7 @@ def _stats_from_slices(ctx, raw, slice_sources):
             try:
                 for part, src in zip(parts, sources):
                     transcode.transcode_etc1s_image(ctx, decoded, part, transcode.RGBA32, out_device=d_out)
-                    out.append(image_metrics(ctx, src, (d_out, w, h, w)))
+                    out.append(_slice_stats(ctx, src, (d_out, w, h, w), hvs))
             finally:
                 ctx.free(d_out)
         return out
@@ -135,19 +216,22 @@ def _stats_from_slices(ctx, raw, slice_sources):
         d_out = ctx.alloc(w * h * 4)
         try:
             transcode.transcode_uastc_blocks(ctx, blocks, im["num_blocks_x"], im["num_blocks_y"], transcode.RGBA32, width=w, height=h, out_device=d_out)
-            out.append(image_metrics(ctx, src, (d_out, w, h, w)))
+            out.append(_slice_stats(ctx, src, (d_out, w, h, w), hvs))
         finally:
             ctx.free(d_out)
     return out
 
 
-def file_stats(ctx, data, images):
+def file_stats(ctx, data, images, hvs=False):
     """The reference's m_stats for a .basis / .ktx2 file of this package (UASTC LDR 4x4 or ETC1S): one image_metrics dict per slice, in the compressor's slice order
     (source image outermost, then its levels; an ETC1S image with alpha has a colour slice and then an alpha slice, each with its own stats).
     images: the source of every image the file holds -- {(level, layer, face): image} or, for a file of one layer and face, a list by level; an image is an
     (h, w, 4) u8 array or a resident (device pointer, width, height, pitch) tuple. The file is decoded on the device to RGBA32 (transcode_uastc_blocks /
     decode_etc1s_file + transcode_etc1s_image), cropped to each slice's original size, and compared there. A colour slice of an ETC1S file with alpha is compared
-    against (r, g, b, 255), its alpha slice -- decoded as a colour image -- against (a, a, a, 255)."""
+    against (r, g, b, 255), its alpha slice -- decoded as a colour image -- against (a, a, a, 255).
+    hvs: every slice dict gains "hvs", psnr_hvs of the same source against the same resident decode (m_psnr_hvs_m_stats, which the tool sets with -stats). A source
+    that is padded beyond the slice's size (the compressor's level rasters) must be padded with duplicated borders, as the compressor's are: a block's coordinates
+    are clamped to each raster's own edge."""
     raw = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
     by_key = images if isinstance(images, dict) else {(level, 0, 0): im for level, im in enumerate(images)}
 
@@ -165,4 +249,4 @@ def file_stats(ctx, data, images):
                 rows.reshape(-1, 4)[:(h - 1) * pitch + w] = ctx.download(d, ((h - 1) * pitch + w, 4), np.uint8)
             src = rows[:, :w]
         return list(split_planes(src))
-    return _stats_from_slices(ctx, raw, slice_sources)
+    return _stats_from_slices(ctx, raw, slice_sources, hvs)

@@ -351,6 +351,30 @@ typedef struct bu_image_metrics_counts {
 BU_HIP_API int bu_hip_k_image_metrics(bu_hip_context*, const void* d_a, uint32_t width_a, uint32_t height_a, uint32_t pitch_a_pixels, const void* d_b, uint32_t width_b,
         uint32_t height_b, uint32_t pitch_b_pixels, bu_image_metrics_counts* h_out);
 
+/* PSNR-HVS / PSNR-HVS-M as psnr_hvs_compute_metrics computes them (encoder/basisu_enc.cpp:2256-2519; the lines after "PSNR-HVS and PSNR-HVS-M metrics:" of the
+ * m_compute_stats stage, comp.cpp:4265-4276, and of `basisu -compare_hvs`), over two resident RGBA8 rasters laid out as for bu_hip_k_image_metrics. The region is
+ * min(width_a, width_b) x min(height_a, height_b), at most 16384 each way, cut into ceil(w / 8) x ceil(h / 8) blocks of 8x8; a block's pixel coordinates are clamped
+ * to each raster's OWN last column and row (extract_block_clamped), not to the region.
+ *   Modes, the index of sum_hvs / sum_hvsm: 0 = BT.601 Y rounded to 8 bits, 1 = BT.601 Y in float, 2-5 = R, G, B, A.
+ *   Per block and mode everything up to the 64 + 64 per-coefficient terms is the reference's binary32 arithmetic in its operation order (csrc/psnr_hvs.h), bit for
+ *   bit; the block's two doubles are its terms added in index order. sum_hvs / sum_hvsm[mode] are the sums of those doubles over all blocks, added in an order that
+ *   depends on the region's size alone (per-workgroup partials, then a fixed tree; no floating-point atomics): the same bits on every run, and within
+ *   2 (blocks - 1) 2^-53 relative of the blocks added in raster order. bu_psnr_hvs_reduce (basisu_hip_image_metrics.h, host code) turns them into mseh and dB.
+ * Versioned by size like bu_image_metrics_counts. Two launches on the context's stream (none for an empty region, whose sums and block count are zero); synchronises
+ * to copy the sums out. Fails -- nothing launched, *h_out untouched -- on a null pointer, a misaligned raster, a pitch below its width or a region beyond 16384.
+ * bu_hip_k_psnr_hvs_blocks is the test hook under it: the same launches, and h_out_blocks[block * 2 + 0 / 1] = the HVS / HVS-M double of every block of ONE mode,
+ * blocks in raster order; capacity_blocks (the doubles h_out_blocks holds, halved) must be at least the region's block count, which *out_blocks (may be NULL) gets. */
+typedef struct bu_psnr_hvs_sums {
+    uint32_t struct_bytes;
+    uint32_t width, height;       /* the region compared */
+    uint32_t blocks;              /* ceil(width / 8) * ceil(height / 8) */
+    double sum_hvs[6], sum_hvsm[6];
+} bu_psnr_hvs_sums;
+BU_HIP_API int bu_hip_k_psnr_hvs(bu_hip_context*, const void* d_a, uint32_t width_a, uint32_t height_a, uint32_t pitch_a_pixels, const void* d_b, uint32_t width_b,
+        uint32_t height_b, uint32_t pitch_b_pixels, bu_psnr_hvs_sums* h_out);
+BU_HIP_API int bu_hip_k_psnr_hvs_blocks(bu_hip_context*, const void* d_a, uint32_t width_a, uint32_t height_a, uint32_t pitch_a_pixels, const void* d_b, uint32_t width_b,
+        uint32_t height_b, uint32_t pitch_b_pixels, uint32_t mode, double* h_out_blocks, uint32_t capacity_blocks, uint32_t* out_blocks);
+
 /* a15 + the list handling inside a9 / a10 / a13 / a14: cluster bookkeeping on the device (basis_universal_amd/csrc/bookkeeping_kernels.hip).
  *     A clustering is two resident per-block arrays, cluster index and position inside the cluster's list; these calls turn distinct-vector level
  *     results into them, rebuild them after a reassignment, apply codebook renumberings to them and produce the CSR lists the per-cluster

@@ -24,6 +24,18 @@ typedef struct bu_image_metrics {
  * pointer or a channel range past 4. */
 BU_HIP_API int bu_image_metrics_reduce(const uint32_t* hist, uint32_t total_chans, uint32_t first_chan, uint32_t width, uint32_t height, int use_601, bu_image_metrics* out);
 
+/* psnr_hvs_compute_metrics from its block sums on (encoder/basisu_enc.cpp:2455-2462, 2481-2514): the sums of bu_hip_k_psnr_hvs -> what psnr_hvs_print_metrics prints.
+ * Per mode mseh = sum / double(blocks * 64) and psnr = 10.0f * log10(1 / mseh) in double, 100000 where mseh <= 0 (PSNR_HVS_LOSSLESS_DB); rgb = the R, G, B mseh
+ * added in that order and divided by 3.0f, rgba = the four divided by 4.0f, each with its own psnr. */
+typedef struct bu_psnr_hvs_chan {
+    double mseh_hvs, mseh_hvsm, psnr_hvs, psnr_hvsm;
+} bu_psnr_hvs_chan;
+typedef struct bu_psnr_hvs_metrics {
+    bu_psnr_hvs_chan y_601_8bit, y_601_float, chan[4], rgb, rgba;
+} bu_psnr_hvs_metrics;
+/* Returns 0 (and leaves *out alone) on a null pointer or a sums struct whose struct_bytes ends before sum_hvsm does. blocks == 0 gives the 0 / 0 (NaN) of the division. */
+BU_HIP_API int bu_psnr_hvs_reduce(const bu_psnr_hvs_sums* sums, bu_psnr_hvs_metrics* out);
+
 #ifdef __cplusplus
 }
 #endif
