@@ -216,6 +216,9 @@ bu_tsvq* bu_hip_tsvq_create_endpoint_device(bu_hip_context* ctx, const uint64_t*
 static int tsvq_split_impl(bu_hip_context* ctx, bu_tsvq* q, const bu_tsvq_node* h_nodes, uint32_t n_nodes, bu_tsvq_split* h_out, uint32_t levels, bu_tsvq_split* h_deep) {
     if (!ctx || !q) return 0;
     if (!n_nodes) return 1;
+    // as bu_hip_tsvq_roots: a record that is no span of the member buffers is refused here, before anything is launched (the kernels index with it as it stands)
+    for (uint32_t i = 0; i < n_nodes; i++)
+        if (h_nodes[i].buf >= bu::TSVQ_BUFS || !h_nodes[i].count || (uint64_t)h_nodes[i].start + h_nodes[i].count > q->n) { set_error(ctx, "tsvq_split: span outside the training set"); return 0; }
     if (levels > bu::TSVQ_MAX_DEEP_LEVELS) levels = bu::TSVQ_MAX_DEEP_LEVELS;   // tsvq_bufs.h: a write must not reach a list that may still become a leaf
     const uint32_t h_deep_levels = h_deep ? levels : 0;   // what the caller's array is laid out for (the round may attempt fewer)
     device_guard g(ctx->device);

@@ -77,7 +77,7 @@ public:
         next_codebook_index_ = 0;
         nodes_.clear();
         nodes_.reserve((size_t)max_leaves * 2 + 1);
-        nodes_.push_back(make_root());
+        nodes_.push_back(make_root(nullptr, n_));
         variance_heap heap;
         heap.reset(0, nodes_[0].var);
         uint32_t leaves = 1;
@@ -114,6 +114,20 @@ public:
         }
     }
 
+    // Per-node hooks for the tests (tests/native/tsvq_node_host.cpp): what generate() computes for ONE node, on an arbitrary member list in list order, through
+    // the bodies generate() itself runs. root_of = make_root over the list; split_of = initial_children + refine of a node with that list, weight and origin:
+    // false where either returns false, else the two sides with their RAW variances (split() substitutes 1e-4 afterwards).
+    struct side { float centroid[N]; uint64_t weight; float var; std::vector<uint32_t> members; };
+    void root_of(const uint32_t* members, uint32_t count, float origin[N], uint64_t& weight, float& var) const {
+        const node r = make_root(members, count);
+        std::memcpy(origin, r.origin, sizeof(r.origin)); weight = r.weight; var = r.var;
+    }
+    bool split_of(const uint32_t* members, uint32_t count, uint64_t weight, const float origin[N], side& L, side& R) const {
+        node nd;
+        nd.weight = weight; std::memcpy(nd.origin, origin, sizeof(nd.origin)); nd.members.assign(members, members + count);
+        return initial_children(nd, L.centroid, R.centroid) && refine(nd, L, R);
+    }
+
 private:
     struct node {
         float var = 0.0f;
@@ -141,13 +155,14 @@ private:
         return true;
     }
 
-    // enc.h:1708-1735
-    node make_root() const {
+    // enc.h:1708-1735, over the whole training set (members == nullptr) or over a member list in list order
+    node make_root(const uint32_t* members, uint32_t count) const {
         node root;
         for (int k = 0; k < N; k++) root.origin[k] = 0.0f;
-        root.members.reserve(n_);
+        root.members.reserve(count);
         double ttsum = 0.0;
-        for (uint32_t i = 0; i < n_; i++) {
+        for (uint32_t j = 0; j < count; j++) {
+            const uint32_t i = members ? members[j] : j;
             const float* v = row(i);
             const uint64_t w = weights_[i];
             const float wf = static_cast<float>(w);
@@ -263,8 +278,6 @@ private:
         }
         return true;
     }
-
-    struct side { float centroid[N]; uint64_t weight; float var; std::vector<uint32_t> members; };
 
     // refine_split (enc.h:1962-2077): up to 6 two-means iterations
     bool refine(const node& nd, side& L, side& R) const {

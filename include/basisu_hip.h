@@ -457,6 +457,8 @@ BU_HIP_API int bu_hip_k_unique_endpoint_vectors(bu_hip_context*, const void* d_e
                                                 uint32_t* d_group_offsets, uint32_t* out_unique);
 BU_HIP_API int bu_hip_k_unique_selector_vectors(bu_hip_context*, const void* d_enc_blocks, const uint64_t* d_weights, uint32_t n_blocks, uint32_t* d_sorted_block_idx,
                                                 uint32_t* d_unique_keys, uint64_t* d_unique_weights, uint32_t* d_group_offsets, uint32_t* out_unique);
+/* Every record of a batch (here, in a deep round and in bu_hip_tsvq_roots) must be a span of the member buffers: buf < BU_TSVQ_BUFFERS, count >= 1, start + count <= n.
+ * Anything else returns 0 with "span outside the training set" before a kernel is launched (the tree driver, tsvq_device.h, only ever queues nodes of two members and more). */
 BU_HIP_API int  bu_hip_tsvq_split(bu_hip_context*, bu_tsvq*, const bu_tsvq_node* h_nodes, uint32_t n_nodes, bu_tsvq_split* h_out); /* synchronises */
 /* A DEEP round: the same, and in the same round trip the splits of the children, grandchildren, ... (`levels` generations, <= BU_TSVQ_BUFFERS - 2) of every node of the batch that went
  * through the one-workgroup kernel -- a split is a pure function of its node, so the caller's replay of the reference's variance queue (enc.h:1636-1655) finds them

@@ -569,6 +569,73 @@ def tt_exact_host():
     return _tt_exact_host
 
 
+_tsvq_node_host = None
+
+# the records of include/basisu_hip.h as numpy structured dtypes
+TSVQ_ROOT = np.dtype([("origin", np.float32, 16), ("weight", np.uint64), ("var", np.float32), ("pad", np.uint32)])
+TSVQ_NODE = np.dtype([("buf", np.uint32), ("start", np.uint32), ("count", np.uint32), ("pad", np.uint32), ("weight", np.uint64), ("origin", np.float32, 16)])
+TSVQ_SPLIT = np.dtype([("ok", np.uint32), ("l_count", np.uint32), ("r_count", np.uint32), ("pad", np.uint32), ("l_weight", np.uint64), ("r_weight", np.uint64),
+                       ("l_var", np.float32), ("r_var", np.float32), ("l_centroid", np.float32, 16), ("r_centroid", np.float32, 16)])
+TSVQ_SPAN = np.dtype([("buf", np.uint32), ("start", np.uint32), ("count", np.uint32), ("value", np.uint32)])
+assert (TSVQ_ROOT.itemsize, TSVQ_NODE.itemsize, TSVQ_SPLIT.itemsize, TSVQ_SPAN.itemsize) == (80, 88, 168, 16)
+
+
+def tsvq_node_host():
+    """csrc/host/tsvq.h one node at a time (tests/native/tsvq_node_host.cpp): the root record of a member list, the split record + child lists of a node."""
+    global _tsvq_node_host
+    if _tsvq_node_host is None:
+        d = ROOT / "tests" / "native"
+        so, srcs = d / "libtsvq_node_host.so", [d / "tsvq_node_host.cpp", ROOT / "basis_universal_amd" / "csrc" / "host" / "tsvq.h"]
+        if not so.exists() or so.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
+            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", str(so), str(srcs[0])])
+        L = C.CDLL(str(so))
+        L.tn_open.restype = C.c_void_p
+        L.tn_open.argtypes = [C.c_uint32, f32p, u64p, C.c_uint32]
+        L.tn_close.argtypes = [C.c_void_p]
+        L.tn_root.argtypes = [C.c_void_p, u32p, C.c_uint32, C.c_void_p]
+        L.tn_split.argtypes = [C.c_void_p, u32p, C.c_uint32, C.c_uint64, f32p, C.c_void_p, u32p]
+        _tsvq_node_host = L
+    return _tsvq_node_host
+
+
+class TsvqNodes:
+    """The per-node host reference over one training set (rows (n, dim) float32, weights (n,) uint64)."""
+
+    def __init__(self, rows, weights):
+        self.L = tsvq_node_host()
+        self.rows = np.ascontiguousarray(rows, np.float32)
+        self.weights = np.ascontiguousarray(weights, np.uint64)
+        self.n, self.dim = self.rows.shape
+        self.h = self.L.tn_open(self.dim, ptr(self.rows, f32p), ptr(self.weights, u64p), self.n)
+        assert self.h
+
+    def root(self, members):
+        """-> TSVQ_ROOT scalar: make_root over `members` in list order"""
+        m = np.ascontiguousarray(members, np.uint32)
+        out = np.zeros(1, TSVQ_ROOT)
+        self.L.tn_root(self.h, ptr(m, u32p), m.size, out.ctypes.data_as(C.c_void_p))
+        return out[0]
+
+    def split(self, members, weight, origin):
+        """-> (TSVQ_SPLIT scalar with RAW variances, left list, right list); ok == 0 (and empty lists) where prep_split / refine_split return false"""
+        m = np.ascontiguousarray(members, np.uint32)
+        o = np.zeros(16, np.float32); o[:self.dim] = np.asarray(origin, np.float32)[:self.dim]
+        out = np.zeros(1, TSVQ_SPLIT); kids = np.zeros(max(m.size, 1), np.uint32)
+        self.L.tn_split(self.h, ptr(m, u32p), m.size, int(weight), ptr(o, f32p), out.ctypes.data_as(C.c_void_p), ptr(kids, u32p))
+        r = out[0]
+        if not r["ok"]:
+            return r, kids[:0], kids[:0]
+        return r, kids[:int(r["l_count"])].copy(), kids[int(r["l_count"]):m.size].copy()
+
+    def close(self):
+        if self.h:
+            self.L.tn_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
 def host_encode_uastc(blocks, flags):
     blocks = np.ascontiguousarray(blocks)
     n = blocks.shape[0]
