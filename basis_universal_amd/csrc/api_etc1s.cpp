@@ -7,6 +7,7 @@
 #include "unique_kernels.h"
 #include "bookkeeping_kernels.h"
 #include "kmeans_kernels.h"
+#include "host/seam_translate.h"
 
 namespace {
 constexpr uint32_t UP_PIECE_BLOCKS = 65536;   // 4 MiB of tiles: 0.08 ms on the link, 0.11 ms of the kernel
@@ -666,55 +667,32 @@ int bu_hip_determine_selectors(bu_hip_context* ctx, const bu_color_rgba* color5_
 int bu_hip_refine_endpoint_clusterization(bu_hip_context* ctx, const bu_block_info* info, uint32_t total_clusters, const bu_endpoint_cluster* clusters,
                                           const uint32_t* /*sorted_block_indices*/, uint32_t* out, int perceptual) {
     // The reference seam passes, per block, a window [first_cluster_ofs, first_cluster_ofs+num_clusters) into a flat list of
-    // {unscaled colour, inten, cluster index} (frontend.cpp:1684-1750). We translate that to the device layer's form:
+    // {unscaled colour, inten, cluster index} (frontend.cpp:1684-1750). host/seam_translate.h turns that into the device layer's form:
     // a parameter table addressed by POSITION in the flat list, one "parent" per distinct window. The block's current
     // cluster is identified by its index value; the kernel's tie rule compares against the candidate's position, so the
-    // position of the current cluster inside the window is looked up here.
+    // position of the current cluster inside the window is looked up there.
     if (!ctx || !ctx->d_pixel_blocks) { if (ctx) set_error(ctx, "no pixel blocks set"); return 0; }
     device_guard g(ctx->device);
     const uint32_t n = (uint32_t)ctx->total_blocks;
-    std::vector<uint32_t> params(total_clusters);
-    for (uint32_t i = 0; i < total_clusters; i++)
-        params[i] = clusters[i].m_unscaled_color.r | (clusters[i].m_unscaled_color.g << 8) | (clusters[i].m_unscaled_color.b << 16) | ((uint32_t)clusters[i].m_etc_inten << 24);
-    // windows -> parents
-    std::vector<uint32_t> win_first, win_count, cand_offsets(1, 0), cand_indices;
-    std::vector<uint8_t> block_parent8;
-    std::vector<uint32_t> block_parent(n), block_cur(n);
-    std::vector<int32_t> first_to_parent(65536, -1);
-    for (uint32_t b = 0; b < n; b++) {
-        const uint32_t f = info[b].m_first_cluster_ofs, c = info[b].m_num_clusters;
-        int32_t p = first_to_parent[f];
-        if (p < 0 || win_count[p] != c) {
-            p = (int32_t)win_first.size();
-            first_to_parent[f] = p;
-            win_first.push_back(f); win_count.push_back(c);
-            for (uint32_t k = 0; k < c; k++) cand_indices.push_back(f + k);
-            cand_offsets.push_back((uint32_t)cand_indices.size());
-        }
-        block_parent[b] = (uint32_t)p;
-        // position of the block's current cluster inside its window (it is always present, frontend.cpp:971-996)
-        uint32_t pos = f;
-        for (uint32_t k = 0; k < c; k++)
-            if (clusters[f + k].m_cluster_index == info[b].m_cur_cluster_index) { pos = f + k; break; }
-        block_cur[b] = pos;
-    }
-    if (win_first.size() > 255) { set_error(ctx, "refine: more than 255 distinct candidate windows"); return 0; }
-    block_parent8.resize(n);
-    for (uint32_t b = 0; b < n; b++) block_parent8[b] = (uint8_t)block_parent[b];
+    if (n && !out) { set_error(ctx, "refine: null pointer"); return 0; }
+    bu::seam::refine_tables t;
+    if (const char* e = bu::seam::translate_refine(info, n, total_clusters, clusters, t)) { set_error(ctx, "%s", e); return 0; }
+    if (!n) return 1;
+    const uint32_t n_parents = t.win.n_parents();
 
     arena &a_par = ctx->scratch[0], &a_cur = ctx->scratch[1], &a_off = ctx->scratch[2], &a_idx = ctx->scratch[3], &a_out = ctx->scratch[4];
     arena& a_bp = ctx->scratch[5];
-    BU_TRY(ctx, a_par.reserve(total_clusters * 4ull)); BU_TRY(ctx, a_cur.reserve(n * 4ull)); BU_TRY(ctx, a_off.reserve(cand_offsets.size() * 4ull));
-    BU_TRY(ctx, a_idx.reserve(cand_indices.size() * 4ull + 4)); BU_TRY(ctx, a_out.reserve(n * 4ull)); BU_TRY(ctx, a_bp.reserve(n));
-    BU_TRY(ctx, h2d(ctx, a_par.p, params.data(), total_clusters * 4ull));
-    BU_TRY(ctx, h2d(ctx, a_cur.p, block_cur.data(), n * 4ull));
-    BU_TRY(ctx, h2d(ctx, a_off.p, cand_offsets.data(), cand_offsets.size() * 4ull));
-    if (!cand_indices.empty()) BU_TRY(ctx, h2d(ctx, a_idx.p, cand_indices.data(), cand_indices.size() * 4ull));
-    BU_TRY(ctx, h2d(ctx, a_bp.p, block_parent8.data(), n));
+    BU_TRY(ctx, a_par.reserve(total_clusters * 4ull)); BU_TRY(ctx, a_cur.reserve(n * 4ull)); BU_TRY(ctx, a_off.reserve(t.win.cand_offsets.size() * 4ull));
+    BU_TRY(ctx, a_idx.reserve(t.win.cand_indices.size() * 4ull + 4)); BU_TRY(ctx, a_out.reserve(n * 4ull)); BU_TRY(ctx, a_bp.reserve(n));
+    BU_TRY(ctx, h2d(ctx, a_par.p, t.params.data(), total_clusters * 4ull));
+    BU_TRY(ctx, h2d(ctx, a_cur.p, t.block_cur.data(), n * 4ull));
+    BU_TRY(ctx, h2d(ctx, a_off.p, t.win.cand_offsets.data(), t.win.cand_offsets.size() * 4ull));
+    BU_TRY(ctx, h2d(ctx, a_idx.p, t.win.cand_indices.data(), t.win.cand_indices.size() * 4ull));
+    BU_TRY(ctx, h2d(ctx, a_bp.p, t.win.block_parent.data(), n));
     void* work = nullptr;
-    if (const size_t wb = bu::refine_workspace_bytes(total_clusters, (uint32_t)win_first.size())) { BU_TRY(ctx, ctx->refine_lists.reserve(wb)); work = ctx->refine_lists.p; }
+    if (const size_t wb = ctx->tuning.refine_unsorted ? 0 : bu::refine_workspace_bytes(total_clusters, n_parents)) { BU_TRY(ctx, ctx->refine_lists.reserve(wb)); work = ctx->refine_lists.p; }
     BU_TRY(ctx, bu::launch_refine_endpoint_clusterization(ctx->stream, ctx->d_pixel_blocks, n, static_cast<const uint32_t*>(a_cur.p),
-                                                          static_cast<const uint8_t*>(a_par.p), total_clusters, (uint32_t)win_first.size(),
+                                                          static_cast<const uint8_t*>(a_par.p), total_clusters, n_parents,
                                                           static_cast<const uint32_t*>(a_off.p), static_cast<const uint32_t*>(a_idx.p),
                                                           static_cast<const uint8_t*>(a_bp.p), perceptual != 0, static_cast<uint32_t*>(a_out.p), work));
     std::vector<uint32_t> pos(n);
@@ -728,49 +706,24 @@ int bu_hip_find_optimal_selector_clusters_for_each_block(bu_hip_context* ctx, co
     if (!ctx || !ctx->d_pixel_blocks) { if (ctx) set_error(ctx, "no pixel blocks set"); return 0; }
     device_guard g(ctx->device);
     const uint32_t n = (uint32_t)ctx->total_blocks;
-    // packed 2-bit selectors [p*2] (frontend.cpp:2462-2464) -> etc_block selector bytes, addressed by position in the flat list
-    std::vector<uint64_t> sel_blocks(total_input_selectors);
-    for (uint32_t i = 0; i < total_input_selectors; i++) {
-        uint32_t bits = 0;
-        for (uint32_t p = 0; p < 16; p++) {
-            const uint32_t s = (selectors[i].m_packed_selectors >> (p * 2)) & 3u, x = p & 3u, y = p >> 2;
-            const uint32_t raw = (0x4Bu >> (s * 2)) & 3u, bit = x * 4 + y;
-            bits |= ((raw & 1u) << bit) | ((raw >> 1) << (16 + bit));
-        }
-        sel_blocks[i] = __builtin_bswap64((uint64_t)bits);
-    }
-    std::vector<uint64_t> enc(n);
-    std::vector<uint32_t> win_first, win_count, cand_offsets(1, 0), cand_indices, block_parent(n);
-    std::vector<uint8_t> bp8(n);
-    for (uint32_t b = 0; b < n; b++) {
-        const bu_color_rgba c = info[b].m_etc_color5_inten;
-        const uint64_t v = ((uint64_t)c.r << 59) | ((uint64_t)c.g << 51) | ((uint64_t)c.b << 43) | ((uint64_t)c.a << 37) | ((uint64_t)c.a << 34) | (3ull << 32);
-        enc[b] = __builtin_bswap64(v);
-        const uint32_t f = info[b].m_first_selector, cnt = info[b].m_num_selectors;
-        int32_t p = -1;
-        for (size_t w = 0; w < win_first.size(); w++) if (win_first[w] == f && win_count[w] == cnt) { p = (int32_t)w; break; }
-        if (p < 0) {
-            p = (int32_t)win_first.size();
-            win_first.push_back(f); win_count.push_back(cnt);
-            for (uint32_t k = 0; k < cnt; k++) cand_indices.push_back(f + k);
-            cand_offsets.push_back((uint32_t)cand_indices.size());
-        }
-        block_parent[b] = (uint32_t)p;
-    }
-    if (win_first.size() > 255) { set_error(ctx, "fosc: more than 255 distinct candidate windows"); return 0; }
-    for (uint32_t b = 0; b < n; b++) bp8[b] = (uint8_t)block_parent[b];
+    if (n && (!out || !selector_cluster_indices)) { set_error(ctx, "fosc: null pointer"); return 0; }
+    // packed 2-bit selectors -> etc_block selector bytes addressed by position in the flat list, colour5 + inten -> etc_block, windows -> parents
+    bu::seam::fosc_tables t;
+    if (const char* e = bu::seam::translate_fosc(info, n, total_input_selectors, selectors, t)) { set_error(ctx, "%s", e); return 0; }
+    if (!n) return 1;
+    const uint32_t n_parents = t.win.n_parents();
 
     arena &a_sel = ctx->scratch[0], &a_enc = ctx->scratch[1], &a_off = ctx->scratch[2], &a_idx = ctx->scratch[3], &a_tmp = ctx->scratch[4], &a_bp = ctx->scratch[5];
-    BU_TRY(ctx, a_sel.reserve(total_input_selectors * 8ull + 8)); BU_TRY(ctx, a_enc.reserve(n * 8ull + n * 4ull)); BU_TRY(ctx, a_off.reserve(cand_offsets.size() * 4ull));
-    BU_TRY(ctx, a_idx.reserve(cand_indices.size() * 4ull + 4)); BU_TRY(ctx, a_tmp.reserve(n * 4ull)); BU_TRY(ctx, a_bp.reserve(n));
+    BU_TRY(ctx, a_sel.reserve(total_input_selectors * 8ull + 8)); BU_TRY(ctx, a_enc.reserve(n * 8ull + n * 4ull)); BU_TRY(ctx, a_off.reserve(t.win.cand_offsets.size() * 4ull));
+    BU_TRY(ctx, a_idx.reserve(t.win.cand_indices.size() * 4ull + 4)); BU_TRY(ctx, a_tmp.reserve(n * 4ull)); BU_TRY(ctx, a_bp.reserve(n));
     uint32_t* d_out = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(a_enc.p) + n * 8ull);
-    if (total_input_selectors) BU_TRY(ctx, h2d(ctx, a_sel.p, sel_blocks.data(), total_input_selectors * 8ull));
-    BU_TRY(ctx, h2d(ctx, a_enc.p, enc.data(), n * 8ull));
-    BU_TRY(ctx, h2d(ctx, a_off.p, cand_offsets.data(), cand_offsets.size() * 4ull));
-    if (!cand_indices.empty()) BU_TRY(ctx, h2d(ctx, a_idx.p, cand_indices.data(), cand_indices.size() * 4ull));
-    BU_TRY(ctx, h2d(ctx, a_bp.p, bp8.data(), n));
+    BU_TRY(ctx, h2d(ctx, a_sel.p, t.selector_blocks.data(), total_input_selectors * 8ull));
+    BU_TRY(ctx, h2d(ctx, a_enc.p, t.encoded_blocks.data(), n * 8ull));
+    BU_TRY(ctx, h2d(ctx, a_off.p, t.win.cand_offsets.data(), t.win.cand_offsets.size() * 4ull));
+    BU_TRY(ctx, h2d(ctx, a_idx.p, t.win.cand_indices.data(), t.win.cand_indices.size() * 4ull));
+    BU_TRY(ctx, h2d(ctx, a_bp.p, t.win.block_parent.data(), n));
     // chunk = 0: the OpenCL seam has no "same tile as previous block" shortcut (ocl_kernels.cl:1159-1225)
-    BU_TRY(ctx, bu::launch_find_optimal_selector_clusters(ctx->stream, ctx->d_pixel_blocks, a_enc.p, n, a_sel.p, total_input_selectors, (uint32_t)win_first.size(),
+    BU_TRY(ctx, bu::launch_find_optimal_selector_clusters(ctx->stream, ctx->d_pixel_blocks, a_enc.p, n, a_sel.p, total_input_selectors, n_parents,
                                                           static_cast<const uint32_t*>(a_off.p), static_cast<const uint32_t*>(a_idx.p), static_cast<const uint8_t*>(a_bp.p),
                                                           perceptual != 0, 0, static_cast<uint32_t*>(a_tmp.p), d_out, nullptr, 0));
     std::vector<uint32_t> pos(n);
@@ -783,55 +736,32 @@ int bu_hip_encode_etc1s_pixel_clusters(bu_hip_context* ctx, bu_etc_block* out, u
                                        uint64_t total_pixels, const bu_color_rgba* pixels, const uint32_t* weights, int perceptual, uint32_t total_perms) {
     // The reference seam hands over de-duplicated colours with multiplicities. The device layer works on unweighted pixel lists
     // (bu_hip_k_generate_endpoint_codebook, which is what our own frontend uses and what INTEGRATION.md binds). For the legacy
-    // call we expand the multiplicities into a temporary tile array laid out as "training vectors" of 8 pixels; clusters whose
-    // expanded size is not a multiple of 8 cannot be expressed that way, so the expansion pads by REPEATING the whole colour
-    // list k times (k = 8 / gcd(n, 8)): errors scale by k, the float mean and min/max are unchanged while sums stay < 2^24,
-    // and the argmin over (colour, table) is invariant under a uniform positive scaling of all errors.
+    // call the multiplicities are expanded into a temporary tile array laid out as "training vectors" of 8 pixels; clusters whose
+    // expanded size is not a multiple of 8 are REPEATED whole (host/seam_translate.h, translate_pixel_clusters, has the argument).
     if (!ctx) return 0;
     device_guard g(ctx->device);
     if (!total_clusters) return 1;
-    std::vector<uint32_t> offsets(total_clusters + 1, 0), expanded;
-    std::vector<uint32_t> words;
-    words.reserve((size_t)total_pixels * 2);
-    for (uint32_t c = 0; c < total_clusters; c++) {
-        const uint64_t first = clusters[c].m_first_pixel_index, cnt = clusters[c].m_total_pixels;
-        if (first + cnt > total_pixels) { set_error(ctx, "pixel cluster out of range"); return 0; }
-        uint64_t n = 0;
-        for (uint64_t i = 0; i < cnt; i++) n += weights[first + i];
-        if (!n) { set_error(ctx, "empty pixel cluster"); return 0; }
-        uint32_t gcd = 8; while (n % gcd) gcd >>= 1;
-        const uint32_t reps = 8 / gcd;
-        if (n * reps > 0x7FFFFFFFull) { set_error(ctx, "pixel cluster too large"); return 0; }
-        const size_t base = words.size();
-        for (uint32_t r = 0; r < reps; r++)
-            for (uint64_t i = 0; i < cnt; i++) {
-                uint32_t w; memcpy(&w, &pixels[first + i], 4);
-                words.insert(words.end(), weights[first + i], w);
-            }
-        const uint32_t tv_first = (uint32_t)(base / 8), tv_cnt = (uint32_t)((words.size() - base) / 8);
-        offsets[c + 1] = offsets[c] + tv_cnt;
-        for (uint32_t t = 0; t < tv_cnt; t++) expanded.push_back(tv_first + t);
-    }
-    words.resize((words.size() + 15) / 16 * 16, 0);
+    if (!out) { set_error(ctx, "pixel clusters: null pointer"); return 0; }
+    bu::seam::pixel_tables t;
+    if (const char* e = bu::seam::translate_pixel_clusters(total_clusters, clusters, total_pixels, pixels, weights, t)) { set_error(ctx, "%s", e); return 0; }
     arena &a_px = ctx->scratch[0], &a_off = ctx->scratch[1], &a_idx = ctx->scratch[2], &a_par = ctx->scratch[3];
     const size_t params_bytes = ((total_clusters * 4ull + 7) / 8) * 8;
-    BU_TRY(ctx, a_px.reserve(words.size() * 4ull)); BU_TRY(ctx, a_off.reserve(offsets.size() * 4ull)); BU_TRY(ctx, a_idx.reserve(expanded.size() * 4ull + 4));
+    BU_TRY(ctx, a_px.reserve(t.texels.size() * 4ull)); BU_TRY(ctx, a_off.reserve(t.offsets.size() * 4ull)); BU_TRY(ctx, a_idx.reserve(t.indices.size() * 4ull + 4));
     BU_TRY(ctx, a_par.reserve(params_bytes + total_clusters * 8ull + total_clusters));
-    BU_TRY(ctx, h2d(ctx, a_px.p, words.data(), words.size() * 4ull));
-    BU_TRY(ctx, h2d(ctx, a_off.p, offsets.data(), offsets.size() * 4ull));
-    BU_TRY(ctx, h2d(ctx, a_idx.p, expanded.data(), expanded.size() * 4ull));
+    BU_TRY(ctx, h2d(ctx, a_px.p, t.texels.data(), t.texels.size() * 4ull));
+    BU_TRY(ctx, h2d(ctx, a_off.p, t.offsets.data(), t.offsets.size() * 4ull));
+    BU_TRY(ctx, h2d(ctx, a_idx.p, t.indices.data(), t.indices.size() * 4ull));
     uint8_t* d_params = static_cast<uint8_t*>(a_par.p);
     uint64_t* d_err = reinterpret_cast<uint64_t*>(d_params + params_bytes);
     uint8_t* d_valid = reinterpret_cast<uint8_t*>(d_err + total_clusters);
-    if (!bu_hip_k_generate_endpoint_codebook(ctx, a_px.p, total_clusters, offsets.data(), static_cast<const uint32_t*>(a_off.p), static_cast<const uint32_t*>(a_idx.p),
+    // the cluster fit has no FAST quality (frontend.cpp:1530-1533): total_perms = 4 is fitted as 16
+    if (!bu_hip_k_generate_endpoint_codebook(ctx, a_px.p, total_clusters, t.offsets.data(), static_cast<const uint32_t*>(a_off.p), static_cast<const uint32_t*>(a_idx.p),
                                              std::max(quality_from_perms(total_perms), (int)bu::BU_Q_MEDIUM), perceptual, 0, d_params, d_err, d_valid))
         return 0;
     std::vector<uint8_t> params(total_clusters * 4ull);
     if (!fetch(ctx, params.data(), d_params, params.size())) return 0;
     for (uint32_t c = 0; c < total_clusters; c++) {
-        const uint64_t v = ((uint64_t)params[c * 4] << 59) | ((uint64_t)params[c * 4 + 1] << 51) | ((uint64_t)params[c * 4 + 2] << 43) |
-                           ((uint64_t)params[c * 4 + 3] << 37) | ((uint64_t)params[c * 4 + 3] << 34) | (3ull << 32);
-        const uint64_t m = __builtin_bswap64(v);
+        const uint64_t m = bu::seam::color5_inten_to_etc_block(params[c * 4], params[c * 4 + 1], params[c * 4 + 2], params[c * 4 + 3]);
         memcpy(&out[c], &m, 8);
     }
     return 1;

@@ -55,16 +55,41 @@ BU_HIP_API void bu_hip_destroy_context(bu_hip_context*);  /* opencl_destroy_cont
 
 /* opencl_set_pixel_blocks :46 -- uploads once; the blocks stay resident in the context */
 BU_HIP_API int bu_hip_set_pixel_blocks(bu_hip_context*, size_t total_blocks, const bu_pixel_block* pixel_blocks);
-/* opencl_encode_etc1s_blocks :48 -- total_perms in {4,16,64,165} selects the etc1_optimizer quality (fast/medium/slow/uber) */
+/* opencl_encode_etc1s_blocks :48 -- total_perms in {4,16,64,165} selects the etc1_optimizer quality (fast/medium/slow/uber); a value off the table takes the next
+ * one up (<= 4 fast, <= 16 medium, <= 64 slow, above that uber) */
 BU_HIP_API int bu_hip_encode_etc1s_blocks(bu_hip_context*, bu_etc_block* output_blocks, int perceptual, uint32_t total_perms);
-/* opencl_encode_etc1s_pixel_clusters :60-68 -- weighted, de-duplicated pixel lists */
+/* opencl_encode_etc1s_pixel_clusters :60-68 -- weighted, de-duplicated pixel lists: cluster c is pixels[first .. first + total) with multiplicities pixel_weights[..]
+ * (zero weights are allowed inside a cluster whose weights do not all vanish). Needs no resident pixel blocks.
+ *   - total_perms as above, except that the cluster fit has no FAST quality (frontend.cpp:1530-1533): 4 is treated as 16.
+ *   - output_blocks[c] is the ETC1S block of the fitted colour5 + intensity table and nothing else: colour5 in the top five bits of bytes 0-2 with zero deltas,
+ *     BOTH table fields of byte 3 = the table, diff and flip bits set, the four selector bytes zero.
+ *   - The device layer fits unweighted lists of 8-texel training vectors, so a cluster is written out weight by weight, and where its total n is no multiple
+ *     of 8 the whole list is written 8 / gcd(n, 8) times over. Errors scale by that factor and the argmin does not move; the float colour mean the optimizer
+ *     starts from is unchanged as long as 255 * n * 8 / gcd(n, 8) < 2^24 (every float sum exact) -- the exact-parity regime: there the block is the one
+ *     etc1_optimizer gives for the list itself. Beyond it the repeated list's mean is a sum of rounded adds, and equality with the unrepeated list is a
+ *     property of the input, not a guarantee (tests/test_gpu_seam_section1.py holds two such lists of 20,001 and 66,001 pixels to it).
+ *   - Refused (0, nothing written): a cluster that reaches past total_pixels, a cluster whose weights are all zero, a cluster of more than 2^31 - 1 texels
+ *     after expansion, more than 2^31 - 1 texels after expansion over the WHOLE call (what 32-bit texel arithmetic addresses; checked before anything is
+ *     expanded), null pointers with non-zero counts. */
 BU_HIP_API int bu_hip_encode_etc1s_pixel_clusters(bu_hip_context*, bu_etc_block* output_blocks, uint32_t total_clusters,
     const bu_pixel_cluster* clusters, uint64_t total_pixels, const bu_color_rgba* pixels, const uint32_t* pixel_weights,
     int perceptual, uint32_t total_perms);
-/* opencl_refine_endpoint_clusterization :89-96 */
+/* opencl_refine_endpoint_clusterization :89-96 -- per block the best cluster of its candidate window [m_first_cluster_ofs, + m_num_clusters) of cluster_info,
+ * returned as that entry's m_cluster_index (frontend.cpp:1684-1750, ocl_kernels.cl:1063-1136).
+ *   - Windows are told apart by (first, count): they may overlap, nest or share a first offset, the layout may hold empty parents, and a cluster may be filed in
+ *     several windows (frontend.cpp:1706). At most 255 DISTINCT windows per call.
+ *   - A block's window is never empty and lies inside cluster_info, and the block's m_cur_cluster_index is the m_cluster_index of one of its entries (the reference
+ *     always files it there, frontend.cpp:971-996): the intensity filter and the tie rule go by that entry. m_cur_cluster_etc_inten is not read.
+ *   - Ties go to the block's current cluster, otherwise to the lower position. sorted_block_indices only orders the reference's work items: not read, may be NULL.
+ *   - Refused on the host (0, a text in bu_hip_last_error, nothing written, nothing launched): a window past the end, an empty window, a current cluster that is
+ *     not in its window, a 256th window, null pointers with non-zero counts. */
 BU_HIP_API int bu_hip_refine_endpoint_clusterization(bu_hip_context*, const bu_block_info* pixel_block_info, uint32_t total_clusters,
     const bu_endpoint_cluster* cluster_info, const uint32_t* sorted_block_indices, uint32_t* output_cluster_indices, int perceptual);
-/* opencl_find_optimal_selector_clusters_for_each_block :120-127 */
+/* opencl_find_optimal_selector_clusters_for_each_block :120-127 -- per block the selector of its window [m_first_selector, + m_num_selectors) of input_selectors
+ * (texel y * 4 + x at bits [2p, 2p + 2), frontend.cpp:2462-2464) with the least error under the block's colour5 + table, returned as
+ * selector_cluster_indices[position in input_selectors] (any mapping, not only the identity); the first minimum in window order wins; no "same tile as the previous
+ * block" shortcut (ocl_kernels.cl:1159-1216). Windows as for refine: overlapping, nested, sharing a first offset, a selector in several of them; at most 255 distinct
+ * ones; a block's own window non-empty and inside input_selectors -- anything else is refused on the host in the same way. */
 BU_HIP_API int bu_hip_find_optimal_selector_clusters_for_each_block(bu_hip_context*, const bu_fosc_block* input_block_info,
     uint32_t total_input_selectors, const bu_fosc_selector* input_selectors, const uint32_t* selector_cluster_indices,
     uint32_t* output_selector_cluster_indices, int perceptual);

@@ -165,6 +165,44 @@ def orc_encode_blocks(blocks, level, perceptual=True):
     return out
 
 
+def etc1s_test_tiles():
+    """The ~3,500 tiles of the ETC1S kernel parity tests: a synthetic image, uniform noise, flat tiles (white, black, one dark red run) and a two-channel gradient."""
+    a = to_pixel_blocks(synth(256, 192, 1234))
+    b = to_pixel_blocks(uniform_random(64, 64, 42))
+    flat = np.zeros((64, 4, 4, 4), np.uint8)
+    flat[:, :, :, 3] = 255
+    flat[:32, :, :, :3] = 255
+    flat[40:48, :, :, 0] = 17
+    grad = np.zeros((32, 64, 4), np.uint8)
+    grad[..., 0] = np.arange(64)[None, :] * 4
+    grad[..., 1] = np.arange(32)[:, None] * 8
+    grad[..., 3] = 255
+    return np.concatenate([a, b, flat, to_pixel_blocks(grad)])
+
+
+def clusters_by_luma(blocks, k, rng):
+    """A plausible endpoint clustering: blocks sorted by mean luma cut into k uneven runs; both subblocks stay together."""
+    n = blocks.shape[0]
+    order = np.argsort(blocks[..., :3].reshape(n, -1).astype(np.int64).sum(axis=1), kind="stable")
+    cuts = np.sort(rng.choice(np.arange(1, n), size=k - 1, replace=False))
+    lists, block_cluster = [], np.zeros(n, np.uint32)
+    for ci, run in enumerate(np.split(order, cuts)):
+        run = rng.permutation(run)
+        lists.append(np.stack([run * 2, run * 2 + 1], axis=1).reshape(-1).astype(np.uint32))
+        block_cluster[run] = ci
+    return lists, block_cluster
+
+
+def endpoint_codebook(blocks, k, seed, level=1, perceptual=1):
+    """-> (k x {r5, g5, b5, inten} of the oracle's fit of clusters_by_luma's clusters, the cluster of every block)"""
+    rng = np.random.default_rng(seed)
+    lists, block_cluster = clusters_by_luma(blocks, k, rng)
+    offs, idx = csr_from_lists(lists)
+    params = np.zeros((k, 4), np.uint8); err = np.zeros(k, np.uint64); valid = np.zeros(k, np.uint8)
+    oracle().orc_generate_endpoint_codebook(ptr(blocks), k, ptr(offs, u32p), ptr(idx, u32p), level, perceptual, 0, ptr(params), ptr(err, u64p), ptr(valid))
+    return params, block_cluster
+
+
 # ----------------------------------------------------------------------------- the real reference
 
 _ref = None
@@ -634,6 +672,92 @@ class TsvqNodes:
 
     def __del__(self):
         self.close()
+
+
+# the packed PODs of include/basisu_hip.h section 1 (= encoder/basisu_opencl.h) as numpy structured dtypes
+BU_COLOR = np.dtype([("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("a", np.uint8)])
+BU_PIXEL_CLUSTER = np.dtype([("total_pixels", np.uint64), ("first_pixel_index", np.uint64)])
+BU_BLOCK_INFO = np.dtype([("first_cluster_ofs", np.uint16), ("num_clusters", np.uint16), ("cur_cluster_index", np.uint16), ("cur_cluster_etc_inten", np.uint8)])
+BU_ENDPOINT_CLUSTER = np.dtype([("unscaled_color", BU_COLOR), ("etc_inten", np.uint8), ("cluster_index", np.uint16)])
+BU_FOSC_SELECTOR = np.dtype([("packed_selectors", np.uint32)])
+BU_FOSC_BLOCK = np.dtype([("etc_color5_inten", BU_COLOR), ("first_selector", np.uint32), ("num_selectors", np.uint32)])
+assert (BU_PIXEL_CLUSTER.itemsize, BU_BLOCK_INFO.itemsize, BU_ENDPOINT_CLUSTER.itemsize, BU_FOSC_SELECTOR.itemsize, BU_FOSC_BLOCK.itemsize) == (16, 7, 7, 4, 12)
+
+_seam_translate_host = None
+
+
+def seam_translate_host():
+    """csrc/host/seam_translate.h (the host translations behind section 1 of include/basisu_hip.h) compiled for the host: tests/native/seam_translate_host.cpp."""
+    global _seam_translate_host
+    if _seam_translate_host is None:
+        d = ROOT / "tests" / "native"
+        so, srcs = d / "libseam_translate_host.so", [d / "seam_translate_host.cpp", ROOT / "basis_universal_amd" / "csrc" / "host" / "seam_translate.h",
+                                                     ROOT / "include" / "basisu_hip.h"]
+        if not so.exists() or so.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
+            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(so), str(srcs[0])])
+        L = C.CDLL(str(so))
+        errp = C.POINTER(C.c_char_p)
+        L.st_refine.restype = C.c_void_p
+        L.st_refine.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, errp]
+        L.st_fosc.restype = C.c_void_p
+        L.st_fosc.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, errp]
+        L.st_pixel_clusters.restype = C.c_void_p
+        L.st_pixel_clusters.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, errp]
+        L.st_get.restype = C.c_uint64
+        L.st_get.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]
+        L.st_free.argtypes = [C.c_void_p]
+        L.st_selectors_to_etc_block.argtypes = [C.c_uint32, u8p]
+        L.st_color5_inten_to_etc_block.argtypes = [C.c_uint32] * 4 + [u8p]
+        L.st_max_windows.restype = C.c_uint32
+        L.st_max_expanded_texels.restype = C.c_uint64
+        _seam_translate_host = L
+    return _seam_translate_host
+
+
+def _seam_tables(handle, err, layout):
+    """-> (dict of arrays, None) for a translation that succeeded, (None, the refusal's text) otherwise"""
+    L = seam_translate_host()
+    if not handle:
+        assert err.value, "refused without a text"
+        return None, err.value.decode()
+    assert err.value is None
+    out = {}
+    for i, (name, dtype) in enumerate(layout):
+        need = L.st_get(handle, i, None, 0)
+        assert need != 2 ** 64 - 1 and need % np.dtype(dtype).itemsize == 0
+        buf = np.zeros(need // np.dtype(dtype).itemsize, dtype)
+        L.st_get(handle, i, buf.ctypes.data_as(C.c_void_p), need)
+        out[name] = buf
+    L.st_free(handle)
+    return out, None
+
+
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+
+
+_WINDOWS = [("cand_offsets", np.uint32), ("cand_indices", np.uint32), ("block_parent", np.uint8)]
+
+
+def seam_refine_tables(info, clusters, null=()):
+    """translate_refine over BU_BLOCK_INFO / BU_ENDPOINT_CLUSTER arrays; `null` names arguments handed over as NULL with their counts kept"""
+    err = C.c_char_p()
+    h = seam_translate_host().st_refine(None if "info" in null else _vp(info), info.size, clusters.size, None if "clusters" in null else _vp(clusters), C.byref(err))
+    return _seam_tables(h, err, [("params", np.uint32)] + _WINDOWS + [("block_cur", np.uint32)])
+
+
+def seam_fosc_tables(info, selectors, null=()):
+    err = C.c_char_p()
+    h = seam_translate_host().st_fosc(None if "info" in null else _vp(info), info.size, selectors.size, None if "selectors" in null else _vp(selectors), C.byref(err))
+    return _seam_tables(h, err, [("selector_blocks", np.dtype((np.uint8, 8))), ("encoded_blocks", np.dtype((np.uint8, 8)))] + _WINDOWS)
+
+
+def seam_pixel_tables(clusters, pixels, weights, total_pixels=None, null=()):
+    err = C.c_char_p()
+    total = pixels.shape[0] if total_pixels is None else total_pixels
+    h = seam_translate_host().st_pixel_clusters(clusters.size, None if "clusters" in null else _vp(clusters), total, None if "pixels" in null else _vp(pixels),
+                                                None if "weights" in null else _vp(weights), C.byref(err))
+    return _seam_tables(h, err, [("texels", np.uint32), ("offsets", np.uint32), ("indices", np.uint32), ("reps", np.uint32), ("totals", np.uint64)])
 
 
 def host_encode_uastc(blocks, flags):

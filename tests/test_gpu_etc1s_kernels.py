@@ -9,24 +9,11 @@ import numpy as np
 import pytest
 
 from helpers import (oracle, ptr, u8p, u32p, u64p, f32p, synth, uniform_random, to_pixel_blocks, csr_from_lists)
+from helpers import etc1s_test_tiles as _images, clusters_by_luma as _clusters_by_luma, endpoint_codebook as _codebook
 
 pytestmark = pytest.mark.gpu
 
 VP = C.c_void_p
-
-
-def _images():
-    a = to_pixel_blocks(synth(256, 192, 1234))
-    b = to_pixel_blocks(uniform_random(64, 64, 42))
-    flat = np.zeros((64, 4, 4, 4), np.uint8)
-    flat[:, :, :, 3] = 255
-    flat[:32, :, :, :3] = 255
-    flat[40:48, :, :, 0] = 17
-    grad = np.zeros((32, 64, 4), np.uint8)
-    grad[..., 0] = np.arange(64)[None, :] * 4
-    grad[..., 1] = np.arange(32)[:, None] * 8
-    grad[..., 3] = 255
-    return np.concatenate([a, b, flat, to_pixel_blocks(grad)])
 
 
 @pytest.fixture(scope="module")
@@ -147,19 +134,6 @@ def test_endpoint_training_vectors(hip_ctx, blocks):
     oracle().orc_endpoint_training_vectors(ptr(etc), n, ptr(exp, f32p))
     assert (got.view(np.uint32) == exp.view(np.uint32)).all()
     hip_ctx.free(d_etc); hip_ctx.free(d_out)
-
-
-def _clusters_by_luma(blocks, k, rng):
-    """A plausible endpoint clustering: blocks sorted by mean luma cut into k uneven runs; both subblocks stay together."""
-    n = blocks.shape[0]
-    order = np.argsort(blocks[..., :3].reshape(n, -1).astype(np.int64).sum(axis=1), kind="stable")
-    cuts = np.sort(rng.choice(np.arange(1, n), size=k - 1, replace=False))
-    lists, block_cluster = [], np.zeros(n, np.uint32)
-    for ci, run in enumerate(np.split(order, cuts)):
-        run = rng.permutation(run)
-        lists.append(np.stack([run * 2, run * 2 + 1], axis=1).reshape(-1).astype(np.uint32))
-        block_cluster[run] = ci
-    return lists, block_cluster
 
 
 # wide_min: bu_hip_tuning::codebook_wide_min -- None = the default (32,768 texels: only the giant cluster below takes the many-workgroup passes of
@@ -288,15 +262,6 @@ def test_ordered_colour_mean_of_clusters(hip_ctx, kind):
             want = np.float32(seq) / np.float32(tex.shape[0])
             assert got[ci, c].view(np.uint32) == np.float32(want).view(np.uint32), (kind, ci, c, tex.shape[0], float(got[ci, c]), float(want))
     hip_ctx.free(d_blocks); hip_ctx.free(d_idx)
-
-
-def _codebook(blocks, k, seed, level=1, perceptual=1):
-    rng = np.random.default_rng(seed)
-    lists, block_cluster = _clusters_by_luma(blocks, k, rng)
-    offs, idx = csr_from_lists(lists)
-    params = np.zeros((k, 4), np.uint8); err = np.zeros(k, np.uint64); valid = np.zeros(k, np.uint8)
-    oracle().orc_generate_endpoint_codebook(ptr(blocks), k, ptr(offs, u32p), ptr(idx, u32p), level, perceptual, 0, ptr(params), ptr(err, u64p), ptr(valid))
-    return params, block_cluster
 
 
 @pytest.mark.parametrize("presorted", [True, False])
