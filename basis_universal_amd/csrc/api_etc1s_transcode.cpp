@@ -4,18 +4,12 @@
 
 static const char* const kEtc1sTargets = "ETC1_RGB (0), BC1_RGB (2), RGBA32 (13), RGB565 (14), BGR565 (15), RGBA4444 (16)";
 
-static const char* etc1s_target_name(uint32_t target) {   // the reference's transcoder_texture_format names, for the refusal
-    static const char* const names[] = { "ETC1_RGB", "ETC2_RGBA", "BC1_RGB", "BC3_RGBA", "BC4_R", "BC5_RG", "BC7_RGBA", "BC7_ALT", "PVRTC1_4_RGB", "PVRTC1_4_RGBA", "ASTC_4x4_RGBA",
-                                         "ATC_RGB", "ATC_RGBA", "RGBA32", "RGB565", "BGR565", "RGBA4444", "FXT1_RGB", "PVRTC2_4_RGB", "PVRTC2_4_RGBA", "ETC2_EAC_R11", "ETC2_EAC_RG11" };
-    return target < sizeof(names) / sizeof(names[0]) ? names[target] : "unknown";
-}
-
 // the checks both entry points share; fills the launch arguments
 static int etc1s_transcode_args_from(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
                                      const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, void* d_out,
                                      uint32_t pitch_px, uint32_t rows_px, bu::etc1s_transcode_args& a) {
     if (!bu::etc1s_transcode_unit_bytes(target)) {
-        set_error(ctx, "transcode_etc1s: target %u (%s) is not supported (supported: %s)", target, etc1s_target_name(target), kEtc1sTargets);
+        set_error(ctx, "transcode_etc1s: target %u (%s) is not supported (supported: %s)", target, transcoder_format_name(target), kEtc1sTargets);
         return 0;
     }
     if (!d_ep_pal || !d_sel_pal || !d_ep_idx || !d_sel_idx || !d_out) { set_error(ctx, "transcode_etc1s: null device pointer"); return 0; }

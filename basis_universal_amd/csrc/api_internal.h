@@ -102,6 +102,13 @@ hipStream_t make_dedicated_stream(int device, uint32_t reserve = 0, bool reserve
 int quality_from_perms(uint32_t total_perms);
 inline uint32_t next_seq(uint32_t& seq) { return ++seq ? seq : ++seq; }   // the next sequence number a kernel stores for wait_flag: never 0
 
+// the reference's transcoder_texture_format names, for the refusals of the transcoders and the unpacker
+inline const char* transcoder_format_name(uint32_t format) {
+    static const char* const names[] = { "ETC1_RGB", "ETC2_RGBA", "BC1_RGB", "BC3_RGBA", "BC4_R", "BC5_RG", "BC7_RGBA", "BC7_ALT", "PVRTC1_4_RGB", "PVRTC1_4_RGBA", "ASTC_4x4_RGBA",
+                                         "ATC_RGB", "ATC_RGBA", "RGBA32", "RGB565", "BGR565", "RGBA4444", "FXT1_RGB", "PVRTC2_4_RGB", "PVRTC2_4_RGBA", "ETC2_EAC_R11", "ETC2_EAC_RG11" };
+    return format < sizeof(names) / sizeof(names[0]) ? names[format] : "unknown";
+}
+
 struct device_guard {
     int prev = -1; bool ok = false;
     explicit device_guard(int dev) {

@@ -12,7 +12,13 @@ comp.cpp:4265-4276; psnr_hvs_compute_metrics, enc.cpp:2256-2519; `basisu -compar
 to 8 bits, BT.601 Y in float, R, G, B, A) two float DCTs, two masking strengths and 128 weighted differences, binary32 in the reference's operation order
 (csrc/psnr_hvs.h), one wave per block and mode (csrc/psnr_hvs_kernels.hip, bu_hip_k_psnr_hvs); the per-block doubles are the reference's bit for bit, their sum over
 the image is added in a fixed order of the kernel's own (deterministic; within 2 (blocks - 1) 2^-53 relative of raster order). mseh and dB are host code
-(bu_psnr_hvs_reduce). Not here: SSIM, the "(BC7)" variant of these lines (there is no BC7 decoder in this package) and the best-ETC1S stats."""
+(bu_psnr_hvs_reduce).
+
+With bc7=True (file_stats) / stats_bc7=True (compress) every slice of a UASTC file also carries, under "bc7", the tool's second block, "Quality stats vs. transcoded BC7
+texture:" (comp.cpp:3818-3842, 3875-3883, 4278-4337): the same eight lines -- and with hvs its own "hvs", "PSNR-HVS and PSNR-HVS-M metrics (BC7):" -- of the same source
+against what the slice's BC7 transcode samples as: the resident blocks through the device's UASTC -> BC7 transcoder and then through the block unpacker
+(transcode.unpack_blocks, csrc/block_unpack_kernels.hip), never downloaded. UASTC files only: the ETC1S transcoder here has no BC7 target, and the flag raises for an
+ETC1S file. Not here: SSIM and the best-ETC1S stats."""
 import ctypes as C
 
 import numpy as np
@@ -185,10 +191,15 @@ def _slice_order(images):
     return sorted(range(len(images)), key=lambda k: (images[k]["layer"], images[k]["face"], images[k]["level"]))
 
 
-def _stats_from_slices(ctx, raw, slice_sources, hvs=False):
+BC7_REFUSAL = "BC7 stats are for UASTC files only: the ETC1S transcoder here has no BC7 target"
+
+
+def _stats_from_slices(ctx, raw, slice_sources, hvs=False, bc7=False):
     """slice_sources(level, layer, face, n_slices) -> one source raster per slice of that image (array or resident tuple). -> the per-slice dicts, slice order."""
     out = []
     if _is_etc1s(raw):
+        if bc7:
+            raise ValueError(BC7_REFUSAL)
         decoded = transcode.decode_etc1s_file(raw)
         for k in _slice_order(decoded["images"]):
             im = decoded["images"][k]
@@ -215,14 +226,28 @@ def _stats_from_slices(ctx, raw, slice_sources, hvs=False):
         (src,) = slice_sources(im["level"], im["layer"], im["face"], 1)
         d_out = ctx.alloc(w * h * 4)
         try:
-            transcode.transcode_uastc_blocks(ctx, blocks, im["num_blocks_x"], im["num_blocks_y"], transcode.RGBA32, width=w, height=h, out_device=d_out)
-            out.append(_slice_stats(ctx, src, (d_out, w, h, w), hvs))
+            if not bc7:
+                transcode.transcode_uastc_blocks(ctx, blocks, im["num_blocks_x"], im["num_blocks_y"], transcode.RGBA32, width=w, height=h, out_device=d_out)
+                out.append(_slice_stats(ctx, src, (d_out, w, h, w), hvs))
+                continue
+            # the blocks go up once; the BC7 texture and both rasters stay on the device
+            d_blocks, d_bc7 = ctx.upload(blocks), ctx.alloc(blocks.shape[0] * 16)
+            try:
+                transcode.transcode_uastc_blocks(ctx, d_blocks, im["num_blocks_x"], im["num_blocks_y"], transcode.RGBA32, width=w, height=h, out_device=d_out)
+                one = _slice_stats(ctx, src, (d_out, w, h, w), hvs)
+                transcode.transcode_uastc_blocks(ctx, d_blocks, im["num_blocks_x"], im["num_blocks_y"], transcode.BC7_RGBA, out_device=d_bc7)
+                transcode.unpack_blocks(ctx, d_bc7, im["num_blocks_x"], im["num_blocks_y"], transcode.BC7_RGBA, width=w, height=h, out_device=d_out)
+                one["bc7"] = _slice_stats(ctx, src, (d_out, w, h, w), hvs)
+                out.append(one)
+            finally:
+                ctx.free(d_blocks)
+                ctx.free(d_bc7)
         finally:
             ctx.free(d_out)
     return out
 
 
-def file_stats(ctx, data, images, hvs=False):
+def file_stats(ctx, data, images, hvs=False, bc7=False):
     """The reference's m_stats for a .basis / .ktx2 file of this package (UASTC LDR 4x4 or ETC1S): one image_metrics dict per slice, in the compressor's slice order
     (source image outermost, then its levels; an ETC1S image with alpha has a colour slice and then an alpha slice, each with its own stats).
     images: the source of every image the file holds -- {(level, layer, face): image} or, for a file of one layer and face, a list by level; an image is an
@@ -231,8 +256,12 @@ def file_stats(ctx, data, images, hvs=False):
     against (r, g, b, 255), its alpha slice -- decoded as a colour image -- against (a, a, a, 255).
     hvs: every slice dict gains "hvs", psnr_hvs of the same source against the same resident decode (m_psnr_hvs_m_stats, which the tool sets with -stats). A source
     that is padded beyond the slice's size (the compressor's level rasters) must be padded with duplicated borders, as the compressor's are: a block's coordinates
-    are clamped to each raster's own edge."""
+    are clamped to each raster's own edge.
+    bc7: every slice dict of a UASTC file gains "bc7": the same dict (the eight lines, sums and size, and "hvs" when hvs is set) of the same source against the slice's
+    BC7 transcode, unpacked on the device. An ETC1S file raises ValueError before any work."""
     raw = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
+    if bc7 and _is_etc1s(raw):
+        raise ValueError(BC7_REFUSAL)
     by_key = images if isinstance(images, dict) else {(level, 0, 0): im for level, im in enumerate(images)}
 
     def slice_sources(level, layer, face, n_slices):
@@ -249,4 +278,4 @@ def file_stats(ctx, data, images, hvs=False):
                 rows.reshape(-1, 4)[:(h - 1) * pitch + w] = ctx.download(d, ((h - 1) * pitch + w, 4), np.uint8)
             src = rows[:, :w]
         return list(split_planes(src))
-    return _stats_from_slices(ctx, raw, slice_sources, hvs)
+    return _stats_from_slices(ctx, raw, slice_sources, hvs, bc7)

@@ -22,10 +22,10 @@ DECODE_FLAGS_HIGH_QUALITY = 32   # cDecodeFlagsHighQuality
 
 
 class InvalidBlocksError(ValueError):
-    """Some blocks did not unpack as UASTC (their output was zero-filled). `count` is how many."""
+    """Some blocks did not unpack as UASTC -- or, from unpack_blocks, as BC7 -- (their output was zero-filled). `count` is how many."""
 
-    def __init__(self, count, total):
-        super().__init__(f"{count} of {total} blocks are not valid UASTC LDR 4x4 blocks")
+    def __init__(self, count, total, what="UASTC LDR 4x4"):
+        super().__init__(f"{count} of {total} blocks are not valid {what} blocks")
         self.count = count
 
 
@@ -70,6 +70,53 @@ def transcode_uastc_blocks(ctx, blocks, nbx, nby, target, *, width=None, height=
         if target == RGBA32:
             return ctx.download(d_out, (height, width, 4), np.uint8) if n else np.zeros((0, 0, 4), np.uint8)
         return ctx.download(d_out, (n, BYTES_PER_BLOCK[target]), np.uint8) if n else np.zeros((0, BYTES_PER_BLOCK[target]), np.uint8)
+    finally:
+        if own:
+            ctx.free(own)
+        if out_device is None:
+            ctx.free(d_out)
+
+
+# ---------------------------------------------------------------- block formats back to pixels
+
+UNPACK_BYTES_PER_BLOCK = {BC1_RGB: 8, BC3_RGBA: 16, BC4_R: 8, BC5_RG: 16, BC7_RGBA: 16}
+
+
+def unpack_blocks(ctx, blocks, nbx, nby, fmt, *, width=None, height=None, out_device=None, out_row_pitch=0, out_rows=0):
+    """gpu_image::unpack on the GPU: what a BC1 / BC3 / BC4 / BC5 / BC7 texture (fmt: the transcoder's target value, UNPACK_BYTES_PER_BLOCK) samples as, RGBA8.
+    blocks: (nby * nbx, 8 | 16) uint8 array in raster order (uploaded once) or a device pointer (int) to that many resident blocks, as transcode_uastc_blocks writes them.
+    Returns the (height, width, 4) raster, or None when out_device (a device pointer with room for out_rows x out_row_pitch pixels, 0 = height / width) receives it;
+    width / height default to the padded size. BC1 keeps its punch-through alpha, BC4 fills R and BC5 R, G (the rest (0, 0, 255)). The one invalid block is a BC7
+    block whose first byte is 0: zero-filled, and InvalidBlocksError is raised with their count. There is no CPU implementation."""
+    nbx, nby, fmt = int(nbx), int(nby), int(fmt)
+    if fmt not in UNPACK_BYTES_PER_BLOCK:
+        name = _TARGET_NAMES[fmt] if 0 <= fmt < len(_TARGET_NAMES) else "unknown"
+        raise ValueError(f"block format {fmt} ({name}) does not unpack here (supported: {sorted(UNPACK_BYTES_PER_BLOCK)})")
+    n, unit = nbx * nby, UNPACK_BYTES_PER_BLOCK[fmt]
+    width, height = int(width or nbx * 4), int(height or nby * 4)
+    if not (0 < width <= nbx * 4 and 0 < height <= nby * 4) and n:
+        raise ValueError(f"{width} x {height} pixels do not fit {nbx} x {nby} blocks")
+    if out_device is None and (out_row_pitch or out_rows):
+        raise ValueError("out_row_pitch / out_rows describe a caller-owned raster: give out_device")
+    own = None
+    if isinstance(blocks, np.ndarray):
+        blocks = np.ascontiguousarray(blocks, np.uint8)
+        if blocks.size != n * unit:
+            raise ValueError(f"{nbx} x {nby} blocks need {n * unit} bytes, got {blocks.size}")
+        d_blk = own = ctx.upload(blocks) if n else 0
+    else:
+        d_blk = blocks
+    d_out = out_device if out_device is not None else ctx.alloc(max(ctx.lib.unpack_output_bytes(nbx, nby, width, height, 0, 0), 1))
+    try:
+        invalid = C.c_uint32(0)
+        if n:
+            ctx.check(ctx.lib.k_unpack_blocks(ctx.h, C.c_void_p(d_blk), nbx, nby, width, height, fmt, C.c_void_p(d_out), int(out_row_pitch), int(out_rows), C.byref(invalid)),
+                      "unpack_blocks")
+        if invalid.value:
+            raise InvalidBlocksError(invalid.value, n, "BC7")
+        if out_device is not None:
+            return None
+        return ctx.download(d_out, (height, width, 4), np.uint8) if n else np.zeros((0, 0, 4), np.uint8)
     finally:
         if own:
             ctx.free(own)

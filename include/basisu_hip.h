@@ -356,6 +356,20 @@ BU_HIP_API int bu_hip_etc1s_bc1_endpoint_tables(bu_hip_context*, uint32_t* h_out
 BU_HIP_API size_t bu_hip_etc1s_transcode_output_bytes(uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height, uint32_t target,
         uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
 
+/* gpu_image::unpack (encoder/basisu_gpu_texture.cpp:1218-1266) over resident blocks: what a GPU samples from a BC1 / BC3 / BC4 / BC5 / BC7 texture, as RGBA8.
+ * format: the transcoder_texture_format value the transcoders above take as a target -- cTFBC1_RGB (2), cTFBC3_RGBA (3), cTFBC4_R (4), cTFBC5_RG (5), cTFBC7_RGBA (6);
+ * any other fails with an error that names it. d_blocks: num_blocks_x * num_blocks_y blocks of 8 (BC1, BC4) or 16 bytes in raster order, aligned to their size;
+ * d_out: 4-byte aligned, room for bu_hip_unpack_output_bytes. orig_width / orig_height: 0 = the padded size; row_pitch / rows: in pixels, 0 = orig size.
+ * BC1 decodes with its punch-through alpha (three-colour blocks' index 3 is (0, 0, 0, 0)), BC3's colour half always with four colours; BC4 writes R and BC5 R, G,
+ * the other colour channels are 0 and alpha 255. Exactly orig_width x orig_height pixels are written (rows cut at `rows`): ragged blocks are clipped and a padded
+ * pitch stays untouched. The only invalid block is a BC7 block whose first byte is 0 (the reserved mode): its texels are zero-filled and it is counted -- the
+ * reference leaves the previous block's pixels there. One launch on the context's stream; the call synchronises once to read that count. */
+BU_HIP_API int bu_hip_k_unpack_blocks(bu_hip_context*, const void* d_blocks, uint32_t num_blocks_x, uint32_t num_blocks_y,
+        uint32_t orig_width, uint32_t orig_height, uint32_t format, void* d_out_rgba, uint32_t out_row_pitch_pixels,
+        uint32_t out_rows_pixels, uint32_t* out_invalid_blocks);
+BU_HIP_API size_t bu_hip_unpack_output_bytes(uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height,
+        uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
+
 /* The counting half of image_metrics::calc (encoder/basisu_enc.cpp:2155-2226) for all eight lines basis_compressor's m_compute_stats stage reports per slice
  * (comp.cpp:4195-4253), in one pass over two resident RGBA8 rasters (4 bytes per pixel, 4-byte aligned; a row pitch in pixels, 0 = the width; each raster reaches
  * to pixel (height - 1) * pitch + width). The region compared is min(width_a, width_b) x min(height_a, height_b), as calc crops; at most 16384 each way.

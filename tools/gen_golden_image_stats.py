@@ -50,7 +50,7 @@ def cases():
 
 def parse_stats(text):
     """the tool's output -> (slices, 8, 4): after every `Slice: N` header of the stats stage, the eight lines in order (the `BC7 ...` lines that follow them are
-    another decode's and are skipped); asserts one complete block per slice"""
+    another decode's: tools/gen_golden_bc7_stats.py reads those); asserts one complete block per slice"""
     total = int(re.search(r"^Total slices: (\d+)$", text, re.M).group(1))
     out, lines = [], text.splitlines()
     for at, line in enumerate(lines):
