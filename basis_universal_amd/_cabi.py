@@ -2,7 +2,8 @@
 
 Every `BU_*API <ret> bu_name(<args>);` prototype becomes (restype, argtypes) by one rule: a scalar maps to its exact ctypes type, `const char*` to c_char_p,
 every other pointer, array parameter or `*_fn` call-back typedef to c_void_p (which takes byref(), ctypes arrays, data_as(c_void_p), ints, None and CFUNCTYPE
-instances). A type the rule does not know raises at import. The ctypes.Structure mirrors of the headers' structs stay hand-written next to their users."""
+instances). A type the rule does not know raises at import. parse_prototypes takes other marks and names too, and definitions as well as prototypes: the test
+checkers (tests/native_libs.py) derive their signatures from their sources with it. The ctypes.Structure mirrors of the headers' structs stay hand-written next to their users."""
 import ctypes as C
 import functools
 import os
@@ -21,8 +22,9 @@ LIBRARIES = {
     "rccl": ("libbasisu_rccl.so", ("basisu_hip_comm.h",), "not found: build it (make -C basis_universal_amd/csrc)"),
 }
 
-_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
-_PROTOTYPE = re.compile(r"\bBU_\w*API\s+([^;()]*?)\b(bu_\w+)\s*\(([^()]*)\)\s*;")
+_SCALARS = {"int": C.c_int, "uint8_t": C.c_uint8, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+            "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
+_SPELLED_OUT = re.compile(r'\bextern\s+"C"(?!\s*\{)|\b__attribute__\s*\(\((?:[^()]|\([^()]*\))*\)\)')   # what a mark macro expands to, where a declaration writes it out as well
 
 
 class HipError(RuntimeError):
@@ -45,17 +47,22 @@ def _ctype(decl, function, is_return=False):
     raise TypeError(f"{function}: no ctypes mapping for `{decl.strip()}`")
 
 
-def parse_prototypes(text):
-    """The text of a header -> {function: (restype, [argtypes])} for every BU_*API prototype in it."""
+def parse_prototypes(text, mark=r"BU_\w*API", name=r"bu_\w+"):
+    """The text of a header or a source file -> {function: (restype, [argtypes])} for every `<mark> <ret> <name>(<args>)` in it that ends in `;` or opens a body.
+    A function declared twice must be declared the same way both times."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
-    out = {}
-    for ret, name, params in _PROTOTYPE.findall(text):
+    text = _SPELLED_OUT.sub(" ", text)
+    out, found = {}, re.findall(rf"\b(?:{mark})\s+([^;{{}}()]*?)\b({name})\s*\(([^(){{}};]*)\)\s*[;{{]", text)
+    for ret, fn, params in found:
         params = [] if params.strip() in ("", "void") else params.split(",")
-        out[name] = (_ctype(ret, name, True), [_ctype(p, name) for p in params])
-    marks = len(re.findall(r"\bBU_\w*API\b", text))
-    if len(out) != marks:
-        raise TypeError(f"{marks} BU_*API marks but {len(out)} prototypes understood: {', '.join(out)}")
+        sig = (_ctype(ret, fn, True), [_ctype(p, fn) for p in params])
+        if out.setdefault(fn, sig) != sig:
+            raise TypeError(f"{fn}: declared twice with different signatures")
+    marks = len(re.findall(rf"\b(?:{mark})\b", text))
+    if len(found) != marks:
+        shown = mark.replace(r"\w*", "*")   # the pattern as prose writes it: BU_\w*API -> BU_*API
+        raise TypeError(f"{marks} {shown} marks but {len(found)} prototypes understood: {', '.join(fn for _, fn, _ in found)}")
     return out
 
 

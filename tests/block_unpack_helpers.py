@@ -2,11 +2,11 @@
 (tests/golden/block_unpack_vectors.npz, bc7_stats_vectors.npz) and what the generator and the tests both need to know about a BC7 block's leading fields."""
 import ctypes as C
 import functools
-import json
 import pathlib
-import subprocess
 
 import numpy as np
+
+import native_libs
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 GOLDEN = ROOT / "tests" / "golden" / "block_unpack_vectors.npz"
@@ -20,24 +20,9 @@ NAMES = {BC1: "bc1", BC3: "bc3", BC4: "bc4", BC5: "bc5", BC7: "bc7"}
 # the encoder-made members: array of uastc_transcode_vectors.npz -> format
 ENCODER_MADE = {"level2_bc1": BC1, "level2_bc1_hq": BC1, "level2_bc3": BC3, "level2_bc4_r": BC4, "level2_bc5_ra": BC5, "level2_bc7": BC7}
 
-_lib = None
-
 
 def host():
-    global _lib
-    if _lib is None:
-        d, csrc = ROOT / "tests" / "native", ROOT / "basis_universal_amd" / "csrc"
-        so = d / "libblock_unpack_host.so"
-        srcs = [d / "block_unpack_host.cpp"] + [csrc / n for n in ("block_unpack.h", "uastc_transcode.h", "uastc_transcode_tables.inc", "uastc_rdo.h", "uastc_core.h", "uastc_tables.inc")]
-        if not so.exists() or so.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fvisibility=hidden", "-o", str(so), str(srcs[0])])
-        L = C.CDLL(str(so))
-        L.bh_unpack.restype = C.c_uint32
-        L.bh_unpack.argtypes = [u8p, C.c_uint32, C.c_uint32, u8p, u8p]
-        L.bh_bc1_four.restype = None
-        L.bh_bc1_four.argtypes = [u8p, C.c_uint32, u8p]
-        _lib = L
-    return _lib
+    return native_libs.load("block_unpack_host")
 
 
 def host_unpack(blocks, fmt):
@@ -61,23 +46,15 @@ def to_raster(texels, nbx, nby, width, height):
     return texels.reshape(nby, nbx, 4, 4, 4).transpose(0, 2, 1, 3, 4).reshape(nby * 4, nbx * 4, 4)[:height, :width]
 
 
-def _load(path):
-    z = np.load(path)
-    arrays = {k: z[k] for k in z.files}
-    for a in arrays.values():
-        a.setflags(write=False)
-    return arrays, json.loads(arrays["meta"].tobytes().decode())
-
-
 @functools.lru_cache(maxsize=None)
 def golden():
     """-> (arrays, meta) of block_unpack_vectors.npz: loaded once and shared; nobody writes into the arrays"""
-    return _load(GOLDEN)
+    return native_libs.load_npz_golden(GOLDEN)
 
 
 @functools.lru_cache(maxsize=None)
 def golden_stats():
-    return _load(GOLDEN_STATS)
+    return native_libs.load_npz_golden(GOLDEN_STATS)
 
 
 def format_set(fmt):

@@ -2,10 +2,11 @@
 written from the format definition (the expected value of the pixel targets is the reference tool's ETC1 output decoded by it), the 16-bit packings, and the builders
 of synthetic ETC1S states that the backend here wraps into files without a GPU."""
 import functools
-import json
 import pathlib
 
 import numpy as np
+
+import native_libs
 
 GOLDEN = pathlib.Path(__file__).resolve().parent / "golden" / "etc1s_transcode_vectors.npz"
 INTEN = np.array([[-8, -2, 2, 8], [-17, -5, 5, 17], [-29, -9, 9, 29], [-42, -13, 13, 42], [-60, -18, 18, 60], [-80, -24, 24, 80], [-106, -33, 33, 106], [-183, -47, 47, 183]])
@@ -16,11 +17,7 @@ BC1_MAPPINGS = 10
 @functools.lru_cache(maxsize=None)
 def golden():
     """-> (arrays, meta): loaded once and shared; nobody writes into the arrays"""
-    z = np.load(GOLDEN)
-    arrays = {k: z[k] for k in z.files}
-    for a in arrays.values():
-        a.setflags(write=False)
-    return arrays, json.loads(arrays["meta"].tobytes().decode())
+    return native_libs.load_npz_golden(GOLDEN)
 
 
 def image_key(name, level, layer, face):

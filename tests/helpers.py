@@ -1,15 +1,16 @@
-"""Shared test plumbing: ctypes bindings for the CPU checkers and the synthetic inputs.
+"""Shared test plumbing: the CPU checkers (loaded and bound by native_libs.py) behind numpy-level calls, and the synthetic inputs.
 
 Nothing here touches the product; see basis_universal_amd/ for that. The two checkers are
   * oracle/liboracle_etc1s.so   -- our plain-C restatement (travels to the GPU box as source + .so)
   * oracle/_ref/libref_harness.so -- the REAL reference compiled from /root/reference (prebuilt; travels as a binary)
 """
 import ctypes as C
-import os
+import functools
 import pathlib
-import subprocess
 
 import numpy as np
+
+import native_libs
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 ORACLE_DIR = ROOT / "oracle"
@@ -124,38 +125,8 @@ def csr_blob_split(blob):
 
 # ----------------------------------------------------------------------------- C oracle
 
-_oracle = None
-
-
 def oracle():
-    global _oracle
-    if _oracle is None:
-        so = ORACLE_DIR / "liboracle_etc1s.so"
-        src = ORACLE_DIR / "etc1s_oracle.c"
-        if not so.exists() or so.stat().st_mtime < src.stat().st_mtime:
-            subprocess.check_call(["make", "-C", str(ORACLE_DIR), "liboracle_etc1s.so"], stdout=subprocess.DEVNULL)
-        L = C.CDLL(str(so))
-        L.orc_color_distance.restype = C.c_uint32
-        L.orc_color_distance.argtypes = [C.c_int, u8p, u8p]
-        L.orc_hash_hsieh3.restype = C.c_uint32
-        L.orc_hash_hsieh3.argtypes = [C.c_uint8] * 3
-        L.orc_etc1_optimize.restype = C.c_int
-        L.orc_etc1_optimize.argtypes = [u8p, C.c_uint32, C.c_int, C.c_int, u8p, u32p, u64p, u8p]
-        L.orc_etc1_optimize_forced.restype = C.c_int
-        L.orc_etc1_optimize_forced.argtypes = [u8p, C.c_uint32, C.c_int, C.c_int, u8p, u8p, u32p, u64p]
-        L.orc_refit_endpoints_given_selectors.argtypes = [u8p, u8p, C.c_uint32, u32p, u32p, C.c_int, C.c_int, u8p, u64p, u8p, u64p]
-        L.orc_subblock_errors.argtypes = [u8p, C.c_uint32, u32p, u8p, C.c_int, u64p]
-        L.orc_backend_block_errors.argtypes = [u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, u32p, u32p]
-        L.orc_encode_etc1s_blocks.argtypes = [u8p, C.c_uint32, C.c_int, C.c_int, u8p]
-        L.orc_determine_selectors.argtypes = [u8p, C.c_uint32, u8p, C.c_int, u8p]
-        L.orc_generate_endpoint_codebook.argtypes = [u8p, C.c_uint32, u32p, u32p, C.c_int, C.c_int, C.c_uint32, u8p, u64p, u8p]
-        L.orc_refine_endpoint_clusterization.argtypes = [u8p, C.c_uint32, u32p, u8p, C.c_uint32, C.c_uint32, u32p, u32p, u8p, C.c_int, u32p]
-        L.orc_create_optimized_selector_codebook.argtypes = [u8p, u8p, C.c_uint32, u32p, u32p, C.c_int, u8p]
-        L.orc_find_optimal_selector_clusters.argtypes = [u8p, u8p, C.c_uint32, u8p, C.c_uint32, C.c_uint32, u32p, u32p, u8p, C.c_int, C.c_uint32, u32p]
-        L.orc_endpoint_training_vectors.argtypes = [u8p, C.c_uint32, f32p]
-        L.orc_selector_training_vectors.argtypes = [u8p, C.c_uint32, C.c_int, f32p, u64p]
-        _oracle = L
-    return _oracle
+    return native_libs.load("oracle")
 
 
 def orc_encode_blocks(blocks, level, perceptual=True):
@@ -205,9 +176,6 @@ def endpoint_codebook(blocks, k, seed, level=1, perceptual=1):
 
 # ----------------------------------------------------------------------------- the real reference
 
-_ref = None
-
-
 def have_ref():
     return (ORACLE_DIR / "_ref" / "libref_harness.so").exists()
 
@@ -220,54 +188,14 @@ def ref_harness_version():
     L = ref()
     if not hasattr(L, "ref_harness_version"):
         return 1
-    L.ref_harness_version.restype = C.c_int
     return int(L.ref_harness_version())
 
 
+@functools.lru_cache(maxsize=None)
 def ref():
-    global _ref
-    if _ref is None:
-        L = C.CDLL(str(ORACLE_DIR / "_ref" / "libref_harness.so"))
-        L.ref_init.restype = C.c_int
-        L.ref_etc1_optimize.restype = C.c_int
-        L.ref_etc1_optimize.argtypes = [u8p, C.c_uint32, C.c_int, C.c_int, u8p, u32p, u64p, u8p]
-        if hasattr(L, "ref_etc1_optimize_forced"):   # harness version 2 (ref_harness_version)
-            L.ref_etc1_optimize_forced.restype = C.c_int
-            L.ref_etc1_optimize_forced.argtypes = [u8p, C.c_uint32, C.c_int, C.c_int, u8p, u8p, u32p, u64p]
-        if hasattr(L, "ref_transcode_uastc"):   # harness version 3
-            L.ref_transcode_uastc.restype = C.c_int
-            L.ref_transcode_uastc.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, u8p, u8p]
-        L.ref_encode_etc1s_blocks.argtypes = [u8p, C.c_uint32, C.c_int, C.c_int, u8p]
-        L.ref_determine_selectors.argtypes = [u8p, C.c_uint32, u8p, C.c_int, u8p]
-        L.ref_color_distance.restype = C.c_uint32
-        L.ref_color_distance.argtypes = [C.c_int, u8p, u8p]
-        L.ref_frontend_create.restype = C.c_void_p
-        L.ref_frontend_create.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int]
-        L.ref_frontend_destroy.argtypes = [C.c_void_p]
-        L.ref_frontend_call.restype = C.c_int64
-        L.ref_frontend_call.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32]
-        L.ref_frontend_get.restype = C.c_uint64
-        L.ref_frontend_get.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64]
-        L.ref_tsvq.restype = C.c_int
-        L.ref_tsvq.argtypes = [C.c_uint32, f32p, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u32p, C.c_uint64, u32p, C.c_uint64]
-        L.ref_tsvq_mt.restype = C.c_int
-        L.ref_tsvq_mt.argtypes = [C.c_uint32, f32p, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u32p, C.c_uint64, u32p, C.c_uint64]
-        L.ref_encode_uastc.argtypes = [u8p, C.c_uint32, C.c_uint32, u8p]
-        L.ref_uastc_rdo.restype = C.c_int
-        L.ref_uastc_rdo.argtypes = [u8p, u8p, C.c_uint32, f32p, u32p, C.c_uint32, C.c_uint32]
-        L.ref_color_cell_compression.restype = C.c_uint64
-        L.ref_color_cell_compression.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, u8p, u8p]
-        L.ref_ccell_est.restype = C.c_uint64
-        L.ref_ccell_est.argtypes = [C.c_uint32, C.c_uint32, u8p, C.c_uint32, C.c_uint64]
-        L.ref_table.restype = C.c_uint64
-        L.ref_table.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64]
-        L.ref_compress_etc1s.restype = C.c_int
-        L.ref_compress_etc1s.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, u32p, u32p, u8p, C.c_uint64, u64p]
-        L.ref_quality_effort.restype = C.c_int
-        L.ref_quality_effort.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), f32p]
-        assert L.ref_init() == 1
-        _ref = L
-    return _ref
+    L = native_libs.load("ref")
+    assert L.ref_init() == 1
+    return L
 
 
 def ref_quality_effort(uastc, quality, effort):
@@ -287,8 +215,6 @@ class RefFrontend:
         if threads == 1:
             self.h = self.L.ref_frontend_create(ptr(self.blocks), self.blocks.shape[0], max_ep, max_sel, level, int(perceptual))
         else:
-            self.L.ref_frontend_create_mt.restype = C.c_void_p
-            self.L.ref_frontend_create_mt.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32]
             self.h = self.L.ref_frontend_create_mt(ptr(self.blocks), self.blocks.shape[0], max_ep, max_sel, level, int(perceptual), threads)
         assert self.h
 
@@ -315,8 +241,6 @@ class RefFrontend:
         o2n, n2o = np.full(k_ep, 0xFFFFFFFF, np.uint32), np.full(k_ep, 0xFFFFFFFF, np.uint32)
         secs = C.c_double(0)
         f = self.L.ref_backend_create_encoder_blocks
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         assert f(self.h, nbx, nby, endpoint_thresh, selector_thresh, ep.ctypes.data, pred.ctypes.data, sel.ctypes.data, o2n.ctypes.data, n2o.ctypes.data, C.byref(secs)) == 1
         return {"endpoint_index": ep, "predictor": pred, "selector_index": sel, "endpoint_old_to_new": o2n[o2n != 0xFFFFFFFF],
                 "selector_new_to_old": n2o[n2o != 0xFFFFFFFF], "seconds": secs.value}
@@ -324,15 +248,11 @@ class RefFrontend:
     def backend_run(self, slices, endpoint_thresh=1.5, selector_thresh=1.25):
         """basisu_backend::encode on the finished frontend; slices = [(first_block, nbx, nby), ...]. Returns (bytes, seconds)."""
         sl = np.ascontiguousarray(np.asarray(slices, np.uint32).reshape(-1, 3))
-        self.L.ref_backend_run.restype = C.c_uint32
-        self.L.ref_backend_run.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_void_p]
         secs = C.c_double(0)
         n = self.L.ref_backend_run(self.h, sl.ctypes.data_as(C.c_void_p), sl.shape[0], endpoint_thresh, selector_thresh, C.byref(secs))
         return n, secs.value
 
     def backend_get(self, name, slice_index=0, dtype=np.uint8):
-        self.L.ref_backend_get.restype = C.c_uint64
-        self.L.ref_backend_get.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint64]
         need = self.L.ref_backend_get(self.h, name.encode(), slice_index, None, 0)
         assert need != 2 ** 64 - 1, name
         buf = np.zeros(need, np.uint8)
@@ -341,15 +261,11 @@ class RefFrontend:
 
     def set_tex_type(self, tex_type):
         """basist::basis_texture_type of the frontend params (3 = video frames); before compress."""
-        self.L.ref_frontend_set_tex_type.restype = None
-        self.L.ref_frontend_set_tex_type.argtypes = [C.c_void_p, C.c_uint32]
         self.L.ref_frontend_set_tex_type(self.h, tex_type)
 
     def set_state(self, color5_inten, selectors16, block_endpoint, block_selector):
         """Overwrite the finished frontend state with arbitrary codebooks / assignments (backend fuzzing)."""
         f = self.L.ref_frontend_set_state
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         ep = np.ascontiguousarray(color5_inten, np.uint8).reshape(-1, 4)
         sel = np.ascontiguousarray(selectors16, np.uint8).reshape(-1, 16)
         be, bs = np.ascontiguousarray(block_endpoint, np.uint32), np.ascontiguousarray(block_selector, np.uint32)
@@ -358,8 +274,6 @@ class RefFrontend:
     def reoptimize(self, new_block_endpoints, final_codebook, block_selector_indices=None):
         """basisu_frontend::reoptimize_remapped_endpoints on this frontend -> old_to_new (int32, one per endpoint cluster before the call)."""
         f = self.L.ref_frontend_reoptimize
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
         nb = np.ascontiguousarray(new_block_endpoints, np.uint32)
         k = self.get("endpoint_cluster_etc_params").size // 16
         o2n = np.full(max(k, 1), -1, np.int32)
@@ -370,8 +284,6 @@ class RefFrontend:
     def basis_file(self, tex_type=0, userdata0=0, userdata1=0, y_flipped=False, us_per_frame=0, key_values=()):
         """basisu_file::init on the last backend_run's output -> the .basis file bytes."""
         f = self.L.ref_basis_file
-        f.restype = C.c_uint64
-        f.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]
         n = len(key_values)
         keys = (C.c_char_p * max(n, 1))(*[k.encode() for k, _ in key_values])
         bufs = [np.frombuffer(bytes(v), np.uint8) if len(v) else np.zeros(1, np.uint8) for _, v in key_values]
@@ -529,85 +441,21 @@ def host_uastc_rdo(packed, blocks, flags, total_jobs=0, table_trials=False, **kw
     return out
 
 
-_uastc_host = None
-
-
 def uastc_host():
     """The UASTC device core compiled for the host (tests/native/uastc_host.cpp): a checker for the CPU-only suite."""
-    global _uastc_host
-    if _uastc_host is None:
-        d = ROOT / "tests" / "native"
-        so, srcs = d / "libuastc_host.so", [d / "uastc_host.cpp", ROOT / "basis_universal_amd" / "csrc" / "uastc_core.h",
-                                            ROOT / "basis_universal_amd" / "csrc" / "uastc_rdo.h",
-                                            ROOT / "basis_universal_amd" / "csrc" / "uastc_tables.inc"]
-        if not so.exists() or so.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", str(so), str(srcs[0])])
-        L = C.CDLL(str(so))
-        L.hc_encode_uastc.argtypes = [u8p, C.c_uint32, C.c_uint32, u8p]
-        L.hc_uastc_rdo.restype = C.c_int
-        L.hc_uastc_rdo.argtypes = [u8p, u8p, C.c_uint32, f32p, u32p, C.c_uint32, C.c_uint32]
-        L.hc_rehint.argtypes = [u8p, C.c_uint32, C.c_uint32, u8p]
-        L.hc_unpack_block.argtypes = [u8p, u8p]
-        L.hc_decode_uastc.restype = C.c_int
-        L.hc_decode_uastc.argtypes = [u8p, C.c_uint32, u8p]
-        L.hc_cell_compress.restype = C.c_uint64
-        L.hc_cell_compress.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, u8p]
-        L.hc_cell_estimate.restype = C.c_uint64
-        L.hc_cell_estimate.argtypes = [C.c_uint32, C.c_uint32, u8p, C.c_uint32]
-        L.hc_weight_of.restype = C.c_uint32
-        L.hc_weight_of.argtypes = [C.c_uint32, C.c_uint32]
-        L.hc_weight_table.restype = C.c_uint32
-        L.hc_weight_table.argtypes = [C.c_uint32, C.c_uint32]
-        _uastc_host = L
-    return _uastc_host
-
-
-_fsum_host = None
+    return native_libs.load("uastc_host")
 
 
 def fsum_host():
     """csrc/fsum_scan.h (the order-preserving float sum of the wide TSVQ kernels) compiled for the host: tests/native/fsum_host.cpp."""
-    global _fsum_host
-    if _fsum_host is None:
-        d = ROOT / "tests" / "native"
-        so, srcs = d / "libfsum_host.so", [d / "fsum_host.cpp", ROOT / "basis_universal_amd" / "csrc" / "fsum_scan.h"]
-        if not so.exists() or so.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", str(so), str(srcs[0])])
-        L = C.CDLL(str(so))
-        L.fsum_sequential.restype = C.c_float
-        L.fsum_sequential.argtypes = [f32p, C.c_uint64, C.c_float]
-        L.fsum_blocked.restype = C.c_float
-        L.fsum_blocked.argtypes = [f32p, C.c_uint64, C.c_float, C.c_uint32, u64p]
-        L.fsum_compose_check.restype = C.c_int
-        L.fsum_compose_check.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, C.c_uint32]
-        _fsum_host = L
-    return _fsum_host
-
-
-_tt_exact_host = None
+    return native_libs.load("fsum_host")
 
 
 def tt_exact_host():
     """csrc/tt_exact.h (when a block of the reference's double accumulators can be taken in one step: tsvq_wide6_kernels.hip, tt_walk) compiled for the host:
     tests/native/tt_exact_host.cpp."""
-    global _tt_exact_host
-    if _tt_exact_host is None:
-        d = ROOT / "tests" / "native"
-        so, srcs = d / "libtt_exact_host.so", [d / "tt_exact_host.cpp", ROOT / "basis_universal_amd" / "csrc" / "tt_exact.h"]
-        if not so.exists() or so.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", str(so), str(srcs[0])])
-        L = C.CDLL(str(so))
-        L.tt_sequential.restype = C.c_double
-        L.tt_sequential.argtypes = [f32p, C.c_uint64]
-        L.tt_blocked.restype = C.c_double
-        L.tt_blocked.argtypes = [f32p, C.c_uint64, C.c_uint32, u64p]
-        L.tt_low_bit.restype = C.c_int
-        L.tt_low_bit.argtypes = [C.c_double]
-        _tt_exact_host = L
-    return _tt_exact_host
+    return native_libs.load("tt_exact_host")
 
-
-_tsvq_node_host = None
 
 # the records of include/basisu_hip.h as numpy structured dtypes
 TSVQ_ROOT = np.dtype([("origin", np.float32, 16), ("weight", np.uint64), ("var", np.float32), ("pad", np.uint32)])
@@ -620,20 +468,7 @@ assert (TSVQ_ROOT.itemsize, TSVQ_NODE.itemsize, TSVQ_SPLIT.itemsize, TSVQ_SPAN.i
 
 def tsvq_node_host():
     """csrc/host/tsvq.h one node at a time (tests/native/tsvq_node_host.cpp): the root record of a member list, the split record + child lists of a node."""
-    global _tsvq_node_host
-    if _tsvq_node_host is None:
-        d = ROOT / "tests" / "native"
-        so, srcs = d / "libtsvq_node_host.so", [d / "tsvq_node_host.cpp", ROOT / "basis_universal_amd" / "csrc" / "host" / "tsvq.h"]
-        if not so.exists() or so.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", str(so), str(srcs[0])])
-        L = C.CDLL(str(so))
-        L.tn_open.restype = C.c_void_p
-        L.tn_open.argtypes = [C.c_uint32, f32p, u64p, C.c_uint32]
-        L.tn_close.argtypes = [C.c_void_p]
-        L.tn_root.argtypes = [C.c_void_p, u32p, C.c_uint32, C.c_void_p]
-        L.tn_split.argtypes = [C.c_void_p, u32p, C.c_uint32, C.c_uint64, f32p, C.c_void_p, u32p]
-        _tsvq_node_host = L
-    return _tsvq_node_host
+    return native_libs.load("tsvq_node_host")
 
 
 class TsvqNodes:
@@ -683,35 +518,10 @@ BU_FOSC_SELECTOR = np.dtype([("packed_selectors", np.uint32)])
 BU_FOSC_BLOCK = np.dtype([("etc_color5_inten", BU_COLOR), ("first_selector", np.uint32), ("num_selectors", np.uint32)])
 assert (BU_PIXEL_CLUSTER.itemsize, BU_BLOCK_INFO.itemsize, BU_ENDPOINT_CLUSTER.itemsize, BU_FOSC_SELECTOR.itemsize, BU_FOSC_BLOCK.itemsize) == (16, 7, 7, 4, 12)
 
-_seam_translate_host = None
-
 
 def seam_translate_host():
     """csrc/host/seam_translate.h (the host translations behind section 1 of include/basisu_hip.h) compiled for the host: tests/native/seam_translate_host.cpp."""
-    global _seam_translate_host
-    if _seam_translate_host is None:
-        d = ROOT / "tests" / "native"
-        so, srcs = d / "libseam_translate_host.so", [d / "seam_translate_host.cpp", ROOT / "basis_universal_amd" / "csrc" / "host" / "seam_translate.h",
-                                                     ROOT / "include" / "basisu_hip.h"]
-        if not so.exists() or so.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(so), str(srcs[0])])
-        L = C.CDLL(str(so))
-        errp = C.POINTER(C.c_char_p)
-        L.st_refine.restype = C.c_void_p
-        L.st_refine.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, errp]
-        L.st_fosc.restype = C.c_void_p
-        L.st_fosc.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, errp]
-        L.st_pixel_clusters.restype = C.c_void_p
-        L.st_pixel_clusters.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, errp]
-        L.st_get.restype = C.c_uint64
-        L.st_get.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]
-        L.st_free.argtypes = [C.c_void_p]
-        L.st_selectors_to_etc_block.argtypes = [C.c_uint32, u8p]
-        L.st_color5_inten_to_etc_block.argtypes = [C.c_uint32] * 4 + [u8p]
-        L.st_max_windows.restype = C.c_uint32
-        L.st_max_expanded_texels.restype = C.c_uint64
-        _seam_translate_host = L
-    return _seam_translate_host
+    return native_libs.load("seam_translate_host")
 
 
 def _seam_tables(handle, err, layout):
@@ -799,8 +609,6 @@ def ref_transcode_uastc(blocks, target, high_quality=False, channels=(0, 3)):
 def ref_decode_uastc(packed):
     """the reference's unpack_uastc (transcoder/basisu_transcoder.cpp:15743) per block -> (n, 4, 4, 4) u8"""
     L = ref()
-    L.ref_unpack_uastc.restype = C.c_int
-    L.ref_unpack_uastc.argtypes = [u8p, u8p]
     packed = np.ascontiguousarray(packed, np.uint8).reshape(-1, 16)
     out = np.zeros((packed.shape[0], 4, 4, 4), np.uint8)
     for i in range(packed.shape[0]):
@@ -924,25 +732,9 @@ def basis_file_key_values(data):
     return out
 
 
-_block_metric_host = None
-
-
 def block_metric_host():
     """csrc/host/block_metric.h (the backend's inner loops, one variant per instruction set) compiled for the host: tests/native/block_metric_host.cpp."""
-    global _block_metric_host
-    if _block_metric_host is None:
-        d = ROOT / "tests" / "native"
-        so, srcs = d / "libblock_metric_host.so", [d / "block_metric_host.cpp", ROOT / "basis_universal_amd" / "csrc" / "host" / "block_metric.h"]
-        if not so.exists() or so.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(so), str(srcs[0])])
-        L = C.CDLL(str(so))
-        L.bm_variants.restype = C.c_int
-        L.bm_scan_check.restype = C.c_int
-        L.bm_scan_check.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int]
-        L.bm_search_check.restype = C.c_int
-        L.bm_search_check.argtypes = [C.c_uint64, C.c_int, C.c_int]
-        _block_metric_host = L
-    return _block_metric_host
+    return native_libs.load("block_metric_host")
 
 
 # g_uastc_huff_modes (transcoder/basisu_transcoder.cpp:14409-14413): the mode of a UASTC block from the low 7 bits of its first byte

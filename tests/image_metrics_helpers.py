@@ -1,14 +1,13 @@
 """What the image-metrics tests share: the golden file (tests/golden/image_stats_vectors.npz, written by tools/gen_golden_image_stats.py), the host build of
 csrc/image_metrics.h (tests/native/image_metrics_host.cpp), a numpy restatement of image_metrics::calc (encoder/basisu_enc.cpp:2155-2226) -- counts in integers,
 the reduction in Python doubles narrowed through float32 where the reference narrows -- and host decodes of the golden files."""
-import ctypes as C
 import functools
-import json
 import math
 import pathlib
-import subprocess
 
 import numpy as np
+
+import native_libs
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 GOLDEN = ROOT / "tests" / "golden" / "image_stats_vectors.npz"
@@ -18,33 +17,15 @@ FIGURES = ["max", "mean", "rms", "psnr"]
 # From the print precision, not from a measurement.
 PRINT_TOLERANCE = 0.00055
 
-_host = None
-
 
 def host():
-    global _host
-    if _host is None:
-        d = ROOT / "tests" / "native"
-        so, srcs = d / "libimage_metrics_host.so", [d / "image_metrics_host.cpp", ROOT / "basis_universal_amd" / "csrc" / "image_metrics.h"]
-        if not so.exists() or so.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", str(so), str(srcs[0])])
-        L = C.CDLL(str(so))
-        L.imh_counts.restype = None
-        L.imh_counts.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.imh_reduce.restype = None
-        L.imh_reduce.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
-        _host = L
-    return _host
+    return native_libs.load("image_metrics_host")
 
 
 @functools.lru_cache(maxsize=None)
 def golden():
     """-> (arrays, meta): loaded once and shared; nobody writes into the arrays"""
-    z = np.load(GOLDEN)
-    arrays = {k: z[k] for k in z.files}
-    for a in arrays.values():
-        a.setflags(write=False)
-    return arrays, json.loads(arrays["meta"].tobytes().decode())
+    return native_libs.load_npz_golden(GOLDEN)
 
 
 def padded(img, pitch):

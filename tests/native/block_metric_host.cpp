@@ -1,19 +1,18 @@
 // block_metric_host.cpp -- TEST-ONLY host build of csrc/host/block_metric.h: every ISA variant of the backend's history scan against the
 // plain C++ one on tables, histories and limits the backend tests do not reach (distances up to the metric's maximum, limits from 0 to
-// beyond every error, SAD test on and off). Compiled by tests/helpers.py with g++ -O2.
+// beyond every error, SAD test on and off). Built and bound by tests/native_libs.py.
 #include <cstdint>
 #include <cstring>
 
 #include "../../basis_universal_amd/csrc/host/block_metric.h"
+#include "host_api.h"
 
 using namespace bu::metric;
 
 static uint64_t rng_next(uint64_t& s) { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return s; }
 
-extern "C" {
-
 // bit i of the result: variant i exists on this CPU (0 plain, 1 avx2, 2 avx512, 3 vbmi)
-int bm_variants() {
+HOST_API int bm_variants() {
     int m = 1;
     if (__builtin_cpu_supports("avx2")) m |= 2;
     if (__builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512bw") && __builtin_cpu_supports("avx512vl")) m |= 4;
@@ -23,7 +22,7 @@ int bm_variants() {
 
 // `cases` random scans; magnitude: distances are drawn below 2^magnitude (26 covers one perceptual distance, < 41e6). Returns the number of
 // (case, variant) pairs that differ from the plain scan, 0 if all agree.
-int bm_scan_check(uint64_t seed, int cases, int magnitude, int variants) {
+HOST_API int bm_scan_check(uint64_t seed, int cases, int magnitude, int variants) {
     int bad = 0;
     uint64_t s = seed * 0x9E3779B97F4A7C15ull + 1;
     alignas(64) sel16 hist[64];
@@ -69,7 +68,7 @@ int bm_scan_check(uint64_t seed, int cases, int magnitude, int variants) {
 }
 
 // the per-block search (search_prepare: pixels -> table -> own error -> limit; search_history: own pattern look-up, scan) of every variant against the plain one, on random pixels and colours
-int bm_search_check(uint64_t seed, int cases, int variants) {
+HOST_API int bm_search_check(uint64_t seed, int cases, int variants) {
     int bad = 0;
     uint64_t s = seed * 0x9E3779B97F4A7C15ull + 7;
     alignas(64) sel16 hist[64];
@@ -111,5 +110,3 @@ int bm_search_check(uint64_t seed, int cases, int variants) {
     }
     return bad;
 }
-
-}  // extern "C"

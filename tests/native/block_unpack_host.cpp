@@ -1,12 +1,11 @@
 // Test-only host build of basis_universal_amd/csrc/block_unpack.h (g++): the same texel functions the kernel runs, called sixteen times per block.
 #include "../../basis_universal_amd/csrc/block_unpack.h"
+#include "host_api.h"
 
 using namespace bu_unpack;
 
-extern "C" {
-
 // n blocks of `format` (transcoder_texture_format value) -> out (n, 64) texels, ok (n,) flags; returns 0 for a format that does not unpack here
-__attribute__((visibility("default"))) uint32_t bh_unpack(const uint8_t* blocks, uint32_t n, uint32_t format, uint8_t* out, uint8_t* ok) {
+HOST_API uint32_t bh_unpack(const uint8_t* blocks, uint32_t n, uint32_t format, uint8_t* out, uint8_t* ok) {
     const uint32_t unit = unpack_bytes_per_block(format);
     if (!unit) return 0;
     for (uint32_t i = 0; i < n; i++) {
@@ -26,7 +25,7 @@ __attribute__((visibility("default"))) uint32_t bh_unpack(const uint8_t* blocks,
 }
 
 // BC1's colour decode in forced four-colour mode (BC3's colour half), for the plumbing identities
-__attribute__((visibility("default"))) void bh_bc1_four(const uint8_t* blocks, uint32_t n, uint8_t* out) {
+HOST_API void bh_bc1_four(const uint8_t* blocks, uint32_t n, uint8_t* out) {
     for (uint32_t i = 0; i < n; i++) {
         const uint64_t v = load64(blocks + (size_t)i * 8);
         for (uint32_t t = 0; t < 16; t++) {
@@ -34,6 +33,4 @@ __attribute__((visibility("default"))) void bh_bc1_four(const uint8_t* blocks, u
             for (uint32_t k = 0; k < 4; k++) out[(size_t)i * 64 + t * 4 + k] = (uint8_t)(px >> (8 * k));
         }
     }
-}
-
 }

@@ -1,12 +1,13 @@
 // fsum_host.cpp -- TEST-ONLY host build of csrc/fsum_scan.h (the order-preserving float sum the wide TSVQ kernels use):
 // the blocked algorithm (per-block stretches for predicted binades, serial walk with plain adds as the fallback) against the
-// plain sequential float sum it must reproduce bit for bit. Compiled by tests/helpers.py with g++ -O2 -ffp-contract=off.
+// plain sequential float sum it must reproduce bit for bit. Built and bound by tests/native_libs.py.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "../../basis_universal_amd/csrc/fsum_scan.h"
+#include "host_api.h"
 
 using namespace bu::fsum;
 
@@ -15,12 +16,10 @@ static inline float u2f(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f;
 
 static int g_fast = 0;
 
-extern "C" {
-
-void fsum_set_fast(int on) { g_fast = on; }
+HOST_API void fsum_set_fast(int on) { g_fast = on; }
 
 // s <- RN(s + a[i]) for i = 0..n-1, from `start`
-float fsum_sequential(const float* a, uint64_t n, float start) {
+HOST_API float fsum_sequential(const float* a, uint64_t n, float start) {
     volatile float s = start;
     for (uint64_t i = 0; i < n; i++) s = s + a[i];
     return s;
@@ -28,7 +27,7 @@ float fsum_sequential(const float* a, uint64_t n, float start) {
 
 // The blocked form. block: addends per block; stats[0] = blocks applied as a stretch, stats[1] = blocks walked with plain adds,
 // stats[2] = blocks whose predicted binades did not contain the state's.
-float fsum_blocked(const float* a, uint64_t n, float start, uint32_t block, uint64_t* stats) {
+HOST_API float fsum_blocked(const float* a, uint64_t n, float start, uint32_t block, uint64_t* stats) {
     const uint64_t nb = (n + block - 1) / block;
     struct summ { int E; bool neg; stretch s[2]; };
     std::vector<summ> sm(nb);
@@ -78,7 +77,7 @@ float fsum_blocked(const float* a, uint64_t n, float start, uint32_t block, uint
 }
 
 // Composition check: the stretch of a whole range built by composing per-piece stretches equals the stretch pushed in one go.
-int fsum_compose_check(const float* a, uint64_t n, int E, int neg, uint32_t piece) {
+HOST_API int fsum_compose_check(const float* a, uint64_t n, int E, int neg, uint32_t piece) {
     stretch whole = identity(), acc = identity();
     for (uint64_t i = 0; i < n; i++) push(whole, decode(f2u(a[i]), E, neg != 0));
     for (uint64_t i0 = 0; i0 < n; i0 += piece) {
@@ -94,5 +93,3 @@ int fsum_compose_check(const float* a, uint64_t n, int E, int neg, uint32_t piec
     }
     return 1;
 }
-
-} // extern "C"

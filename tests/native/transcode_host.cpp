@@ -3,12 +3,11 @@
 // the core refused (their output is zero-filled, as the kernel leaves it) and, where `ok` is given, one flag per block.
 #include <string.h>
 #include "../../basis_universal_amd/csrc/uastc_transcode.h"
+#include "host_api.h"
 
 using namespace bu_uastc;
 
-extern "C" {
-
-uint32_t ht_rgba32(const uint8_t* blocks, uint32_t n, uint8_t* out64, uint8_t* ok) {
+HOST_API uint32_t ht_rgba32(const uint8_t* blocks, uint32_t n, uint8_t* out64, uint8_t* ok) {
     uint32_t bad = 0;
     for (uint32_t i = 0; i < n; i++) {
         rgba8 px[16];
@@ -19,7 +18,7 @@ uint32_t ht_rgba32(const uint8_t* blocks, uint32_t n, uint8_t* out64, uint8_t* o
     return bad;
 }
 
-uint32_t ht_astc(const uint8_t* blocks, uint32_t n, uint8_t* out16, uint8_t* ok) {
+HOST_API uint32_t ht_astc(const uint8_t* blocks, uint32_t n, uint8_t* out16, uint8_t* ok) {
     uint32_t bad = 0;
     for (uint32_t i = 0; i < n; i++) {
         const bool good = transcode_astc(blocks + (size_t)i * 16, out16 + (size_t)i * 16);
@@ -29,7 +28,7 @@ uint32_t ht_astc(const uint8_t* blocks, uint32_t n, uint8_t* out16, uint8_t* ok)
     return bad;
 }
 
-uint32_t ht_bc7(const uint8_t* blocks, uint32_t n, uint8_t* out16, uint8_t* ok) {
+HOST_API uint32_t ht_bc7(const uint8_t* blocks, uint32_t n, uint8_t* out16, uint8_t* ok) {
     uint32_t bad = 0;
     for (uint32_t i = 0; i < n; i++) {
         const bool good = transcode_bc7(blocks + (size_t)i * 16, out16 + (size_t)i * 16);
@@ -40,7 +39,7 @@ uint32_t ht_bc7(const uint8_t* blocks, uint32_t n, uint8_t* out16, uint8_t* ok) 
 }
 
 // target: TF_BC1_RGB, TF_BC3_RGBA, TF_BC4_R or TF_BC5_RG
-uint32_t ht_bcn(const uint8_t* blocks, uint32_t n, uint32_t target, int high_quality, uint32_t chan0, uint32_t chan1, uint8_t* out, uint8_t* ok) {
+HOST_API uint32_t ht_bcn(const uint8_t* blocks, uint32_t n, uint32_t target, int high_quality, uint32_t chan0, uint32_t chan1, uint8_t* out, uint8_t* ok) {
     const uint32_t bytes = transcode_bytes_per_block(target);
     uint32_t bad = 0;
     for (uint32_t i = 0; i < n; i++) {
@@ -54,7 +53,7 @@ uint32_t ht_bcn(const uint8_t* blocks, uint32_t n, uint32_t target, int high_qua
 }
 
 // the two BC1 hint bits of a block: 0 invalid / solid, otherwise 1 | hint0 << 1 | hint1 << 2
-uint32_t ht_bc1_hints(const uint8_t* blk) {
+HOST_API uint32_t ht_bc1_hints(const uint8_t* blk) {
     cand c;
     if (!unpack_block(blk, c) || c.mode == 8) return 0;
     bool h0, h1;
@@ -62,10 +61,10 @@ uint32_t ht_bc1_hints(const uint8_t* blk) {
     return 1u | (h0 ? 2u : 0u) | (h1 ? 4u : 0u);
 }
 
-uint32_t ht_mode(const uint8_t* blk) { cand c; return unpack_block(blk, c) ? c.mode : 255u; }
+HOST_API uint32_t ht_mode(const uint8_t* blk) { cand c; return unpack_block(blk, c) ? c.mode : 255u; }
 
 // ht_mode / ht_bc1_hints over an array: modes[i] = 255 for a refused block
-void ht_modes_routes(const uint8_t* blocks, uint32_t n, uint8_t* modes, uint8_t* routes) {
+HOST_API void ht_modes_routes(const uint8_t* blocks, uint32_t n, uint8_t* modes, uint8_t* routes) {
     for (uint32_t i = 0; i < n; i++) {
         modes[i] = (uint8_t)ht_mode(blocks + (size_t)i * 16);
         routes[i] = (uint8_t)ht_bc1_hints(blocks + (size_t)i * 16);
@@ -80,7 +79,7 @@ void ht_modes_routes(const uint8_t* blocks, uint32_t n, uint8_t* modes, uint8_t*
 //   [22] offset of the raw endpoint bits, [23] raw bits per endpoint value, [24] endpoint values, [25] values per packed group
 //   [26] weight field offset, [27] its length          [28] subsets, [29] components, [30] planes, [31] weight bits
 // Mode 8 (solid): [6] is the offset of the four colour bytes; every other field is 0.
-void ht_mode_layout(uint32_t mode, uint32_t* out) {
+HOST_API void ht_mode_layout(uint32_t mode, uint32_t* out) {
     for (uint32_t i = 0; i < 32; i++) out[i] = 0;
     if (mode >= 19) return;
     out[0] = ku_mode_code[mode]; out[1] = ku_mode_code_len[mode];
@@ -116,12 +115,10 @@ void ht_mode_layout(uint32_t mode, uint32_t* out) {
 }
 
 // what unpack_block made of a block: endpoints (18), weights (32), pattern, component selector; returns the mode, 255 for a refused block
-uint32_t ht_unpack(const uint8_t* blk, uint8_t* endpoints18, uint8_t* weights32, uint32_t* pattern, uint32_t* ccs) {
+HOST_API uint32_t ht_unpack(const uint8_t* blk, uint8_t* endpoints18, uint8_t* weights32, uint32_t* pattern, uint32_t* ccs) {
     cand c;
     if (!unpack_block(blk, c)) return 255u;
     memcpy(endpoints18, c.endpoints, 18); memcpy(weights32, c.weights, 32);
     *pattern = c.pattern; *ccs = c.ccs;
     return c.mode;
-}
-
 }

@@ -4,10 +4,11 @@
 // Both go through the bodies generate() runs (tsvq<N>::root_of / split_of); tests/test_tsvq_node_host.py replays the reference's queue over them and
 // compares the tree with bu_host_tsvq, so the per-node records the GPU tests compare against are tied to the tree builder and, through it, to the reference.
 // The records have the layout of include/basisu_hip.h (origin / centroid components N..15 and pad are 0). Variances are RAW: split() substitutes 1e-4 afterwards.
-// Build: g++ -O2 -std=c++17 -fPIC -shared -ffp-contract=off
+// Built and bound by tests/native_libs.py.
 #include <cstdint>
 #include <cstring>
 #include "../../basis_universal_amd/csrc/host/tsvq.h"
+#include "host_api.h"
 
 namespace {
 struct root_rec { float origin[16]; uint64_t weight; float var; uint32_t pad; };
@@ -42,24 +43,22 @@ template <int N> void split(const bu::tsvq<N>& q, const uint32_t* members, uint3
 }
 }  // namespace
 
-extern "C" {
-void* tn_open(uint32_t dim, const float* rows, const uint64_t* weights, uint32_t n) {
+HOST_API void* tn_open(uint32_t dim, const float* rows, const uint64_t* weights, uint32_t n) {
     if (dim != 6 && dim != 16) return nullptr;
     handle* h = new handle();
     h->dim = (int)dim;
     if (dim == 6) h->q6.set_training(rows, weights, n); else h->q16.set_training(rows, weights, n);
     return h;
 }
-void tn_close(void* p) { delete static_cast<handle*>(p); }
-void tn_root(void* p, const uint32_t* members, uint32_t count, void* out_root) {
+HOST_API void tn_close(void* p) { delete static_cast<handle*>(p); }
+HOST_API void tn_root(void* p, const uint32_t* members, uint32_t count, void* out_root) {
     handle* h = static_cast<handle*>(p);
     if (h->dim == 6) root<6>(h->q6, members, count, static_cast<root_rec*>(out_root));
     else root<16>(h->q16, members, count, static_cast<root_rec*>(out_root));
 }
 // out_children: room for `count` indices; left list first, then the right one (untouched where ok == 0)
-void tn_split(void* p, const uint32_t* members, uint32_t count, uint64_t weight, const float* origin, void* out_split, uint32_t* out_children) {
+HOST_API void tn_split(void* p, const uint32_t* members, uint32_t count, uint64_t weight, const float* origin, void* out_split, uint32_t* out_children) {
     handle* h = static_cast<handle*>(p);
     if (h->dim == 6) split<6>(h->q6, members, count, weight, origin, static_cast<split_rec*>(out_split), out_children);
     else split<16>(h->q16, members, count, weight, origin, static_cast<split_rec*>(out_split), out_children);
-}
 }

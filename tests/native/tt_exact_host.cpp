@@ -1,20 +1,19 @@
 // tt_exact_host.cpp -- TEST-ONLY host build of csrc/tt_exact.h: the block walk tsvq_wide6_kernels.hip (tt_walk) does for the reference's double accumulators --
 // blocks that pass tt::block_is_exact taken in one step with a tree-summed block total, the others added member by member -- against the plain sequential sum
 //     s <- s + (double)a[i]
-// it must reproduce bit for bit. Compiled by tests/helpers.py with g++ -O2 -ffp-contract=off.
+// it must reproduce bit for bit. Built and bound by tests/native_libs.py.
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "../../basis_universal_amd/csrc/tt_exact.h"
+#include "host_api.h"
 
 using namespace bu::tt;
 
 static inline uint32_t f2u(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 
-extern "C" {
-
-double tt_sequential(const float* a, uint64_t n) {
+HOST_API double tt_sequential(const float* a, uint64_t n) {
     volatile double s = 0.0;
     for (uint64_t i = 0; i < n; i++) s = s + (double)a[i];
     return s;
@@ -22,7 +21,7 @@ double tt_sequential(const float* a, uint64_t n) {
 
 // stats[0] = blocks taken in one step, stats[1] = blocks added member by member, stats[2] = blocks that passed the test although two different summation orders of
 // the block (a pairwise tree, and last-to-first) disagree or differ from the in-order result -- must stay 0: the test promises exactness in ANY order
-double tt_blocked(const float* a, uint64_t n, uint32_t block, uint64_t* stats) {
+HOST_API double tt_blocked(const float* a, uint64_t n, uint32_t block, uint64_t* stats) {
     double s = 0.0;
     int L = L_FREE;
     stats[0] = stats[1] = stats[2] = 0;
@@ -60,6 +59,4 @@ double tt_blocked(const float* a, uint64_t n, uint32_t block, uint64_t* stats) {
     return s;
 }
 
-int tt_low_bit(double x) { return low_bit(x); }
-
-}
+HOST_API int tt_low_bit(double x) { return low_bit(x); }

@@ -6,12 +6,12 @@
 #include <vector>
 #include <utility>
 #include "../../basis_universal_amd/csrc/uastc_rdo.h"
+#include "host_api.h"
 
 using namespace bu_uastc;
-#define HC_API extern "C" __attribute__((visibility("default")))
 
 // `mask` selects the texels of the 16 given ones that form the cell (the reference sees them gathered, in the same order)
-HC_API uint64_t hc_cell_compress(const uint8_t* px16, uint32_t mask, uint32_t wbits, uint32_t range, int alpha, uint32_t uber, uint32_t ls_passes, uint8_t* out24) {
+HOST_API uint64_t hc_cell_compress(const uint8_t* px16, uint32_t mask, uint32_t wbits, uint32_t range, int alpha, uint32_t uber, uint32_t ls_passes, uint8_t* out24) {
     cell_cfg cfg;
     cfg.wbits = (uint8_t)wbits; cfg.range = (uint8_t)range; cfg.alpha = (uint8_t)alpha; cfg.uber = (uint8_t)uber; cfg.ls_passes = (uint8_t)ls_passes; cfg.ls_weights = ku_weights_ls + ((1u << wbits) - 2u) * 4;
     uint32_t px[16];
@@ -23,15 +23,15 @@ HC_API uint64_t hc_cell_compress(const uint8_t* px16, uint32_t mask, uint32_t wb
     for (int i = 0; i < 16; i++) out24[8 + i] = (uint8_t)sel_get(f.sel, i);
     return e;
 }
-HC_API uint64_t hc_cell_estimate(uint32_t wbits, uint32_t comps, const uint8_t* px16, uint32_t mask) {
+HOST_API uint64_t hc_cell_estimate(uint32_t wbits, uint32_t comps, const uint8_t* px16, uint32_t mask) {
     uint32_t px[16];
     for (int i = 0; i < 16; i++) px[i] = pack_px(px16 + i * 4);
     return estimate_masked_any(wbits, comps, px, mask);
 }
-HC_API uint32_t hc_weight_of(uint32_t bits, uint32_t s) { return weight_of(bits, s); }
-HC_API uint32_t hc_weight_table(uint32_t bits, uint32_t s) { return weight_set(bits)[s]; }
+HOST_API uint32_t hc_weight_of(uint32_t bits, uint32_t s) { return weight_of(bits, s); }
+HOST_API uint32_t hc_weight_table(uint32_t bits, uint32_t s) { return weight_set(bits)[s]; }
 
-HC_API void hc_encode_uastc(const uint8_t* blocks, uint32_t n, uint32_t flags, uint8_t* out) {
+HOST_API void hc_encode_uastc(const uint8_t* blocks, uint32_t n, uint32_t flags, uint8_t* out) {
     static cand scratch[MAX_SLOTS];
     for (uint32_t i = 0; i < n; i++) encode_block(blocks + (size_t)i * 64, flags, out + (size_t)i * 16, scratch);
 }
@@ -125,7 +125,7 @@ static bool rdo_strip(uint32_t first, uint32_t last, uint8_t* blocks, const uint
     return true;
 }
 
-HC_API int hc_uastc_rdo(uint8_t* blocks, const uint8_t* pixels, uint32_t n, const float* fp, const uint32_t* up, uint32_t flags, uint32_t total_jobs) {
+HOST_API int hc_uastc_rdo(uint8_t* blocks, const uint8_t* pixels, uint32_t n, const float* fp, const uint32_t* up, uint32_t flags, uint32_t total_jobs) {
     g_table_trials = (total_jobs >> 31) != 0;  // test switch in the top bit
     total_jobs &= 0x7FFFFFFFu;
     rdo_params p;
@@ -139,7 +139,7 @@ HC_API int hc_uastc_rdo(uint8_t* blocks, const uint8_t* pixels, uint32_t n, cons
     return 1;
 }
 
-HC_API int hc_unpack_block(const uint8_t* blk, uint8_t* out64) {
+HOST_API int hc_unpack_block(const uint8_t* blk, uint8_t* out64) {
     cand c;
     const bool ok = unpack_block(blk, c);
     memcpy(out64, &c, 64);
@@ -147,7 +147,7 @@ HC_API int hc_unpack_block(const uint8_t* blk, uint8_t* out64) {
 }
 
 // whole decoder: 16-byte UASTC blocks -> 4x4 RGBA texels (unpack_uastc + the per-texel interpolation of the core: what a transcoder to RGBA32 yields)
-HC_API int hc_decode_uastc(const uint8_t* blocks, uint32_t n, uint8_t* out_rgba64) {
+HOST_API int hc_decode_uastc(const uint8_t* blocks, uint32_t n, uint8_t* out_rgba64) {
     for (uint32_t i = 0; i < n; i++) {
         cand c;
         if (!unpack_block(blocks + (size_t)i * 16, c)) return 0;
@@ -158,7 +158,7 @@ HC_API int hc_decode_uastc(const uint8_t* blocks, uint32_t n, uint8_t* out_rgba6
     return 1;
 }
 
-HC_API int hc_rehint(const uint8_t* pixels, uint32_t n, uint32_t flags, uint8_t* blocks) {
+HOST_API int hc_rehint(const uint8_t* pixels, uint32_t n, uint32_t flags, uint8_t* blocks) {
     enc_cfg e;
     make_cfg(flags, e);
     for (uint32_t i = 0; i < n; i++)
@@ -167,7 +167,7 @@ HC_API int hc_rehint(const uint8_t* pixels, uint32_t n, uint32_t flags, uint8_t*
 }
 
 // every candidate of every block: the fused decode + error (uastc_errors / bc7_errors, what score_candidate uses) against the general decoders + block_error
-HC_API uint32_t hc_score_selfcheck(const uint8_t* blocks, uint32_t n, uint32_t flags, uint32_t* checked) {
+HOST_API uint32_t hc_score_selfcheck(const uint8_t* blocks, uint32_t n, uint32_t flags, uint32_t* checked) {
     enc_cfg e;
     make_cfg(flags, e);
     uint32_t bad = 0, seen = 0;

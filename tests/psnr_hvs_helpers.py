@@ -4,16 +4,14 @@
 The restatement is vectorised over blocks only: every array is float32 with the blocks on the first axis, every constant an np.float32, and every summation of the
 reference is an explicit loop along its axis in the reference's order (never np.sum, whose pairwise order is numpy's own). It reads the committed constant table
 (csrc/psnr_hvs_tables.inc)."""
-import ctypes as C
 import functools
-import json
 import math
 import pathlib
 import re
-import subprocess
 
 import numpy as np
 
+import native_libs
 from image_metrics_helpers import PRINT_TOLERANCE, padded  # noqa: F401  (the print tolerance is the one argued there: the tool prints these figures with {1.3} too)
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
@@ -25,33 +23,15 @@ REDUCED = ["y_601_8bit", "y_601_float", "r", "g", "b", "a", "rgb", "rgba"]      
 FIGURES = ["mseh_hvs", "mseh_hvsm", "psnr_hvs", "psnr_hvsm"]
 f32 = np.float32
 
-_host = None
-
 
 def host():
-    global _host
-    if _host is None:
-        d, csrc = ROOT / "tests" / "native", ROOT / "basis_universal_amd" / "csrc"
-        so, srcs = d / "libpsnr_hvs_host.so", [d / "psnr_hvs_host.cpp", csrc / "psnr_hvs.h", csrc / "psnr_hvs_tables.inc"]
-        if not so.exists() or so.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", str(so), str(srcs[0])])
-        L = C.CDLL(str(so))
-        L.phh_blocks.restype = C.c_uint32
-        L.phh_blocks.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-        L.phh_reduce.restype = None
-        L.phh_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-        _host = L
-    return _host
+    return native_libs.load("psnr_hvs_host")
 
 
 @functools.lru_cache(maxsize=None)
 def golden():
     """-> (arrays, meta): loaded once and shared; nobody writes into the arrays"""
-    z = np.load(GOLDEN)
-    arrays = {k: z[k] for k in z.files}
-    for a in arrays.values():
-        a.setflags(write=False)
-    return arrays, json.loads(arrays["meta"].tobytes().decode())
+    return native_libs.load_npz_golden(GOLDEN)
 
 
 @functools.lru_cache(maxsize=None)

@@ -101,12 +101,9 @@ def test_backend_above_level_1_needs_the_frontend():
 
 
 def _huffman(L, fn, freq, max_size):
-    import ctypes as C
     f = np.ascontiguousarray(freq, np.uint32)
     sizes, codes, out = np.zeros(f.size, np.uint8), np.zeros(f.size, np.uint16), np.zeros(f.size * 4 + 256, np.uint8)
     g = getattr(L, fn)
-    g.restype = C.c_uint64
-    g.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     n = g(f.ctypes.data, f.size, max_size, sizes.ctypes.data, codes.ctypes.data, out.ctypes.data, out.size)
     return (None, None, None) if n == 2 ** 64 - 1 else (sizes, codes, out[:n].copy())
 
@@ -149,24 +146,17 @@ def test_huffman_tables_match_reference():
 
 
 def test_crc16_matches_reference():
-    import ctypes as C
     from helpers import ref
     from basis_universal_amd.etc1s import load_frontend_library
     R, L = ref(), load_frontend_library()
     rng = np.random.default_rng(1)
     for n, crc in [(0, 0), (1, 0), (7, 0x8001), (8, 0), (9, 0xFFFF), (15, 1), (4097, 0), (100, 0x1234), (65536, 0xFFFF)]:
         d = rng.integers(0, 256, max(n, 1), dtype=np.uint8)
-        for lib in (R, L):
-            for fn in ("ref_crc16", "bu_backend_test_crc16"):
-                if hasattr(lib, fn):
-                    getattr(lib, fn).restype = C.c_uint32
-                    getattr(lib, fn).argtypes = [C.c_void_p, C.c_uint64, C.c_uint32]
         assert L.bu_backend_test_crc16(d.ctypes.data, n, crc) == R.ref_crc16(d.ctypes.data, n, crc), (n, crc)
 
 
 def test_palette_reordering_matches_reference():
     """reorder_palette_by_adjacency (sparse adjacency) against palette_index_reorderer (dense matrix), degenerate inputs included."""
-    import ctypes as C
     from helpers import ref
     from basis_universal_amd.etc1s import load_frontend_library
     R, L = ref(), load_frontend_library()
@@ -190,8 +180,6 @@ def test_palette_reordering_matches_reference():
         a, b = np.zeros(k, np.uint32), np.zeros(k, np.uint32)
         for lib, fn, out in ((L, "bu_backend_test_reorder", a), (R, "ref_palette_reorder", b)):
             g = getattr(lib, fn)
-            g.restype = None
-            g.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
             g(idx.ctypes.data, idx.size, k, out.ctypes.data)
         assert (a == b).all(), name
 

@@ -226,21 +226,15 @@ def test_frontend_outlives_its_context_at_the_c_level():
     from basis_universal_amd import capi, etc1s
     lib = capi.load_library().dll
     F = etc1s.load_frontend_library()
-    lib.bu_hip_create_context.restype = C.c_void_p
-    lib.bu_hip_destroy_context.argtypes = [C.c_void_p]
     ctx = lib.bu_hip_create_context()
     assert ctx
     blocks = to_pixel_blocks(synth(64, 64, 1))
-    F.bu_frontend_create.restype = C.c_void_p
     fe = F.bu_frontend_create()
     assert F.bu_frontend_init(C.c_void_p(fe), C.c_void_p(ctx), blocks.ctypes.data_as(C.c_void_p), None, blocks.shape[0], 32, 32, 1, 1) == 1
     assert F.bu_frontend_compress(C.c_void_p(fe)) == 1
     lib.bu_hip_destroy_context(ctx)
-    F.bu_frontend_get.restype = C.c_uint64
-    F.bu_frontend_get.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64]
     assert F.bu_frontend_get(fe, b"encoded_blocks", None, 0) == blocks.shape[0] * 8
     assert F.bu_frontend_compress(C.c_void_p(fe)) == 0          # fails cleanly, no device access through the dead context
-    F.bu_frontend_destroy.argtypes = [C.c_void_p]
     F.bu_frontend_destroy(fe)
 
 

@@ -75,6 +75,92 @@ def test_prototype_parser():
         assert "bu_" in str(e.value)       # the function is named too
     with pytest.raises(TypeError, match="1 BU_\\*API marks but 0 prototypes"):   # a call-back written inline: nothing this parser reads may pass silently
         parse_prototypes("BU_HIP_API int bu_inline_callback(void (*fn)(void* user));")
+    # another mark and any name: definitions as well as prototypes, what the mark stands for written out, helpers in between
+    i = C.c_int
+    got = parse_prototypes("""
+        #define HOST_API extern "C" __attribute__((visibility("default")))
+        HOST_API void* h_open(uint32_t dim, const float* rows) {
+            if (dim != 6) return nullptr;   // HOST_API int h_in_a_comment(void) {
+            return new handle();
+        }
+        static int helper(int x) { return x + 1; }
+        HOST_API int64_t h_multi_line(void* p,
+                                      uint8_t small, int64_t big)
+        {
+            return helper(small) + big;
+        }
+        HOST_API uint32_t h_void_list(void) { return 7; }
+        HOST_API int h_empty_list() { return 3; }
+        HOST_API void h_array(uint32_t packed, uint8_t out[8]) { std::memcpy(out, &packed, 4); }
+        HOST_API void* h_forward(const uint8_t* px, uint32_t threads);
+        int not_exported(void) { return h_empty_list(); }
+        HOST_API void* h_forward(const uint8_t* px, uint32_t threads) { return nullptr; }
+        HOST_API extern "C" __attribute__((visibility("default"))) int h_spelled_out(void);
+    """, mark="HOST_API", name=r"\w+")
+    assert got == {
+        "h_open": (vp, [u32, vp]),
+        "h_multi_line": (C.c_int64, [vp, C.c_uint8, C.c_int64]),
+        "h_void_list": (u32, []),
+        "h_empty_list": (i, []),
+        "h_array": (None, [u32, vp]),
+        "h_forward": (vp, [vp, u32]),
+        "h_spelled_out": (i, []),
+    }
+    with pytest.raises(TypeError, match="h_twice"):
+        parse_prototypes("HOST_API int h_twice(uint32_t n);\nHOST_API int h_twice(uint64_t n) { return 0; }", mark="HOST_API", name=r"\w+")
+    with pytest.raises(TypeError, match="2 HOST_API marks but 1 prototypes"):   # the count is of declarations, not of names
+        parse_prototypes("HOST_API int h_one(void);\nHOST_API int (*h_returns_a_function(void))(int);", mark="HOST_API", name=r"\w+")
+    assert parse_prototypes("HOST_API int h_one(void);") == {}   # the defaults look for BU_*API marks only
+
+
+def test_every_checker_function_is_exported_and_bound():
+    """Every marked function of every checker's source is exported by the library built from it, and the loader has put the signature derived from the source on it
+    (tests/native_libs.py). The prebuilt reference harness may lack functions only where it says that it is older than its source."""
+    import re
+    import helpers
+    import native_libs
+    sources = [source for _, source, _, _ in native_libs.CHECKERS.values()]
+    assert sorted(s for s in sources if s.parent == native_libs.NATIVE) == sorted(native_libs.NATIVE.glob("*.cpp")), "every tests/native/*.cpp is one checker"
+    assert len(set(sources)) == len(sources)
+    for name, (library, source, mark, how) in native_libs.CHECKERS.items():
+        protos = native_libs.prototypes(name)
+        assert len(re.findall(rf"\b{mark}\b", re.sub(r"^[ \t]*#.*$", "", source.read_text(), flags=re.M))) >= len(protos) > 0, name
+        if not library.exists() and how == "prebuilt":
+            continue
+        dll, exported = native_libs.load(name), _exports(library)
+        missing = sorted(set(protos) - exported)
+        if name == "ref":
+            (source_version,) = re.findall(r"ref_harness_version\(\)\s*\{\s*return (\d+);", source.read_text())
+            assert not missing or helpers.ref_harness_version() < int(source_version), missing
+        else:
+            assert not missing, (name, missing)
+        for fn_name, (res, args) in protos.items():
+            if fn_name not in missing:
+                fn = getattr(dll, fn_name)
+                assert fn.restype is res and fn.argtypes is not None and list(fn.argtypes) == args, fn_name
+
+
+def test_checker_staleness_and_build(tmp_path):
+    """native_libs on a two-file toy: the include closure, staleness by the newest file of it, and a failed compile that leaves the library it had."""
+    import os
+    import subprocess
+    import native_libs
+    a, b, lib = tmp_path / "a.cpp", tmp_path / "sub" / "b.h", tmp_path / "liba.so"
+    b.parent.mkdir()
+    a.write_text('#include <cstdint>\n  #  include "sub/b.h"\nextern "C" __attribute__((visibility("default"))) int a_value(void) { return B_VALUE; }\n')
+    b.write_text('#define B_VALUE 41\n')
+    assert native_libs.include_closure(a) == [a.resolve(), b.resolve()]
+    assert native_libs.is_stale(lib, a)
+    native_libs.build(lib, a)
+    assert not native_libs.is_stale(lib, a) and "a_value" in _exports(lib)
+    built = lib.stat().st_mtime_ns
+    os.utime(b, ns=(built + 10 ** 9, built + 10 ** 9))
+    assert native_libs.is_stale(lib, a), "a newer included file makes the library stale"
+    b.write_text("#define B_VALUE this does not compile +\n")
+    before = lib.read_bytes()
+    with pytest.raises(subprocess.CalledProcessError):
+        native_libs.build(lib, a)
+    assert lib.read_bytes() == before and sorted(p.name for p in tmp_path.iterdir()) == ["a.cpp", "liba.so", "sub"], "the old library stays, nothing else is left behind"
 
 
 def test_frontend_library_loads():

@@ -2,7 +2,6 @@
 pass order, sRGB tables = what Resampler / image_resample decide before touching pixels) is applied here by a float32 numpy emulation of
 mipmap_kernels.hip -- same operations, same order -- and the result has to equal the REAL image_resample (oracle/_ref) byte for byte.
 The GPU test (tests/test_gpu_mipmap.py) then only has to show that the kernels do what the emulation does."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -65,8 +64,6 @@ def emulate(src, dw, dh, p, srgb, num_comps):
 
 def reference(src, dw, dh, srgb, flt, scale, wrap, num_comps):
     R = ref()
-    R.ref_image_resample.restype = C.c_int
-    R.ref_image_resample.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_char_p, C.c_float, C.c_int, C.c_uint32, C.c_uint32]
     src = np.ascontiguousarray(src)
     out = np.zeros((dh, dw, 4), np.uint8)
     assert R.ref_image_resample(src.ctypes.data, src.shape[1], src.shape[0], out.ctypes.data, dw, dh, int(srgb), flt.encode(), scale, int(wrap), 0, num_comps)

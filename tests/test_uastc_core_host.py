@@ -131,7 +131,6 @@ def test_fused_scoring_equals_the_general_decoders(flags):
     flat = rgb.copy(); flat[:, :, :, :3] = (flat[:, :, :, :3] // 64) * 64 + 7      # few distinct values per block: degenerate cells, two-level planes
     blocks = np.ascontiguousarray(np.concatenate([rgb, rgba, la, flat]))
     L = uastc_host()
-    L.hc_score_selfcheck.restype = C.c_uint32
     checked = C.c_uint32(0)
     bad = L.hc_score_selfcheck(blocks.ctypes.data_as(C.POINTER(C.c_uint8)), blocks.shape[0], flags, C.byref(checked))
     assert checked.value > 2 * blocks.shape[0] and bad == 0, (bad, checked.value)

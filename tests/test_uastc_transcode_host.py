@@ -179,12 +179,7 @@ def test_random_blocks_every_target_against_reference(name):
 def test_random_blocks_validity_and_bc7_against_reference():
     """20,000 random-bit blocks that unpack as valid: BC7 bytes equal the reference's; and on every random block drawn the core agrees with the reference on validity.
     Runs on any build of the harness: the batched ref_transcode_uastc where it is there (version 3), the per-block entries of the older builds otherwise."""
-    import ctypes as C
     L = helpers.ref()
-    L.ref_unpack_uastc.restype = C.c_int
-    L.ref_unpack_uastc.argtypes = [helpers.u8p, helpers.u8p]
-    L.ref_uastc_to_bc7_pixels.restype = C.c_int
-    L.ref_uastc_to_bc7_pixels.argtypes = [helpers.u8p, helpers.u8p, helpers.u8p]
     batched = hasattr(L, "ref_transcode_uastc")
     rng = np.random.default_rng(20261016)
     valid_seen, invalid_seen, tmp, px = 0, 0, np.zeros(64, np.uint8), np.zeros(64, np.uint8)

@@ -1,46 +1,19 @@
 """Test-only helpers of the UASTC transcoder tests: the g++ build of basis_universal_amd/csrc/uastc_transcode.h (tests/native/transcode_host.cpp)."""
 import ctypes as C
-import pathlib
-import subprocess
 
 import numpy as np
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
+import native_libs
+
 u8p = C.POINTER(C.c_uint8)
 
 # transcoder_texture_format values (basis_universal_amd.transcode has the same constants; kept here so the host tests do not need the package's library)
 BC1, BC3, BC4, BC5, BC7, ASTC, RGBA32 = 2, 3, 4, 5, 6, 10, 13
 BYTES = {BC1: 8, BC3: 16, BC4: 8, BC5: 16, BC7: 16, ASTC: 16, RGBA32: 64}
 
-_lib = None
-
 
 def transcode_host():
-    global _lib
-    if _lib is None:
-        d, csrc = ROOT / "tests" / "native", ROOT / "basis_universal_amd" / "csrc"
-        so = d / "libtranscode_host.so"
-        srcs = [d / "transcode_host.cpp"] + [csrc / n for n in ("uastc_transcode.h", "uastc_transcode_tables.inc", "uastc_rdo.h", "uastc_core.h", "uastc_tables.inc")]
-        if not so.exists() or so.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", str(so), str(srcs[0])])
-        L = C.CDLL(str(so))
-        for n in ("ht_rgba32", "ht_astc", "ht_bc7"):
-            getattr(L, n).restype = C.c_uint32
-            getattr(L, n).argtypes = [u8p, C.c_uint32, u8p, u8p]
-        L.ht_bcn.restype = C.c_uint32
-        L.ht_bcn.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, u8p, u8p]
-        L.ht_bc1_hints.restype = C.c_uint32
-        L.ht_bc1_hints.argtypes = [u8p]
-        L.ht_mode.restype = C.c_uint32
-        L.ht_mode.argtypes = [u8p]
-        L.ht_modes_routes.restype = None
-        L.ht_modes_routes.argtypes = [u8p, C.c_uint32, u8p, u8p]
-        L.ht_mode_layout.restype = None
-        L.ht_mode_layout.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
-        L.ht_unpack.restype = C.c_uint32
-        L.ht_unpack.argtypes = [u8p, u8p, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        _lib = L
-    return _lib
+    return native_libs.load("transcode_host")
 
 
 def _p(a):

@@ -53,10 +53,7 @@ def sha(a):
 
 
 def ref_decode_uastc(packed, nbx, nby):
-    import ctypes as C
     L = helpers.ref()
-    L.ref_unpack_uastc.restype = C.c_int
-    L.ref_unpack_uastc.argtypes = [helpers.u8p, helpers.u8p]
     out = np.zeros((packed.shape[0], 4, 4, 4), np.uint8)
     for i in range(packed.shape[0]):
         assert L.ref_unpack_uastc(helpers.ptr(packed[i]), helpers.ptr(out[i])) == 1
