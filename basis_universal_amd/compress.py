@@ -45,7 +45,7 @@ def unified_quality_effort(uastc, quality=-1, effort=-1):
 
 
 def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=_uastc.LEVEL_DEFAULT, uastc_rdo_lambda=None, uastc_rdo_jobs=1, mipmaps=False,
-             ktx2=False, srgb=True, key_values=(), max_threads=0, stats=None, stats_hvs=False, stats_bc7=False):
+             ktx2=False, srgb=True, key_values=(), max_threads=0, stats=None, stats_hvs=False, stats_bc7=False, stats_ssim=False):
     """image: (h, w, 4) uint8 RGBA. Returns the file as a uint8 array.
     ETC1S: quality 1-255 (`-q`), comp_level 0-6 (`-comp_level`). UASTC: uastc_level 0-4, uastc_rdo_lambda (`-uastc_rdo_l`; None = no post-pass, any float
     incl. 0.0 = post-pass on, as m_rdo_uastc_ldr_4x4 + its scalar), uastc_rdo_jobs = the strips of the post-pass (the reference: min(4, pool threads) when
@@ -57,7 +57,8 @@ def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=
     planes that are resident here anyway; None = the stage does not run: the call's launches and bytes are what they are without it.
     stats_hvs: with stats, every slice dict gains "hvs" (PSNR-HVS / PSNR-HVS-M, stats.psnr_hvs: the reference's m_psnr_hvs_m_stats).
     stats_bc7: with stats and uastc, every slice dict gains "bc7", the same stats against the slice's BC7 transcode (stats.file_stats's bc7); without uastc it raises
-    ValueError before any work: the ETC1S transcoder here has no BC7 target."""
+    ValueError before any work: the ETC1S transcoder here has no BC7 target.
+    stats_ssim: with stats, every slice dict (and with stats_bc7 its "bc7" dict) gains "ssim", the seven figures of `basisu -compare_ssim` (stats.ssim)."""
     if stats_bc7 and not uastc:
         from .stats import BC7_REFUSAL
         raise ValueError(BC7_REFUSAL)
@@ -105,7 +106,7 @@ def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=
         def finish(data):   # m_compute_stats (comp.cpp:4195-4253) while the sources are still resident
             if stats is not None:
                 from . import stats as _stats
-                stats.extend(_stats._stats_from_slices(ctx, bytes(data), lambda level, layer, face, n_slices: level_planes[level], hvs=stats_hvs, bc7=stats_bc7))
+                stats.extend(_stats._stats_from_slices(ctx, bytes(data), lambda level, layer, face, n_slices: level_planes[level], hvs=stats_hvs, bc7=stats_bc7, ssim=stats_ssim))
             return data
         # ---- encode
         if uastc:

@@ -5,7 +5,7 @@ image_metrics::calc (encoder/basisu_enc.cpp:2155-2226) is a 256-bin histogram of
 sums) of all eight lines are counted on the GPU in one pass over two resident RGBA8 rasters (csrc/image_metrics_kernels.hip, bu_hip_k_image_metrics): integer counts,
 hence exactly the reference's, whatever the order of accumulation. The doubles are host code in the reference's own expression order (csrc/image_metrics.h,
 bu_image_metrics_reduce in libbasisu_frontend.so). The decode that is compared is the device transcoders' RGBA32 (transcode.py), resident, never downloaded.
-There is no CPU implementation of the counting: without the HIP library and a GPU `image_metrics` raises. No SSIM: this overload of calc never sets m_ssim.
+There is no CPU implementation of the counting: without the HIP library and a GPU `image_metrics` raises. This overload of calc never sets m_ssim; SSIM is `ssim` below.
 
 With hvs=True (file_stats) / stats_hvs=True (compress) every slice also carries what the tool prints under "PSNR-HVS and PSNR-HVS-M metrics:" (m_psnr_hvs_m_stats,
 comp.cpp:4265-4276; psnr_hvs_compute_metrics, enc.cpp:2256-2519; `basisu -compare_hvs` for any two images = psnr_hvs below). Per 8x8 block and mode (BT.601 Y rounded
@@ -18,7 +18,13 @@ With bc7=True (file_stats) / stats_bc7=True (compress) every slice of a UASTC fi
 texture:" (comp.cpp:3818-3842, 3875-3883, 4278-4337): the same eight lines -- and with hvs its own "hvs", "PSNR-HVS and PSNR-HVS-M metrics (BC7):" -- of the same source
 against what the slice's BC7 transcode samples as: the resident blocks through the device's UASTC -> BC7 transcoder and then through the block unpacker
 (transcode.unpack_blocks, csrc/block_unpack_kernels.hip), never downloaded. UASTC files only: the ETC1S transcoder here has no BC7 target, and the flag raises for an
-ETC1S file. Not here: SSIM and the best-ETC1S stats."""
+ETC1S file.
+
+With ssim=True (file_stats) / stats_ssim=True (compress) every slice dict -- and with bc7 the "bc7" dict too -- also carries "ssim": the seven figures `basisu -compare
+-compare_ssim` prints for two images (compute_ssim, encoder/basisu_ssim.cpp = ssim below; the reference's -stats stage does not print them, its compare mode does).
+Per pixel and channel five 11x11 Gaussian filterings of float images and the smap formula, binary32 in the reference's operation order (csrc/ssim.h), one lane per
+pixel (csrc/ssim_kernels.hip, bu_hip_k_ssim); then the mean as the reference's one running float sum in raster order, evaluated in chunks with csrc/fsum_scan.h
+(csrc/ssim_reduce.h): the figures are the reference's bit for bit, and print as the tool prints them. Not here: the best-ETC1S stats."""
 import ctypes as C
 
 import numpy as np
@@ -51,6 +57,13 @@ class _HvsMetrics(C.Structure):  # = bu_psnr_hvs_metrics
     _fields_ = [("y_601_8bit", _HvsChan), ("y_601_float", _HvsChan), ("chan", _HvsChan * 4), ("rgb", _HvsChan), ("rgba", _HvsChan)]
 
 
+class SsimResult(C.Structure):  # = bu_ssim_result, include/basisu_hip.h
+    _fields_ = [("struct_bytes", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("chunks_walked", C.c_uint32), ("r", C.c_float), ("g", C.c_float),
+                ("b", C.c_float), ("rgb", C.c_float), ("a", C.c_float), ("luma_709", C.c_float), ("luma_601", C.c_float), ("chunks", C.c_uint32)]
+
+
+SSIM_FIGURES = ("r", "g", "b", "rgb", "a", "luma_709", "luma_601")   # in the order the reference prints them (basisu_tool.cpp, -compare_ssim)
+SSIM_MODES = ("rgba", "luma_709", "luma_601")                        # the mode of bu_hip_k_ssim_map
 HVS_MODES = ("y_601_8bit", "y_601_float", "r", "g", "b", "a")   # the index of bu_psnr_hvs_sums::sum_hvs / sum_hvsm
 HVS_ENTRIES = ("y_601_float", "y_601_8bit", "rgb", "rgba", "r", "g", "b", "a")   # in the order the reference prints them (psnr_hvs_print_metrics)
 
@@ -160,11 +173,57 @@ def psnr_hvs(ctx, a, b):
     return out
 
 
-def _slice_stats(ctx, src, decoded, hvs):
-    """the dict of one slice: image_metrics, and under "hvs" psnr_hvs of the same two resident rasters when asked for"""
+def ssim_result(ctx, a, b):
+    """bu_hip_k_ssim: a, b as for image_metrics -> the filled SsimResult (the seven floats, width, height, and the reduction's chunks / chunks_walked)."""
+    owned = []
+    try:
+        (da, wa, ha, pa), (db, wb, hb, pb) = _resident(ctx, a, owned), _resident(ctx, b, owned)
+        s = SsimResult()
+        s.struct_bytes = C.sizeof(SsimResult)
+        ctx.check(ctx.lib.k_ssim(ctx.h, C.c_void_p(da), wa, ha, pa, C.c_void_p(db), wb, hb, pb, C.byref(s)), "ssim")
+        return s
+    finally:
+        for d in owned:
+            ctx.free(d)
+
+
+def ssim_map(ctx, a, b, mode):
+    """bu_hip_k_ssim_map (the test hook): the smap values of one call of compute_ssim in raster order -> (h, w, 4) f32 for mode 0 (the RGBA call), (h, w) f32 for
+    mode 1 / 2 (channel 0 of the 709 / 601 luma call)."""
+    owned = []
+    try:
+        (da, wa, ha, pa), (db, wb, hb, pb) = _resident(ctx, a, owned), _resident(ctx, b, owned)
+        w, h = min(wa, wb), min(ha, hb)
+        out, n = np.zeros((h, w, 4) if int(mode) == 0 else (h, w), np.float32), C.c_uint32(0)
+        ctx.check(ctx.lib.k_ssim_map(ctx.h, C.c_void_p(da), wa, ha, pa, C.c_void_p(db), wb, hb, pb, int(mode), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)),
+                  "ssim_map")
+        if n.value != w * h:
+            raise RuntimeError(f"ssim_map: {n.value} pixels for a region of {w} x {h}")
+        return out
+    finally:
+        for d in owned:
+            ctx.free(d)
+
+
+def ssim(ctx, a, b):
+    """compute_ssim of `a` against `b`: the seven figures `basisu -compare -compare_ssim a b` prints. a, b: (h, w, 4) u8 arrays (uploaded) or (device pointer, width,
+    height, row pitch in pixels, 0 = width) tuples of resident RGBA8 rasters; the region is min(widths) x min(heights), and the filter's coordinates are clamped to it.
+    -> {"r", "g", "b", "rgb", "a", "luma_709", "luma_601": Python floats of the binary32 results ("%f" % value is the tool's text), "width", "height"}.
+    An empty region raises (the reference asserts), as does one beyond 2^25 pixels. From 2^24 pixels on the reference's running float sum stops growing for addends
+    near 1 (an identical pair then gives less than 1.0); that is reproduced, not repaired."""
+    s = ssim_result(ctx, a, b)
+    out = {name: float(getattr(s, name)) for name in SSIM_FIGURES}
+    out.update({"width": int(s.width), "height": int(s.height)})
+    return out
+
+
+def _slice_stats(ctx, src, decoded, hvs, with_ssim=False):
+    """the dict of one slice: image_metrics, and under "hvs" / "ssim" psnr_hvs / ssim of the same two resident rasters when asked for"""
     out = image_metrics(ctx, src, decoded)
     if hvs:
         out["hvs"] = psnr_hvs(ctx, src, decoded)
+    if with_ssim:
+        out["ssim"] = ssim(ctx, src, decoded)
     return out
 
 
@@ -194,7 +253,7 @@ def _slice_order(images):
 BC7_REFUSAL = "BC7 stats are for UASTC files only: the ETC1S transcoder here has no BC7 target"
 
 
-def _stats_from_slices(ctx, raw, slice_sources, hvs=False, bc7=False):
+def _stats_from_slices(ctx, raw, slice_sources, hvs=False, bc7=False, ssim=False):
     """slice_sources(level, layer, face, n_slices) -> one source raster per slice of that image (array or resident tuple). -> the per-slice dicts, slice order."""
     out = []
     if _is_etc1s(raw):
@@ -214,7 +273,7 @@ def _stats_from_slices(ctx, raw, slice_sources, hvs=False, bc7=False):
             try:
                 for part, src in zip(parts, sources):
                     transcode.transcode_etc1s_image(ctx, decoded, part, transcode.RGBA32, out_device=d_out)
-                    out.append(_slice_stats(ctx, src, (d_out, w, h, w), hvs))
+                    out.append(_slice_stats(ctx, src, (d_out, w, h, w), hvs, ssim))
             finally:
                 ctx.free(d_out)
         return out
@@ -228,16 +287,16 @@ def _stats_from_slices(ctx, raw, slice_sources, hvs=False, bc7=False):
         try:
             if not bc7:
                 transcode.transcode_uastc_blocks(ctx, blocks, im["num_blocks_x"], im["num_blocks_y"], transcode.RGBA32, width=w, height=h, out_device=d_out)
-                out.append(_slice_stats(ctx, src, (d_out, w, h, w), hvs))
+                out.append(_slice_stats(ctx, src, (d_out, w, h, w), hvs, ssim))
                 continue
             # the blocks go up once; the BC7 texture and both rasters stay on the device
             d_blocks, d_bc7 = ctx.upload(blocks), ctx.alloc(blocks.shape[0] * 16)
             try:
                 transcode.transcode_uastc_blocks(ctx, d_blocks, im["num_blocks_x"], im["num_blocks_y"], transcode.RGBA32, width=w, height=h, out_device=d_out)
-                one = _slice_stats(ctx, src, (d_out, w, h, w), hvs)
+                one = _slice_stats(ctx, src, (d_out, w, h, w), hvs, ssim)
                 transcode.transcode_uastc_blocks(ctx, d_blocks, im["num_blocks_x"], im["num_blocks_y"], transcode.BC7_RGBA, out_device=d_bc7)
                 transcode.unpack_blocks(ctx, d_bc7, im["num_blocks_x"], im["num_blocks_y"], transcode.BC7_RGBA, width=w, height=h, out_device=d_out)
-                one["bc7"] = _slice_stats(ctx, src, (d_out, w, h, w), hvs)
+                one["bc7"] = _slice_stats(ctx, src, (d_out, w, h, w), hvs, ssim)
                 out.append(one)
             finally:
                 ctx.free(d_blocks)
@@ -247,7 +306,7 @@ def _stats_from_slices(ctx, raw, slice_sources, hvs=False, bc7=False):
     return out
 
 
-def file_stats(ctx, data, images, hvs=False, bc7=False):
+def file_stats(ctx, data, images, hvs=False, bc7=False, ssim=False):
     """The reference's m_stats for a .basis / .ktx2 file of this package (UASTC LDR 4x4 or ETC1S): one image_metrics dict per slice, in the compressor's slice order
     (source image outermost, then its levels; an ETC1S image with alpha has a colour slice and then an alpha slice, each with its own stats).
     images: the source of every image the file holds -- {(level, layer, face): image} or, for a file of one layer and face, a list by level; an image is an
@@ -258,7 +317,9 @@ def file_stats(ctx, data, images, hvs=False, bc7=False):
     that is padded beyond the slice's size (the compressor's level rasters) must be padded with duplicated borders, as the compressor's are: a block's coordinates
     are clamped to each raster's own edge.
     bc7: every slice dict of a UASTC file gains "bc7": the same dict (the eight lines, sums and size, and "hvs" when hvs is set) of the same source against the slice's
-    BC7 transcode, unpacked on the device. An ETC1S file raises ValueError before any work."""
+    BC7 transcode, unpacked on the device. An ETC1S file raises ValueError before any work.
+    ssim: every slice dict (and with bc7 the "bc7" dict) gains "ssim", ssim() of the same source against the same resident decode. The filter is clamped to the
+    slice's own size, whatever padding the source raster has beyond it."""
     raw = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
     if bc7 and _is_etc1s(raw):
         raise ValueError(BC7_REFUSAL)
@@ -278,4 +339,4 @@ def file_stats(ctx, data, images, hvs=False, bc7=False):
                 rows.reshape(-1, 4)[:(h - 1) * pitch + w] = ctx.download(d, ((h - 1) * pitch + w, 4), np.uint8)
             src = rows[:, :w]
         return list(split_planes(src))
-    return _stats_from_slices(ctx, raw, slice_sources, hvs, bc7)
+    return _stats_from_slices(ctx, raw, slice_sources, hvs, bc7, ssim)

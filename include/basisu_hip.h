@@ -414,6 +414,32 @@ BU_HIP_API int bu_hip_k_psnr_hvs(bu_hip_context*, const void* d_a, uint32_t widt
 BU_HIP_API int bu_hip_k_psnr_hvs_blocks(bu_hip_context*, const void* d_a, uint32_t width_a, uint32_t height_a, uint32_t pitch_a_pixels, const void* d_b, uint32_t width_b,
         uint32_t height_b, uint32_t pitch_b_pixels, uint32_t mode, double* h_out_blocks, uint32_t capacity_blocks, uint32_t* out_blocks);
 
+/* SSIM as compute_ssim computes it (encoder/basisu_ssim.cpp) and `basisu -compare -compare_ssim` prints it (basisu_tool.cpp: "R SSIM" .. "Y 601 SSIM"), over two
+ * resident RGBA8 rasters laid out as for bu_hip_k_image_metrics. The region is min(width_a, width_b) x min(height_a, height_b); the filter's coordinates are clamped
+ * to the REGION (compute_ssim crops both images first). Three calls of the reference in one: RGBA (r, g, b, a; rgb = (r + g + b) / 3.0f in float) and channel 0 of
+ * the 709-luma and the 601-luma call.
+ *   Every figure is the reference's binary32 arithmetic in its operation order, bit for bit (csrc/ssim.h): per pixel and channel five 121-tap Gaussian filterings and
+ *   the smap formula (csrc/ssim_kernels.hip, one lane per pixel), then the mean as ONE running float sum over the pixels in raster order -- evaluated in chunks with
+ *   csrc/fsum_scan.h, with plain float adds wherever a chunk's shortcut is not valid, so the sum's bits are the serial sum's. That includes what the serial sum does
+ *   from 2^24 pixels on: an identical pair's sum stops at 16777216, so its figures fall below 1.
+ *   chunks / chunks_walked: how many chunks of 256 addends the six sums had, and how many of them had to be added one by one (diagnostic).
+ * Versioned by size like bu_image_metrics_counts. Six launches on the context's stream; synchronises to copy the result out. The six float planes of the region
+ * (24 bytes per pixel) are reserved from the context for the call and given back after it when they exceed 64 MiB. Fails -- nothing launched, *h_out untouched -- on
+ * a null pointer, a misaligned raster, a pitch below its width, an EMPTY region (the reference asserts), a region beyond 16384 each way or beyond 2^25 pixels.
+ * bu_hip_k_ssim_map is the test hook under it: the smap values of ONE call in raster order -- mode 0 = RGBA, 4 floats per pixel; 1 / 2 = channel 0 of the 709 / 601
+ * luma call, 1 float per pixel; capacity_floats must cover them; *out_pixels (may be NULL) gets the region's pixel count. */
+typedef struct bu_ssim_result {
+    uint32_t struct_bytes;
+    uint32_t width, height;       /* the region compared */
+    uint32_t chunks_walked;
+    float r, g, b, rgb, a, luma_709, luma_601;
+    uint32_t chunks;
+} bu_ssim_result;
+BU_HIP_API int bu_hip_k_ssim(bu_hip_context*, const void* d_a, uint32_t width_a, uint32_t height_a, uint32_t pitch_a_pixels, const void* d_b, uint32_t width_b,
+        uint32_t height_b, uint32_t pitch_b_pixels, bu_ssim_result* h_out);
+BU_HIP_API int bu_hip_k_ssim_map(bu_hip_context*, const void* d_a, uint32_t width_a, uint32_t height_a, uint32_t pitch_a_pixels, const void* d_b, uint32_t width_b,
+        uint32_t height_b, uint32_t pitch_b_pixels, uint32_t mode, float* h_out, uint64_t capacity_floats, uint32_t* out_pixels);
+
 /* a15 + the list handling inside a9 / a10 / a13 / a14: cluster bookkeeping on the device (basis_universal_amd/csrc/bookkeeping_kernels.hip).
  *     A clustering is two resident per-block arrays, cluster index and position inside the cluster's list; these calls turn distinct-vector level
  *     results into them, rebuild them after a reassignment, apply codebook renumberings to them and produce the CSR lists the per-cluster

@@ -4,7 +4,7 @@
  *
  * The reference's expression order: 256 bins in ascending order, sum += i * h[i] and sum2 += i * (i * h[i]) in double; mean, mean_squared and rms narrowed to float;
  * psnr = rms ? clamp(log10(255.0 / rms) * 20, 0, 100) : 100; avg_comp_error = true as basis_compressor calls it (the divisor is width * height * channels).
- * This overload of calc never sets m_ssim, so there is no SSIM here.
+ * This overload of calc never sets m_ssim; SSIM is bu_hip_k_ssim (basisu_hip.h), whose filter weights bu_ssim_gaussian_weights below computes.
  */
 #ifndef BASISU_HIP_IMAGE_METRICS_H
 #define BASISU_HIP_IMAGE_METRICS_H
@@ -35,6 +35,11 @@ typedef struct bu_psnr_hvs_metrics {
 } bu_psnr_hvs_metrics;
 /* Returns 0 (and leaves *out alone) on a null pointer or a sums struct whose struct_bytes ends before sum_hvsm does. blocks == 0 gives the 0 / 0 (NaN) of the division. */
 BU_HIP_API int bu_psnr_hvs_reduce(const bu_psnr_hvs_sums* sums, bu_psnr_hvs_metrics* out);
+
+/* The 11 x 11 Gaussian of compute_ssim (compute_gaussian_kernel(11, 11, 1.5f * 1.5f, normalize), encoder/basisu_ssim.cpp) in the reference's own order: gauss() with
+ * expf / sqrtf of the host's libm, three quadrants copied from the first, the sum a double accumulated x outer and y inner, one_over_sum a double division, every
+ * weight float(w * one_over_sum). out[(yd + 5) * 11 + (xd + 5)], yd and xd = -5 .. 5. Returns 0 on a null pointer. */
+BU_HIP_API int bu_ssim_gaussian_weights(float out[121]);
 
 #ifdef __cplusplus
 }
