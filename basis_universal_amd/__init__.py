@@ -7,6 +7,7 @@ Layers:
   etc1s   host-side mirror of the reference's basisu_frontend over the device-resident layer
   transcode  UASTC LDR 4x4 blocks / files -> RGBA32, BC1-BC5, BC7, ASTC 4x4 on the device; ETC1S files -> RGBA32, ETC1, BC1, 16-bit pixels (host decode + device)
   stats   the reference's per-slice quality stats (Max / Mean / RMS / PSNR per channel set) of a file against its source: histograms on the device, doubles on the host; on request PSNR-HVS / PSNR-HVS-M and the SSIM figures of `basisu -compare_ssim`, bit for bit
+  source  the compressor's source-image options on the resident raster (renormalise, swizzle, alpha policy, flip, resample; the `-normal_map` preset), in front of compress()
 
 There is deliberately no CPU fallback anywhere in this package: if the HIP library is missing or no GPU is visible the
 entry points raise.

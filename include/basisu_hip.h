@@ -193,6 +193,24 @@ BU_HIP_API const void* bu_hip_get_pixel_blocks_device(const bu_hip_context*, siz
  * image::extract_block_clamped. The result can be adopted with bu_hip_set_pixel_blocks_device. */
 BU_HIP_API int bu_hip_k_extract_blocks(bu_hip_context*, const void* d_rgba, uint32_t width, uint32_t height, uint32_t pitch_bytes, void* d_out_pixel_blocks);
 
+/* The compressor's source-image options (basis_compressor::read_source_images, comp.cpp:2569-2640) over resident RGBA8 rasters: 4-byte aligned, row pitches in
+ * bytes (>= 4 * width, multiples of 4), 1..16384 pixels each way. Per pixel, in the reference's order (csrc/source_prep.h): image::renormalize_normal_map when
+ * `renormalize`; the swizzle, one source-channel index 0..3 per byte (s0 | s1 << 8 | s2 << 16 | s3 << 24; 0x03020100 = none, 0x01000000 = the tool's
+ * -separate_rg_to_color_alpha); the alpha policy -- force_alpha or s3 != 3: alpha is kept and the image has alpha; else without check_for_alpha: alpha becomes 255;
+ * else the image has alpha where a prepared alpha value is below 255 --; and with y_flip destination row y is made from source row height - 1 - y.
+ * *out_has_alpha (may be NULL) gets the policy's answer, *out_alpha_below_255 (may be NULL) whether any prepared alpha value is below 255 (what image::has_alpha
+ * says of the prepared raster). d_dst may equal d_src unless y_flip is set. One launch on the context's stream; the call synchronises once to read the flag.
+ * bu_hip_k_renormalize_normal_map: image::renormalize_normal_map in place (the mip levels of m_mip_renormalize); one launch, no synchronisation.
+ * bu_hip_k_split_alpha: the two ETC1S slices of a level with alpha (comp.cpp:2883-2903): (r, g, b, 255) to d_out_rgb, which may equal d_rgba, and (a, a, a, 255) to
+ * d_out_alpha, which may not; one read, two writes, one launch, no synchronisation. Only width x height pixels are written: a padded pitch stays untouched.
+ * Each fails -- nothing launched, nothing written, the reason by name in bu_hip_last_error -- on a null pointer, a zero dimension, a pitch below 4 * width, a
+ * misaligned raster or pitch, more than 16384 pixels a side, a swizzle entry above 3, or source equal to destination with y_flip. */
+BU_HIP_API int bu_hip_k_prepare_source(bu_hip_context*, const void* d_src, uint32_t width, uint32_t height, uint32_t src_pitch_bytes, void* d_dst, uint32_t dst_pitch_bytes,
+        int renormalize, uint32_t swizzle, int check_for_alpha, int force_alpha, int y_flip, uint32_t* out_has_alpha, uint32_t* out_alpha_below_255);
+BU_HIP_API int bu_hip_k_renormalize_normal_map(bu_hip_context*, void* d_rgba, uint32_t width, uint32_t height, uint32_t pitch_bytes);
+BU_HIP_API int bu_hip_k_split_alpha(bu_hip_context*, const void* d_rgba, uint32_t width, uint32_t height, uint32_t pitch_bytes, void* d_out_rgb, uint32_t rgb_pitch_bytes,
+        void* d_out_alpha, uint32_t alpha_pitch_bytes);
+
 /* etc1_optimizer quality (basis_etc_quality, basisu_etc.h:794-801) */
 enum { BU_ETC_QUALITY_FAST = 0, BU_ETC_QUALITY_MEDIUM = 1, BU_ETC_QUALITY_SLOW = 2, BU_ETC_QUALITY_UBER = 3 };
 
