@@ -111,13 +111,55 @@ class Context:
         arr = np.ascontiguousarray(arr)
         p = self.alloc(max(arr.nbytes, 1))
         if arr.nbytes:
-            self.check(self.lib.memcpy_h2d(self.h, p, arr.ctypes.data_as(_vp), arr.nbytes), "memcpy_h2d")
+            self.memcpy_h2d(p, arr)
         return p
+
+    def memcpy_h2d(self, d, arr):
+        """bu_hip_memcpy_h2d: `arr` (C-contiguous) to device pointer `d`; synchronises."""
+        if not arr.flags.c_contiguous:
+            raise ValueError("memcpy_h2d takes a C-contiguous array")
+        self.check(self.lib.memcpy_h2d(self.h, _vp(d), arr.ctypes.data_as(_vp), arr.nbytes), "memcpy_h2d")
 
     def download(self, p, shape, dtype):
         out = np.empty(shape, dtype)
         self.check(self.lib.memcpy_d2h(self.h, out.ctypes.data_as(_vp), p, out.nbytes), "memcpy_d2h")
         return out
+
+    def memcpy_h2d_async(self, d, arr):
+        """bu_hip_memcpy_h2d_async: `arr` (C-contiguous) to device pointer `d`, ordered on the context's stream; `arr` may be overwritten or released on return."""
+        if not arr.flags.c_contiguous:
+            raise ValueError("memcpy_h2d_async takes a C-contiguous array")
+        self.check(self.lib.memcpy_h2d_async(self.h, _vp(d), arr.ctypes.data_as(_vp), arr.nbytes), "memcpy_h2d_async")
+
+    def memcpy_d2d(self, dst, src, nbytes):
+        """bu_hip_memcpy_d2d: ordered on the context's stream, no host synchronisation."""
+        self.check(self.lib.memcpy_d2d(self.h, _vp(dst), _vp(src), int(nbytes)), "memcpy_d2d")
+
+    def memcpy_d2h(self, arr, src):
+        """bu_hip_memcpy_d2h into an existing (C-contiguous, writable) array; synchronises."""
+        if not (arr.flags.c_contiguous and arr.flags.writeable):
+            raise ValueError("memcpy_d2h takes a writable C-contiguous array")
+        self.check(self.lib.memcpy_d2h(self.h, arr.ctypes.data_as(_vp), _vp(src), arr.nbytes), "memcpy_d2h")
+
+    def memset(self, d, value, nbytes):
+        """bu_hip_memset: ordered on the context's stream."""
+        self.check(self.lib.memset(self.h, _vp(d), int(value), int(nbytes)), "memset")
+
+    def device(self):
+        """bu_hip_context_device"""
+        return self.lib.context_device(self.h)
+
+    def set_stream(self, stream=None):
+        """bu_hip_set_stream: run on an externally owned hipStream_t (its address as an int: torch's cuda_stream, another context's get_stream()); None = back to the context's own."""
+        self.check(self.lib.set_stream(self.h, _vp(stream)), "set_stream")
+
+    def get_stream(self):
+        """bu_hip_get_stream: the address of the hipStream_t the context enqueues on."""
+        return self.lib.get_stream(self.h)
+
+    def set_wait_hook(self, fn=None, user=None):
+        """bu_hip_set_wait_hook: fn is a ctypes.CFUNCTYPE(None, c_void_p) instance the caller keeps alive while it is installed; None removes the hook."""
+        self.check(self.lib.set_wait_hook(self.h, fn, _vp(user)), "set_wait_hook")
 
     def profile_enable(self, on=True):
         self.check(self.lib.profile_enable(self.h, int(on)), "profile_enable")

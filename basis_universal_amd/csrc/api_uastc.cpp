@@ -15,12 +15,14 @@ struct bu_uastc_pipeline {
     bu_hip_context* parent = nullptr;
     std::vector<lane> lanes;
     uint64_t next_ticket = 1;
+    size_t ws_bytes = 0;   // what create sized every lane's workspace for: submit's limit (a parked lane context may come back with a larger arena; the limit does not move with it)
 };
 
 extern "C" {
 // ---------------------------------------------------------------- UASTC (rows a16-a19)
 
 size_t bu_hip_uastc_workspace_bytes(uint32_t n_blocks, uint32_t flags) { return bu::uastc_workspace_bytes(n_blocks, flags); }
+size_t bu_hip_uastc_rdo_workspace_bytes(uint32_t n_blocks, uint32_t total_jobs) { return bu::uastc_rdo_workspace_bytes(n_blocks, total_jobs); }
 
 int bu_hip_k_encode_uastc_blocks(bu_hip_context* ctx, const void* d_px, uint32_t n_blocks, uint32_t flags, void* d_out) {
     if (!ctx) return 0;
@@ -87,6 +89,13 @@ void bu_hip_uastc_rdo_default_params(bu_uastc_rdo_params* p) {
     p->m_endpoint_refinement = 1; p->m_lz_literal_cost = 100; p->m_max_smooth_block_std_dev = 18.0f; p->m_smooth_block_max_error_scale = 10.0f;
 }
 
+// uastc_rdo's asserts (uastc_enc.cpp:4097-4099) as errors
+static bool uastc_rdo_params_ok(bu_hip_context* ctx, const bu_uastc_rdo_params* params) {
+    if (params->m_max_allowed_rms_increase_ratio > 1.0f && params->m_lz_dict_size && params->m_lambda > 0.0f) return true;
+    set_error(ctx, "uastc_rdo: need max_allowed_rms_increase_ratio > 1, lz_dict_size > 0, lambda > 0");
+    return false;
+}
+
 // The strip walks of uastc_rdo behind its prepare pass: the lean build (strips without a block of a sensitive mode: four waves per SIMD) on the context's stream and,
 // when endpoint refinement is on, the build with the refit in it (the flagged strips) on the side stream beside it -- forked and joined with events, nobody waits on
 // the host. Without a side stream the two launches simply follow each other.
@@ -125,11 +134,7 @@ int bu_hip_k_uastc_rdo(bu_hip_context* ctx, void* d_blocks, const void* d_px, ui
                        uint32_t total_jobs, uint32_t out_stats[4]) {
     if (!ctx) return 0;
     if (!d_blocks || !d_px || !params) { set_error(ctx, "uastc_rdo: null pointer"); return 0; }
-    // uastc_rdo's asserts (uastc_enc.cpp:4097-4099) as errors
-    if (!(params->m_max_allowed_rms_increase_ratio > 1.0f) || !params->m_lz_dict_size || !(params->m_lambda > 0.0f)) {
-        set_error(ctx, "uastc_rdo: need max_allowed_rms_increase_ratio > 1, lz_dict_size > 0, lambda > 0");
-        return 0;
-    }
+    if (!uastc_rdo_params_ok(ctx, params)) return 0;
     device_guard g(ctx->device);
     if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = 0, out_stats[3] = bu::uastc_rdo_strips(n_blocks, total_jobs);
     if (!n_blocks) return 1;
@@ -173,10 +178,7 @@ int bu_hip_k_uastc_rdo(bu_hip_context* ctx, void* d_blocks, const void* d_px, ui
 
 static int uastc_rdo_enqueue(bu_hip_context* ctx, void* d_blocks, const void* d_px, uint32_t n_blocks, const bu_uastc_rdo_params* params, uint32_t flags, uint32_t total_jobs,
                              uint32_t* h_pinned_counters) {
-    if (!(params->m_max_allowed_rms_increase_ratio > 1.0f) || !params->m_lz_dict_size || !(params->m_lambda > 0.0f)) {
-        set_error(ctx, "uastc_rdo: need max_allowed_rms_increase_ratio > 1, lz_dict_size > 0, lambda > 0");
-        return 0;
-    }
+    if (!uastc_rdo_params_ok(ctx, params)) return 0;
     const float fp[5] = { params->m_lambda, params->m_max_allowed_rms_increase_ratio, params->m_skip_block_rms_thresh, params->m_max_smooth_block_std_dev,
                           params->m_smooth_block_max_error_scale };
     const uint32_t up[3] = { params->m_lz_dict_size, params->m_lz_literal_cost, params->m_endpoint_refinement };
@@ -201,7 +203,7 @@ bu_uastc_pipeline* bu_hip_uastc_pipeline_create(bu_hip_context* ctx, uint32_t la
     p->parent = ctx;
     p->lanes.resize(lanes);
     // every workspace at its final size now: growing one later would free it under the kernels of an earlier submission
-    const size_t ws_bytes = std::max(bu::uastc_workspace_bytes(max_blocks, flags), bu::uastc_rdo_workspace_bytes(max_blocks, max_total_jobs));
+    const size_t ws_bytes = p->ws_bytes = std::max(bu::uastc_workspace_bytes(max_blocks, flags), bu::uastc_rdo_workspace_bytes(max_blocks, max_total_jobs));
     for (auto& l : p->lanes) {
         l.ctx = create_context_kind(ctx->device, true);
         if (l.ctx) {
@@ -263,12 +265,14 @@ int bu_hip_uastc_pipeline_submit(bu_uastc_pipeline* p, const void* d_px, uint32_
     if (!p) return 0;
     bu_hip_context* ctx = p->parent;
     if (!d_px || !d_out || !n_blocks) { set_error(ctx, "uastc_pipeline_submit: null pointer / no blocks"); return 0; }
+    // every refusal comes before the first enqueue: a submission that fails here has left nothing in flight on its lane, which wait() would not know to wait for
+    const size_t need = std::max(bu::uastc_workspace_bytes(n_blocks, flags), rdo ? bu::uastc_rdo_workspace_bytes(n_blocks, total_jobs) : (size_t)0);
+    if (need > p->ws_bytes) { set_error(ctx, "uastc_pipeline_submit: %u blocks / %u jobs exceed what the pipeline was created for", n_blocks, total_jobs); return 0; }
+    if (rdo && !uastc_rdo_params_ok(ctx, rdo)) return 0;
     device_guard g(ctx->device);
     const uint64_t ticket = p->next_ticket;
     bu_uastc_pipeline::lane& l = p->lanes[(size_t)(ticket % p->lanes.size())];
     if (!uastc_pipeline_collect(p, l, nullptr)) return 0;   // the lane's previous submission (its results are complete from here on; nobody asked for its statistics)
-    const size_t need = std::max(bu::uastc_workspace_bytes(n_blocks, flags), rdo ? bu::uastc_rdo_workspace_bytes(n_blocks, total_jobs) : (size_t)0);
-    if (need > l.ctx->scratch[5].cap) { set_error(ctx, "uastc_pipeline_submit: %u blocks / %u jobs exceed what the pipeline was created for", n_blocks, total_jobs); return 0; }
     // the input tiles may still be being produced on the caller's stream
     BU_TRY(ctx, hipEventRecord(l.input, ctx->stream));
     BU_TRY(ctx, hipStreamWaitEvent(l.ctx->stream, l.input, 0));

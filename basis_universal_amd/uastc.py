@@ -103,6 +103,16 @@ def uastc_rdo(ctx, uastc_blocks, pixel_blocks, params=None, flags=LEVEL_DEFAULT,
             ctx.free(d)
 
 
+def workspace_bytes(n_blocks, flags=LEVEL_DEFAULT, lib=None):
+    """bu_hip_uastc_workspace_bytes: the context workspace encode_uastc_blocks needs (host arithmetic: no GPU, no context)."""
+    return (lib or capi.load_library()).uastc_workspace_bytes(int(n_blocks), int(flags))
+
+
+def rdo_workspace_bytes(n_blocks, total_jobs=0, lib=None):
+    """bu_hip_uastc_rdo_workspace_bytes: the same for uastc_rdo over total_jobs strips."""
+    return (lib or capi.load_library()).uastc_rdo_workspace_bytes(int(n_blocks), int(total_jobs))
+
+
 class UastcPipeline:
     """encode_uastc (+ uastc_rdo) over a stream of images with several in flight on one GPU (bu_hip_uastc_pipeline_*, include/basisu_hip.h): every submission is
     enqueued on one of `lanes` private streams without a host synchronisation, so one image's RDO walk (a serial chain per strip that leaves most of the chip idle)

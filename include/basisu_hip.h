@@ -298,6 +298,8 @@ BU_HIP_API int bu_hip_k_find_optimal_selector_clusters(bu_hip_context*, const vo
 BU_HIP_API int bu_hip_k_encode_uastc_blocks(bu_hip_context*, const void* d_pixel_blocks, uint32_t n_blocks, uint32_t flags, void* d_out_uastc_blocks);
 /* Bytes of context workspace that call needs (27 candidate slots x 76 B per block at level 2; 170 at level 4). */
 BU_HIP_API size_t bu_hip_uastc_workspace_bytes(uint32_t n_blocks, uint32_t flags);
+/* ... and what bu_hip_k_uastc_rdo needs for the same blocks cut into total_jobs strips (the two calls share the one workspace; a UASTC pipeline sizes its lanes' for the larger of the two) */
+BU_HIP_API size_t bu_hip_uastc_rdo_workspace_bytes(uint32_t n_blocks, uint32_t total_jobs);
 
 /* a20 (SURVEY.md 8a "next" row f1): basisu::uastc_rdo (encoder/basisu_uastc_enc.h:139, uastc_enc.cpp:4095-4163) in place over n_blocks
  * resident UASTC blocks and the pixel blocks they were encoded from. `params` mirrors uastc_rdo_params (uastc_enc.h:94-134) field for
@@ -329,6 +331,8 @@ BU_HIP_API int bu_hip_uastc_rdo(bu_hip_context*, bu_uastc_block* blocks, const b
  * previous one's hint refit run beside this one's walk. Bytes out = bu_hip_k_encode_uastc_blocks followed (rdo != NULL) by bu_hip_k_uastc_rdo; `flags` as there (callers
  * add cPackUASTCFavorSimplerModes for RDO themselves, as comp.cpp:2016-2018 does).
  *   create : lanes 1..8 (3 fills an MI355X with Kodak-sized batches); max_blocks / max_total_jobs size the workspaces once (they never grow afterwards)
+ *   submit : refuses (0, error text on the context, nothing enqueued, the lane as it was) null pointers, n_blocks 0, RDO parameters bu_hip_k_uastc_rdo refuses, and a
+ *            submission whose workspace (the larger of bu_hip_uastc_workspace_bytes and, with rdo, bu_hip_uastc_rdo_workspace_bytes) exceeds that of create's arguments
  *   submit : d_px (n_blocks x 64 B) must stay valid and d_out (n_blocks x 16 B) unread until the ticket is waited for; inputs may still be in flight on the context's
  *            stream (the lane waits for them on the device). Blocks only when its lane's previous submission has not finished yet.
  *   wait   : ticket 0 = everything submitted so far; out_stats (may be NULL) = {modified, refined, skipped, strips} of that ticket, as bu_hip_k_uastc_rdo reports them */

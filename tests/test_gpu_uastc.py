@@ -39,6 +39,27 @@ def test_ragged_sizes(hip_ctx, golden, n):
     assert got.shape == (n, 16) and (got == golden["level2"][:n]).all()
 
 
+@pytest.mark.parametrize("n", [7 * 1464, 2 * 4096 + 1])
+@pytest.mark.parametrize("level", [0, 2, 3])
+def test_every_block_at_sizes_with_several_ordering_workgroups(hip_ctx, golden, n, level):
+    """The finish kernel takes the blocks in the order a counting sort leaves (k_uastc_order_hist / _scan / _scatter, one workgroup per 4,096 blocks): a block the
+    scatter loses or lists twice is a block nobody writes. The vector blocks tiled 7 times under a fixed permutation (10,248 blocks: three workgroups) and cut to
+    2 * 4096 + 1 (three workgroups, 2,731 blocks each: a range that ends inside the 256-block stride), EVERY block against the vectors, into a buffer that held 0xA5."""
+    src = np.random.default_rng(20).permutation(np.tile(np.arange(1464), 7))[:n]
+    assert (n + 4095) // 4096 == 3
+    d_out = hip_ctx.alloc(n * 16 + 256)
+    try:
+        hip_ctx.memset(d_out, 0xA5, n * 16 + 256)
+        uastc.encode_uastc_blocks(hip_ctx, np.ascontiguousarray(golden["blocks"][src]), level, out_device=d_out)
+        got = hip_ctx.download(d_out, (n + 16, 16), np.uint8)
+    finally:
+        hip_ctx.free(d_out)
+    want = golden[f"level{level}"][src]
+    bad = np.nonzero((got[:n] != want).any(1))[0]
+    assert bad.size == 0, f"{bad.size} of {n} blocks differ, first {bad[:5]}, {int((got[:n] == 0xA5).all(1).sum())} never written"
+    assert (got[n:] == 0xA5).all()
+
+
 def test_blocking_host_pointer_entry(hip_ctx, golden):
     """Section-1 style entry: tiles set once with bu_hip_set_pixel_blocks, host output pointer, blocking."""
     blocks = np.ascontiguousarray(golden["blocks"])
