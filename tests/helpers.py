@@ -441,6 +441,17 @@ def host_uastc_rdo(packed, blocks, flags, total_jobs=0, table_trials=False, **kw
     return out
 
 
+def host_uastc_rdo_counted(packed, blocks, flags, total_jobs=0, table_trials=False, **kw):
+    """host_uastc_rdo plus {"modified", "refined", "skipped"}, counted where the kernels count them (bu_hip_k_uastc_rdo's out_stats)."""
+    fp, up = rdo_param_arrays(**kw)
+    total_jobs |= 0x80000000 if table_trials else 0
+    out = np.ascontiguousarray(packed).copy()
+    blocks = np.ascontiguousarray(blocks)
+    counts = np.zeros(3, np.uint32)
+    assert uastc_host().hc_uastc_rdo_counted(ptr(out), ptr(blocks), out.shape[0], ptr(fp, f32p), ptr(up, u32p), flags, total_jobs, ptr(counts, u32p)) == 1
+    return out, dict(modified=int(counts[0]), refined=int(counts[1]), skipped=int(counts[2]))
+
+
 def uastc_host():
     """The UASTC device core compiled for the host (tests/native/uastc_host.cpp): a checker for the CPU-only suite."""
     return native_libs.load("uastc_host")

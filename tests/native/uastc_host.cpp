@@ -39,7 +39,11 @@ HOST_API void hc_encode_uastc(const uint8_t* blocks, uint32_t n, uint32_t flags,
 // uastc_rdo (uastc_enc.cpp:3824-4163) as a scalar loop over the shared per-block pieces of uastc_rdo.h: the order-defining part of the
 // GPU strips kernel (history of selector fields, window scan newest-first, strict "<" on the cost) restated the plain way.
 static bool g_table_trials = false;  // score trials from the per-block error table (what the GPU strips kernel does) instead of decoding them
-static bool rdo_strip(uint32_t first, uint32_t last, uint8_t* blocks, const uint8_t* pixels, const rdo_params& p, uint32_t flags) {
+// counts (may be null): [0] walks that replaced a block's selectors, [1] refits that changed a block, [2] blocks rdo_prepare says to skip: what k_rdo_strips,
+// settle_window and k_rdo_finish count on the device
+static bool rdo_strip(uint32_t first, uint32_t last, uint8_t* blocks, const uint8_t* pixels, const rdo_params& p, uint32_t flags, uint32_t* counts = nullptr) {
+    uint32_t none[3] = { 0, 0, 0 };
+    if (!counts) counts = none;
     enc_cfg e;
     make_cfg(flags, e);
     const int window = (int)(p.lz_dict_size / 16 > 1 ? p.lz_dict_size / 16 : 1);
@@ -58,12 +62,13 @@ static bool rdo_strip(uint32_t first, uint32_t last, uint8_t* blocks, const uint
                 if (state[j - first] == 1) {
                     bool refined;
                     if (!rdo_refit_block((const rgba8*)(pixels + (size_t)j * 64), p, blocks + (size_t)j * 16, refined)) return false;
+                    counts[1] += refined ? 1u : 0u;
                     state[j - first] = 2;
                 }
         }
         const uint32_t fsb = ku_sel_first[info.mode], len = ku_sel_len[info.mode], len_lo = len < 64 ? len : 64;
         const uint64_t cur_lo = block_bits(blk, fsb, len_lo);
-        if (info.skip) { history[{ fsb, cur_lo }] = i; continue; }
+        if (info.skip) { counts[2]++; history[{ fsb, cur_lo }] = i; continue; }
         int cur_bits;
         auto it = history.find({ fsb, cur_lo });
         if (it == history.end()) cur_bits = (int)((len * p.lz_literal_cost) / 100);
@@ -103,12 +108,14 @@ static bool rdo_strip(uint32_t first, uint32_t last, uint8_t* blocks, const uint
         }
         uint64_t final_lo = cur_lo;
         if (best_j >= 0) {
+            counts[0]++;
             if (g_table_trials) {  // the GPU schedule: raw trial bits now, refit + hints later (uastc_rdo.h, "Deferred form")
                 put_field(blk, fsb, len, best_lo, best_hi);
                 state[i - first] = (p.endpoint_refinement && info.mode == 0) ? 1 : 2;
             } else {
                 bool refined;
                 rdo_write_back(cur, best_lo, best_hi, px, p, blk, refined);
+                counts[1] += refined ? 1u : 0u;
                 if (!rdo_rehint(px, e, blk)) return false;
             }
             final_lo = block_bits(blk, fsb, len_lo);
@@ -119,13 +126,17 @@ static bool rdo_strip(uint32_t first, uint32_t last, uint8_t* blocks, const uint
         if (!state[i - first]) continue;
         const rgba8* px = (const rgba8*)(pixels + (size_t)i * 64);
         bool refined;
-        if (state[i - first] == 1 && !rdo_refit_block(px, p, blocks + (size_t)i * 16, refined)) return false;
+        if (state[i - first] == 1) {
+            if (!rdo_refit_block(px, p, blocks + (size_t)i * 16, refined)) return false;
+            counts[1] += refined ? 1u : 0u;
+        }
         if (!rdo_rehint(px, e, blocks + (size_t)i * 16)) return false;
     }
     return true;
 }
 
-HOST_API int hc_uastc_rdo(uint8_t* blocks, const uint8_t* pixels, uint32_t n, const float* fp, const uint32_t* up, uint32_t flags, uint32_t total_jobs) {
+// hc_uastc_rdo plus the three counters of bu_hip_k_uastc_rdo's out_stats: modified, refined, skipped (summed over the strips)
+HOST_API int hc_uastc_rdo_counted(uint8_t* blocks, const uint8_t* pixels, uint32_t n, const float* fp, const uint32_t* up, uint32_t flags, uint32_t total_jobs, uint32_t* counts3) {
     g_table_trials = (total_jobs >> 31) != 0;  // test switch in the top bit
     total_jobs &= 0x7FFFFFFFu;
     rdo_params p;
@@ -133,10 +144,15 @@ HOST_API int hc_uastc_rdo(uint8_t* blocks, const uint8_t* pixels, uint32_t n, co
     p.smooth_block_max_error_scale = fp[4];
     p.lz_dict_size = up[0]; p.lz_literal_cost = up[1]; p.endpoint_refinement = up[2];
     const uint32_t per_job = total_jobs ? n / total_jobs : 0;
-    if (total_jobs <= 1 || per_job <= 8) return rdo_strip(0, n, blocks, pixels, p, flags) ? 1 : 0;
+    counts3[0] = counts3[1] = counts3[2] = 0;
+    if (total_jobs <= 1 || per_job <= 8) return rdo_strip(0, n, blocks, pixels, p, flags, counts3) ? 1 : 0;
     for (uint32_t f = 0; f < n; f += per_job)
-        if (!rdo_strip(f, f + per_job < n ? f + per_job : n, blocks, pixels, p, flags)) return 0;
+        if (!rdo_strip(f, f + per_job < n ? f + per_job : n, blocks, pixels, p, flags, counts3)) return 0;
     return 1;
+}
+HOST_API int hc_uastc_rdo(uint8_t* blocks, const uint8_t* pixels, uint32_t n, const float* fp, const uint32_t* up, uint32_t flags, uint32_t total_jobs) {
+    uint32_t counts[3];
+    return hc_uastc_rdo_counted(blocks, pixels, n, fp, up, flags, total_jobs, counts);
 }
 
 HOST_API int hc_unpack_block(const uint8_t* blk, uint8_t* out64) {

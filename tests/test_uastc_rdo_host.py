@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import helpers
+import uastc_rdo_cases as K
 from helpers import ptr
 
 GOLDEN = pathlib.Path(__file__).resolve().parent / "golden" / "uastc_rdo_vectors.npz"
@@ -93,3 +94,121 @@ def test_host_rdo_vs_reference_random_params():
             got = helpers.host_uastc_rdo(packed, blocks, level, jobs, table, **kw)
             bad = np.nonzero((got != want).any(1))[0]
             assert bad.size == 0, f"trial {trial} level {level} jobs {jobs} table {table} {kw}: {bad.size} blocks differ, first {bad[:5]}"
+
+
+def test_counters_of_the_golden_cases_are_self_consistent(golden):
+    """hc_uastc_rdo_counted: `modified` counts walks that replaced a block's selectors (a winner may carry the very bits the block had: never fewer than the blocks
+    that changed), `skipped` the blocks rdo_prepare says to leave alone -- a property of the block alone, so the sum over one-block runs -- and both scoring modes
+    count the same, refits included."""
+    alone = {}
+    for name, flags, jobs, kw in helpers.uastc_rdo_cases():
+        packed, blocks = golden[f"packed_l{flags & 7}"], golden["blocks"]
+        got, counts = helpers.host_uastc_rdo_counted(packed, blocks, flags, jobs, True, **kw)
+        assert (got == golden[name]).all()
+        if name in ("default_l2", "norefine_l0", "settle_l0"):   # the decoding form refits at once, the table form later or in front of a sensitive block: same count
+            plain, plain_counts = helpers.host_uastc_rdo_counted(packed, blocks, flags, jobs, False, **kw)
+            assert (plain == got).all() and plain_counts == counts, (name, counts, plain_counts)
+        changed = int((got != packed).any(1).sum())
+        assert counts["modified"] == changed > 0, (name, counts, changed)   # equal in these eight; in general never fewer
+        assert counts["refined"] <= counts["modified"] and (counts["refined"] > 0) == bool(kw.get("refine", 1)), (name, counts)
+        key = (flags & 7, kw.get("skip_rms", helpers.RDO_DEFAULTS["skip_rms"]))
+        if key not in alone:
+            alone[key] = sum(helpers.host_uastc_rdo_counted(packed[i:i + 1], blocks[i:i + 1], flags, 0, True, **kw)[1]["skipped"] for i in range(packed.shape[0]))
+        assert counts["skipped"] == alone[key] > 0, (name, counts, alone[key])
+
+
+def test_window_is_dict_size_over_sixteen_rounded_down(golden):
+    """lz_dict_size 1, 15, 16 and 31 are all a window of one block, 47 is 32: pinned here so that the GPU test of such sizes has a host result that means what it
+    says. 32768 on the golden blocks is the reference's own known answer (bigdict_l1, test_host_rdo_matches_reference_vectors); 32767 gives the same."""
+    packed, blocks = golden["packed_l2"], golden["blocks"]
+    one = helpers.host_uastc_rdo(packed, blocks, 2, 0, True, lam=3.0, dict_size=16)
+    assert (one != packed).any()
+    for size in (1, 15, 31):
+        assert (helpers.host_uastc_rdo(packed, blocks, 2, 0, True, lam=3.0, dict_size=size) == one).all(), size
+    assert (helpers.host_uastc_rdo(packed, blocks, 2, 0, True, lam=3.0, dict_size=32) != one).any()   # two blocks are not one
+    assert (helpers.host_uastc_rdo(packed, blocks, 2, 0, True, lam=3.0, dict_size=47) == helpers.host_uastc_rdo(packed, blocks, 2, 0, True, lam=3.0, dict_size=32)).all()
+    # 32767 -> 2047 blocks, 32768 -> 2048: equal only because the answer at this size almost never depends on the window's last block (what the period cases are for)
+    assert (helpers.host_uastc_rdo(golden["packed_l1"], blocks, 1, 0, True, lam=2.0, dict_size=32767) == golden["bigdict_l1"]).all()
+
+
+def test_period_cases_meet_their_condition():
+    """The inputs of the window-edge tests (uastc_rdo_cases.py) on the host core alone, small periods: the windows P - 1 and P differ in at least 20 blocks, all in the
+    tail, a window of 8 P gives what P gives (where the tail is one period), and with luminance-alpha tiles the strip holds sensitive modes, in the tail too."""
+    for P in (5, 257):
+        for la in (0, 5):
+            tail = K.PERIOD_TAIL[P]
+            packed, blocks = K.rdo_period_case(P, tail, K.PERIOD_SEED, la)
+            (short, _), (exact, counts) = K.period_pair(P, tail, K.PERIOD_SEED, la)
+            K.check_condition(P, packed, short, exact, la)
+            if tail <= P:   # one period only: nothing but the twin is worth looking at
+                wide = helpers.host_uastc_rdo(packed, blocks, 0, 0, True, dict_size=16 * 8 * P, **K.PERIOD_PARAMS)
+                assert (wide == exact).all()
+            if la:
+                assert np.isin(K.modes_of(packed[P:]), K.SENSITIVE_MODES).any()
+
+
+def test_inactive_case_meets_its_condition():
+    packed, blocks, shared = K.inactive_case()
+    n = K.INACTIVE_STRIP
+    assert shared.size >= K.MIN_SHARED_FIELDS
+    assert (K.modes_of(packed[n:2 * n]) == 8).all() and (K.modes_of(packed[2 * n + 1::3]) == 8).all()
+    for jobs in (3, 0):
+        got, counts = helpers.host_uastc_rdo_counted(packed, blocks, 0, jobs, True)
+        assert (got[:2 * n] == packed[:2 * n]).all()   # a strip of skipped blocks, a strip of solid ones: nothing to do
+        assert counts["skipped"] == n + (n + 2) // 3   # every noise tile and every loud one
+        # a quiet block whose selectors the skipped block in front left in the history keeps them (its own cost is a match's, no candidate is strictly cheaper);
+        # without that entry a candidate with the same bits would win and count as a modification
+        assert (got[shared] == packed[shared]).all()
+        assert 0 < counts["modified"] == int((got != packed).any(1).sum()) <= got[2 * n + 2::3].shape[0] - shared.size, counts
+
+
+@pytest.mark.ref
+@pytest.mark.skipif(not helpers.have_ref(), reason="oracle/_ref not built")
+@pytest.mark.parametrize("P,la,refine", [(P, la, refine) for P in K.PERIODS for la in (0, 5) for refine in (1, 0)] + [(2050, 0, 1), (2050, 5, 1)],
+                         ids=lambda v: str(v))
+def test_host_rdo_vs_reference_at_window_edges(P, la, refine):
+    """The host core against the reference where the answer depends on the window's last block: period cases at w = P - 1 and w = P (rings of 4 / 8 and 256 / 512,
+    the largest ring and the first window past it, two windows that slide through HBM), both scoring modes, bit for bit."""
+    tail = K.PERIOD_TAIL[P]
+    packed, blocks = K.rdo_period_case(P, tail, K.PERIOD_SEED, la)
+    pair = K.period_pair(P, tail, K.PERIOD_SEED, la, refine, True)
+    diff = K.check_condition(P, packed, pair[0][0], pair[1][0], la)
+    print(f"P {P} la {la} refine {refine}: windows {P - 1} / {P} differ in {diff.size} of {packed.shape[0]} blocks; counts {pair[0][1]} / {pair[1][1]}")
+    plain = K.period_pair(P, tail, K.PERIOD_SEED, la, refine, False)
+    for k, w in enumerate((P - 1, P)):
+        want = K.ref_period(P, tail, K.PERIOD_SEED, la, refine, w)
+        for table, (got, counts) in ((True, pair[k]), (False, plain[k])):
+            bad = np.nonzero((got != want).any(1))[0]
+            assert bad.size == 0, f"P {P} w {w} table {table}: {bad.size} blocks differ, first {bad[:5]}"
+        assert pair[k][1] == plain[k][1], (w, pair[k][1], plain[k][1])
+
+
+@pytest.mark.ref
+@pytest.mark.skipif(not helpers.have_ref(), reason="oracle/_ref not built")
+@pytest.mark.parametrize("name,kw", K.PARAM_CORNERS, ids=[c[0] for c in K.PARAM_CORNERS])
+def test_host_rdo_vs_reference_parameter_corners(golden, name, kw):
+    packed, blocks = golden["packed_l2"][:K.CORNER_BLOCKS], golden["blocks"][:K.CORNER_BLOCKS]
+    want = helpers.ref_uastc_rdo(packed, blocks, 2, 0, **kw)
+    for table in (False, True):
+        got, counts = helpers.host_uastc_rdo_counted(packed, blocks, 2, 0, table, **kw)
+        bad = np.nonzero((got != want).any(1))[0]
+        assert bad.size == 0, f"{name} table {table}: {bad.size} blocks differ, first {bad[:5]}"
+        print(f"{name} table {table}: {int((want != packed).any(1).sum())} blocks changed, counts {counts}")
+
+
+@pytest.mark.ref
+@pytest.mark.skipif(not helpers.have_ref(), reason="oracle/_ref not built")
+def test_host_rdo_vs_reference_inactive_blocks():
+    packed, blocks, _ = K.inactive_case()
+    for jobs in (3, 0):
+        assert (helpers.ref_uastc_rdo(packed, blocks, 0, jobs) == helpers.host_uastc_rdo(packed, blocks, 0, jobs, True)).all()
+
+
+@pytest.mark.ref
+@pytest.mark.skipif(not helpers.have_ref(), reason="oracle/_ref not built")
+@pytest.mark.parametrize("size", K.DICT_SIZES)
+def test_host_rdo_vs_reference_odd_windows(golden, size):
+    """the host expectations of the GPU test of these dictionary sizes, one strip and three"""
+    packed, blocks = golden["packed_l2"], golden["blocks"]
+    for jobs in (0, 3):
+        assert (helpers.ref_uastc_rdo(packed, blocks, 2, jobs, lam=3.0, dict_size=size) == helpers.host_uastc_rdo(packed, blocks, 2, jobs, True, lam=3.0, dict_size=size)).all(), jobs
