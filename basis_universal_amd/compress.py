@@ -6,8 +6,12 @@ basis_compressor::process, comp.cpp:619-1040) for the two hot paths of this pack
       UASTC : encode_uastc kernels (-> uastc_rdo kernels) -> .basis / .ktx2 (KTX2_SS_NONE: what the reference's library default,
               comp.h:323, and `basisu -ktx2_no_zstandard` write; Zstandard supercompression of the levels is not part of this package)
 
-The result is the file the reference command line tool writes for the same options (tests/test_gpu_backend.py, test_gpu_mipmap.py), given the
-same key-values. No stage has a CPU implementation here: without the HIP libraries and a GPU the context cannot be created."""
+Several source images per call -- texture arrays, cubemaps, video, volumes (`-tex_type`) -- take the same stages per image; all their slices are tiled by ONE launch
+(bu_hip_k_extract_slices) into one tile array and go through one frontend / backend run.
+The result is the file the reference command line tool writes for the same options (tests/test_gpu_backend.py, test_gpu_mipmap.py,
+test_gpu_compress_multi_image.py), given the same key-values. No stage has a CPU implementation here: without the HIP libraries and a GPU the context cannot be created."""
+import struct
+
 import numpy as np
 
 from . import mipmap, source as _source, uastc as _uastc
@@ -48,8 +52,8 @@ def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=
              ktx2=False, srgb=True, key_values=(), max_threads=0, stats=None, stats_hvs=False, stats_bc7=False, stats_ssim=False,
              renormalize=False, swizzle=None, check_for_alpha=True, force_alpha=False, y_flip=False, resample=None,
              mip_filter="kaiser", mip_scale=1.0, mip_wrapping=True, mip_srgb=None, mip_renormalize=False, mip_fast=True, mip_smallest_dimension=1,
-             no_selector_rdo=False, no_endpoint_rdo=False):
-    """image: (h, w, 4) uint8 RGBA. Returns the file as a uint8 array.
+             no_selector_rdo=False, no_endpoint_rdo=False, tex_type="2d", us_per_frame=0, userdata=(0, 0), ktx2_animdata=(1, 15, 0)):
+    """image: (h, w, 4) uint8 RGBA, or a sequence of such arrays (below). Returns the file as a uint8 array.
     ETC1S: quality 1-255 (`-q`), comp_level 0-6 (`-comp_level`). UASTC: uastc_level 0-4, uastc_rdo_lambda (`-uastc_rdo_l`; None = no post-pass, any float
     incl. 0.0 = post-pass on, as m_rdo_uastc_ldr_4x4 + its scalar), uastc_rdo_jobs = the strips of the post-pass (the reference: min(4, pool threads) when
     multithreaded, else 1; comp.cpp:2078). `**unified_quality_effort(...)` gives the settings of `-quality` / `-effort`.
@@ -74,10 +78,28 @@ def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=
       mip_srgb (None = follows srgb; False = `-mip_linear`), mip_renormalize (`-mip_renorm`: every level renormalised after it is made), mip_fast=False (`-mip_slow`:
       every level from level 0 instead of the level above), mip_smallest_dimension (`-mip_smallest`).
     no_selector_rdo / no_endpoint_rdo (ETC1S): the backend's threshold stays 0 (comp.cpp:3536-3540).
-    A bad swizzle, filter name, scale or size raises ValueError before ctx is touched."""
+    A bad swizzle, filter name, scale or size raises ValueError before ctx is touched.
+    Several images in one file (basis_compressor::read_source_images with more than one source, comp.cpp:2773-3044): `image` is a sequence of (h, w, 4) arrays and
+      tex_type (`-tex_type`) says what they are: "2darray" (a layer each), "cubemap" (six consecutive images are the faces of a layer), "video" (frames) or "volume"
+      (`-tex_type 3d`); "2d" takes exactly one image -- the tool compresses several 2D images as separate files, which here is a call each.
+      Every source option above applies to every image and each image gets its own mip chain. The slices go source image outermost, then level, then (ETC1S with
+      alpha) colour and alpha, into one tile array: one codebook pair for the whole file. The file has alpha when ANY prepared image has (or force_alpha): an ETC1S
+      file then carries an alpha slice for every image; a UASTC slice carries its own image's flag. Video: ETC1S runs the frontend and the backend in video mode with
+      the slices of image 0 as i-frames; every UASTC slice is an i-frame.
+      us_per_frame (`-framerate`, as microseconds; .basis header, at most 0xFFFFFF as basisu_file::init clamps it), userdata (`-userdata0`, `-userdata1`; .basis header).
+      ktx2_animdata = (duration, timescale, loop count) (`-ktx2_animdata_*`): a video .ktx2 gains the KTXanimData key/value the tool adds (basisu_tool.cpp:2382-2401),
+      unless key_values already holds that key.
+      stats: one dict per slice in slice order; ETC1S video with stats raises ValueError before any work (the ETC1S reader does not read video files).
+      ValueError before ctx is touched: several images with tex_type "2d", a cubemap whose image count is not a multiple of 6, images of different sizes (after
+      `resample`) in anything but "2d", more slices than BASISU_MAX_SLICES, an empty sequence.
+    A single array with tex_type "2d" and these four at their defaults takes the single-image path: its launches and bytes are what they were without them."""
+    opts = {k: v for k, v in locals().items() if k not in ("ctx", "image")}   # every keyword as given, for the several-images path
     if stats_bc7 and not uastc:
         from .stats import BC7_REFUSAL
         raise ValueError(BC7_REFUSAL)
+    several = isinstance(image, (list, tuple)) and (not len(image) or np.ndim(image[0]) == 3) or (isinstance(image, np.ndarray) and image.ndim == 4)
+    if several or tex_type != "2d" or us_per_frame or tuple(userdata) != (0, 0) or tuple(ktx2_animdata) != (1, 15, 0):
+        return _compress_images(ctx, list(image) if several else [image], **opts)
     img = np.ascontiguousarray(image, np.uint8)
     if img.ndim != 3 or img.shape[2] != 4:
         raise ValueError("image must be (h, w, 4) uint8")
@@ -144,44 +166,169 @@ def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=
                 slice_blocks.append(nbx * nby)
                 first += nbx * nby
 
-        def finish(data):   # m_compute_stats (comp.cpp:4195-4253) while the sources are still resident
-            if stats is not None:
-                from . import stats as _stats
-                stats.extend(_stats._stats_from_slices(ctx, bytes(data), lambda level, layer, face, n_slices: level_planes[level], hvs=stats_hvs, bc7=stats_bc7, ssim=stats_ssim))
-            return data
-        # ---- encode
-        if uastc:
-            rdo = uastc_rdo_lambda is not None and uastc_rdo_lambda is not False
-            flags = int(uastc_level) | (_uastc.FAVOR_SIMPLER_MODES if rdo else 0)       # comp.cpp:2016-2018
-            d_out = ctx.alloc(total_blocks * 16)
-            owned.append(d_out)
-            _uastc.encode_uastc_blocks(ctx, d_all, flags, n_blocks=total_blocks, out_device=d_out)
-            if rdo:
-                at = 0
-                for n in slice_blocks:   # the post-pass runs per slice (comp.cpp:2066-2082)
-                    _uastc.uastc_rdo(ctx, d_out + at * 16, d_all + at * 64, _uastc.RdoParams(m_lambda=float(uastc_rdo_lambda)), int(uastc_level), uastc_rdo_jobs, n_blocks=n)
-                    at += n
-            packed = ctx.download(d_out, (total_blocks, 16), np.uint8)
-            if ktx2:
-                return finish(uastc_ktx2_file(packed, slices, srgb=srgb, has_alpha=has_alpha, key_values=key_values))
-            # encode_slices_to_uastc_4x4_ldr (comp.cpp:1973-1985) never sets basisu_backend_output::m_srgb, which basisu_backend_output::clear() leaves true
-            # (backend.h:243): the reference's UASTC .basis files carry the sRGB header flag whatever -linear says (the .ktx2 DFD does follow the option)
-            return finish(uastc_basis_file(packed, slices, srgb=True, y_flipped=bool(y_flip), key_values=key_values))
-        max_ep, max_sel = quality_to_clusters(quality, total_blocks)
-        fe = Etc1sFrontend(ctx, max_threads=max_threads)
+        return _encode(ctx, owned, d_all, slices, slice_blocks, total_blocks, has_alpha, lambda level, layer, face, n_slices: level_planes[level], uastc=uastc, quality=quality,
+                       comp_level=comp_level, uastc_level=uastc_level, uastc_rdo_lambda=uastc_rdo_lambda, uastc_rdo_jobs=uastc_rdo_jobs, ktx2=ktx2, srgb=srgb,
+                       key_values=key_values, max_threads=max_threads, stats=stats, stats_hvs=stats_hvs, stats_bc7=stats_bc7, stats_ssim=stats_ssim, y_flip=y_flip,
+                       no_selector_rdo=no_selector_rdo, no_endpoint_rdo=no_endpoint_rdo)
+    finally:
+        for d in owned:
+            ctx.free(d)
+
+
+VIDEO_STATS_REFUSAL = ("stats of an ETC1S video file: video files are not supported: a P-frame's blocks may repeat the previous frame's indices, which this reader "
+                       "does not keep (csrc/host/etc1s_decode.cpp)")
+
+
+def _encode(ctx, owned, d_all, slices, slice_blocks, total_blocks, has_alpha, slice_sources, *, uastc, quality, comp_level, uastc_level, uastc_rdo_lambda, uastc_rdo_jobs,
+            ktx2, srgb, key_values, max_threads, stats, stats_hvs, stats_bc7, stats_ssim, y_flip, no_selector_rdo, no_endpoint_rdo, tex_type=0, us_per_frame=0,
+            userdata=(0, 0)):
+    """resident tiles of every slice -> the file. slice_sources(level, layer, face, n_slices): the resident source of every slice of that image, for the stats stage."""
+    video = tex_type == 3
+    ud0, ud1 = (int(v) for v in userdata)
+
+    def finish(data):   # m_compute_stats (comp.cpp:4195-4253) while the sources are still resident
+        if stats is not None:
+            from . import stats as _stats
+            stats.extend(_stats._stats_from_slices(ctx, bytes(data), slice_sources, hvs=stats_hvs, bc7=stats_bc7, ssim=stats_ssim))
+        return data
+    if uastc:
+        rdo = uastc_rdo_lambda is not None and uastc_rdo_lambda is not False
+        flags = int(uastc_level) | (_uastc.FAVOR_SIMPLER_MODES if rdo else 0)       # comp.cpp:2016-2018
+        d_out = ctx.alloc(total_blocks * 16)
+        owned.append(d_out)
+        _uastc.encode_uastc_blocks(ctx, d_all, flags, n_blocks=total_blocks, out_device=d_out)
+        if rdo:
+            at = 0
+            for n in slice_blocks:   # the post-pass runs per slice (comp.cpp:2066-2082)
+                _uastc.uastc_rdo(ctx, d_out + at * 16, d_all + at * 64, _uastc.RdoParams(m_lambda=float(uastc_rdo_lambda)), int(uastc_level), uastc_rdo_jobs, n_blocks=n)
+                at += n
+        packed = ctx.download(d_out, (total_blocks, 16), np.uint8)
+        if ktx2:
+            return finish(uastc_ktx2_file(packed, slices, srgb=srgb, tex_type=tex_type, has_alpha=has_alpha, key_values=key_values))
+        # encode_slices_to_uastc_4x4_ldr (comp.cpp:1973-1985) never sets basisu_backend_output::m_srgb, which basisu_backend_output::clear() leaves true
+        # (backend.h:243): the reference's UASTC .basis files carry the sRGB header flag whatever -linear says (the .ktx2 DFD does follow the option)
+        return finish(uastc_basis_file(packed, slices, srgb=True, tex_type=tex_type, userdata0=ud0, userdata1=ud1, y_flipped=bool(y_flip), us_per_frame=int(us_per_frame),
+                                       key_values=key_values))
+    max_ep, max_sel = quality_to_clusters(quality, total_blocks)
+    fe = Etc1sFrontend(ctx, max_threads=max_threads, video=video)
+    try:
+        fe.init(d_all, max_ep, max_sel, comp_level, srgb, n_blocks=total_blocks)
+        fe.compress()
+        ept, selt = default_params(quality, comp_level)
+        ept, selt = (0.0 if no_endpoint_rdo else ept), (0.0 if no_selector_rdo else selt)   # comp.cpp:3536-3540
+        be = Etc1sBackend.from_frontend(fe, slices, ept, selt, comp_level, video=video)
         try:
-            fe.init(d_all, max_ep, max_sel, comp_level, srgb, n_blocks=total_blocks)
-            fe.compress()
-            ept, selt = default_params(quality, comp_level)
-            ept, selt = (0.0 if no_endpoint_rdo else ept), (0.0 if no_selector_rdo else selt)   # comp.cpp:3536-3540
-            be = Etc1sBackend.from_frontend(fe, slices, ept, selt, comp_level)
-            try:
-                be.encode()
-                return finish(be.ktx2_file(has_alpha=has_alpha, key_values=key_values) if ktx2 else be.basis_file(y_flipped=bool(y_flip), key_values=key_values))
-            finally:
-                be.close()
+            be.encode()
+            if ktx2:
+                return finish(be.ktx2_file(tex_type=tex_type, has_alpha=has_alpha, key_values=key_values))
+            return finish(be.basis_file(tex_type=tex_type, userdata0=ud0, userdata1=ud1, y_flipped=bool(y_flip), us_per_frame=int(us_per_frame), key_values=key_values))
         finally:
-            fe.close()
+            be.close()
+    finally:
+        fe.close()
+
+
+def _compress_images(ctx, images, *, uastc, quality, comp_level, uastc_level, uastc_rdo_lambda, uastc_rdo_jobs, mipmaps, ktx2, srgb, key_values, max_threads, stats, stats_hvs,
+                     stats_bc7, stats_ssim, renormalize, swizzle, check_for_alpha, force_alpha, y_flip, resample, mip_filter, mip_scale, mip_wrapping, mip_srgb, mip_renormalize,
+                     mip_fast, mip_smallest_dimension, no_selector_rdo, no_endpoint_rdo, tex_type, us_per_frame, userdata, ktx2_animdata):
+    """compress() for a sequence of source images (and for one image with a texture type or header fields of its own): every check first, then per image the
+    single-image stages, then every slice of the call tiled by one launch."""
+    # ---- everything that can be refused, before ctx is touched
+    imgs = []
+    for k, image in enumerate(images):
+        img = np.ascontiguousarray(image, np.uint8)
+        if img.ndim != 3 or img.shape[2] != 4:
+            raise ValueError(f"image {k} must be (h, w, 4) uint8")
+        h, w = img.shape[:2]
+        if not w or not h or w > _source.MAX_DIMENSION or h > _source.MAX_DIMENSION:
+            raise ValueError(f"image {k} of {w} x {h} pixels: 1..{_source.MAX_DIMENSION} each way")
+        imgs.append(img)
+    prepare = not _source.is_identity(renormalize, swizzle, check_for_alpha, force_alpha, y_flip)   # parses the swizzle: ValueError
+    _source.check_mip_options(mip_filter, mip_scale, mip_smallest_dimension)
+    new_sizes = [_source.resampled_size(img.shape[1], img.shape[0], resample) for img in imgs]
+    sizes = [new or (img.shape[1], img.shape[0]) for new, img in zip(new_sizes, imgs)]
+    type_index = _source.check_texture_type(tex_type, sizes)
+    video = tex_type == "video"
+    if video and not uastc and stats is not None:
+        raise ValueError(VIDEO_STATS_REFUSAL)
+    if len(tuple(userdata)) != 2 or len(tuple(ktx2_animdata)) != 3 or any(not 0 <= int(v) < 2 ** 32 for v in (*userdata, *ktx2_animdata, us_per_frame)):
+        raise ValueError("userdata is two, ktx2_animdata three and us_per_frame one unsigned 32-bit value")
+    level_sizes = [[size] + (mipmap.level_sizes(size[0], size[1], int(mip_smallest_dimension)) if mipmaps else []) for size in sizes]
+    host_alpha = [bool((img[..., 3] != 255).any()) for img in imgs] if not prepare else None      # image::has_alpha of an image that is not prepared
+    # the alpha slices double the count; where only the device can say whether there are any (the prepare kernel's flag), the count is checked again below
+    alpha_known = bool(force_alpha) or (host_alpha is not None and any(host_alpha))
+    _source.check_slice_count(len(imgs), len(level_sizes[0]), not uastc and alpha_known)
+    if video and ktx2 and not any(k == "KTXanimData" for k, _ in key_values):   # basisu_tool.cpp:2382-2401: three little-endian 32-bit words
+        key_values = list(key_values) + [("KTXanimData", struct.pack("<III", *(int(v) for v in ktx2_animdata)))]
+    mip_srgb = srgb if mip_srgb is None else mip_srgb
+    owned = []
+    try:
+        # ---- every source image, resident and prepared; m_any_source_image_has_alpha over all of them
+        level0, image_alpha, has_alpha = [], [], False
+        for k, img in enumerate(imgs):
+            h, w = img.shape[:2]
+            d_src = ctx.upload(img)
+            owned.append(d_src)
+            d_level0 = d_src
+            if prepare:
+                if y_flip:                                                # the flip reads another row than it writes: not in place
+                    d_level0 = ctx.alloc(w * h * 4)
+                    owned.append(d_level0)
+                one_has, one_any = _source.prepare_resident(ctx, d_src, w, h, d_level0, renormalize=renormalize, swizzle=swizzle, check_for_alpha=check_for_alpha,
+                                                            force_alpha=force_alpha, y_flip=y_flip)
+            else:
+                one_has = one_any = host_alpha[k]
+            if new_sizes[k] is not None:
+                d_level0 = _source.resample_resident(ctx, d_level0, w, h, new_sizes[k][0], new_sizes[k][1], srgb)
+                owned.append(d_level0)
+            level0.append(d_level0)
+            image_alpha.append(one_any)
+            has_alpha = has_alpha or one_has
+        split_alpha = has_alpha and not uastc
+        _source.check_slice_count(len(imgs), len(level_sizes[0]), split_alpha)
+        # ---- each image's own mip chain, resident (generate_mipmaps with m_any_source_image_has_alpha: four components for every image when any has alpha)
+        rasters = []
+        for d_level0, levels in zip(level0, level_sizes):
+            chain = [d_level0]
+            for lw, lh in levels[1:]:
+                d = ctx.alloc(lw * lh * 4)
+                owned.append(d)
+                at = len(chain) - 1 if mip_fast else 0
+                sw, sh = levels[at]
+                ctx.check(mipmap._lib().bu_generate_mipmap_level(ctx.h, chain[at], sw, sh, d, lw, lh, int(bool(mip_srgb)), mip_filter.encode(), float(mip_scale),
+                                                                 int(bool(mip_wrapping)), 4 if has_alpha else 3), "bu_generate_mipmap_level")
+                if mip_renormalize:
+                    _source.renormalize_resident(ctx, d, lw, lh)
+                chain.append(d)
+            rasters.append(chain)
+        # ---- the slices, and their tiles by one launch
+        slices, sources = _source.slice_table(level_sizes, uastc=uastc, any_alpha=has_alpha, image_alpha=image_alpha, video=video)
+        slice_blocks = [s[1] * s[2] for s in slices]
+        total_blocks = sum(slice_blocks)
+        d_all = ctx.alloc(total_blocks * 64)   # one contiguous tile array: every image, level and alpha slice shares the codebooks
+        owned.append(d_all)
+        planes = {}                            # (level, layer, face) -> the resident source of each of its slices, for the stats stage
+        if stats is not None:
+            for k, (chain, levels) in enumerate(zip(rasters, level_sizes)):
+                for level, (d_raster, (lw, lh)) in enumerate(zip(chain, levels)):
+                    one = [d_raster]
+                    if split_alpha:            # the stats stage reads planes: (r, g, b, 255) in the level's own buffer -- every level is made already -- and (a, a, a, 255) beside it
+                        one.append(ctx.alloc(lw * lh * 4))
+                        owned.append(one[1])
+                        _source.split_alpha_resident(ctx, d_raster, lw, lh, one[0], one[1])
+                    planes[(level, *_source.image_layer_face(tex_type, k))] = [(d, lw, lh, lw) for d in one]
+        entries = []
+        for s, (k, level, mode) in zip(slices, sources):
+            if stats is not None and split_alpha:
+                d_raster, mode = planes[(level, *_source.image_layer_face(tex_type, k))][mode == _source.SLICE_ALPHA][0], _source.SLICE_AS_IS
+            else:
+                d_raster = rasters[k][level]
+            entries.append((d_raster, s[3], s[4], 0, mode, s[0]))
+        _source.extract_slices_resident(ctx, entries, d_all)
+        return _encode(ctx, owned, d_all, slices, slice_blocks, total_blocks, has_alpha, lambda level, layer, face, n_slices: planes[(level, layer, face)], uastc=uastc,
+                       quality=quality, comp_level=comp_level, uastc_level=uastc_level, uastc_rdo_lambda=uastc_rdo_lambda, uastc_rdo_jobs=uastc_rdo_jobs, ktx2=ktx2, srgb=srgb,
+                       key_values=key_values, max_threads=max_threads, stats=stats, stats_hvs=stats_hvs, stats_bc7=stats_bc7, stats_ssim=stats_ssim, y_flip=y_flip,
+                       no_selector_rdo=no_selector_rdo, no_endpoint_rdo=no_endpoint_rdo, tex_type=type_index, us_per_frame=us_per_frame, userdata=userdata)
     finally:
         for d in owned:
             ctx.free(d)

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <vector>
+#include "../../include/basisu_hip.h"   // bu_hip_slice_source
 
 namespace bu {
 
@@ -67,5 +68,7 @@ hipError_t launch_find_optimal_selector_clusters(hipStream_t st, const void* d_p
                                                  uint32_t* d_scratch_idx, uint32_t* d_out_idx, uint32_t* d_cand_words /* scratch for the candidates' selector words, or NULL */, size_t cand_words_capacity /* entries */);
 
 hipError_t launch_extract_blocks(hipStream_t st, const void* d_rgba, uint32_t width, uint32_t height, uint32_t pitch_bytes, void* d_out_blocks);
+// every slice of a call in one launch: d_slices = n_slices records, d_prefix = n_slices + 1 ascending tile counts (the last = total_tiles <= 2^30); both resident
+hipError_t launch_extract_slices(hipStream_t st, const bu_hip_slice_source* d_slices, const uint32_t* d_prefix, uint32_t n_slices, uint32_t total_tiles, void* d_out_blocks);
 
 } // namespace bu

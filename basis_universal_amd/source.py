@@ -1,7 +1,10 @@
 """The compressor's source-image options on the device: what basis_compressor::read_source_images (encoder/basisu_comp.cpp:2569-2697) does to a source image before the
 first block is cut -- `basisu -renorm`, `-swizzle` / `-separate_rg_to_color_alpha`, `-force_alpha` / `-no_alpha`, `-y_flip` in one pass of source_prep_kernels.hip
 (the per-pixel rules: csrc/source_prep.h), then `-resample` / `-resample_factor` through the mip generator's resampler -- and the argument checks compress() shares.
+For several source images per call (texture arrays, cubemaps, video, volumes): the texture-type rules of basis_compressor::validate_texture_type_constraints, the
+slice table of read_source_images (both pure functions), and the one-launch tiling of every slice (bu_hip_k_extract_slices).
 Nothing here has a CPU implementation."""
+import ctypes
 import math
 
 import numpy as np
@@ -10,6 +13,9 @@ MIP_FILTERS = ("box", "tent", "bell", "mitchell", "blackman", "lanczos3", "lancz
 IDENTITY_SWIZZLE = 0x03020100
 MAX_DIMENSION = 16384          # basist::BASISU_MAX_SUPPORTED_TEXTURE_DIMENSION
 _LETTERS = {"r": 0, "g": 1, "b": 2, "a": 3, "0": 0, "1": 1, "2": 2, "3": 3}
+TEX_TYPES = {"2d": 0, "2darray": 1, "cubemap": 2, "video": 3, "volume": 4}   # basist::basis_texture_type; the tool's -tex_type 2d|2darray|cubemap|video|3d
+MAX_SLICES = 0xFFFFFF          # BASISU_MAX_SLICES (comp.h:67)
+SLICE_AS_IS, SLICE_RGB, SLICE_ALPHA = 0, 1, 2   # BU_HIP_SLICE_*: the pixels as they are, (r, g, b, 255), (a, a, a, 255)
 
 
 def normal_map_options():
@@ -144,3 +150,75 @@ def prepare_source(ctx, image_or_device, width=None, height=None, *, renormalize
 
 def packed_entries(packed):
     return [(packed >> (8 * i)) & 255 for i in range(4)]
+
+
+# ---- several source images per call
+
+def check_texture_type(tex_type, sizes):
+    """validate_texture_type_constraints (comp.cpp:3143-3200) and what comes before it, on the images' (width, height) alone. -> the basis_texture_type number."""
+    if tex_type not in TEX_TYPES:
+        raise ValueError(f"tex_type {tex_type!r} is not one of {', '.join(TEX_TYPES)}")
+    if not sizes:
+        raise ValueError("no source images: the sequence is empty")
+    if tex_type == "2d":
+        if len(sizes) > 1:
+            raise ValueError(f"{len(sizes)} source images with tex_type '2d': the reference tool compresses those as separate files, one call each; for one file of "
+                             "several images pass tex_type '2darray', 'cubemap', 'video' or 'volume'")
+        return 0
+    if tex_type == "cubemap" and len(sizes) % 6:
+        raise ValueError(f"a cubemap of {len(sizes)} images: for cubemaps the total number of input images must be a multiple of 6")
+    if any(size != sizes[0] for size in sizes):
+        k = next(i for i, size in enumerate(sizes) if size != sizes[0])
+        raise ValueError(f"the source image resolutions are not all equal (image 0 is {sizes[0][0]} x {sizes[0][1]}, image {k} is {sizes[k][0]} x {sizes[k][1]}): "
+                         f"the images of a {tex_type} must all have one size")
+    return TEX_TYPES[tex_type]
+
+
+def check_slice_count(n_images, n_levels, split_alpha):
+    n = n_images * n_levels * (2 if split_alpha else 1)
+    if n > MAX_SLICES:
+        raise ValueError(f"{n} slices ({n_images} images x {n_levels} levels{' x colour and alpha' if split_alpha else ''}): too many slices, "
+                         f"BASISU_MAX_SLICES is {MAX_SLICES}")
+    return n
+
+
+def image_layer_face(tex_type, image):
+    """where a source image lies in the file: cubemap faces are six consecutive images of a layer, everything else is a layer per image"""
+    return (image // 6, image % 6) if tex_type in ("cubemap", 2) else (image, 0)
+
+
+def slice_table(level_sizes, *, uastc, any_alpha, image_alpha=None, video=False):
+    """The slices basis_compressor::read_source_images makes (comp.cpp:2773-3044), in its order: source image outermost, then level, then -- ETC1S with
+    m_any_source_image_has_alpha -- the colour and the alpha slice.
+    level_sizes: per source image the (width, height) of its levels; any_alpha: m_any_source_image_has_alpha; image_alpha: per image whether its raster has an alpha
+    value below 255 (UASTC: the slice's own flag, image::has_alpha of the slice; without any_alpha no slice has one).
+    -> (slices, sources): slices[i] = (first_block, num_blocks_x, num_blocks_y, width, height, image, level, alpha, iframe) as backend.slice_descs takes them;
+    sources[i] = (image, level, mode) with mode one of SLICE_AS_IS / SLICE_RGB / SLICE_ALPHA: what the slice's tiles are cut from.
+    video: ETC1S -- the slices of image 0 are i-frames; UASTC -- every slice is (comp.cpp:3016-3030)."""
+    slices, sources, first = [], [], 0
+    for image, levels in enumerate(level_sizes):
+        for level, (w, h) in enumerate(levels):
+            nbx, nby = (w + 3) // 4, (h + 3) // 4
+            if uastc:
+                parts = [(SLICE_AS_IS, int(bool(any_alpha and image_alpha is not None and image_alpha[image])))]
+            else:
+                parts = [(SLICE_RGB, 0), (SLICE_ALPHA, 1)] if any_alpha else [(SLICE_AS_IS, 0)]
+            for mode, alpha in parts:
+                iframe = int(bool(video) and (bool(uastc) or image == 0))
+                slices.append((first, nbx, nby, w, h, image, level, alpha, iframe))
+                sources.append((image, level, mode))
+                first += nbx * nby
+    return slices, sources
+
+
+class SliceSource(ctypes.Structure):   # = bu_hip_slice_source, include/basisu_hip.h
+    _fields_ = [("d_raster", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("pitch_bytes", ctypes.c_uint32), ("mode", ctypes.c_uint32),
+                ("first_block", ctypes.c_uint64)]
+
+
+def extract_slices_resident(ctx, entries, d_out_blocks):
+    """bu_hip_k_extract_slices: entries = [(d_raster, width, height, pitch_bytes or 0, mode, first_block)], every slice of the call tiled in ONE launch; no synchronisation"""
+    arr = (SliceSource * max(len(entries), 1))()
+    for i, (d, w, h, pitch, mode, first) in enumerate(entries):
+        arr[i] = SliceSource(d, w, h, pitch or w * 4, mode, first)
+    ctx.check(ctx.lib.k_extract_slices(ctx.h, arr, len(entries), ctypes.c_void_p(d_out_blocks)), "k_extract_slices")

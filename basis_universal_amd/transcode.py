@@ -163,11 +163,11 @@ def _read_basis(data):
         at = descs_ofs + _BASIS_SLICE * i
         image, level, sflags = int.from_bytes(data[at:at + 3], "little"), data[at + 3], data[at + 4]
         ow, oh, nbx, nby, ofs, size, _crc = struct.unpack_from("<HHHHIIH", data, at + 5)
-        if sflags & 1:
-            raise ValueError("an alpha slice in a UASTC .basis file")
         if image >= total_images or not ow or not oh or nbx != (ow + 3) // 4 or nby != (oh + 3) // 4 or size != nbx * nby * 16:
             raise ValueError(f"slice {i}: inconsistent descriptor")
-        images.append(_image(level, image // faces, image % faces, ow, oh, ofs, f"slice {i}", data))
+        # cSliceDescFlagsHasAlpha (bit 0) on a UASTC slice says that ITS image has alpha (comp.cpp:2928-2933: one face of a cubemap, one frame of a video); the
+        # blocks are the same 16 bytes either way. Bit 1 marks an i-frame, which every UASTC video slice is.
+        images.append(dict(_image(level, image // faces, image % faces, ow, oh, ofs, f"slice {i}", data), has_alpha=bool(sflags & 1)))
     return {"container": "basis", "format": "UASTC_LDR_4x4", "width": images[0]["width"], "height": images[0]["height"], "has_alpha": bool(flags & 4),
             "levels": sorted({im["level"] for im in images}), "layers": total_images // faces, "faces": faces, "images": images}
 

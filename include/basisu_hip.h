@@ -193,6 +193,25 @@ BU_HIP_API const void* bu_hip_get_pixel_blocks_device(const bu_hip_context*, siz
  * image::extract_block_clamped. The result can be adopted with bu_hip_set_pixel_blocks_device. */
 BU_HIP_API int bu_hip_k_extract_blocks(bu_hip_context*, const void* d_rgba, uint32_t width, uint32_t height, uint32_t pitch_bytes, void* d_out_pixel_blocks);
 
+/* The same for EVERY slice of a call in one launch: what a multi-image call (array layers, cubemap faces, video frames, each with its levels, for ETC1S with alpha a
+ * colour and an alpha slice per level) would otherwise pay a launch per slice for. `slices` is a HOST array of n records; slice i's ceil(w/4)*ceil(h/4) tiles are
+ * written in block-raster order from tile first_block on (64 bytes per tile, counted from d_out_pixel_blocks), edges clamped exactly as bu_hip_k_extract_blocks
+ * clamps them. mode: BU_HIP_SLICE_AS_IS the pixels as they are; BU_HIP_SLICE_RGB (r, g, b, 255); BU_HIP_SLICE_ALPHA (a, a, a, 255) -- the two ETC1S slices of a
+ * level with alpha (comp.cpp:2883-2903) straight from the RGBA raster, so no split plane is needed. The records and the table of the slices' tile counts go up in
+ * one stream-ordered copy; `slices` may be released on return. One launch on the context's stream, no synchronisation.
+ * Fails -- nothing copied, nothing launched, nothing written, the reason by name in bu_hip_last_error -- on n == 0, a null pointer, an output that is not 16-byte
+ * aligned, a slice of zero size, a pitch below 4 * width, an unknown mode, a first_block that is not at or beyond the end of the slice before it (the ranges must
+ * ascend and may not overlap; gaps are left untouched), or more than 2^30 tiles in all. */
+enum { BU_HIP_SLICE_AS_IS = 0, BU_HIP_SLICE_RGB = 1, BU_HIP_SLICE_ALPHA = 2 };
+typedef struct bu_hip_slice_source {
+    const void* d_raster;        /* resident RGBA8 raster */
+    uint32_t width, height;      /* pixels */
+    uint32_t pitch_bytes;        /* >= 4 * width */
+    uint32_t mode;               /* BU_HIP_SLICE_* */
+    uint64_t first_block;        /* index of the slice's first tile in d_out_pixel_blocks */
+} bu_hip_slice_source;
+BU_HIP_API int bu_hip_k_extract_slices(bu_hip_context*, const bu_hip_slice_source* slices, uint32_t n, void* d_out_pixel_blocks);
+
 /* The compressor's source-image options (basis_compressor::read_source_images, comp.cpp:2569-2640) over resident RGBA8 rasters: 4-byte aligned, row pitches in
  * bytes (>= 4 * width, multiples of 4), 1..16384 pixels each way. Per pixel, in the reference's order (csrc/source_prep.h): image::renormalize_normal_map when
  * `renormalize`; the swizzle, one source-channel index 0..3 per byte (s0 | s1 << 8 | s2 << 16 | s3 << 24; 0x03020100 = none, 0x01000000 = the tool's
