@@ -1,13 +1,13 @@
 """One call from an image to a file: the C-style entry of the reference (`basis_compress`, encoder/basisu_comp.cpp:5561-5900 ->
 basis_compressor::process, comp.cpp:619-1040) for the two hot paths of this package, every stage in its MI355X-native form:
 
-    raster in HBM -> source-image options (source_prep_kernels.hip; source.py) -> mip levels (mipmap_kernels.hip) -> 4x4 tiles (k_extract_blocks)
+    raster in HBM -> source-image options (source_prep_kernels.hip; source.py) -> mip levels (mipmap_kernels.hip) -> 4x4 tiles of every slice in one launch (bu_hip_k_extract_slices)
       ETC1S : resident frontend (etc1s.Etc1sFrontend) -> host backend (backend.Etc1sBackend) -> .basis / .ktx2
       UASTC : encode_uastc kernels (-> uastc_rdo kernels) -> .basis / .ktx2 (KTX2_SS_NONE: what the reference's library default,
               comp.h:323, and `basisu -ktx2_no_zstandard` write; Zstandard supercompression of the levels is not part of this package)
 
-Several source images per call -- texture arrays, cubemaps, video, volumes (`-tex_type`) -- take the same stages per image; all their slices are tiled by ONE launch
-(bu_hip_k_extract_slices) into one tile array and go through one frontend / backend run.
+There is one pipeline: a single image is a sequence of one. Several source images per call -- texture arrays, cubemaps, video, volumes (`-tex_type`) -- take the source and
+mip stages per image; all their slices are tiled into one tile array and go through one frontend / backend run.
 The result is the file the reference command line tool writes for the same options (tests/test_gpu_backend.py, test_gpu_mipmap.py,
 test_gpu_compress_multi_image.py), given the same key-values. No stage has a CPU implementation here: without the HIP libraries and a GPU the context cannot be created."""
 import struct
@@ -92,84 +92,33 @@ def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=
       stats: one dict per slice in slice order; ETC1S video with stats raises ValueError before any work (the ETC1S reader does not read video files).
       ValueError before ctx is touched: several images with tex_type "2d", a cubemap whose image count is not a multiple of 6, images of different sizes (after
       `resample`) in anything but "2d", more slices than BASISU_MAX_SLICES, an empty sequence.
-    A single array with tex_type "2d" and these four at their defaults takes the single-image path: its launches and bytes are what they were without them."""
-    opts = {k: v for k, v in locals().items() if k not in ("ctx", "image")}   # every keyword as given, for the several-images path
+    A single array is a sequence of one: the same stages, the same launches, the same bytes."""
     if stats_bc7 and not uastc:
         from .stats import BC7_REFUSAL
         raise ValueError(BC7_REFUSAL)
-    several = isinstance(image, (list, tuple)) and (not len(image) or np.ndim(image[0]) == 3) or (isinstance(image, np.ndarray) and image.ndim == 4)
-    if several or tex_type != "2d" or us_per_frame or tuple(userdata) != (0, 0) or tuple(ktx2_animdata) != (1, 15, 0):
-        return _compress_images(ctx, list(image) if several else [image], **opts)
-    img = np.ascontiguousarray(image, np.uint8)
-    if img.ndim != 3 or img.shape[2] != 4:
-        raise ValueError("image must be (h, w, 4) uint8")
-    h, w = img.shape[:2]
-    if not w or not h or w > _source.MAX_DIMENSION or h > _source.MAX_DIMENSION:
-        raise ValueError(f"image of {w} x {h} pixels: 1..{_source.MAX_DIMENSION} each way")
-    prepare = not _source.is_identity(renormalize, swizzle, check_for_alpha, force_alpha, y_flip)   # parses the swizzle: ValueError
-    _source.check_mip_options(mip_filter, mip_scale, mip_smallest_dimension)
-    new_size = _source.resampled_size(w, h, resample)
-    mip_srgb = srgb if mip_srgb is None else mip_srgb
+    bare = not (isinstance(image, (list, tuple)) and (not len(image) or np.ndim(image[0]) == 3) or (isinstance(image, np.ndarray) and image.ndim == 4))
+    prepare_options = dict(renormalize=renormalize, swizzle=swizzle, check_for_alpha=check_for_alpha, force_alpha=force_alpha, y_flip=y_flip)
+    imgs, level_sizes, type_index, host_alpha, key_values = _checked(
+        [image] if bare else list(image), bare, prepare_options, uastc=uastc, mipmaps=mipmaps, ktx2=ktx2, key_values=key_values, stats=stats, resample=resample,
+        mip_filter=mip_filter, mip_scale=mip_scale, mip_smallest_dimension=mip_smallest_dimension, tex_type=tex_type, us_per_frame=us_per_frame, userdata=userdata,
+        ktx2_animdata=ktx2_animdata)
     owned = []
     try:
-        # ---- the source image, resident and prepared
-        d_src = ctx.upload(img)
-        owned.append(d_src)
-        if prepare:
-            d_level0 = d_src
-            if y_flip:                                                    # the flip reads another row than it writes: not in place
-                d_level0 = ctx.alloc(w * h * 4)
-                owned.append(d_level0)
-            # has_alpha -> m_any_source_image_has_alpha; any_alpha = image::has_alpha of the prepared raster
-            has_alpha, any_alpha = _source.prepare_resident(ctx, d_src, w, h, d_level0, renormalize=renormalize, swizzle=swizzle, check_for_alpha=check_for_alpha,
-                                                            force_alpha=force_alpha, y_flip=y_flip)
-        else:
-            d_level0 = d_src
-            has_alpha = any_alpha = bool((img[..., 3] != 255).any())      # image::has_alpha -> m_any_source_image_has_alpha
-        if new_size is not None:
-            d_level0 = _source.resample_resident(ctx, d_level0, w, h, new_size[0], new_size[1], srgb)
-            owned.append(d_level0)
-            w, h = new_size
-        # ---- the levels, resident
-        sizes = [(w, h)] + (mipmap.level_sizes(w, h, int(mip_smallest_dimension)) if mipmaps else [])
-        rasters = [d_level0]
-        for lw, lh in sizes[1:]:
-            d = ctx.alloc(lw * lh * 4)
-            owned.append(d)
-            at = len(rasters) - 1 if mip_fast else 0                      # m_mip_fast: from the level above; else every level from level 0
-            sw, sh = sizes[at]
-            ctx.check(mipmap._lib().bu_generate_mipmap_level(ctx.h, rasters[at], sw, sh, d, lw, lh, int(bool(mip_srgb)), mip_filter.encode(), float(mip_scale),
-                                                             int(bool(mip_wrapping)), 4 if has_alpha else 3), "bu_generate_mipmap_level")
-            if mip_renormalize:
-                _source.renormalize_resident(ctx, d, lw, lh)
-            rasters.append(d)
-        # ---- the slices: one per level, for ETC1S with alpha a colour slice and an (a, a, a) slice per level (comp.cpp:2880-2910)
-        split_alpha = has_alpha and not uastc
-        per_level = [((lw + 3) // 4) * ((lh + 3) // 4) for lw, lh in sizes]
-        total_blocks = sum(per_level) * (2 if split_alpha else 1)
-        d_all = ctx.alloc(total_blocks * 64)   # one contiguous tile array: the levels (and the alpha slices) share the codebooks
-        owned.append(d_all)
-        slices, slice_blocks, first, level_planes = [], [], 0, []
-        for mip, ((lw, lh), d_raster) in enumerate(zip(sizes, rasters)):
-            nbx, nby = (lw + 3) // 4, (lh + 3) // 4
-            if split_alpha:   # (r, g, b, 255) in the level's own buffer -- every level below it is made already -- and (a, a, a, 255) beside it
-                planes = [d_raster, ctx.alloc(lw * lh * 4)]
-                owned.append(planes[1])
-                _source.split_alpha_resident(ctx, d_raster, lw, lh, planes[0], planes[1])
-            else:
-                planes = [d_raster]
-            level_planes.append([(d_plane, lw, lh, lw) for d_plane in planes])
-            for k, d_plane in enumerate(planes):   # basis_compressor::extract_source_blocks on the resident plane, straight into its place
-                ctx.check(ctx.lib.k_extract_blocks(ctx.h, d_plane, lw, lh, lw * 4, d_all + first * 64), "k_extract_blocks")
-                # the slice's alpha flag: ETC1S the alpha plane; UASTC image::has_alpha of the slice (comp.cpp:2928-2937), known for the prepared raster
-                slices.append((first, nbx, nby, lw, lh, 0, mip, k if split_alpha else int(has_alpha and any_alpha)))
-                slice_blocks.append(nbx * nby)
-                first += nbx * nby
-
-        return _encode(ctx, owned, d_all, slices, slice_blocks, total_blocks, has_alpha, lambda level, layer, face, n_slices: level_planes[level], uastc=uastc, quality=quality,
-                       comp_level=comp_level, uastc_level=uastc_level, uastc_rdo_lambda=uastc_rdo_lambda, uastc_rdo_jobs=uastc_rdo_jobs, ktx2=ktx2, srgb=srgb,
-                       key_values=key_values, max_threads=max_threads, stats=stats, stats_hvs=stats_hvs, stats_bc7=stats_bc7, stats_ssim=stats_ssim, y_flip=y_flip,
-                       no_selector_rdo=no_selector_rdo, no_endpoint_rdo=no_endpoint_rdo)
+        level0, image_alpha, has_alpha = _resident_level0(ctx, owned, imgs, level_sizes, host_alpha, prepare_options, resample=resample, srgb=srgb)
+        _source.check_slice_count(len(imgs), len(level_sizes[0]), has_alpha and not uastc)
+        # each image's own chain (generate_mipmaps with m_any_source_image_has_alpha: four components for every image when any has alpha)
+        rasters = [mipmap.resident_chain(ctx, owned, d, sizes, srgb=srgb if mip_srgb is None else mip_srgb, filter=mip_filter, filter_scale=mip_scale, wrapping=mip_wrapping,
+                                         num_comps=4 if has_alpha else 3, fast=mip_fast, renormalize=mip_renormalize) for d, sizes in zip(level0, level_sizes)]
+        d_all, slices, planes = _tiles(ctx, owned, rasters, level_sizes, tex_type=tex_type, uastc=uastc, has_alpha=has_alpha, image_alpha=image_alpha,
+                                       video=tex_type == "video", with_planes=stats is not None)
+        data = _encode(ctx, owned, d_all, slices, has_alpha, uastc=uastc, quality=quality, comp_level=comp_level, uastc_level=uastc_level, uastc_rdo_lambda=uastc_rdo_lambda,
+                       uastc_rdo_jobs=uastc_rdo_jobs, ktx2=ktx2, srgb=srgb, key_values=key_values, max_threads=max_threads, y_flip=y_flip, no_selector_rdo=no_selector_rdo,
+                       no_endpoint_rdo=no_endpoint_rdo, tex_type=type_index, us_per_frame=us_per_frame, userdata=userdata)
+        if stats is not None:   # m_compute_stats (comp.cpp:4195-4253) while the sources are still resident
+            from . import stats as _stats
+            stats.extend(_stats._stats_from_slices(ctx, bytes(data), lambda level, layer, face, n_slices: planes[(level, layer, face)], hvs=stats_hvs, bc7=stats_bc7,
+                                                   ssim=stats_ssim))
+        return data
     finally:
         for d in owned:
             ctx.free(d)
@@ -179,18 +128,97 @@ VIDEO_STATS_REFUSAL = ("stats of an ETC1S video file: video files are not suppor
                        "does not keep (csrc/host/etc1s_decode.cpp)")
 
 
-def _encode(ctx, owned, d_all, slices, slice_blocks, total_blocks, has_alpha, slice_sources, *, uastc, quality, comp_level, uastc_level, uastc_rdo_lambda, uastc_rdo_jobs,
-            ktx2, srgb, key_values, max_threads, stats, stats_hvs, stats_bc7, stats_ssim, y_flip, no_selector_rdo, no_endpoint_rdo, tex_type=0, us_per_frame=0,
-            userdata=(0, 0)):
-    """resident tiles of every slice -> the file. slice_sources(level, layer, face, n_slices): the resident source of every slice of that image, for the stats stage."""
-    video = tex_type == 3
-    ud0, ud1 = (int(v) for v in userdata)
+def _checked(images, bare, prepare_options, *, uastc, mipmaps, ktx2, key_values, stats, resample, mip_filter, mip_scale, mip_smallest_dimension, tex_type, us_per_frame,
+             userdata, ktx2_animdata):
+    """Everything that can be refused, before ctx is touched. -> the images as uint8 arrays, per image the (width, height) of its levels (level 0: after `resample`), the
+    basis_texture_type number, per image image::has_alpha decided on the host (None where the prepare kernel decides it), and key_values with a video .ktx2's KTXanimData."""
+    imgs = []
+    for k, image in enumerate(images):
+        name = "image" if bare else f"image {k}"
+        img = np.ascontiguousarray(image, np.uint8)
+        if img.ndim != 3 or img.shape[2] != 4:
+            raise ValueError(f"{name} must be (h, w, 4) uint8")
+        h, w = img.shape[:2]
+        if not w or not h or w > _source.MAX_DIMENSION or h > _source.MAX_DIMENSION:
+            raise ValueError(f"{name} of {w} x {h} pixels: 1..{_source.MAX_DIMENSION} each way")
+        imgs.append(img)
+    prepare = not _source.is_identity(**prepare_options)   # parses the swizzle: ValueError
+    _source.check_mip_options(mip_filter, mip_scale, mip_smallest_dimension)
+    sizes = [_source.resampled_size(img.shape[1], img.shape[0], resample) or (img.shape[1], img.shape[0]) for img in imgs]
+    type_index = _source.check_texture_type(tex_type, sizes)
+    video = tex_type == "video"
+    if video and not uastc and stats is not None:
+        raise ValueError(VIDEO_STATS_REFUSAL)
+    if len(tuple(userdata)) != 2 or len(tuple(ktx2_animdata)) != 3 or any(not 0 <= int(v) < 2 ** 32 for v in (*userdata, *ktx2_animdata, us_per_frame)):
+        raise ValueError("userdata is two, ktx2_animdata three and us_per_frame one unsigned 32-bit value")
+    level_sizes = [[size] + (mipmap.level_sizes(size[0], size[1], int(mip_smallest_dimension)) if mipmaps else []) for size in sizes]
+    host_alpha = [bool((img[..., 3] != 255).any()) for img in imgs] if not prepare else None      # image::has_alpha of an image that is not prepared
+    # the alpha slices double the count; where only the device can say whether there are any (the prepare kernel's flag), the count is checked again once it has
+    alpha_known = bool(prepare_options["force_alpha"]) or (host_alpha is not None and any(host_alpha))
+    _source.check_slice_count(len(imgs), len(level_sizes[0]), not uastc and alpha_known)
+    if video and ktx2 and not any(k == "KTXanimData" for k, _ in key_values):   # basisu_tool.cpp:2382-2401: three little-endian 32-bit words
+        key_values = list(key_values) + [("KTXanimData", struct.pack("<III", *(int(v) for v in ktx2_animdata)))]
+    return imgs, level_sizes, type_index, host_alpha, key_values
 
-    def finish(data):   # m_compute_stats (comp.cpp:4195-4253) while the sources are still resident
-        if stats is not None:
-            from . import stats as _stats
-            stats.extend(_stats._stats_from_slices(ctx, bytes(data), slice_sources, hvs=stats_hvs, bc7=stats_bc7, ssim=stats_ssim))
-        return data
+
+def _resident_level0(ctx, owned, imgs, level_sizes, host_alpha, prepare_options, *, resample, srgb):
+    """Every source image resident, prepared and resampled -> (level-0 rasters, per image image::has_alpha of the prepared raster, m_any_source_image_has_alpha)."""
+    level0, image_alpha, has_alpha = [], [], False
+    for k, img in enumerate(imgs):
+        h, w = img.shape[:2]
+        d_level0 = d_src = ctx.upload(img)
+        owned.append(d_src)
+        if host_alpha is None:
+            if prepare_options["y_flip"]:                                 # the flip reads another row than it writes: not in place
+                d_level0 = ctx.alloc(w * h * 4)
+                owned.append(d_level0)
+            one_has, one_any = _source.prepare_resident(ctx, d_src, w, h, d_level0, **prepare_options)
+        else:
+            one_has = one_any = host_alpha[k]
+        if resample is not None:   # has_alpha is decided before the resample, as the reference decides it
+            d_level0 = _source.resample_resident(ctx, d_level0, w, h, *level_sizes[k][0], srgb)
+            owned.append(d_level0)
+        level0.append(d_level0)
+        image_alpha.append(one_any)
+        has_alpha = has_alpha or one_has
+    return level0, image_alpha, has_alpha
+
+
+def _tiles(ctx, owned, rasters, level_sizes, *, tex_type, uastc, has_alpha, image_alpha, video, with_planes):
+    """The slice table and the tiles of every slice by ONE launch -> (resident tile array, slices, {(level, layer, face): the resident source of each of its slices}; the
+    last only with_planes, for the stats stage, which reads planes: ETC1S alpha is then split into planes and the tiles are cut from those)."""
+    slices, sources = _source.slice_table(level_sizes, uastc=uastc, any_alpha=has_alpha, image_alpha=image_alpha, video=video)
+    d_all = ctx.alloc(sum(s[1] * s[2] for s in slices) * 64)   # one contiguous tile array: every image, level and alpha slice shares the codebooks
+    owned.append(d_all)
+    split_alpha = has_alpha and not uastc
+    planes = {}
+    if with_planes:
+        for k, (chain, levels) in enumerate(zip(rasters, level_sizes)):
+            for level, (d_raster, (lw, lh)) in enumerate(zip(chain, levels)):
+                one = [d_raster]
+                if split_alpha:            # (r, g, b, 255) in the level's own buffer -- every level is made already -- and (a, a, a, 255) beside it
+                    one.append(ctx.alloc(lw * lh * 4))
+                    owned.append(one[1])
+                    _source.split_alpha_resident(ctx, d_raster, lw, lh, one[0], one[1])
+                planes[(level, *_source.image_layer_face(tex_type, k))] = [(d, lw, lh, lw) for d in one]
+    entries = []
+    for s, (k, level, mode) in zip(slices, sources):
+        if with_planes and split_alpha:
+            d_raster, mode = planes[(level, *_source.image_layer_face(tex_type, k))][mode == _source.SLICE_ALPHA][0], _source.SLICE_AS_IS
+        else:
+            d_raster = rasters[k][level]
+        entries.append((d_raster, s[3], s[4], 0, mode, s[0]))
+    _source.extract_slices_resident(ctx, entries, d_all)
+    return d_all, slices, planes
+
+
+def _encode(ctx, owned, d_all, slices, has_alpha, *, uastc, quality, comp_level, uastc_level, uastc_rdo_lambda, uastc_rdo_jobs, ktx2, srgb, key_values, max_threads, y_flip,
+            no_selector_rdo, no_endpoint_rdo, tex_type, us_per_frame, userdata):
+    """resident tiles of every slice -> the file"""
+    video = tex_type == 3
+    header = dict(tex_type=tex_type, userdata0=int(userdata[0]), userdata1=int(userdata[1]), y_flipped=bool(y_flip), us_per_frame=int(us_per_frame), key_values=key_values)
+    slice_blocks = [s[1] * s[2] for s in slices]
+    total_blocks = sum(slice_blocks)
     if uastc:
         rdo = uastc_rdo_lambda is not None and uastc_rdo_lambda is not False
         flags = int(uastc_level) | (_uastc.FAVOR_SIMPLER_MODES if rdo else 0)       # comp.cpp:2016-2018
@@ -204,11 +232,10 @@ def _encode(ctx, owned, d_all, slices, slice_blocks, total_blocks, has_alpha, sl
                 at += n
         packed = ctx.download(d_out, (total_blocks, 16), np.uint8)
         if ktx2:
-            return finish(uastc_ktx2_file(packed, slices, srgb=srgb, tex_type=tex_type, has_alpha=has_alpha, key_values=key_values))
+            return uastc_ktx2_file(packed, slices, srgb=srgb, tex_type=tex_type, has_alpha=has_alpha, key_values=key_values)
         # encode_slices_to_uastc_4x4_ldr (comp.cpp:1973-1985) never sets basisu_backend_output::m_srgb, which basisu_backend_output::clear() leaves true
         # (backend.h:243): the reference's UASTC .basis files carry the sRGB header flag whatever -linear says (the .ktx2 DFD does follow the option)
-        return finish(uastc_basis_file(packed, slices, srgb=True, tex_type=tex_type, userdata0=ud0, userdata1=ud1, y_flipped=bool(y_flip), us_per_frame=int(us_per_frame),
-                                       key_values=key_values))
+        return uastc_basis_file(packed, slices, srgb=True, **header)
     max_ep, max_sel = quality_to_clusters(quality, total_blocks)
     fe = Etc1sFrontend(ctx, max_threads=max_threads, video=video)
     try:
@@ -220,115 +247,9 @@ def _encode(ctx, owned, d_all, slices, slice_blocks, total_blocks, has_alpha, sl
         try:
             be.encode()
             if ktx2:
-                return finish(be.ktx2_file(tex_type=tex_type, has_alpha=has_alpha, key_values=key_values))
-            return finish(be.basis_file(tex_type=tex_type, userdata0=ud0, userdata1=ud1, y_flipped=bool(y_flip), us_per_frame=int(us_per_frame), key_values=key_values))
+                return be.ktx2_file(tex_type=tex_type, has_alpha=has_alpha, key_values=key_values)
+            return be.basis_file(**header)
         finally:
             be.close()
     finally:
         fe.close()
-
-
-def _compress_images(ctx, images, *, uastc, quality, comp_level, uastc_level, uastc_rdo_lambda, uastc_rdo_jobs, mipmaps, ktx2, srgb, key_values, max_threads, stats, stats_hvs,
-                     stats_bc7, stats_ssim, renormalize, swizzle, check_for_alpha, force_alpha, y_flip, resample, mip_filter, mip_scale, mip_wrapping, mip_srgb, mip_renormalize,
-                     mip_fast, mip_smallest_dimension, no_selector_rdo, no_endpoint_rdo, tex_type, us_per_frame, userdata, ktx2_animdata):
-    """compress() for a sequence of source images (and for one image with a texture type or header fields of its own): every check first, then per image the
-    single-image stages, then every slice of the call tiled by one launch."""
-    # ---- everything that can be refused, before ctx is touched
-    imgs = []
-    for k, image in enumerate(images):
-        img = np.ascontiguousarray(image, np.uint8)
-        if img.ndim != 3 or img.shape[2] != 4:
-            raise ValueError(f"image {k} must be (h, w, 4) uint8")
-        h, w = img.shape[:2]
-        if not w or not h or w > _source.MAX_DIMENSION or h > _source.MAX_DIMENSION:
-            raise ValueError(f"image {k} of {w} x {h} pixels: 1..{_source.MAX_DIMENSION} each way")
-        imgs.append(img)
-    prepare = not _source.is_identity(renormalize, swizzle, check_for_alpha, force_alpha, y_flip)   # parses the swizzle: ValueError
-    _source.check_mip_options(mip_filter, mip_scale, mip_smallest_dimension)
-    new_sizes = [_source.resampled_size(img.shape[1], img.shape[0], resample) for img in imgs]
-    sizes = [new or (img.shape[1], img.shape[0]) for new, img in zip(new_sizes, imgs)]
-    type_index = _source.check_texture_type(tex_type, sizes)
-    video = tex_type == "video"
-    if video and not uastc and stats is not None:
-        raise ValueError(VIDEO_STATS_REFUSAL)
-    if len(tuple(userdata)) != 2 or len(tuple(ktx2_animdata)) != 3 or any(not 0 <= int(v) < 2 ** 32 for v in (*userdata, *ktx2_animdata, us_per_frame)):
-        raise ValueError("userdata is two, ktx2_animdata three and us_per_frame one unsigned 32-bit value")
-    level_sizes = [[size] + (mipmap.level_sizes(size[0], size[1], int(mip_smallest_dimension)) if mipmaps else []) for size in sizes]
-    host_alpha = [bool((img[..., 3] != 255).any()) for img in imgs] if not prepare else None      # image::has_alpha of an image that is not prepared
-    # the alpha slices double the count; where only the device can say whether there are any (the prepare kernel's flag), the count is checked again below
-    alpha_known = bool(force_alpha) or (host_alpha is not None and any(host_alpha))
-    _source.check_slice_count(len(imgs), len(level_sizes[0]), not uastc and alpha_known)
-    if video and ktx2 and not any(k == "KTXanimData" for k, _ in key_values):   # basisu_tool.cpp:2382-2401: three little-endian 32-bit words
-        key_values = list(key_values) + [("KTXanimData", struct.pack("<III", *(int(v) for v in ktx2_animdata)))]
-    mip_srgb = srgb if mip_srgb is None else mip_srgb
-    owned = []
-    try:
-        # ---- every source image, resident and prepared; m_any_source_image_has_alpha over all of them
-        level0, image_alpha, has_alpha = [], [], False
-        for k, img in enumerate(imgs):
-            h, w = img.shape[:2]
-            d_src = ctx.upload(img)
-            owned.append(d_src)
-            d_level0 = d_src
-            if prepare:
-                if y_flip:                                                # the flip reads another row than it writes: not in place
-                    d_level0 = ctx.alloc(w * h * 4)
-                    owned.append(d_level0)
-                one_has, one_any = _source.prepare_resident(ctx, d_src, w, h, d_level0, renormalize=renormalize, swizzle=swizzle, check_for_alpha=check_for_alpha,
-                                                            force_alpha=force_alpha, y_flip=y_flip)
-            else:
-                one_has = one_any = host_alpha[k]
-            if new_sizes[k] is not None:
-                d_level0 = _source.resample_resident(ctx, d_level0, w, h, new_sizes[k][0], new_sizes[k][1], srgb)
-                owned.append(d_level0)
-            level0.append(d_level0)
-            image_alpha.append(one_any)
-            has_alpha = has_alpha or one_has
-        split_alpha = has_alpha and not uastc
-        _source.check_slice_count(len(imgs), len(level_sizes[0]), split_alpha)
-        # ---- each image's own mip chain, resident (generate_mipmaps with m_any_source_image_has_alpha: four components for every image when any has alpha)
-        rasters = []
-        for d_level0, levels in zip(level0, level_sizes):
-            chain = [d_level0]
-            for lw, lh in levels[1:]:
-                d = ctx.alloc(lw * lh * 4)
-                owned.append(d)
-                at = len(chain) - 1 if mip_fast else 0
-                sw, sh = levels[at]
-                ctx.check(mipmap._lib().bu_generate_mipmap_level(ctx.h, chain[at], sw, sh, d, lw, lh, int(bool(mip_srgb)), mip_filter.encode(), float(mip_scale),
-                                                                 int(bool(mip_wrapping)), 4 if has_alpha else 3), "bu_generate_mipmap_level")
-                if mip_renormalize:
-                    _source.renormalize_resident(ctx, d, lw, lh)
-                chain.append(d)
-            rasters.append(chain)
-        # ---- the slices, and their tiles by one launch
-        slices, sources = _source.slice_table(level_sizes, uastc=uastc, any_alpha=has_alpha, image_alpha=image_alpha, video=video)
-        slice_blocks = [s[1] * s[2] for s in slices]
-        total_blocks = sum(slice_blocks)
-        d_all = ctx.alloc(total_blocks * 64)   # one contiguous tile array: every image, level and alpha slice shares the codebooks
-        owned.append(d_all)
-        planes = {}                            # (level, layer, face) -> the resident source of each of its slices, for the stats stage
-        if stats is not None:
-            for k, (chain, levels) in enumerate(zip(rasters, level_sizes)):
-                for level, (d_raster, (lw, lh)) in enumerate(zip(chain, levels)):
-                    one = [d_raster]
-                    if split_alpha:            # the stats stage reads planes: (r, g, b, 255) in the level's own buffer -- every level is made already -- and (a, a, a, 255) beside it
-                        one.append(ctx.alloc(lw * lh * 4))
-                        owned.append(one[1])
-                        _source.split_alpha_resident(ctx, d_raster, lw, lh, one[0], one[1])
-                    planes[(level, *_source.image_layer_face(tex_type, k))] = [(d, lw, lh, lw) for d in one]
-        entries = []
-        for s, (k, level, mode) in zip(slices, sources):
-            if stats is not None and split_alpha:
-                d_raster, mode = planes[(level, *_source.image_layer_face(tex_type, k))][mode == _source.SLICE_ALPHA][0], _source.SLICE_AS_IS
-            else:
-                d_raster = rasters[k][level]
-            entries.append((d_raster, s[3], s[4], 0, mode, s[0]))
-        _source.extract_slices_resident(ctx, entries, d_all)
-        return _encode(ctx, owned, d_all, slices, slice_blocks, total_blocks, has_alpha, lambda level, layer, face, n_slices: planes[(level, layer, face)], uastc=uastc,
-                       quality=quality, comp_level=comp_level, uastc_level=uastc_level, uastc_rdo_lambda=uastc_rdo_lambda, uastc_rdo_jobs=uastc_rdo_jobs, ktx2=ktx2, srgb=srgb,
-                       key_values=key_values, max_threads=max_threads, stats=stats, stats_hvs=stats_hvs, stats_bc7=stats_bc7, stats_ssim=stats_ssim, y_flip=y_flip,
-                       no_selector_rdo=no_selector_rdo, no_endpoint_rdo=no_endpoint_rdo, tex_type=type_index, us_per_frame=us_per_frame, userdata=userdata)
-    finally:
-        for d in owned:
-            ctx.free(d)

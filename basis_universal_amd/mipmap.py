@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import capi
+from . import capi, source
 from .etc1s import load_frontend_library
 
 _vp = C.c_void_p
@@ -38,18 +38,29 @@ def generate_mipmaps(ctx, image, has_alpha=False, srgb=True, filter="kaiser", fi
     the one above it, all on the device: one upload, one download per level."""
     img = np.ascontiguousarray(image, np.uint8)
     h, w = img.shape[:2]
-    sizes = level_sizes(w, h, smallest_dimension)
-    bufs = [(ctx.upload(img), w, h)]
-    out = []
+    sizes = [(w, h)] + level_sizes(w, h, smallest_dimension)
+    owned = [ctx.upload(img)]
     try:
-        for lw, lh in sizes:
-            src, sw, sh = bufs[-1] if fast else bufs[0]
-            d = ctx.alloc(lw * lh * 4)
-            bufs.append((d, lw, lh))
-            ctx.check(_lib().bu_generate_mipmap_level(ctx.h, src, sw, sh, d, lw, lh, int(srgb), filter.encode(), filter_scale, int(wrapping), 4 if has_alpha else 3),
-                      "bu_generate_mipmap_level")
-            out.append(ctx.download(d, (lh, lw, 4), np.uint8))
+        chain = resident_chain(ctx, owned, owned[0], sizes, srgb=srgb, filter=filter, filter_scale=filter_scale, wrapping=wrapping, num_comps=4 if has_alpha else 3, fast=fast)
+        return [ctx.download(d, (lh, lw, 4), np.uint8) for d, (lw, lh) in zip(chain[1:], sizes[1:])]
     finally:
-        for d, _, _ in bufs:
+        for d in owned:
             ctx.free(d)
-    return out
+
+
+def resident_chain(ctx, owned, d_level0, sizes, *, srgb=True, filter="kaiser", filter_scale=1.0, wrapping=True, num_comps=4, fast=True, renormalize=False):
+    """The mip chain of a resident level 0, resident: sizes = the (width, height) of level 0 and of every level below it (level_sizes). With `fast` (m_mip_fast) every
+    level is made from the one above it, else from level 0; `renormalize` (m_mip_renormalize): every level renormalised after it is made. What is allocated here is
+    appended to the caller's `owned`, level by level, so that a failure half way leaks nothing. -> [d_level0, d_level1, ...]; no synchronisation."""
+    chain = [d_level0]
+    for lw, lh in sizes[1:]:
+        d = ctx.alloc(lw * lh * 4)
+        owned.append(d)
+        at = len(chain) - 1 if fast else 0
+        sw, sh = sizes[at]
+        ctx.check(_lib().bu_generate_mipmap_level(ctx.h, chain[at], sw, sh, d, lw, lh, int(bool(srgb)), filter.encode(), float(filter_scale), int(bool(wrapping)), num_comps),
+                  "bu_generate_mipmap_level")
+        if renormalize:
+            source.renormalize_resident(ctx, d, lw, lh)
+        chain.append(d)
+    return chain

@@ -74,23 +74,20 @@ def is_identity(renormalize, swizzle, check_for_alpha, force_alpha, y_flip):
 def prepare_resident(ctx, d_src, w, h, d_dst, *, renormalize=False, swizzle=None, check_for_alpha=True, force_alpha=False, y_flip=False, src_pitch=None, dst_pitch=None):
     """bu_hip_k_prepare_source on resident rasters -> (has_alpha, any prepared alpha below 255). With only `renormalize` set and d_dst == d_src it is the in-place
     renormalisation plus the flag. force_alpha wins over check_for_alpha=False, as in the reference (comp.cpp:2616-2621)."""
-    import ctypes as C
-    has_alpha, below = C.c_uint32(0), C.c_uint32(0)
-    ctx.check(ctx.lib.k_prepare_source(ctx.h, C.c_void_p(d_src), w, h, src_pitch or w * 4, C.c_void_p(d_dst), dst_pitch or w * 4, int(bool(renormalize)), parse_swizzle(swizzle),
-                                       int(bool(check_for_alpha)), int(bool(force_alpha)), int(bool(y_flip)), C.byref(has_alpha), C.byref(below)), "k_prepare_source")
+    has_alpha, below = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    ctx.check(ctx.lib.k_prepare_source(ctx.h, ctypes.c_void_p(d_src), w, h, src_pitch or w * 4, ctypes.c_void_p(d_dst), dst_pitch or w * 4, int(bool(renormalize)), parse_swizzle(swizzle),
+                                       int(bool(check_for_alpha)), int(bool(force_alpha)), int(bool(y_flip)), ctypes.byref(has_alpha), ctypes.byref(below)), "k_prepare_source")
     return bool(has_alpha.value), bool(below.value)
 
 
 def renormalize_resident(ctx, d_raster, w, h, pitch=None):
     """image::renormalize_normal_map in place on a resident raster (the mip levels of mip_renormalize); no synchronisation"""
-    import ctypes as C
-    ctx.check(ctx.lib.k_renormalize_normal_map(ctx.h, C.c_void_p(d_raster), w, h, pitch or w * 4), "k_renormalize_normal_map")
+    ctx.check(ctx.lib.k_renormalize_normal_map(ctx.h, ctypes.c_void_p(d_raster), w, h, pitch or w * 4), "k_renormalize_normal_map")
 
 
 def split_alpha_resident(ctx, d_raster, w, h, d_rgb, d_alpha, pitch=None, rgb_pitch=None, alpha_pitch=None):
     """(r, g, b, 255) -> d_rgb (may be d_raster) and (a, a, a, 255) -> d_alpha: the two ETC1S slices of a level with alpha; no synchronisation"""
-    import ctypes as C
-    ctx.check(ctx.lib.k_split_alpha(ctx.h, C.c_void_p(d_raster), w, h, pitch or w * 4, C.c_void_p(d_rgb), rgb_pitch or w * 4, C.c_void_p(d_alpha), alpha_pitch or w * 4), "k_split_alpha")
+    ctx.check(ctx.lib.k_split_alpha(ctx.h, ctypes.c_void_p(d_raster), w, h, pitch or w * 4, ctypes.c_void_p(d_rgb), rgb_pitch or w * 4, ctypes.c_void_p(d_alpha), alpha_pitch or w * 4), "k_split_alpha")
 
 
 def resample_resident(ctx, d_src, w, h, new_w, new_h, srgb):

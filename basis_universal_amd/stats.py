@@ -25,6 +25,7 @@ With ssim=True (file_stats) / stats_ssim=True (compress) every slice dict -- and
 Per pixel and channel five 11x11 Gaussian filterings of float images and the smap formula, binary32 in the reference's operation order (csrc/ssim.h), one lane per
 pixel (csrc/ssim_kernels.hip, bu_hip_k_ssim); then the mean as the reference's one running float sum in raster order, evaluated in chunks with csrc/fsum_scan.h
 (csrc/ssim_reduce.h): the figures are the reference's bit for bit, and print as the tool prints them. Not here: the best-ETC1S stats."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -84,31 +85,34 @@ def reduce_counts(hist, width, height):
     return out
 
 
-def _resident(ctx, raster, owned):
-    """a numpy (h, w, 4) u8 image (uploaded; the pointer goes to `owned`) or a (device pointer, w, h, pitch in pixels) tuple -> that tuple"""
-    if isinstance(raster, np.ndarray):
-        img = np.ascontiguousarray(raster, np.uint8)
-        if img.ndim != 3 or img.shape[2] != 4:
-            raise ValueError("an image must be (h, w, 4) uint8")
-        d = ctx.upload(img)
-        owned.append(d)
-        return d, img.shape[1], img.shape[0], img.shape[1]
-    d, w, h, pitch = raster
-    return int(d), int(w), int(h), int(pitch)
+@contextlib.contextmanager
+def _resident_pair(ctx, a, b):
+    """a, b: a numpy (h, w, 4) u8 image (uploaded, and freed on the way out) or a (device pointer, w, h, pitch in pixels) tuple each -> the two
+    (pointer, w, h, pitch) tuples as the kernels' entry points take them"""
+    owned, out = [], []
+    try:
+        for raster in (a, b):
+            if isinstance(raster, np.ndarray):
+                img = np.ascontiguousarray(raster, np.uint8)
+                if img.ndim != 3 or img.shape[2] != 4:
+                    raise ValueError("an image must be (h, w, 4) uint8")
+                owned.append(ctx.upload(img))
+                raster = owned[-1], img.shape[1], img.shape[0], img.shape[1]
+            d, w, h, pitch = raster
+            out.append((C.c_void_p(int(d)), int(w), int(h), int(pitch)))
+        yield out
+    finally:
+        for d in owned:
+            ctx.free(d)
 
 
 def image_counts(ctx, a, b):
     """bu_hip_k_image_metrics: a, b as for image_metrics -> (hist (6, 256) u32, sum_a (4,) u64, sum_b (4,) u64, width, height) of the region both cover."""
-    owned = []
-    try:
-        (da, wa, ha, pa), (db, wb, hb, pb) = _resident(ctx, a, owned), _resident(ctx, b, owned)
+    with _resident_pair(ctx, a, b) as (ra, rb):
         c = Counts()
         c.struct_bytes = C.sizeof(Counts)
-        ctx.check(ctx.lib.k_image_metrics(ctx.h, C.c_void_p(da), wa, ha, pa, C.c_void_p(db), wb, hb, pb, C.byref(c)), "image_metrics")
-        return np.ctypeslib.as_array(c.hist).copy(), np.array(list(c.sum_a), np.uint64), np.array(list(c.sum_b), np.uint64), int(c.width), int(c.height)
-    finally:
-        for d in owned:
-            ctx.free(d)
+        ctx.check(ctx.lib.k_image_metrics(ctx.h, *ra, *rb, C.byref(c)), "image_metrics")
+    return np.ctypeslib.as_array(c.hist).copy(), np.array(list(c.sum_a), np.uint64), np.array(list(c.sum_b), np.uint64), int(c.width), int(c.height)
 
 
 def image_metrics(ctx, a, b):
@@ -124,32 +128,21 @@ def image_metrics(ctx, a, b):
 
 def psnr_hvs_sums(ctx, a, b):
     """bu_hip_k_psnr_hvs: a, b as for image_metrics -> the filled HvsSums (sum_hvs / sum_hvsm per mode of HVS_MODES, blocks, width, height)."""
-    owned = []
-    try:
-        (da, wa, ha, pa), (db, wb, hb, pb) = _resident(ctx, a, owned), _resident(ctx, b, owned)
+    with _resident_pair(ctx, a, b) as (ra, rb):
         s = HvsSums()
         s.struct_bytes = C.sizeof(HvsSums)
-        ctx.check(ctx.lib.k_psnr_hvs(ctx.h, C.c_void_p(da), wa, ha, pa, C.c_void_p(db), wb, hb, pb, C.byref(s)), "psnr_hvs")
-        return s
-    finally:
-        for d in owned:
-            ctx.free(d)
+        ctx.check(ctx.lib.k_psnr_hvs(ctx.h, *ra, *rb, C.byref(s)), "psnr_hvs")
+    return s
 
 
 def psnr_hvs_block_sums(ctx, a, b, mode):
     """bu_hip_k_psnr_hvs_blocks (the test hook): -> (blocks, 2) f64, the HVS and the HVS-M double of every 8x8 block of mode HVS_MODES[mode], raster order."""
-    owned = []
-    try:
-        (da, wa, ha, pa), (db, wb, hb, pb) = _resident(ctx, a, owned), _resident(ctx, b, owned)
-        w, h = min(wa, wb), min(ha, hb)
+    with _resident_pair(ctx, a, b) as (ra, rb):
+        w, h = min(ra[1], rb[1]), min(ra[2], rb[2])
         cap = ((w + 7) // 8) * ((h + 7) // 8)
         out, n = np.zeros((max(cap, 1), 2), np.float64), C.c_uint32(0)
-        ctx.check(ctx.lib.k_psnr_hvs_blocks(ctx.h, C.c_void_p(da), wa, ha, pa, C.c_void_p(db), wb, hb, pb, int(mode), out.ctypes.data_as(C.c_void_p), cap, C.byref(n)),
-                  "psnr_hvs_blocks")
-        return out[:n.value]
-    finally:
-        for d in owned:
-            ctx.free(d)
+        ctx.check(ctx.lib.k_psnr_hvs_blocks(ctx.h, *ra, *rb, int(mode), out.ctypes.data_as(C.c_void_p), cap, C.byref(n)), "psnr_hvs_blocks")
+    return out[:n.value]
 
 
 def reduce_hvs_sums(sums):
@@ -175,34 +168,23 @@ def psnr_hvs(ctx, a, b):
 
 def ssim_result(ctx, a, b):
     """bu_hip_k_ssim: a, b as for image_metrics -> the filled SsimResult (the seven floats, width, height, and the reduction's chunks / chunks_walked)."""
-    owned = []
-    try:
-        (da, wa, ha, pa), (db, wb, hb, pb) = _resident(ctx, a, owned), _resident(ctx, b, owned)
+    with _resident_pair(ctx, a, b) as (ra, rb):
         s = SsimResult()
         s.struct_bytes = C.sizeof(SsimResult)
-        ctx.check(ctx.lib.k_ssim(ctx.h, C.c_void_p(da), wa, ha, pa, C.c_void_p(db), wb, hb, pb, C.byref(s)), "ssim")
-        return s
-    finally:
-        for d in owned:
-            ctx.free(d)
+        ctx.check(ctx.lib.k_ssim(ctx.h, *ra, *rb, C.byref(s)), "ssim")
+    return s
 
 
 def ssim_map(ctx, a, b, mode):
     """bu_hip_k_ssim_map (the test hook): the smap values of one call of compute_ssim in raster order -> (h, w, 4) f32 for mode 0 (the RGBA call), (h, w) f32 for
     mode 1 / 2 (channel 0 of the 709 / 601 luma call)."""
-    owned = []
-    try:
-        (da, wa, ha, pa), (db, wb, hb, pb) = _resident(ctx, a, owned), _resident(ctx, b, owned)
-        w, h = min(wa, wb), min(ha, hb)
+    with _resident_pair(ctx, a, b) as (ra, rb):
+        w, h = min(ra[1], rb[1]), min(ra[2], rb[2])
         out, n = np.zeros((h, w, 4) if int(mode) == 0 else (h, w), np.float32), C.c_uint32(0)
-        ctx.check(ctx.lib.k_ssim_map(ctx.h, C.c_void_p(da), wa, ha, pa, C.c_void_p(db), wb, hb, pb, int(mode), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)),
-                  "ssim_map")
-        if n.value != w * h:
-            raise RuntimeError(f"ssim_map: {n.value} pixels for a region of {w} x {h}")
-        return out
-    finally:
-        for d in owned:
-            ctx.free(d)
+        ctx.check(ctx.lib.k_ssim_map(ctx.h, *ra, *rb, int(mode), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)), "ssim_map")
+    if n.value != w * h:
+        raise RuntimeError(f"ssim_map: {n.value} pixels for a region of {w} x {h}")
+    return out
 
 
 def ssim(ctx, a, b):

@@ -9,6 +9,7 @@ ETC1S files have their own three functions at the end of this module (`read_etc1
 (ETC1S_BYTES_PER_BLOCK / ETC1S_BYTES_PER_PIXEL): the serial half -- containers, Huffman tables, palettes, the per-slice symbol walk -- is host code in
 libbasisu_frontend.so (csrc/host/etc1s_decode.cpp, needs no GPU), the texel half is one HIP kernel launch per image (csrc/etc1s_transcode_kernels.hip).
 """
+import contextlib
 import ctypes as C
 import struct
 
@@ -29,6 +30,21 @@ class InvalidBlocksError(ValueError):
         self.count = count
 
 
+@contextlib.contextmanager
+def _output(ctx, out_device, out_row_pitch, out_rows, nbytes):
+    """where a transcode writes: the caller's out_device, or a buffer of nbytes() bytes of our own, freed on the way out"""
+    if out_device is not None:
+        yield out_device
+        return
+    if out_row_pitch or out_rows:
+        raise ValueError("out_row_pitch / out_rows describe a caller-owned raster: give out_device")
+    d_out = ctx.alloc(max(nbytes(), 1))
+    try:
+        yield d_out
+    finally:
+        ctx.free(d_out)
+
+
 def transcode_uastc_blocks(ctx, blocks, nbx, nby, target, *, width=None, height=None, high_quality=False, channels=None, out_device=None,
                            out_row_pitch=0, out_rows=0):
     """blocks: (nby * nbx, 16) uint8 array in raster order (uploaded once) or a device pointer (int) to that many resident blocks.
@@ -47,34 +63,27 @@ def transcode_uastc_blocks(ctx, blocks, nbx, nby, target, *, width=None, height=
         raise ValueError("channels: up to two values in 0..3")
     c0, c1 = (int(ch[0]) if len(ch) > 0 else -1), (int(ch[1]) if len(ch) > 1 else -1)
     own = None
-    if isinstance(blocks, np.ndarray):
-        blocks = np.ascontiguousarray(blocks, np.uint8)
-        if blocks.size != n * 16:
-            raise ValueError(f"{nbx} x {nby} blocks need {n * 16} bytes, got {blocks.size}")
-        d_blk = own = ctx.upload(blocks) if n else 0
-    else:
-        d_blk = blocks
-    if out_device is None and (out_row_pitch or out_rows):
-        raise ValueError("out_row_pitch / out_rows describe a caller-owned raster: give out_device")
-    nbytes = ctx.lib.transcode_output_bytes(nbx, nby, width, height, target)
-    d_out = out_device if out_device is not None else ctx.alloc(max(nbytes, 1))
     try:
-        invalid = C.c_uint32(0)
-        if n:
-            ctx.check(ctx.lib.k_transcode_uastc(ctx.h, C.c_void_p(d_blk), nbx, nby, width, height, target, DECODE_FLAGS_HIGH_QUALITY if high_quality else 0, c0, c1,
-                                                C.c_void_p(d_out), int(out_row_pitch), int(out_rows), C.byref(invalid)), "transcode_uastc")
-        if invalid.value:
-            raise InvalidBlocksError(invalid.value, n)
-        if out_device is not None:
-            return None
-        if target == RGBA32:
-            return ctx.download(d_out, (height, width, 4), np.uint8) if n else np.zeros((0, 0, 4), np.uint8)
-        return ctx.download(d_out, (n, BYTES_PER_BLOCK[target]), np.uint8) if n else np.zeros((0, BYTES_PER_BLOCK[target]), np.uint8)
+        if isinstance(blocks, np.ndarray):
+            blocks = np.ascontiguousarray(blocks, np.uint8)
+            if blocks.size != n * 16:
+                raise ValueError(f"{nbx} x {nby} blocks need {n * 16} bytes, got {blocks.size}")
+            blocks = own = ctx.upload(blocks) if n else 0
+        with _output(ctx, out_device, out_row_pitch, out_rows, lambda: ctx.lib.transcode_output_bytes(nbx, nby, width, height, target)) as d_out:
+            invalid = C.c_uint32(0)
+            if n:
+                ctx.check(ctx.lib.k_transcode_uastc(ctx.h, C.c_void_p(blocks), nbx, nby, width, height, target, DECODE_FLAGS_HIGH_QUALITY if high_quality else 0, c0, c1,
+                                                    C.c_void_p(d_out), int(out_row_pitch), int(out_rows), C.byref(invalid)), "transcode_uastc")
+            if invalid.value:
+                raise InvalidBlocksError(invalid.value, n)
+            if out_device is not None:
+                return None
+            if target == RGBA32:
+                return ctx.download(d_out, (height, width, 4), np.uint8) if n else np.zeros((0, 0, 4), np.uint8)
+            return ctx.download(d_out, (n, BYTES_PER_BLOCK[target]), np.uint8) if n else np.zeros((0, BYTES_PER_BLOCK[target]), np.uint8)
     finally:
         if own:
             ctx.free(own)
-        if out_device is None:
-            ctx.free(d_out)
 
 
 # ---------------------------------------------------------------- block formats back to pixels
@@ -96,32 +105,26 @@ def unpack_blocks(ctx, blocks, nbx, nby, fmt, *, width=None, height=None, out_de
     width, height = int(width or nbx * 4), int(height or nby * 4)
     if not (0 < width <= nbx * 4 and 0 < height <= nby * 4) and n:
         raise ValueError(f"{width} x {height} pixels do not fit {nbx} x {nby} blocks")
-    if out_device is None and (out_row_pitch or out_rows):
-        raise ValueError("out_row_pitch / out_rows describe a caller-owned raster: give out_device")
-    own = None
-    if isinstance(blocks, np.ndarray):
-        blocks = np.ascontiguousarray(blocks, np.uint8)
-        if blocks.size != n * unit:
-            raise ValueError(f"{nbx} x {nby} blocks need {n * unit} bytes, got {blocks.size}")
-        d_blk = own = ctx.upload(blocks) if n else 0
-    else:
-        d_blk = blocks
-    d_out = out_device if out_device is not None else ctx.alloc(max(ctx.lib.unpack_output_bytes(nbx, nby, width, height, 0, 0), 1))
-    try:
-        invalid = C.c_uint32(0)
-        if n:
-            ctx.check(ctx.lib.k_unpack_blocks(ctx.h, C.c_void_p(d_blk), nbx, nby, width, height, fmt, C.c_void_p(d_out), int(out_row_pitch), int(out_rows), C.byref(invalid)),
-                      "unpack_blocks")
-        if invalid.value:
-            raise InvalidBlocksError(invalid.value, n, "BC7")
-        if out_device is not None:
-            return None
-        return ctx.download(d_out, (height, width, 4), np.uint8) if n else np.zeros((0, 0, 4), np.uint8)
-    finally:
-        if own:
-            ctx.free(own)
-        if out_device is None:
-            ctx.free(d_out)
+    with _output(ctx, out_device, out_row_pitch, out_rows, lambda: ctx.lib.unpack_output_bytes(nbx, nby, width, height, 0, 0)) as d_out:
+        own = None
+        try:
+            if isinstance(blocks, np.ndarray):
+                blocks = np.ascontiguousarray(blocks, np.uint8)
+                if blocks.size != n * unit:
+                    raise ValueError(f"{nbx} x {nby} blocks need {n * unit} bytes, got {blocks.size}")
+                blocks = own = ctx.upload(blocks) if n else 0
+            invalid = C.c_uint32(0)
+            if n:
+                ctx.check(ctx.lib.k_unpack_blocks(ctx.h, C.c_void_p(blocks), nbx, nby, width, height, fmt, C.c_void_p(d_out), int(out_row_pitch), int(out_rows), C.byref(invalid)),
+                          "unpack_blocks")
+            if invalid.value:
+                raise InvalidBlocksError(invalid.value, n, "BC7")
+            if out_device is not None:
+                return None
+            return ctx.download(d_out, (height, width, 4), np.uint8) if n else np.zeros((0, 0, 4), np.uint8)
+        finally:
+            if own:
+                ctx.free(own)
 
 
 # ---------------------------------------------------------------- containers
@@ -314,36 +317,31 @@ def transcode_etc1s_image(ctx, decoded, image, target, *, out_device=None, out_r
     the (height, width, 4) u8 raster for RGBA32 and the (height, width) u16 raster for the 16-bit formats; with out_device (room for out_rows x out_row_pitch
     pixels when those are given) the output stays there and None is returned."""
     target = _check_etc1s_target(target)
-    if out_device is None and (out_row_pitch or out_rows):
-        raise ValueError("out_row_pitch / out_rows describe a caller-owned raster: give out_device")
     nbx, nby, w, h = image["num_blocks_x"], image["num_blocks_y"], image["width"], image["height"]
     ep_pal = np.ascontiguousarray(decoded["endpoint_palette"], np.uint8).reshape(-1, 4)
     sel_pal = np.ascontiguousarray(decoded["selector_palette"], np.uint32).reshape(-1)
     with_alpha = image["alpha_endpoint_indices"] is not None and target in (RGBA32, RGBA4444)
     names = ["endpoint_indices", "selector_indices"] + (["alpha_endpoint_indices", "alpha_selector_indices"] if with_alpha else [])
     held = []
-    try:
-        for a in [ep_pal, sel_pal] + [np.ascontiguousarray(image[k], np.uint16).reshape(-1) for k in names]:
-            held.append(ctx.upload(a))
-        d_alpha = (held[4], held[5]) if with_alpha else (None, None)
-        nbytes = ctx.lib.etc1s_transcode_output_bytes(nbx, nby, w, h, target, 0, 0)
-        d_out = out_device if out_device is not None else ctx.alloc(max(nbytes, 1))
-        if out_device is None:
-            held.append(d_out)
-        invalid = C.c_uint32(0)
-        ctx.check(ctx.lib.k_transcode_etc1s_counted(ctx.h, C.c_void_p(held[0]), ep_pal.shape[0], C.c_void_p(held[1]), sel_pal.size, C.c_void_p(held[2]), C.c_void_p(held[3]),
-                                                    C.c_void_p(d_alpha[0]), C.c_void_p(d_alpha[1]), nbx, nby, w, h, target, C.c_void_p(d_out), int(out_row_pitch), int(out_rows),
-                                                    C.byref(invalid)), "transcode_etc1s")
-        if invalid.value:
-            raise ValueError(f"{invalid.value} of {nbx * nby} blocks have an index past its palette")
-        if out_device is not None:
-            return None
-        if target in ETC1S_BYTES_PER_BLOCK:
-            return ctx.download(d_out, (nbx * nby, 8), np.uint8)
-        return ctx.download(d_out, (h, w, 4), np.uint8) if target == RGBA32 else ctx.download(d_out, (h, w), np.uint16)
-    finally:
-        for p in held:
-            ctx.free(p)
+    with _output(ctx, out_device, out_row_pitch, out_rows, lambda: ctx.lib.etc1s_transcode_output_bytes(nbx, nby, w, h, target, 0, 0)) as d_out:
+        try:
+            for a in [ep_pal, sel_pal] + [np.ascontiguousarray(image[k], np.uint16).reshape(-1) for k in names]:
+                held.append(ctx.upload(a))
+            d_alpha = (held[4], held[5]) if with_alpha else (None, None)
+            invalid = C.c_uint32(0)
+            ctx.check(ctx.lib.k_transcode_etc1s_counted(ctx.h, C.c_void_p(held[0]), ep_pal.shape[0], C.c_void_p(held[1]), sel_pal.size, C.c_void_p(held[2]), C.c_void_p(held[3]),
+                                                        C.c_void_p(d_alpha[0]), C.c_void_p(d_alpha[1]), nbx, nby, w, h, target, C.c_void_p(d_out), int(out_row_pitch),
+                                                        int(out_rows), C.byref(invalid)), "transcode_etc1s")
+            if invalid.value:
+                raise ValueError(f"{invalid.value} of {nbx * nby} blocks have an index past its palette")
+            if out_device is not None:
+                return None
+            if target in ETC1S_BYTES_PER_BLOCK:
+                return ctx.download(d_out, (nbx * nby, 8), np.uint8)
+            return ctx.download(d_out, (h, w, 4), np.uint8) if target == RGBA32 else ctx.download(d_out, (h, w), np.uint16)
+        finally:
+            for p in held:
+                ctx.free(p)
 
 
 def transcode_etc1s_file(ctx, data, target, *, level=0, layer=0, face=0):

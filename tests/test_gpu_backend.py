@@ -178,6 +178,32 @@ def test_compress_matches_reference_command_line(hip_ctx, tmp_path, name, kw, cl
     assert mine.shape == cli.shape and (mine == cli).all(), name
 
 
+def tiny_alpha_image(w, h):
+    """a bare image with an alpha that is neither 255 nor constant (one pixel: 77)"""
+    img = np.ascontiguousarray(synth(24, 16, 40 + w)[:h, :w])
+    yy, xx = np.mgrid[0:h, 0:w]
+    img[..., 3] = (77 + 37 * xx + 23 * yy) % 251
+    return img
+
+
+@pytest.mark.skipif(not __import__("helpers").have_ref_cli(), reason="oracle/_ref/basisu not present")
+@pytest.mark.parametrize("kw,cli_args", [(dict(quality=128, mipmaps=True), ["-etc1s", "-q", "128", "-mipmap"]),
+                                         (dict(uastc=True, mipmaps=True, ktx2=True), ["-uastc", "-mipmap", "-ktx2_no_zstandard"])], ids=["etc1s_basis", "uastc_ktx2"])
+@pytest.mark.parametrize("w,h", [(1, 1), (5, 7), (21, 13)])
+def test_tiny_bare_images_with_alpha_match_reference_command_line(hip_ctx, tmp_path, w, h, kw, cli_args):
+    """the bare-image route where the one-launch tiling can go wrong: pixel-by-pixel clamped loads, the colour and alpha modes of an ETC1S slice, levels of one block,
+    a wave that covers many one-block slices -- against `basisu <options> x.png`, byte for byte"""
+    from helpers import save_png, run_ref_cli, basis_file_key_values, ktx2_file_key_values
+    from basis_universal_amd.compress import compress
+    img = tiny_alpha_image(w, h)
+    assert (img[..., 3] != 255).any()
+    save_png(tmp_path / "x.png", img)
+    ktx2 = bool(kw.get("ktx2"))
+    cli = run_ref_cli(tmp_path / "x.png", *cli_args, ktx2=ktx2)
+    mine = compress(hip_ctx, img, key_values=(ktx2_file_key_values if ktx2 else basis_file_key_values)(cli), **kw)
+    assert mine.shape == cli.shape and (mine == cli).all(), (w, h)
+
+
 @needs_ref
 @pytest.mark.parametrize("level", [1, 2])
 def test_video_clip_matches_reference(hip_ctx, level):

@@ -182,9 +182,25 @@ def test_defaults_change_nothing_and_do_not_launch_the_prepare_kernel(hip_ctx, c
         hip_ctx.profile_enable(False)
     assert named.tobytes() == plain.tobytes()
     assert "prepare_source" not in regions and "renormalize_normal_map" not in regions
-    assert ("split_alpha" in regions) == ("uastc" not in codec)
-    if "split_alpha" in regions:
-        assert regions["split_alpha"][1] == 5      # one launch per level
+    # every slice of the call is tiled by one launch, straight from the level rasters: no plane is split off and nothing is tiled slice by slice
+    assert "split_alpha" not in regions and "extract_blocks" not in regions
+    assert regions["extract_slices"][1] == 1
+
+
+def test_with_stats_the_etc1s_alpha_planes_are_split_and_the_file_is_the_same(hip_ctx):
+    """the stats stage reads planes: one split per level (the five levels of 20x28), the tiles cut from those planes by the one launch, the same bytes"""
+    img, codec = H.alpha_image(20, 28, 5), dict(quality=128, mipmaps=True)
+    plain = compress(hip_ctx, img, **codec)
+    hip_ctx.profile_enable(True)
+    try:
+        named = compress(hip_ctx, img, **codec, **DEFAULTS, stats=[])
+        regions = profile_regions(hip_ctx)
+    finally:
+        hip_ctx.profile_enable(False)
+    assert named.tobytes() == plain.tobytes()
+    assert "prepare_source" not in regions and "renormalize_normal_map" not in regions and "extract_blocks" not in regions
+    assert regions["split_alpha"][1] == 5
+    assert regions["extract_slices"][1] == 1
 
 
 def test_etc1s_alpha_golden_survives_the_device_split(hip_ctx):

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""The source side of compress() with several images, measured on the device: resident level-0 rasters -> resident tiles of every slice, once with the batched
-kernel (bu_hip_k_extract_slices: the mip launches, then ONE launch for every slice) and once the way the single-image path does it per image and level
-(split_alpha + an allocation, then k_extract_blocks per slice), alternating; the same two from resident LEVELS (the tiling alone, without the mip launches both
-sides share); plus the whole compress() call and the launch counts of both.
+"""The source side of compress(), measured on the device: resident level-0 rasters -> resident tiles of every slice, once the way compress() does it (the mip launches,
+then ONE bu_hip_k_extract_slices launch for every slice) and once slice by slice (per level split_alpha + an allocation, then k_extract_blocks per slice),
+alternating; the same two from resident LEVELS (the tiling alone, without the mip chain both sides share); plus the whole compress() call and the launch counts of both.
+The mip chains are mipmap.resident_chain's, as in compress(): both sides allocate their levels inside the timed part.
 
-Workloads: `video` -- 64 frames of 256x256 with alpha, ETC1S video (128 slices); `cubemap` -- six 1024x1024 faces with mips, UASTC (66 slices).
+Workloads: `video` -- 64 frames of 256x256 with alpha, ETC1S video (128 slices); `cubemap` -- six 1024x1024 faces with mips, UASTC (66 slices); and the bare images
+`bare_etc1s_4096` (one opaque 4096x4096, ETC1S q128, no mips: ONE large slice), `bare_etc1s_alpha_2048` and `bare_uastc_alpha_2048` (one 2048x2048 with alpha, mips),
+whose compress() call is timed over all --repeats rounds after 3 warm-up calls.
 Times are host clock around work that ends in a stream synchronise, after warm-up; per side the median and the extremes of --repeats rounds.
 The launch counts come from a separate profiled pass (bu_hip_profile_*), not from the timed rounds. One JSON line per workload.
-usage: multi_image_bench.py [--workload video|cubemap|all] [--repeats N] [--out FILE]"""
+usage: multi_image_bench.py [--workload NAME|bare|all] [--repeats N] [--out FILE]"""
 import argparse
 import json
 import pathlib
@@ -39,7 +41,17 @@ def workloads():
 
     def cubemap():
         return [helpers.synth(1024, 1024, 910 + i) for i in range(6)], dict(tex_type="cubemap", uastc=True, mipmaps=True), True
-    return {"video": video, "cubemap": cubemap}
+
+    def bare(side, alpha, **kw):
+        def make():
+            img = np.ascontiguousarray(helpers.synth(side, side, 920 + side % 7))
+            if alpha:
+                yy, xx = np.mgrid[0:side, 0:side]
+                img[..., 3] = np.clip(128 + 100 * np.sin(xx / 17.0) * np.cos(yy / 13.0), 0, 255).astype(np.uint8)
+            return img, kw, True
+        return make
+    return {"video": video, "cubemap": cubemap, "bare_etc1s_4096": bare(4096, False, quality=128), "bare_etc1s_alpha_2048": bare(2048, True, mipmaps=True),
+            "bare_uastc_alpha_2048": bare(2048, True, uastc=True, mipmaps=True)}
 
 
 class Resident:
@@ -53,12 +65,16 @@ class Resident:
         self.slices, self.sources = source.slice_table([self.levels] * len(images), uastc=uastc, any_alpha=self.any_alpha, image_alpha=[self.any_alpha] * len(images))
         self.total = sum(s[1] * s[2] for s in self.slices)
         self.d_tiles = ctx.alloc(self.total * 64)
-        # every level's buffer is allocated once, so that neither side pays for it; the per-slice side splits alpha IN PLACE (as compress() does for one image), so it
-        # works on a copy of level 0 that is restored outside the timed part (restore_copies)
-        self.chains = [[ctx.upload(np.ascontiguousarray(img))] + [ctx.alloc(lw * lh * 4) for lw, lh in self.levels[1:]] for img in images]
+        # resident levels for the tiling alone; the per-slice side splits alpha IN PLACE, so it works on a copy that is restored outside the timed part (restore_copies)
+        self.owned = [self.d_tiles]
+        self.chains = self.make_levels([[self.upload(img)] for img in images], self.owned)
         self.copies = [[ctx.alloc(lw * lh * 4) for lw, lh in self.levels] for _ in images]
-        self.make_levels(self.chains)
+        self.owned += [d for copy in self.copies for d in copy]
         self.restore_copies()
+
+    def upload(self, img):
+        self.owned.append(self.ctx.upload(np.ascontiguousarray(img)))
+        return self.owned[-1]
 
     def restore_copies(self):
         for chain, copy in zip(self.chains, self.copies):
@@ -66,46 +82,40 @@ class Resident:
                 self.ctx.memcpy_d2d(d_dst, d_src, lw * lh * 4)
         self.ctx.sync()
 
-    def make_levels(self, chains):
-        ctx = self.ctx
-        for chain in chains:
-            for at, (lw, lh) in enumerate(self.levels[1:]):
-                sw, sh = self.levels[at]
-                ctx.check(mipmap._lib().bu_generate_mipmap_level(ctx.h, chain[at], sw, sh, chain[at + 1], lw, lh, 1, b"kaiser", 1.0, 1, 4 if self.any_alpha else 3),
-                          "bu_generate_mipmap_level")
+    def make_levels(self, chains, owned):
+        return [mipmap.resident_chain(self.ctx, owned, chain[0], self.levels, num_comps=4 if self.any_alpha else 3) for chain in chains]
 
     def batched(self, levels=True):
-        if levels:
-            self.make_levels(self.chains)
-        entries = [(self.chains[k][level], s[3], s[4], 0, mode, s[0]) for s, (k, level, mode) in zip(self.slices, self.sources)]
+        made = []
+        chains = self.make_levels(self.chains, made) if levels else self.chains
+        entries = [(chains[k][level], s[3], s[4], 0, mode, s[0]) for s, (k, level, mode) in zip(self.slices, self.sources)]
         source.extract_slices_resident(self.ctx, entries, self.d_tiles)
         self.ctx.sync()
+        for d in made:
+            self.ctx.free(d)
 
     def per_slice(self, levels=True):
-        """what compress() does for ONE image, here per image: per level split_alpha into the level's own buffer and a newly allocated alpha plane, then
-        k_extract_blocks per plane"""
-        ctx, split, planes_owned, first = self.ctx, self.any_alpha and not self.uastc, [], 0
-        if levels:
-            self.make_levels(self.copies)
-        for chain in self.copies:
+        """slice by slice: per level split_alpha into the level's own buffer and a newly allocated alpha plane, then k_extract_blocks per plane"""
+        ctx, split, made, first = self.ctx, self.any_alpha and not self.uastc, [], 0
+        for chain in (self.make_levels(self.copies, made) if levels else self.copies):
             for d_raster, (lw, lh) in zip(chain, self.levels):
                 planes = [d_raster]
                 if split:
                     planes.append(ctx.alloc(lw * lh * 4))
-                    planes_owned.append(planes[1])
+                    made.append(planes[1])
                     source.split_alpha_resident(ctx, d_raster, lw, lh, planes[0], planes[1])
                 for d_plane in planes:
                     ctx.check(ctx.lib.k_extract_blocks(ctx.h, d_plane, lw, lh, lw * 4, self.d_tiles + first * 64), "k_extract_blocks")
                     first += ((lw + 3) // 4) * ((lh + 3) // 4)
         ctx.sync()
-        for d in planes_owned:
+        for d in made:
             ctx.free(d)
 
     def tiles(self):
         return self.ctx.download(self.d_tiles, (self.total, 64), np.uint8)
 
     def close(self):
-        for d in [self.d_tiles] + [d for chain in self.chains + self.copies for d in chain]:
+        for d in self.owned:
             self.ctx.free(d)
 
 
@@ -129,7 +139,8 @@ def launches(ctx, fn):
 
 def run(ctx, name, make, repeats):
     images, kw, _ = make()
-    res = Resident(ctx, images, bool(kw.get("uastc")), bool(kw.get("mipmaps")))
+    bare = isinstance(images, np.ndarray)
+    res = Resident(ctx, [images] if bare else images, bool(kw.get("uastc")), bool(kw.get("mipmaps")))
     try:
         res.per_slice()
         expected = res.tiles()
@@ -150,9 +161,10 @@ def run(ctx, name, make, repeats):
         count_a = launches(ctx, res.batched)
         res.restore_copies()
         count_b = launches(ctx, res.per_slice)
-        compress(ctx, images, **kw)                           # warm-up of the whole call
-        whole = [timed(lambda: compress(ctx, images, **kw)) for _ in range(3)]
-        return {"workload": name, "images": len(images), "size": list(images[0].shape[1::-1]), "slices": len(res.slices), "blocks": res.total, "tiles_identical": same,
+        for _ in range(3 if bare else 1):                     # warm-up of the whole call
+            compress(ctx, images, **kw)
+        whole = [timed(lambda: compress(ctx, images, **kw)) for _ in range(repeats if bare else 3)]
+        return {"workload": name, "images": len(res.chains), "size": list(res.levels[0]), "slices": len(res.slices), "blocks": res.total, "tiles_identical": same,
                 "rasters_to_tiles_batched": summary(a), "rasters_to_tiles_per_slice": summary(b), "levels_to_tiles_batched": summary(a_tiles),
                 "levels_to_tiles_per_slice": summary(b_tiles), "launches_batched": count_a, "launches_per_slice": count_b,
                 "compress_call": summary(whole), "repeats": repeats}
@@ -162,14 +174,14 @@ def run(ctx, name, make, repeats):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="all", choices=["video", "cubemap", "all"])
+    ap.add_argument("--workload", default="all", choices=[*workloads(), "bare", "all"])
     ap.add_argument("--repeats", type=int, default=50)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     ctx = capi.Context(0)       # no device, no numbers: this raises
     lines = []
     for name, make in workloads().items():
-        if args.workload in ("all", name):
+        if args.workload in ("all", name) or (args.workload == "bare" and name.startswith("bare_")):
             lines.append(json.dumps(run(ctx, name, make, args.repeats)))
             print(lines[-1], flush=True)
     ctx.close()
