@@ -56,7 +56,8 @@ def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=
     """image: (h, w, 4) uint8 RGBA, or a sequence of such arrays (below). Returns the file as a uint8 array.
     ETC1S: quality 1-255 (`-q`), comp_level 0-6 (`-comp_level`). UASTC: uastc_level 0-4, uastc_rdo_lambda (`-uastc_rdo_l`; None = no post-pass, any float
     incl. 0.0 = post-pass on, as m_rdo_uastc_ldr_4x4 + its scalar), uastc_rdo_jobs = the strips of the post-pass (the reference: min(4, pool threads) when
-    multithreaded, else 1; comp.cpp:2078). `**unified_quality_effort(...)` gives the settings of `-quality` / `-effort`.
+    multithreaded, else 1; comp.cpp:2078). The post-pass works per slice, as the reference's does, and is ONE uastc.uastc_rdo_slices call for all slices of the file:
+    the strips of every image and level walk side by side. `**unified_quality_effort(...)` gives the settings of `-quality` / `-effort`.
     max_threads: the reference's codebook-thread configuration (0 / 1 = `-no_multithreading`; T > 1 = the T-way partitioned codebook build its
     multi-threaded default takes from 262,144 distinct training vectors up, enc.h:2086-2215: etc1s.reference_max_threads() gives the T a host would use).
     mipmaps: the compressor's defaults (Kaiser, sRGB-aware, wrapping, down to 1x1). srgb: perceptual metrics + sRGB transfer function flag.
@@ -226,10 +227,8 @@ def _encode(ctx, owned, d_all, slices, has_alpha, *, uastc, quality, comp_level,
         owned.append(d_out)
         _uastc.encode_uastc_blocks(ctx, d_all, flags, n_blocks=total_blocks, out_device=d_out)
         if rdo:
-            at = 0
-            for n in slice_blocks:   # the post-pass runs per slice (comp.cpp:2066-2082)
-                _uastc.uastc_rdo(ctx, d_out + at * 16, d_all + at * 64, _uastc.RdoParams(m_lambda=float(uastc_rdo_lambda)), int(uastc_level), uastc_rdo_jobs, n_blocks=n)
-                at += n
+            # the post-pass works per slice (comp.cpp:2066-2082): one call, every slice's strips side by side
+            _uastc.uastc_rdo_slices(ctx, d_out, d_all, slice_blocks, _uastc.RdoParams(m_lambda=float(uastc_rdo_lambda)), int(uastc_level), uastc_rdo_jobs)
         packed = ctx.download(d_out, (total_blocks, 16), np.uint8)
         if ktx2:
             return uastc_ktx2_file(packed, slices, srgb=srgb, tex_type=tex_type, has_alpha=has_alpha, key_values=key_values)

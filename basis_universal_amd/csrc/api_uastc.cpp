@@ -1,6 +1,7 @@
 // api_uastc.cpp -- UASTC behind the C ABI of libbasisu_hip.so (rows a16-a19): encode (device-resident and blocking), transcode, RDO, the pipeline of images in flight.
 #include "api_internal.h"
 #include "uastc_kernels.h"
+#include "uastc_rdo_strips.h"
 #include "uastc_transcode_kernels.h"
 
 // ---------------------------------------------------------------- UASTC (+ RDO) over a stream of images: several in flight (BASELINE configs[4])
@@ -99,18 +100,19 @@ static bool uastc_rdo_params_ok(bu_hip_context* ctx, const bu_uastc_rdo_params* 
 // The strip walks of uastc_rdo behind its prepare pass: the lean build (strips without a block of a sensitive mode: four waves per SIMD) on the context's stream and,
 // when endpoint refinement is on, the build with the refit in it (the flagged strips) on the side stream beside it -- forked and joined with events, nobody waits on
 // the host. Without a side stream the two launches simply follow each other.
-static int uastc_rdo_walks(bu_hip_context* ctx, void* d_blocks, const void* d_px, uint32_t n_blocks, const float* fp, const uint32_t* up, uint32_t flags, uint32_t total_jobs, void* ws) {
-    const bool refit = up[2] != 0;
+// launch(stream, phase): one build of the walk (phase 1 lean, 3 with the refit) over the call's strips
+extern "C++" template <class Launch>
+static int uastc_rdo_walks(bu_hip_context* ctx, bool refit, Launch launch) {
     if (ctx->walk_stream) {
         // a pipeline lane with reserved walk CUs: both builds of the walk on streams of their own whose CU masks are the reserved set, forked off and joined back to the
         // lane's stream (which may not use those CUs): the walks' waves never wait for a slot behind a chip-filling kernel, and never share a SIMD with one
         BU_TRY(ctx, hipEventRecord(ctx->side_fork, ctx->stream));
         BU_TRY(ctx, hipStreamWaitEvent(ctx->walk_stream, ctx->side_fork, 0));
-        BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->walk_stream, 1, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws));
+        BU_TRY(ctx, launch(ctx->walk_stream, 1));
         BU_TRY(ctx, hipEventRecord(ctx->walk_join, ctx->walk_stream));
         if (refit) {
             BU_TRY(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->side_fork, 0));
-            BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->side_stream, 3, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws));
+            BU_TRY(ctx, launch(ctx->side_stream, 3));
             BU_TRY(ctx, hipEventRecord(ctx->side_join, ctx->side_stream));
             BU_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_join, 0));
         }
@@ -121,12 +123,12 @@ static int uastc_rdo_walks(bu_hip_context* ctx, void* d_blocks, const void* d_px
     if (side) {
         BU_TRY(ctx, hipEventRecord(ctx->side_fork, ctx->stream));
         BU_TRY(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->side_fork, 0));
-        BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->side_stream, 3, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws));
+        BU_TRY(ctx, launch(ctx->side_stream, 3));
         BU_TRY(ctx, hipEventRecord(ctx->side_join, ctx->side_stream));
     }
-    BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->stream, 1, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws));
+    BU_TRY(ctx, launch(ctx->stream, 1));
     if (side) BU_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_join, 0));
-    else if (refit) BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->stream, 3, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws));
+    else if (refit) BU_TRY(ctx, launch(ctx->stream, 3));
     return 1;
 }
 
@@ -149,7 +151,7 @@ int bu_hip_k_uastc_rdo(bu_hip_context* ctx, void* d_blocks, const void* d_px, ui
     }
     {
         prof_scope ps(ctx, "uastc_rdo_strips");   // both walks: the scope ends behind the join
-        if (!uastc_rdo_walks(ctx, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p)) return 0;
+        if (!uastc_rdo_walks(ctx, up[2] != 0, [&](hipStream_t st, int phase) { return bu::launch_uastc_rdo_phase(st, phase, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p); })) return 0;
     }
     // how many blocks each strip modified: sizes the finish launch (a 16-byte copy per 4 strips; the walk has to be over anyway)
     std::vector<uint32_t> per_strip(bu::uastc_rdo_strips(n_blocks, total_jobs));
@@ -176,6 +178,73 @@ int bu_hip_k_uastc_rdo(bu_hip_context* ctx, void* d_blocks, const void* d_px, ui
     return 1;
 }
 
+size_t bu_hip_uastc_rdo_slices_workspace_bytes(const uint32_t* slice_blocks, uint32_t n_slices, uint32_t total_jobs) {
+    bu::rdo_slices_layout L;
+    if (!slice_blocks || !n_slices || !bu::rdo_slices_layout_build(slice_blocks, n_slices, total_jobs, L)) return 0;
+    return L.total_bytes;
+}
+
+// bu_hip_k_uastc_rdo over every slice of a file in one pass: the strips of all slices walk side by side (one prepare launch, one launch per build of the walk,
+// one finish launch), and the host waits twice whatever n_slices is: for the strip counts that size the finish, and for the counters.
+int bu_hip_k_uastc_rdo_slices(bu_hip_context* ctx, void* d_blocks, const void* d_px, const uint32_t* slice_blocks, uint32_t n_slices, const bu_uastc_rdo_params* params,
+                              uint32_t flags, uint32_t total_jobs, uint32_t* out_stats) {
+    if (!ctx) return 0;
+    if (!d_blocks || !d_px || !slice_blocks || !params) { set_error(ctx, "uastc_rdo_slices: null pointer"); return 0; }
+    if (!n_slices) { set_error(ctx, "uastc_rdo_slices: no slices"); return 0; }
+    bu::rdo_slices_layout L;
+    if (!bu::rdo_slices_layout_build(slice_blocks, n_slices, total_jobs, L)) { set_error(ctx, "uastc_rdo_slices: more than %u blocks in all", bu::RDO_SLICES_MAX_BLOCKS); return 0; }
+    if (!uastc_rdo_params_ok(ctx, params)) return 0;
+    device_guard g(ctx->device);
+    if (out_stats)
+        for (uint32_t s = 0; s < n_slices; s++) out_stats[4 * s] = out_stats[4 * s + 1] = out_stats[4 * s + 2] = 0, out_stats[4 * s + 3] = L.slice_strips[s];
+    if (!L.total_blocks) return 1;
+    if (L.recs.back().slice == L.recs.front().slice) {
+        // ONE slice holds all the blocks (a bare image without mips): nothing to overlap, and the single-slice entry's builds of the walk were measured 0.4 - 0.9 %
+        // faster per block than the strip table's on a 4096^2 chain -- the call is that entry's, launch for launch
+        const uint32_t s = L.recs.front().slice, first = L.recs.front().first;
+        uint32_t one[4] = { 0, 0, 0, 0 };
+        if (!bu_hip_k_uastc_rdo(ctx, static_cast<char*>(d_blocks) + (size_t)first * 16, static_cast<const char*>(d_px) + (size_t)first * 64, slice_blocks[s], params, flags,
+                                total_jobs, one)) {
+            if (ctx->error.find("does not unpack") != std::string::npos) set_error(ctx, "uastc_rdo_slices: a block of slice %u does not unpack as UASTC", s);
+            return 0;
+        }
+        if (out_stats) { out_stats[4 * s] = one[0]; out_stats[4 * s + 1] = one[1]; out_stats[4 * s + 2] = one[2]; }
+        return 1;
+    }
+    const float fp[5] = { params->m_lambda, params->m_max_allowed_rms_increase_ratio, params->m_skip_block_rms_thresh, params->m_max_smooth_block_std_dev,
+                          params->m_smooth_block_max_error_scale };
+    const uint32_t up[3] = { params->m_lz_dict_size, params->m_lz_literal_cost, params->m_endpoint_refinement };
+    arena& ws = ctx->scratch[5];
+    BU_TRY(ctx, ws.reserve(L.total_bytes));
+    char* base = static_cast<char*>(ws.p);
+    BU_TRY(ctx, h2d(ctx, base + L.strips, L.recs.data(), L.recs.size() * sizeof(bu::rdo_strip_rec)));
+    BU_TRY(ctx, h2d(ctx, base + L.order_at, L.order.data(), L.order.size() * 4));
+    {
+        prof_scope ps(ctx, "uastc_rdo_slices_prepare");
+        BU_TRY(ctx, bu::launch_uastc_rdo_slices_phase(ctx->stream, 0, d_blocks, d_px, L, fp, up, ws.p));
+    }
+    {
+        prof_scope ps(ctx, "uastc_rdo_slices_strips");   // both walks: the scope ends behind the join
+        if (!uastc_rdo_walks(ctx, up[2] != 0, [&](hipStream_t st, int phase) { return bu::launch_uastc_rdo_slices_phase(st, phase, d_blocks, d_px, L, fp, up, ws.p); })) return 0;
+    }
+    // how many blocks each strip modified: sizes the finish launch (one download for all slices; the walks have to be over anyway)
+    std::vector<uint32_t> per_strip(L.recs.size());
+    if (!fetch(ctx, per_strip.data(), base + L.strip_counts, per_strip.size() * 4)) return 0;
+    uint32_t longest = 0;
+    for (uint32_t c : per_strip) longest = c > longest ? c : longest;
+    {
+        prof_scope ps(ctx, "uastc_rdo_slices_finish");
+        BU_TRY(ctx, bu::launch_uastc_rdo_slices_finish(ctx->stream, d_blocks, d_px, L, fp, up, flags, ws.p, longest));
+    }
+    std::vector<uint32_t> counters((size_t)n_slices * 4);   // per slice: modified, failed, refined, skipped
+    if (!fetch(ctx, counters.data(), base + L.counters, counters.size() * 4)) return 0;
+    for (uint32_t s = 0; s < n_slices; s++)
+        if (counters[4 * s + 1]) { set_error(ctx, "uastc_rdo_slices: a block of slice %u does not unpack as UASTC", s); return 0; }
+    if (out_stats)
+        for (uint32_t s = 0; s < n_slices; s++) { out_stats[4 * s] = counters[4 * s]; out_stats[4 * s + 1] = counters[4 * s + 2]; out_stats[4 * s + 2] = counters[4 * s + 3]; }
+    return 1;
+}
+
 static int uastc_rdo_enqueue(bu_hip_context* ctx, void* d_blocks, const void* d_px, uint32_t n_blocks, const bu_uastc_rdo_params* params, uint32_t flags, uint32_t total_jobs,
                              uint32_t* h_pinned_counters) {
     if (!uastc_rdo_params_ok(ctx, params)) return 0;
@@ -185,7 +254,7 @@ static int uastc_rdo_enqueue(bu_hip_context* ctx, void* d_blocks, const void* d_
     arena& ws = ctx->scratch[5];
     BU_TRY(ctx, ws.reserve(bu::uastc_rdo_workspace_bytes(n_blocks, total_jobs)));
     BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->stream, 0, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p));
-    if (!uastc_rdo_walks(ctx, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p)) return 0;
+    if (!uastc_rdo_walks(ctx, up[2] != 0, [&](hipStream_t st, int phase) { return bu::launch_uastc_rdo_phase(st, phase, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p); })) return 0;
     // the longest list a strip can have (every block of it modified): the launch does not wait for the walk to know better, surplus workgroups leave at once
     const uint32_t strips = bu::uastc_rdo_strips(n_blocks, total_jobs);
     const uint32_t longest = strips > 1 ? (total_jobs ? n_blocks / total_jobs : n_blocks) : n_blocks;

@@ -29,4 +29,14 @@ const void* uastc_rdo_strip_counts(void* d_workspace, uint32_t n_blocks, uint32_
 // device address of 4 x uint32 {modified, failed, refined, skipped} inside the workspace, valid after phase 1 (refined: after the finish)
 const void* uastc_rdo_counters(void* d_workspace, uint32_t n_blocks, uint32_t total_jobs);
 
+// uastc_rdo over several slices that lie back to back, every slice cut into its own strips, in one pass: the kernels read a strip table (uastc_rdo_strips.h:
+// rdo_slices_layout_build gives the table and the workspace's carve). The caller copies L.recs to d_workspace + L.strips and L.order to d_workspace + L.order_at
+// first. Phases: 0 clear + prepare over all blocks, 1 the lean walk and 3 the walk with the refit in it, each over all strips of all slices, longest strips first;
+// then the finish for the longest per-strip list (strip counts at d_workspace + L.strip_counts, 4 counters per slice at d_workspace + L.counters).
+struct rdo_slices_layout;
+hipError_t launch_uastc_rdo_slices_phase(hipStream_t st, int phase, void* d_blocks, const void* d_pixel_blocks, const rdo_slices_layout& L, const float* fparams,
+                                         const uint32_t* uparams, void* d_workspace);
+hipError_t launch_uastc_rdo_slices_finish(hipStream_t st, void* d_blocks, const void* d_pixel_blocks, const rdo_slices_layout& L, const float* fparams,
+                                          const uint32_t* uparams, uint32_t flags, void* d_workspace, uint32_t longest_list);
+
 } // namespace bu

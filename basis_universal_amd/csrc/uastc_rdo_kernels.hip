@@ -23,6 +23,7 @@
 
 #include "uastc_rdo.h"
 #include "uastc_kernels.h"
+#include "uastc_rdo_strips.h"
 
 namespace bu {
 using namespace bu_uastc;
@@ -45,13 +46,20 @@ struct rdo_workspace {
 };
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
-void strip_layout(uint32_t n, uint32_t total_jobs, uint32_t& per_job, uint32_t& n_strips, uint32_t& hist_cap) {
-    per_job = total_jobs ? n / total_jobs : 0;  // uastc_rdo, uastc_enc.cpp:4103-4111
-    if (total_jobs <= 1 || per_job <= 8) { per_job = 0; n_strips = 1; }
-    else n_strips = (n + per_job - 1) / per_job;
-    const uint32_t longest = per_job ? per_job : n;
-    hist_cap = 64;
-    while (hist_cap < 4 * (uint64_t)longest && hist_cap < (1u << 30)) hist_cap <<= 1;  // load <= 1/4: a bucket of 4 holds one key on average
+void strip_layout(uint32_t n, uint32_t total_jobs, uint32_t& per_job, uint32_t& n_strips, uint32_t& hist_cap) { rdo_strip_layout(n, total_jobs, per_job, n_strips, hist_cap); }
+static_assert(sizeof(rdo_info4) == RDO_INFO_BYTES && sizeof(hist_entry) == RDO_HIST_ENTRY_BYTES && RDO_TABLE_WORDS * 4 == RDO_TABLE_BYTES && sizeof(rdo_strip_rec) == 32, "uastc_rdo_strips.h");
+
+// The strip table form of the three kernels (TABLE builds of the walk and the finish, recs != nullptr in the prepare pass), for a call over several slices that lie
+// back to back (bu_hip_k_uastc_rdo_slices): a strip's range, history, mod_list offset and slice come from a record of `recs` (block order) instead of per_job and
+// the strip index, and `counters` holds four words per slice.
+// strip_of_block: the strip of block b = the last record whose first block is not behind it
+__device__ inline uint32_t strip_of_block(const rdo_strip_rec* __restrict__ recs, uint32_t n_recs, uint32_t b) {
+    uint32_t lo = 0, hi = n_recs;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (recs[mid].first <= b) lo = mid; else hi = mid;
+    }
+    return lo;
 }
 
 rdo_workspace carve(void* base, uint32_t n, uint32_t total_jobs, size_t* total) {
@@ -79,9 +87,11 @@ __device__ inline void load_tile(const uint4* px, uint32_t b, rgba8* out) {
     for (int k = 0; k < 4; k++) o[k] = px[(size_t)b * 4 + k];
 }
 
+// recs != nullptr: the strip table form. ONE kernel for both forms (a uniform branch where a strip is looked up, a handful of times per image): a second kernel in
+// this file would be a second caller of rdo_prepare and the functions under it, and the compiler then inlines them differently into the first.
 __global__ void __launch_bounds__(64) k_rdo_prepare(const uint4* __restrict__ blocks, const uint4* __restrict__ px, uint32_t n, rdo_params p,
                                                     rdo_info4* __restrict__ info, uint32_t* __restrict__ table, uint32_t* __restrict__ counters,
-                                                    uint32_t* __restrict__ strip_flags, uint32_t per_job) {
+                                                    uint32_t* __restrict__ strip_flags, uint32_t per_job, const rdo_strip_rec* __restrict__ recs, uint32_t n_recs) {
     const uint32_t b = blockIdx.x * 64 + threadIdx.x;
     if (b >= n) return;
     alignas(16) uint8_t blk[16];
@@ -91,7 +101,7 @@ __global__ void __launch_bounds__(64) k_rdo_prepare(const uint4* __restrict__ bl
     cand c;
     rdo_block_info bi;
     if (!rdo_prepare(blk, t, p, c, bi)) {
-        atomicExch(&counters[1], 1u);
+        atomicExch(&counters[recs ? recs[strip_of_block(recs, n_recs, b)].slice * 4 + 1 : 1], 1u);
         bi.mode = 8; bi.skip = 0; bi.ms_err = bi.rms_err = 0.0f; bi.scale = 1.0f;
         c.pattern = 0; c.ccs = 0;
     }
@@ -103,7 +113,7 @@ __global__ void __launch_bounds__(64) k_rdo_prepare(const uint4* __restrict__ bl
     }
     info[b] = o;
     if (bi.mode == 8 || bi.skip) return;
-    if (rdo_mode_reads_endpoint_bits(bi.mode) && p.endpoint_refinement) atomicOr(&strip_flags[per_job ? b / per_job : 0u], 1u);   // a handful per image
+    if (rdo_mode_reads_endpoint_bits(bi.mode) && p.endpoint_refinement) atomicOr(&strip_flags[recs ? strip_of_block(recs, n_recs, b) : (per_job ? b / per_job : 0u)], 1u);   // a handful per image
     texel_ends ends;
     rdo_texel_ends(c, ends);
     const uint32_t planes = ku_mode_planes[bi.mode], wbits = ku_mode_weight_bits[bi.mode];
@@ -281,20 +291,30 @@ struct cand_rec { uint64_t lo, hi; uint32_t slot, pad; };
 // content apart), so most strips take the LEAN build -- no refit in it, four waves per SIMD, a 256-register encode wave of the next batch fits beside it -- and
 // only the flagged ones the FAT one; both launches cover all strips and a workgroup whose strip belongs to the other returns at once. The launcher puts them on
 // two streams, so the chain of a batch is as long as before.
-template <bool RING, bool FAT>
+// TABLE: workgroup w walks strip order[w] (the longest strips start first) and reads it from its record, once, with uniform loads in front of the loop; the
+// candidate window's lower bound is the record's first block, so nothing looks back into another strip or another slice.
+template <bool RING, bool FAT, bool TABLE>
 __global__ void __launch_bounds__(RDO_THREADS) k_rdo_strips(uint4* blocks, const uint4* __restrict__ px, uint32_t n, uint32_t per_job, rdo_params p,
                                                             const rdo_info4* info, const uint32_t* __restrict__ table, hist_entry* hist_all,
                                                             uint32_t hist_cap, uint8_t* state, uint32_t* mod_list, uint32_t* strip_counts, uint32_t* counters,
-                                                            uint32_t ring_slots, const uint32_t* __restrict__ strip_flags) {
-    if ((strip_flags[blockIdx.x] != 0u) != FAT) return;
+                                                            uint32_t ring_slots, const uint32_t* __restrict__ strip_flags, const rdo_strip_rec* __restrict__ recs,
+                                                            const uint32_t* __restrict__ order) {
+    const uint32_t strip = TABLE ? order[blockIdx.x] : blockIdx.x;
+    if ((strip_flags[strip] != 0u) != FAT) return;
     extern __shared__ uint4 s_ring_mem[];
     __shared__ uint32_t s_table[RDO_TABLE_WORDS];
     __shared__ cand_rec s_cand[RDO_THREADS];
     __shared__ unsigned long long s_min;
     const uint32_t tid = threadIdx.x;
-    const uint32_t first = per_job ? blockIdx.x * per_job : 0;
-    const uint32_t last = per_job ? (first + per_job < n ? first + per_job : n) : n;
-    hist_entry* hist = hist_all + (size_t)blockIdx.x * hist_cap;
+    uint32_t first = per_job ? strip * per_job : 0;
+    uint32_t last = per_job ? (first + per_job < n ? first + per_job : n) : n;
+    hist_entry* hist = hist_all + (size_t)strip * hist_cap;
+    if (TABLE) {
+        const rdo_strip_rec r = recs[strip];
+        first = r.first; last = r.last; hist_cap = r.hist_cap;   // mod_ofs == first: a strip lists its modified blocks where they lie
+        hist = hist_all + r.hist_ofs;
+        counters += (size_t)r.slice * 4;
+    }
     const uint32_t bucket_mask = hist_cap / HIST_BUCKET - 1;
     const int window = (int)(p.lz_dict_size / 16 > 1 ? p.lz_dict_size / 16 : 1);
     uint4* ring = RING ? s_ring_mem : nullptr;
@@ -435,23 +455,26 @@ __global__ void __launch_bounds__(RDO_THREADS) k_rdo_strips(uint4* blocks, const
         pre = npre;
     }
     if (tid == 0) {
-        strip_counts[blockIdx.x] = n_modified;
+        strip_counts[strip] = n_modified;
         atomicAdd(&counters[0], n_modified);
         atomicAdd(&counters[3], n_skipped);
 #ifdef RDO_PROFILE
-        if (blockIdx.x == 0) for (int k = 0; k < 16; k++) reinterpret_cast<unsigned long long*>(counters + 16)[k] = (unsigned long long)prof[k];
+        if (strip == 0) for (int k = 0; k < 16; k++) reinterpret_cast<unsigned long long*>(counters + 16)[k] = (unsigned long long)prof[k];
 #endif
     }
 }
 
 // the modified blocks of strip s are listed in mod_list[s * per_job ...) (strip_counts[s] of them)
+// TABLE: strip = strip_base + blockIdx.y (a grid's y extent is limited), its list at its record's mod_list offset, `refined` counted for its slice
+template <bool TABLE>
 __global__ void __launch_bounds__(64, 2) k_rdo_finish(uint4* blocks, const uint4* __restrict__ px, uint32_t n, uint32_t per_job, enc_cfg e, rdo_params p,
                                                    const uint32_t* __restrict__ mod_list, const uint32_t* __restrict__ strip_counts,
-                                                   const uint8_t* __restrict__ state, uint32_t* counters) {
-    const uint32_t strip = blockIdx.y, k = blockIdx.x * 64 + threadIdx.x;  // grid.x covers the longest list
+                                                   const uint8_t* __restrict__ state, uint32_t* counters, const rdo_strip_rec* __restrict__ recs, uint32_t strip_base) {
+    const uint32_t strip = strip_base + blockIdx.y, k = blockIdx.x * 64 + threadIdx.x;  // grid.x covers the longest list
     if (k >= strip_counts[strip]) return;
-    const uint32_t b = mod_list[(size_t)strip * per_job + k];
+    const uint32_t b = mod_list[(TABLE ? (size_t)recs[strip].mod_ofs : (size_t)strip * per_job) + k];
     if (b >= n) return;
+    if (TABLE) counters += (size_t)recs[strip].slice * 4;
     alignas(16) uint8_t blk[16];
     *reinterpret_cast<uint4*>(blk) = blocks[b];
     alignas(16) rgba8 t[16];
@@ -504,7 +527,7 @@ hipError_t launch_uastc_rdo_phase(hipStream_t st, int phase, void* d_blocks, con
     case 0: {
         const hipError_t e = hipMemsetAsync(w.counters, 0, w.zero_bytes, st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_rdo_prepare, dim3(gx), dim3(64), 0, st, blocks, px, n, p, w.info, w.table, w.counters, w.strip_flags, per_job);
+        hipLaunchKernelGGL(k_rdo_prepare, dim3(gx), dim3(64), 0, st, blocks, px, n, p, w.info, w.table, w.counters, w.strip_flags, per_job, nullptr, 0u);
         break;
     }
     case 1:     // the lean walk: strips without a sensitive block
@@ -515,17 +538,17 @@ hipError_t launch_uastc_rdo_phase(hipStream_t st, int phase, void* d_blocks, con
         if (ring > RDO_RING_MAX) ring = 0;
         const bool fat = phase == 3;
         if (ring && fat)
-            hipLaunchKernelGGL((k_rdo_strips<true, true>), dim3(n_strips), dim3(RDO_THREADS), (size_t)ring * 16, st, blocks, px, n, per_job, p, w.info, w.table, w.hist,
-                               cap, w.state, w.mod_list, w.strip_counts, w.counters, ring, w.strip_flags);
+            hipLaunchKernelGGL((k_rdo_strips<true, true, false>), dim3(n_strips), dim3(RDO_THREADS), (size_t)ring * 16, st, blocks, px, n, per_job, p, w.info, w.table, w.hist,
+                               cap, w.state, w.mod_list, w.strip_counts, w.counters, ring, w.strip_flags, nullptr, nullptr);
         else if (ring)
-            hipLaunchKernelGGL((k_rdo_strips<true, false>), dim3(n_strips), dim3(RDO_THREADS), (size_t)ring * 16, st, blocks, px, n, per_job, p, w.info, w.table, w.hist,
-                               cap, w.state, w.mod_list, w.strip_counts, w.counters, ring, w.strip_flags);
+            hipLaunchKernelGGL((k_rdo_strips<true, false, false>), dim3(n_strips), dim3(RDO_THREADS), (size_t)ring * 16, st, blocks, px, n, per_job, p, w.info, w.table, w.hist,
+                               cap, w.state, w.mod_list, w.strip_counts, w.counters, ring, w.strip_flags, nullptr, nullptr);
         else if (fat)
-            hipLaunchKernelGGL((k_rdo_strips<false, true>), dim3(n_strips), dim3(RDO_THREADS), 0, st, blocks, px, n, per_job, p, w.info, w.table, w.hist, cap, w.state,
-                               w.mod_list, w.strip_counts, w.counters, 1u, w.strip_flags);
+            hipLaunchKernelGGL((k_rdo_strips<false, true, false>), dim3(n_strips), dim3(RDO_THREADS), 0, st, blocks, px, n, per_job, p, w.info, w.table, w.hist, cap, w.state,
+                               w.mod_list, w.strip_counts, w.counters, 1u, w.strip_flags, nullptr, nullptr);
         else
-            hipLaunchKernelGGL((k_rdo_strips<false, false>), dim3(n_strips), dim3(RDO_THREADS), 0, st, blocks, px, n, per_job, p, w.info, w.table, w.hist, cap, w.state,
-                               w.mod_list, w.strip_counts, w.counters, 1u, w.strip_flags);
+            hipLaunchKernelGGL((k_rdo_strips<false, false, false>), dim3(n_strips), dim3(RDO_THREADS), 0, st, blocks, px, n, per_job, p, w.info, w.table, w.hist, cap, w.state,
+                               w.mod_list, w.strip_counts, w.counters, 1u, w.strip_flags, nullptr, nullptr);
         break;
     }
     default: {
@@ -544,9 +567,61 @@ hipError_t launch_uastc_rdo_finish(hipStream_t st, void* d_blocks, const void* d
     strip_layout(n, total_jobs, per_job, n_strips, cap);
     enc_cfg e;
     make_cfg(flags, e);
-    hipLaunchKernelGGL(k_rdo_finish, dim3((longest_list + 63) / 64, n_strips), dim3(64), 0, st, static_cast<uint4*>(d_blocks), static_cast<const uint4*>(d_px), n,
-                       per_job, e, to_params(fparams, uparams), w.mod_list, w.strip_counts, w.state, w.counters);
+    hipLaunchKernelGGL(k_rdo_finish<false>, dim3((longest_list + 63) / 64, n_strips), dim3(64), 0, st, static_cast<uint4*>(d_blocks), static_cast<const uint4*>(d_px), n,
+                       per_job, e, to_params(fparams, uparams), w.mod_list, w.strip_counts, w.state, w.counters, nullptr, 0u);
     return hipGetLastError();
+}
+
+// ---- several slices in one pass: the strip table form. The caller has put L.recs at d_ws + L.strips and L.order at d_ws + L.order_at.
+
+hipError_t launch_uastc_rdo_slices_phase(hipStream_t st, int phase, void* d_blocks, const void* d_px, const rdo_slices_layout& L, const float* fparams,
+                                         const uint32_t* uparams, void* d_ws) {
+    const uint32_t n = L.total_blocks, n_strips = (uint32_t)L.recs.size();
+    if (!n) return hipSuccess;
+    char* ws = static_cast<char*>(d_ws);
+    const rdo_params p = to_params(fparams, uparams);
+    uint4* blocks = static_cast<uint4*>(d_blocks);
+    const uint4* px = static_cast<const uint4*>(d_px);
+    rdo_info4* info = reinterpret_cast<rdo_info4*>(ws + L.info);
+    uint32_t* table = reinterpret_cast<uint32_t*>(ws + L.table);
+    uint32_t* counters = reinterpret_cast<uint32_t*>(ws + L.counters);
+    uint32_t* strip_flags = reinterpret_cast<uint32_t*>(ws + L.strip_flags);
+    const rdo_strip_rec* recs = reinterpret_cast<const rdo_strip_rec*>(ws + L.strips);
+    if (phase == 0) {
+        const hipError_t e = hipMemsetAsync(ws, 0, L.zero_bytes, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_rdo_prepare, dim3((n + 63) / 64), dim3(64), 0, st, blocks, px, n, p, info, table, counters, strip_flags, 0u, recs, n_strips);
+        return hipGetLastError();
+    }
+    if (phase != 1 && phase != 3) return hipErrorInvalidValue;
+    const uint32_t window = p.lz_dict_size / 16 > 1 ? p.lz_dict_size / 16 : 1;
+    uint32_t ring = 1;
+    while (ring < window) ring <<= 1;
+    if (ring > RDO_RING_MAX) ring = 0;
+    const bool fat = phase == 3;
+    auto* kernel = ring ? (fat ? k_rdo_strips<true, true, true> : k_rdo_strips<true, false, true>) : (fat ? k_rdo_strips<false, true, true> : k_rdo_strips<false, false, true>);
+    hipLaunchKernelGGL(kernel, dim3(n_strips), dim3(RDO_THREADS), (size_t)ring * 16, st, blocks, px, n, 0u, p, info, table, reinterpret_cast<hist_entry*>(ws + L.hist), 0u,
+                       reinterpret_cast<uint8_t*>(ws + L.state), reinterpret_cast<uint32_t*>(ws + L.mod_list), reinterpret_cast<uint32_t*>(ws + L.strip_counts), counters,
+                       ring ? ring : 1u, strip_flags, recs, reinterpret_cast<const uint32_t*>(ws + L.order_at));
+    return hipGetLastError();
+}
+
+hipError_t launch_uastc_rdo_slices_finish(hipStream_t st, void* d_blocks, const void* d_px, const rdo_slices_layout& L, const float* fparams, const uint32_t* uparams,
+                                          uint32_t flags, void* d_ws, uint32_t longest_list) {
+    const uint32_t n_strips = (uint32_t)L.recs.size();
+    if (!L.total_blocks || !longest_list) return hipSuccess;
+    char* ws = static_cast<char*>(d_ws);
+    enc_cfg e;
+    make_cfg(flags, e);
+    for (uint32_t base = 0; base < n_strips; base += 65535u) {   // a grid's y extent ends at 65535
+        hipLaunchKernelGGL(k_rdo_finish<true>, dim3((longest_list + 63) / 64, std::min(65535u, n_strips - base)), dim3(64), 0, st, static_cast<uint4*>(d_blocks),
+                           static_cast<const uint4*>(d_px), L.total_blocks, 0u, e, to_params(fparams, uparams), reinterpret_cast<const uint32_t*>(ws + L.mod_list),
+                           reinterpret_cast<const uint32_t*>(ws + L.strip_counts), reinterpret_cast<const uint8_t*>(ws + L.state),
+                           reinterpret_cast<uint32_t*>(ws + L.counters), reinterpret_cast<const rdo_strip_rec*>(ws + L.strips), base);
+        const hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
 }
 
 const void* uastc_rdo_counters(void* d_ws, uint32_t n, uint32_t total_jobs) { return carve(d_ws, n, total_jobs, nullptr).counters; }

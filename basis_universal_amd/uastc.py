@@ -103,6 +103,19 @@ def uastc_rdo(ctx, uastc_blocks, pixel_blocks, params=None, flags=LEVEL_DEFAULT,
             ctx.free(d)
 
 
+def uastc_rdo_slices(ctx, d_blocks, d_px, slice_blocks, params=None, flags=LEVEL_DEFAULT, total_jobs=0):
+    """uastc_rdo over every slice of a file in one pass (bu_hip_k_uastc_rdo_slices): the slices lie back to back behind the device pointers d_blocks (16 B per block,
+    modified in place) and d_px (64 B per block), slice s holding slice_blocks[s] blocks. Bytes and stats are those of one uastc_rdo call per slice; the strips of
+    all slices walk side by side. Device pointers only: the call exists for resident data.
+    Returns a list of {"modified", "refined", "skipped", "strips"}, one per slice."""
+    params = params or RdoParams()
+    counts = (C.c_uint32 * len(slice_blocks))(*[int(n) for n in slice_blocks])
+    stats = (C.c_uint32 * (4 * len(slice_blocks)))()
+    ctx.check(ctx.lib.k_uastc_rdo_slices(ctx.h, C.c_void_p(d_blocks), C.c_void_p(d_px), counts, len(slice_blocks), C.byref(params), int(flags), int(total_jobs), stats),
+              "uastc_rdo_slices")
+    return [{"modified": stats[4 * s], "refined": stats[4 * s + 1], "skipped": stats[4 * s + 2], "strips": stats[4 * s + 3]} for s in range(len(slice_blocks))]
+
+
 def workspace_bytes(n_blocks, flags=LEVEL_DEFAULT, lib=None):
     """bu_hip_uastc_workspace_bytes: the context workspace encode_uastc_blocks needs (host arithmetic: no GPU, no context)."""
     return (lib or capi.load_library()).uastc_workspace_bytes(int(n_blocks), int(flags))
@@ -111,6 +124,12 @@ def workspace_bytes(n_blocks, flags=LEVEL_DEFAULT, lib=None):
 def rdo_workspace_bytes(n_blocks, total_jobs=0, lib=None):
     """bu_hip_uastc_rdo_workspace_bytes: the same for uastc_rdo over total_jobs strips."""
     return (lib or capi.load_library()).uastc_rdo_workspace_bytes(int(n_blocks), int(total_jobs))
+
+
+def rdo_slices_workspace_bytes(slice_blocks, total_jobs=0, lib=None):
+    """bu_hip_uastc_rdo_slices_workspace_bytes: the same for uastc_rdo_slices (0 for slice lists the call refuses)."""
+    counts = (C.c_uint32 * len(slice_blocks))(*[int(n) for n in slice_blocks])
+    return (lib or capi.load_library()).uastc_rdo_slices_workspace_bytes(counts, len(slice_blocks), int(total_jobs))
 
 
 class UastcPipeline:

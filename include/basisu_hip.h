@@ -340,6 +340,18 @@ typedef struct bu_uastc_rdo_params {
 BU_HIP_API void bu_hip_uastc_rdo_default_params(bu_uastc_rdo_params* out);   /* uastc_rdo_params::clear(), uastc_enc.h:101-112 */
 BU_HIP_API int bu_hip_k_uastc_rdo(bu_hip_context*, void* d_uastc_blocks, const void* d_pixel_blocks, uint32_t n_blocks, const bu_uastc_rdo_params* params,
                                   uint32_t flags, uint32_t total_jobs, uint32_t out_stats[4]);
+/* The same over every slice of a file in ONE pass (the reference runs uastc_rdo per slice, comp.cpp:2066-2082; the slices' chains are independent). The slices lie
+ * back to back in d_uastc_blocks / d_pixel_blocks in the given order, slice s holding slice_blocks[s] blocks; each is cut into strips by total_jobs exactly as
+ * bu_hip_k_uastc_rdo cuts it alone, and the strips of all slices walk side by side, the longest started first. Bytes and statistics are those of one
+ * bu_hip_k_uastc_rdo call per slice. The host waits for the stream twice per call, however many slices there are. When one slice holds all the blocks the call IS
+ * bu_hip_k_uastc_rdo on that slice.
+ *   out_stats (may be NULL): n_slices x {modified, refined, skipped, strips}. A slice of 0 blocks does no work and reports {0, 0, 0, 1}.
+ *   Refused (0, reason in bu_hip_last_error, nothing enqueued, nothing written): a null pointer, n_slices == 0, more than 2^31 - 1 blocks in all, parameters
+ *   bu_hip_k_uastc_rdo refuses. A block that does not unpack fails the call at its end, as there; the error names the lowest slice that holds one.
+ * bu_hip_uastc_rdo_slices_workspace_bytes: the context workspace the call needs (0 for arguments it refuses). */
+BU_HIP_API int bu_hip_k_uastc_rdo_slices(bu_hip_context*, void* d_uastc_blocks, const void* d_pixel_blocks, const uint32_t* slice_blocks, uint32_t n_slices,
+                                         const bu_uastc_rdo_params* params, uint32_t flags, uint32_t total_jobs, uint32_t* out_stats);
+BU_HIP_API size_t bu_hip_uastc_rdo_slices_workspace_bytes(const uint32_t* slice_blocks, uint32_t n_slices, uint32_t total_jobs);
 /* host-buffer form over the context's resident pixel blocks (bu_hip_set_pixel_blocks): blocks in, blocks out */
 BU_HIP_API int bu_hip_uastc_rdo(bu_hip_context*, bu_uastc_block* blocks, const bu_uastc_rdo_params* params, uint32_t flags, uint32_t total_jobs,
                                 uint32_t out_stats[4]);

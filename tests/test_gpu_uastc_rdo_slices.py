@@ -1,0 +1,280 @@
+"""-m gpu tests of the UASTC RDO post-pass over every slice of a file in one pass (include/basisu_hip.h: bu_hip_k_uastc_rdo_slices; uastc.uastc_rdo_slices).
+
+No expected value comes from the new entry: every one is the existing uastc.uastc_rdo / bu_hip_k_uastc_rdo run on each slice alone (held to the reference and to
+the host build of the core by test_gpu_uastc_rdo.py), and where it is cheap the host build of the core as well."""
+import ctypes as C
+import functools
+import pathlib
+
+import numpy as np
+import pytest
+
+import helpers
+import uastc_rdo_cases as K
+from basis_universal_amd import capi, compress as cm, uastc
+from test_gpu_uastc_rdo import params
+
+pytestmark = pytest.mark.gpu
+GOLDEN = pathlib.Path(__file__).resolve().parent / "golden" / "uastc_rdo_vectors.npz"
+SIZES = [600, 1, 40, 257, 9, 2, 36, 0, 64]   # 36 at 4 jobs: per_job 9, the smallest slice that is split; 9: one strip (per_job <= 8); 257: a ragged fifth strip of one block
+STAT_KEYS = ("modified", "refined", "skipped", "strips")
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return np.load(GOLDEN)
+
+
+def alone(ctx, packed, blocks, sizes, p, flags, jobs):
+    """What the new entry has to give: the existing entry on every slice by itself -> (bytes of all slices, list of stats). An empty slice goes to the C entry with
+    n_blocks = 0 (the Python wrapper does not call it then), behind any valid device pointer."""
+    out, stats, at = [], [], 0
+    for n in sizes:
+        if n:
+            got, info = uastc.uastc_rdo(ctx, np.ascontiguousarray(packed[at:at + n]), np.ascontiguousarray(blocks[at:at + n]), p, flags, jobs)
+            out.append(got)
+        else:
+            d = ctx.alloc(64)
+            raw = (C.c_uint32 * 4)(9, 9, 9, 9)
+            ctx.check(ctx.lib.k_uastc_rdo(ctx.h, C.c_void_p(d), C.c_void_p(d), 0, C.byref(p), int(flags), int(jobs), raw), "uastc_rdo")
+            ctx.free(d)
+            info = dict(zip(STAT_KEYS, raw))
+        stats.append(info)
+        at += n
+    return (np.concatenate(out) if out else np.zeros((0, 16), np.uint8)), stats
+
+
+def in_one_pass(ctx, packed, blocks, sizes, p, flags, jobs, with_stats=True):
+    """The new entry over resident copies of the slices -> (bytes, list of stats or None)."""
+    n = sum(sizes)
+    assert packed.shape[0] == n and blocks.shape[0] == n
+    d_blk, d_px = ctx.upload(np.ascontiguousarray(packed)), ctx.upload(np.ascontiguousarray(blocks))
+    try:
+        if with_stats:
+            stats = uastc.uastc_rdo_slices(ctx, d_blk, d_px, sizes, p, flags, jobs)
+        else:
+            counts = (C.c_uint32 * len(sizes))(*sizes)
+            ctx.check(ctx.lib.k_uastc_rdo_slices(ctx.h, C.c_void_p(d_blk), C.c_void_p(d_px), counts, len(sizes), C.byref(p), int(flags), int(jobs), None), "uastc_rdo_slices")
+            stats = None
+        return ctx.download(d_blk, (n, 16), np.uint8), stats
+    finally:
+        ctx.free(d_blk)
+        ctx.free(d_px)
+
+
+def check_equal(got, want, sizes, what):
+    bad = np.nonzero((got != want).any(1))[0]
+    edges = np.cumsum([0] + list(sizes))
+    assert bad.size == 0, f"{what}: {bad.size} blocks differ from the per-slice runs, first {bad[:5]} (slices {np.searchsorted(edges, bad[:5], 'right') - 1})"
+
+
+def check_case(ctx, packed, blocks, sizes, p, flags, jobs, what):
+    want, want_stats = alone(ctx, packed, blocks, sizes, p, flags, jobs)
+    got, stats = in_one_pass(ctx, packed, blocks, sizes, p, flags, jobs)
+    check_equal(got, want, sizes, what)
+    assert stats == want_stats, what
+    return got, stats
+
+
+# ---- 1. equals slice by slice
+
+@pytest.mark.parametrize("jobs", [0, 4])
+def test_equals_slice_by_slice(hip_ctx, golden, jobs):
+    n = sum(SIZES)
+    packed, blocks = golden["packed_l2"][:n], golden["blocks"][:n]
+    p = params(lam=4.0)
+    got, stats = check_case(hip_ctx, packed, blocks, SIZES, p, 2, jobs, f"jobs {jobs}")
+    assert [s["strips"] for s in stats] == ([1] * 9 if jobs == 0 else [4, 1, 4, 5, 1, 1, 4, 1, 4])
+    assert sum(s["modified"] for s in stats) > 100   # the pass did something
+    no_stats, none = in_one_pass(hip_ctx, packed, blocks, SIZES, p, 2, jobs, with_stats=False)
+    assert none is None and (no_stats == got).all()
+    # the host build of the same core, slice by slice
+    at = 0
+    for n_s, info in zip(SIZES, stats):
+        if n_s:
+            want, counts = helpers.host_uastc_rdo_counted(packed[at:at + n_s], blocks[at:at + n_s], 2, jobs, True, lam=4.0)
+            assert (got[at:at + n_s] == want).all() and {k: info[k] for k in counts} == counts, (jobs, at, n_s)
+        at += n_s
+
+
+@pytest.mark.parametrize("sizes", [[257], [0, 257, 0]], ids=["bare", "between_empty_slices"])
+@pytest.mark.parametrize("jobs", [0, 4])
+def test_one_slice_holds_all_blocks(hip_ctx, golden, sizes, jobs):
+    """one slice with blocks: the call is the single-slice entry's, at the slice's place in the arrays and in out_stats"""
+    packed, blocks = golden["packed_l2"][300:557], golden["blocks"][300:557]
+    check_case(hip_ctx, packed, blocks, sizes, params(lam=4.0), 2, jobs, f"{sizes} jobs {jobs}")
+    junk = packed.copy()
+    junk[7, 0] = 0x45
+    with pytest.raises(capi.HipError, match=f"slice {len(sizes) // 2} "):
+        in_one_pass(hip_ctx, junk, blocks, sizes, params(), 2, jobs)
+
+
+# ---- 2. nothing looks back across a slice boundary
+
+def test_no_look_back_across_a_slice_boundary(hip_ctx, golden):
+    """Three identical slices of 120 blocks under the default dictionary (a window of 256 blocks: all of the previous copy is in reach). As ONE strip the second and the
+    third copy come out differently from the first (the condition, from the existing entry); as three slices they are three copies of A's own result."""
+    A, tiles = golden["packed_l2"][:120], golden["blocks"][:120]
+    p = params(lam=10.0)
+    assert p.m_lz_dict_size == 4096
+    own, own_info = uastc.uastc_rdo(hip_ctx, A, tiles, p, 2, 0)
+    three, three_tiles = np.concatenate([A] * 3), np.concatenate([tiles] * 3)
+    chained, _ = uastc.uastc_rdo(hip_ctx, three, three_tiles, p, 2, 0)
+    differing = (chained.reshape(3, 120, 16) != own[None]).any(2).sum(1)
+    assert differing[0] == 0 and differing[1] >= K.MIN_DIFFERING and differing[2] >= K.MIN_DIFFERING, f"one strip over A A A differs from A's own result in {differing} blocks per copy"
+    got, stats = in_one_pass(hip_ctx, three, three_tiles, [120] * 3, p, 2, 0)
+    check_equal(got, np.concatenate([own] * 3), [120] * 3, "A A A")
+    assert stats == [own_info] * 3
+
+
+# ---- 3. flagged and unflagged strips of different slices in one launch
+
+@functools.lru_cache(maxsize=None)
+def opaque_la_opaque():
+    """(packed, tiles, sizes) at level 2: 300 opaque blocks of no sensitive mode, 200 luminance-alpha blocks, 150 more opaque ones (host encoder; blocks are encoded
+    one by one, so leaving out the opaque blocks of mode 18 changes no other block)"""
+    src = helpers.to_pixel_blocks(helpers.synth(128, 128, 19)).copy()
+    la = src[:200].copy()
+    K.make_la(la, 1)
+    packed_rgb, packed_la = helpers.host_encode_uastc(src, 2), helpers.host_encode_uastc(la, 2)
+    plain = np.nonzero(~np.isin(K.modes_of(packed_rgb), K.SENSITIVE_MODES))[0]
+    assert plain.size >= 450
+    a, b = plain[:300], plain[300:450]
+    return (np.ascontiguousarray(np.concatenate([packed_rgb[a], packed_la, packed_rgb[b]])), np.ascontiguousarray(np.concatenate([src[a], la, src[b]])), [300, 200, 150])
+
+
+@pytest.mark.parametrize("jobs", [0, 3])
+@pytest.mark.parametrize("refine", [1, 0])
+def test_flagged_and_unflagged_slices_in_one_launch(hip_ctx, refine, jobs):
+    packed, tiles, sizes = opaque_la_opaque()
+    sensitive = np.isin(K.modes_of(packed), K.SENSITIVE_MODES)
+    assert not sensitive[:300].any() and sensitive[300:500].any() and not sensitive[500:].any()   # the middle slice's strips take the walk with the refit in it, the others the lean one
+    p = params(lam=3.0, refine=refine)
+    _, stats = check_case(hip_ctx, packed, tiles, sizes, p, 2, jobs, f"refine {refine} jobs {jobs}")
+    if not refine:
+        assert [s["refined"] for s in stats] == [0, 0, 0]
+
+
+# ---- 4. windows past the LDS ring: candidates read back from HBM
+
+@pytest.mark.parametrize("second", ["opaque", "la"])
+def test_hbm_window_build(hip_ctx, golden, second):
+    """lz_dict_size 65536: a look-back of 4096 blocks, past the LDS ring. Slice 0 is the opaque period case of 4400 blocks (its window slides); slice 1 holds 300 blocks,
+    opaque ones (both slices in the lean build) or luminance-alpha ones (the build with the refit in it beside the lean one)."""
+    big, big_tiles = K.rdo_period_case(4097, K.PERIOD_TAIL[4097], K.PERIOD_SEED, 0)
+    assert big.shape[0] == 4400 and not np.isin(K.modes_of(big), K.SENSITIVE_MODES).any()
+    if second == "opaque":
+        small, small_tiles = golden["packed_l0"][:300], golden["blocks"][:300]
+    else:
+        small_tiles = helpers.to_pixel_blocks(helpers.synth(80, 64, 23))[:300].copy()
+        K.make_la(small_tiles, 1)
+        small = helpers.host_encode_uastc(small_tiles, 0)
+        assert np.isin(K.modes_of(small), K.SENSITIVE_MODES).any()
+    packed, tiles = np.concatenate([big, small]), np.concatenate([big_tiles, small_tiles])
+    check_case(hip_ctx, packed, tiles, [4400, 300], params(dict_size=65536, **K.PERIOD_PARAMS), 0, 0, second)
+
+
+# ---- 5. windows and dictionaries that are not the ring's size
+
+@pytest.mark.parametrize("dict_size", [1, 48, 3000])
+def test_dictionary_corners(hip_ctx, golden, dict_size):
+    packed, blocks = golden["packed_l2"][:297], golden["blocks"][:297]
+    check_case(hip_ctx, packed, blocks, [257, 40], params(lam=3.0, dict_size=dict_size), 2, 3, f"dict {dict_size}")
+
+
+# ---- 6. refusals
+
+def test_refusals_leave_everything_untouched(hip_ctx, golden):
+    ctx = hip_ctx
+    n = 64
+    sentinel = np.full((n, 16), 0xA5, np.uint8)
+    d_blk, d_px = ctx.upload(sentinel), ctx.upload(np.ascontiguousarray(golden["blocks"][:n]))
+    good, bad_lambda, bad_ratio, bad_dict = params(), params(lam=0.0), params(max_rms_ratio=1.0), params(dict_size=0)
+    counts = (C.c_uint32 * 2)(40, 24)
+    too_many = (C.c_uint32 * 2)(0x80000000, 0x80000000)
+    vp = C.c_void_p
+    cases = [("null blocks", (None, vp(d_px), counts, 2, C.byref(good)), "null pointer"),
+             ("null tiles", (vp(d_blk), None, counts, 2, C.byref(good)), "null pointer"),
+             ("null slice list", (vp(d_blk), vp(d_px), None, 2, C.byref(good)), "null pointer"),
+             ("null parameters", (vp(d_blk), vp(d_px), counts, 2, None), "null pointer"),
+             ("no slices", (vp(d_blk), vp(d_px), counts, 0, C.byref(good)), "no slices"),
+             ("block total past 32 bits", (vp(d_blk), vp(d_px), too_many, 2, C.byref(good)), "blocks in all"),
+             ("lambda 0", (vp(d_blk), vp(d_px), counts, 2, C.byref(bad_lambda)), "lambda > 0"),
+             ("ratio 1", (vp(d_blk), vp(d_px), counts, 2, C.byref(bad_ratio)), "max_allowed_rms_increase_ratio > 1"),
+             ("dictionary 0", (vp(d_blk), vp(d_px), counts, 2, C.byref(bad_dict)), "lz_dict_size > 0")]
+    try:
+        for name, (blk, px, sl, n_sl, p), reason in cases:
+            stats = (C.c_uint32 * 8)(*[0xDEADBEEF] * 8)
+            assert ctx.lib.k_uastc_rdo_slices(ctx.h, blk, px, sl, n_sl, p, 2, 4, stats) == 0, name
+            assert reason in ctx.lib.last_error(ctx.h), (name, ctx.lib.last_error(ctx.h))
+            assert list(stats) == [0xDEADBEEF] * 8, name
+            assert (ctx.download(d_blk, (n, 16), np.uint8) == sentinel).all(), name
+        assert uastc.rdo_slices_workspace_bytes([0x80000000, 0x80000000], 4) == 0
+        assert uastc.rdo_slices_workspace_bytes([40, 24], 4) > 64 * 2048
+    finally:
+        ctx.free(d_blk)
+        ctx.free(d_px)
+
+
+def test_a_block_that_does_not_unpack_names_its_slice(hip_ctx, golden):
+    packed, blocks = golden["packed_l2"][:192].copy(), golden["blocks"][:192]
+    packed[128 + 5, 0] = 0x45   # not a mode code (test_gpu_uastc_rdo.py, test_rejects_bad_arguments): in slice 2 of [0, 1, 2]
+    with pytest.raises(capi.HipError, match="slice 2 "):
+        in_one_pass(hip_ctx, packed, blocks, [64, 64, 64], params(), 2, 0)
+    packed[5, 0] = 0x45         # and in slice 0 as well: the lowest slice is named
+    with pytest.raises(capi.HipError, match="slice 0 "):
+        in_one_pass(hip_ctx, packed, blocks, [64, 64, 64], params(), 2, 4)
+
+
+# ---- 7. compress() makes one RDO pass
+
+def parent_encode(ctx, owned, d_all, slices, has_alpha, *, uastc_level, uastc_rdo_lambda, uastc_rdo_jobs, srgb, tex_type, key_values, **_):
+    """_encode as it was before uastc_rdo_slices, for a UASTC .ktx2 with the post-pass: one uastc_rdo call per slice"""
+    slice_blocks = [s[1] * s[2] for s in slices]
+    total_blocks = sum(slice_blocks)
+    d_out = ctx.alloc(total_blocks * 16)
+    owned.append(d_out)
+    uastc.encode_uastc_blocks(ctx, d_all, int(uastc_level) | uastc.FAVOR_SIMPLER_MODES, n_blocks=total_blocks, out_device=d_out)
+    at = 0
+    for n in slice_blocks:
+        uastc.uastc_rdo(ctx, d_out + at * 16, d_all + at * 64, uastc.RdoParams(m_lambda=float(uastc_rdo_lambda)), int(uastc_level), uastc_rdo_jobs, n_blocks=n)
+        at += n
+    packed = ctx.download(d_out, (total_blocks, 16), np.uint8)
+    return cm.uastc_ktx2_file(packed, slices, srgb=srgb, tex_type=tex_type, has_alpha=has_alpha, key_values=key_values)
+
+
+def test_compress_makes_one_rdo_pass(monkeypatch):
+    faces = [helpers.synth(16, 16, 60 + k) for k in range(6)]
+    options = dict(tex_type="cubemap", mipmaps=True, uastc=True, uastc_rdo_lambda=1.0, uastc_rdo_jobs=4, ktx2=True)
+    ctx = capi.Context(0)   # its own context: profile_read names 32 scopes at the most
+    try:
+        ctx.profile_enable()
+        data = cm.compress(ctx, faces, **options)
+        scopes = ctx.profile_read()
+        ctx.profile_enable(False)
+        assert {k: v[1] for k, v in scopes.items() if k.startswith("uastc_rdo")} == {"uastc_rdo_slices_prepare": 1, "uastc_rdo_slices_strips": 1, "uastc_rdo_slices_finish": 1}, scopes
+        monkeypatch.setattr(cm, "_encode", parent_encode)
+        want = cm.compress(ctx, faces, **options)
+    finally:
+        ctx.close()
+    assert data.shape == want.shape and (data == want).all()
+
+
+# ---- 8. deterministic, and the same on a caller's stream
+
+def test_deterministic_and_on_a_callers_stream(hip_ctx, golden):
+    n = sum(SIZES)
+    packed, blocks = golden["packed_l2"][:n], golden["blocks"][:n]
+    p = params(lam=4.0)
+    first, first_stats = in_one_pass(hip_ctx, packed, blocks, SIZES, p, 2, 4)
+    again, again_stats = in_one_pass(hip_ctx, packed, blocks, SIZES, p, 2, 4)
+    assert (first == again).all() and first_stats == again_stats
+    a, b = capi.Context(0), capi.Context(0)
+    try:
+        a.set_stream(b.get_stream())
+        other, other_stats = in_one_pass(a, packed, blocks, SIZES, p, 2, 4)
+        a.set_stream(None)
+    finally:
+        a.close()
+        b.close()
+    assert (other == first).all() and other_stats == first_stats

@@ -9,13 +9,21 @@ Workloads: `video` -- 64 frames of 256x256 with alpha, ETC1S video (128 slices);
 whose compress() call is timed over all --repeats rounds after 3 warm-up calls.
 Times are host clock around work that ends in a stream synchronise, after warm-up; per side the median and the extremes of --repeats rounds.
 The launch counts come from a separate profiled pass (bu_hip_profile_*), not from the timed rounds. One JSON line per workload.
-usage: multi_image_bench.py [--workload NAME|bare|all] [--repeats N] [--out FILE]"""
+--rdo: the UASTC RDO post-pass instead (level 2, lambda 1, uastc_rdo_jobs 1 and 4) over `rdo_video` (64 frames of 256x256), `rdo_cubemap` (six 1024x1024 faces with
+mips), `rdo_bare_4096` (one 4096x4096, no mips) and `rdo_bare_4096_mips`: the RDO stage alone on resident encoded blocks, the way this tree's compress() runs it (ONE
+uastc_rdo_slices call; on a tree without that entry, one uastc_rdo call per slice), timed with device events on the context's stream and with the host clock around
+the call, which ends in a stream synchronise; then the whole compress() call by the host clock. On a tree with the one pass, every round also times one uastc_rdo call
+per slice on the same library (`rdo_stage_per_slice_device`): the two forms of the kernels side by side, free of whatever drifts between two runs of the tool. The encoded blocks are restored outside the timed part. Per case
+the workspace bytes and a CRC-32 of the blocks the stage leaves, so that runs of two trees can be compared. A single 4096x4096 chain takes seconds: use --repeats 5 or so.
+usage: multi_image_bench.py [--rdo] [--workload NAME|bare|all] [--repeats N] [--out FILE]"""
 import argparse
+import ctypes as C
 import json
 import pathlib
 import statistics
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -23,7 +31,7 @@ ROOT = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 import helpers  # noqa: E402
-from basis_universal_amd import capi, mipmap, source  # noqa: E402
+from basis_universal_amd import capi, mipmap, source, uastc  # noqa: E402
 from basis_universal_amd.compress import compress  # noqa: E402
 
 
@@ -172,15 +180,112 @@ def run(ctx, name, make, repeats):
         res.close()
 
 
+# ---- the UASTC RDO post-pass
+
+def rdo_workloads():
+    return {"rdo_video": (lambda: [helpers.synth(256, 256, 930 + i) for i in range(64)], dict(tex_type="video")),
+            "rdo_cubemap": (lambda: [helpers.synth(1024, 1024, 910 + i) for i in range(6)], dict(tex_type="cubemap", mipmaps=True)),
+            "rdo_bare_4096": (lambda: np.ascontiguousarray(helpers.synth(4096, 4096, 921)), dict()),
+            "rdo_bare_4096_mips": (lambda: np.ascontiguousarray(helpers.synth(4096, 4096, 921)), dict(mipmaps=True))}
+
+
+class DeviceTimer:
+    """two HIP events on the context's stream around fn, which must leave the stream idle"""
+
+    def __init__(self, ctx):
+        path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)   # the runtime the library has loaded
+        self.hip, self.stream = C.CDLL(path), C.c_void_p(ctx.get_stream())
+        self.start, self.stop = C.c_void_p(), C.c_void_p()
+        for e in (self.start, self.stop):
+            assert self.hip.hipEventCreate(C.byref(e)) == 0
+
+    def ms(self, fn):
+        assert self.hip.hipEventRecord(self.start, self.stream) == 0
+        fn()
+        assert self.hip.hipEventRecord(self.stop, self.stream) == 0 and self.hip.hipEventSynchronize(self.stop) == 0
+        out = C.c_float()
+        assert self.hip.hipEventElapsedTime(C.byref(out), self.start, self.stop) == 0
+        return out.value
+
+    def close(self):
+        for e in (self.start, self.stop):
+            self.hip.hipEventDestroy(e)
+
+
+def rdo_stage(ctx, d_blocks, d_tiles, slice_blocks, params, level, jobs, per_slice=False):
+    """the post-pass as compress() runs it; per_slice: one uastc_rdo call per slice whatever the tree has"""
+    if hasattr(uastc, "uastc_rdo_slices") and not per_slice:
+        uastc.uastc_rdo_slices(ctx, d_blocks, d_tiles, slice_blocks, params, level, jobs)
+        return
+    at = 0
+    for n in slice_blocks:
+        uastc.uastc_rdo(ctx, d_blocks + at * 16, d_tiles + at * 64, params, level, jobs, n_blocks=n)
+        at += n
+
+
+def run_rdo(ctx, name, make, kw, repeats, level=2, lam=1.0):
+    images = make()
+    bare = isinstance(images, np.ndarray)
+    res = Resident(ctx, [images] if bare else images, True, bool(kw.get("mipmaps")))
+    timer = DeviceTimer(ctx)
+    d_encoded, d_work = ctx.alloc(res.total * 16), ctx.alloc(res.total * 16)
+    try:
+        res.batched()
+        uastc.encode_uastc_blocks(ctx, res.d_tiles, level | uastc.FAVOR_SIMPLER_MODES, n_blocks=res.total, out_device=d_encoded)
+        slice_blocks = [s[1] * s[2] for s in res.slices]
+        params = uastc.RdoParams(m_lambda=lam)
+        out = {"workload": name, "images": len(res.chains), "size": list(res.levels[0]), "slices": len(res.slices), "blocks": res.total, "repeats": repeats,
+               "one_pass": hasattr(uastc, "uastc_rdo_slices")}
+        for jobs in (1, 4):
+            stage = lambda: rdo_stage(ctx, d_work, res.d_tiles, slice_blocks, params, level, jobs)   # noqa: E731
+            loop = lambda: rdo_stage(ctx, d_work, res.d_tiles, slice_blocks, params, level, jobs, per_slice=True)   # noqa: E731
+            device, host, loop_device = [], [], []
+            for k in range(repeats + 1):                      # round 0 is the warm-up
+                if out["one_pass"]:                           # the per-slice loop on the same library, alternating with the one pass in every round
+                    ctx.memcpy_d2d(d_work, d_encoded, res.total * 16)
+                    ctx.sync()
+                    loop_device.append(timer.ms(loop))
+                ctx.memcpy_d2d(d_work, d_encoded, res.total * 16)
+                ctx.sync()
+                t = time.perf_counter()
+                d_ms = timer.ms(stage)
+                h_ms = (time.perf_counter() - t) * 1e3
+                if k:
+                    device.append(d_ms)
+                    host.append(h_ms)
+            options = dict(kw, uastc=True, uastc_level=level, uastc_rdo_lambda=lam, uastc_rdo_jobs=jobs)
+            compress(ctx, images, **options)
+            whole = [timed(lambda: compress(ctx, images, **options)) for _ in range(repeats)]
+            if hasattr(uastc, "rdo_slices_workspace_bytes"):
+                workspace = uastc.rdo_slices_workspace_bytes(slice_blocks, jobs)
+            else:
+                workspace = max(uastc.rdo_workspace_bytes(n, jobs) for n in slice_blocks)
+            out[f"jobs{jobs}"] = {"rdo_stage_device": summary(device), "rdo_stage_host": summary(host), "compress_call": summary(whole), "workspace_bytes": workspace,
+                                  "blocks_crc32": zlib.crc32(ctx.download(d_work, (res.total, 16), np.uint8).tobytes())}
+            if loop_device:
+                out[f"jobs{jobs}"]["rdo_stage_per_slice_device"] = summary(loop_device[1:])
+        return out
+    finally:
+        timer.close()
+        ctx.free(d_encoded)
+        ctx.free(d_work)
+        res.close()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="all", choices=[*workloads(), "bare", "all"])
+    ap.add_argument("--rdo", action="store_true")
+    ap.add_argument("--workload", default="all", choices=[*workloads(), *rdo_workloads(), "bare", "all"])
     ap.add_argument("--repeats", type=int, default=50)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     ctx = capi.Context(0)       # no device, no numbers: this raises
     lines = []
-    for name, make in workloads().items():
+    for name, (make, kw) in rdo_workloads().items() if args.rdo else ():
+        if args.workload in ("all", name):
+            lines.append(json.dumps(run_rdo(ctx, name, make, kw, args.repeats)))
+            print(lines[-1], flush=True)
+    for name, make in () if args.rdo else workloads().items():
         if args.workload in ("all", name) or (args.workload == "bare" and name.startswith("bare_")):
             lines.append(json.dumps(run(ctx, name, make, args.repeats)))
             print(lines[-1], flush=True)
