@@ -132,50 +132,87 @@ static int uastc_rdo_walks(bu_hip_context* ctx, bool refit, Launch launch) {
     return 1;
 }
 
-int bu_hip_k_uastc_rdo(bu_hip_context* ctx, void* d_blocks, const void* d_px, uint32_t n_blocks, const bu_uastc_rdo_params* params, uint32_t flags,
-                       uint32_t total_jobs, uint32_t out_stats[4]) {
-    if (!ctx) return 0;
-    if (!d_blocks || !d_px || !params) { set_error(ctx, "uastc_rdo: null pointer"); return 0; }
-    if (!uastc_rdo_params_ok(ctx, params)) return 0;
-    device_guard g(ctx->device);
-    if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = 0, out_stats[3] = bu::uastc_rdo_strips(n_blocks, total_jobs);
-    if (!n_blocks) return 1;
-    const float fp[5] = { params->m_lambda, params->m_max_allowed_rms_increase_ratio, params->m_skip_block_rms_thresh, params->m_max_smooth_block_std_dev,
-                          params->m_smooth_block_max_error_scale };
-    const uint32_t up[3] = { params->m_lz_dict_size, params->m_lz_literal_cost, params->m_endpoint_refinement };
+// bu_uastc_rdo_params as everything below the C ABI takes it
+static bu_uastc::rdo_params uastc_rdo_kernel_params(const bu_uastc_rdo_params* q) {
+    return { q->m_lambda, q->m_max_allowed_rms_increase_ratio, q->m_skip_block_rms_thresh, q->m_max_smooth_block_std_dev, q->m_smooth_block_max_error_scale,
+             q->m_lz_dict_size, q->m_lz_literal_cost, q->m_endpoint_refinement };
+}
+
+// THE run of uastc_rdo over the strips of L, behind its entries' checks: prepare, both builds of the walk, finish, counters.
+//   table: the strip table form, records and order uploaded first; otherwise the arithmetic form, for a layout of one slice
+//   h_pinned_counters == nullptr: the call waits -- for the strip counts that size the finish and for the counters; a block that does not unpack fails it in the
+//     text of the single-slice entry (named_slice < 0) or naming slice named_slice + its slice of L; out_stats (may be nullptr): {modified, refined, skipped} into
+//     the first three words of every slice's row of four
+//   h_pinned_counters != nullptr: nothing waits -- the finish is launched for the longest list a strip can have (every block of it modified: surplus workgroups
+//     leave at once) and the four counters of slice 0 travel to the pinned words behind it. (The scopes record nothing there: a pipeline lane never profiles.)
+static int uastc_rdo_run(bu_hip_context* ctx, void* d_blocks, const void* d_px, const bu::rdo_slices_layout& L, const bu_uastc::rdo_params& p, uint32_t flags, bool table,
+                         uint32_t* h_pinned_counters, int64_t named_slice, uint32_t* out_stats) {
+    static const char* const scopes[2][3] = { { "uastc_rdo_prepare", "uastc_rdo_strips", "uastc_rdo_finish" },
+                                              { "uastc_rdo_slices_prepare", "uastc_rdo_slices_strips", "uastc_rdo_slices_finish" } };
     arena& ws = ctx->scratch[5];
-    BU_TRY(ctx, ws.reserve(bu::uastc_rdo_workspace_bytes(n_blocks, total_jobs)));
-    {
-        prof_scope ps(ctx, "uastc_rdo_prepare");
-        BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->stream, 0, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p));
+    BU_TRY(ctx, ws.reserve(L.total_bytes));
+    char* base = static_cast<char*>(ws.p);
+    if (table) {
+        BU_TRY(ctx, h2d(ctx, base + L.strips, L.recs.data(), L.recs.size() * sizeof(bu::rdo_strip_rec)));
+        BU_TRY(ctx, h2d(ctx, base + L.order_at, L.order.data(), L.order.size() * 4));
     }
     {
-        prof_scope ps(ctx, "uastc_rdo_strips");   // both walks: the scope ends behind the join
-        if (!uastc_rdo_walks(ctx, up[2] != 0, [&](hipStream_t st, int phase) { return bu::launch_uastc_rdo_phase(st, phase, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p); })) return 0;
+        prof_scope ps(ctx, scopes[table][0]);
+        BU_TRY(ctx, bu::launch_uastc_rdo_prepare(ctx->stream, d_blocks, d_px, L, p, ws.p, table));
     }
-    // how many blocks each strip modified: sizes the finish launch (a 16-byte copy per 4 strips; the walk has to be over anyway)
-    std::vector<uint32_t> per_strip(bu::uastc_rdo_strips(n_blocks, total_jobs));
-    if (!fetch(ctx, per_strip.data(), bu::uastc_rdo_strip_counts(ws.p, n_blocks, total_jobs), per_strip.size() * 4)) return 0;
-    uint32_t longest = 0;
-    for (uint32_t c : per_strip) longest = c > longest ? c : longest;
     {
-        prof_scope ps(ctx, "uastc_rdo_finish");
-        BU_TRY(ctx, bu::launch_uastc_rdo_finish(ctx->stream, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p, longest));
+        prof_scope ps(ctx, scopes[table][1]);   // both walks: the scope ends behind the join
+        if (!uastc_rdo_walks(ctx, p.endpoint_refinement != 0, [&](hipStream_t st, int build) { return bu::launch_uastc_rdo_walk(st, build == 3, d_blocks, d_px, L, p, ws.p, table); }))
+            return 0;
     }
-    uint32_t counters[4] = { 0, 0, 0, 0 };
-    if (!fetch(ctx, counters, bu::uastc_rdo_counters(ws.p, n_blocks, total_jobs), sizeof(counters))) return 0;
+    uint32_t longest = L.longest;
+    if (!h_pinned_counters) {
+        // how many blocks each strip modified: sizes the finish launch (one download for all slices; the walks have to be over anyway)
+        std::vector<uint32_t> per_strip(L.recs.size());
+        if (!fetch(ctx, per_strip.data(), base + L.strip_counts, per_strip.size() * 4)) return 0;
+        longest = *std::max_element(per_strip.begin(), per_strip.end());
+    }
+    {
+        prof_scope ps(ctx, scopes[table][2]);
+        BU_TRY(ctx, bu::launch_uastc_rdo_finish(ctx->stream, d_blocks, d_px, L, p, flags, ws.p, table, longest));
+    }
+    if (h_pinned_counters) {
+        BU_TRY(ctx, hipMemcpyAsync(h_pinned_counters, base + L.counters, 16, hipMemcpyDeviceToHost, ctx->stream));
+        return 1;
+    }
+    std::vector<uint32_t> counters((size_t)L.n_slices * 4);   // per slice: modified, failed, refined, skipped
+    if (!fetch(ctx, counters.data(), base + L.counters, counters.size() * 4)) return 0;
 #ifdef RDO_PROFILE
-    {
+    if (!table) {
         unsigned long long prof[16];
-        hipMemcpy(prof, static_cast<const char*>(bu::uastc_rdo_counters(ws.p, n_blocks, total_jobs)) + 64, sizeof(prof), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(prof, base + L.counters + 64, sizeof(prof), hipMemcpyDeviceToHost);
         fprintf(stderr, "rdo strip 0 cycles by phase:");
         for (int k = 0; k < 16; k++) fprintf(stderr, " %llu", prof[k]);
         fprintf(stderr, "\n");
     }
 #endif
-    if (counters[1]) { set_error(ctx, "uastc_rdo: a block does not unpack as UASTC"); return 0; }
-    if (out_stats) { out_stats[0] = counters[0]; out_stats[1] = counters[2]; out_stats[2] = counters[3]; }
+    for (uint32_t s = 0; s < L.n_slices; s++)
+        if (counters[4 * s + 1]) {
+            if (named_slice < 0) set_error(ctx, "uastc_rdo: a block does not unpack as UASTC");
+            else set_error(ctx, "uastc_rdo_slices: a block of slice %u does not unpack as UASTC", (uint32_t)(named_slice + s));
+            return 0;
+        }
+    if (out_stats)
+        for (uint32_t s = 0; s < L.n_slices; s++) { out_stats[4 * s] = counters[4 * s]; out_stats[4 * s + 1] = counters[4 * s + 2]; out_stats[4 * s + 2] = counters[4 * s + 3]; }
     return 1;
+}
+
+int bu_hip_k_uastc_rdo(bu_hip_context* ctx, void* d_blocks, const void* d_px, uint32_t n_blocks, const bu_uastc_rdo_params* params, uint32_t flags,
+                       uint32_t total_jobs, uint32_t out_stats[4]) {
+    if (!ctx) return 0;
+    if (!d_blocks || !d_px || !params) { set_error(ctx, "uastc_rdo: null pointer"); return 0; }
+    if (!uastc_rdo_params_ok(ctx, params)) return 0;
+    bu::rdo_slices_layout L;
+    if (!bu::rdo_slice_layout_build(n_blocks, total_jobs, L)) { set_error(ctx, "uastc_rdo: more than %u blocks", bu::RDO_SLICES_MAX_BLOCKS); return 0; }
+    device_guard g(ctx->device);
+    if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = 0, out_stats[3] = L.slice_strips[0];
+    if (!n_blocks) return 1;
+    return uastc_rdo_run(ctx, d_blocks, d_px, L, uastc_rdo_kernel_params(params), flags, false, nullptr, -1, out_stats);
 }
 
 size_t bu_hip_uastc_rdo_slices_workspace_bytes(const uint32_t* slice_blocks, uint32_t n_slices, uint32_t total_jobs) {
@@ -198,69 +235,15 @@ int bu_hip_k_uastc_rdo_slices(bu_hip_context* ctx, void* d_blocks, const void* d
     if (out_stats)
         for (uint32_t s = 0; s < n_slices; s++) out_stats[4 * s] = out_stats[4 * s + 1] = out_stats[4 * s + 2] = 0, out_stats[4 * s + 3] = L.slice_strips[s];
     if (!L.total_blocks) return 1;
-    if (L.recs.back().slice == L.recs.front().slice) {
-        // ONE slice holds all the blocks (a bare image without mips): nothing to overlap, and the single-slice entry's builds of the walk were measured 0.4 - 0.9 %
-        // faster per block than the strip table's on a 4096^2 chain -- the call is that entry's, launch for launch
-        const uint32_t s = L.recs.front().slice, first = L.recs.front().first;
-        uint32_t one[4] = { 0, 0, 0, 0 };
-        if (!bu_hip_k_uastc_rdo(ctx, static_cast<char*>(d_blocks) + (size_t)first * 16, static_cast<const char*>(d_px) + (size_t)first * 64, slice_blocks[s], params, flags,
-                                total_jobs, one)) {
-            if (ctx->error.find("does not unpack") != std::string::npos) set_error(ctx, "uastc_rdo_slices: a block of slice %u does not unpack as UASTC", s);
-            return 0;
-        }
-        if (out_stats) { out_stats[4 * s] = one[0]; out_stats[4 * s + 1] = one[1]; out_stats[4 * s + 2] = one[2]; }
-        return 1;
-    }
-    const float fp[5] = { params->m_lambda, params->m_max_allowed_rms_increase_ratio, params->m_skip_block_rms_thresh, params->m_max_smooth_block_std_dev,
-                          params->m_smooth_block_max_error_scale };
-    const uint32_t up[3] = { params->m_lz_dict_size, params->m_lz_literal_cost, params->m_endpoint_refinement };
-    arena& ws = ctx->scratch[5];
-    BU_TRY(ctx, ws.reserve(L.total_bytes));
-    char* base = static_cast<char*>(ws.p);
-    BU_TRY(ctx, h2d(ctx, base + L.strips, L.recs.data(), L.recs.size() * sizeof(bu::rdo_strip_rec)));
-    BU_TRY(ctx, h2d(ctx, base + L.order_at, L.order.data(), L.order.size() * 4));
-    {
-        prof_scope ps(ctx, "uastc_rdo_slices_prepare");
-        BU_TRY(ctx, bu::launch_uastc_rdo_slices_phase(ctx->stream, 0, d_blocks, d_px, L, fp, up, ws.p));
-    }
-    {
-        prof_scope ps(ctx, "uastc_rdo_slices_strips");   // both walks: the scope ends behind the join
-        if (!uastc_rdo_walks(ctx, up[2] != 0, [&](hipStream_t st, int phase) { return bu::launch_uastc_rdo_slices_phase(st, phase, d_blocks, d_px, L, fp, up, ws.p); })) return 0;
-    }
-    // how many blocks each strip modified: sizes the finish launch (one download for all slices; the walks have to be over anyway)
-    std::vector<uint32_t> per_strip(L.recs.size());
-    if (!fetch(ctx, per_strip.data(), base + L.strip_counts, per_strip.size() * 4)) return 0;
-    uint32_t longest = 0;
-    for (uint32_t c : per_strip) longest = c > longest ? c : longest;
-    {
-        prof_scope ps(ctx, "uastc_rdo_slices_finish");
-        BU_TRY(ctx, bu::launch_uastc_rdo_slices_finish(ctx->stream, d_blocks, d_px, L, fp, up, flags, ws.p, longest));
-    }
-    std::vector<uint32_t> counters((size_t)n_slices * 4);   // per slice: modified, failed, refined, skipped
-    if (!fetch(ctx, counters.data(), base + L.counters, counters.size() * 4)) return 0;
-    for (uint32_t s = 0; s < n_slices; s++)
-        if (counters[4 * s + 1]) { set_error(ctx, "uastc_rdo_slices: a block of slice %u does not unpack as UASTC", s); return 0; }
-    if (out_stats)
-        for (uint32_t s = 0; s < n_slices; s++) { out_stats[4 * s] = counters[4 * s]; out_stats[4 * s + 1] = counters[4 * s + 2]; out_stats[4 * s + 2] = counters[4 * s + 3]; }
-    return 1;
-}
-
-static int uastc_rdo_enqueue(bu_hip_context* ctx, void* d_blocks, const void* d_px, uint32_t n_blocks, const bu_uastc_rdo_params* params, uint32_t flags, uint32_t total_jobs,
-                             uint32_t* h_pinned_counters) {
-    if (!uastc_rdo_params_ok(ctx, params)) return 0;
-    const float fp[5] = { params->m_lambda, params->m_max_allowed_rms_increase_ratio, params->m_skip_block_rms_thresh, params->m_max_smooth_block_std_dev,
-                          params->m_smooth_block_max_error_scale };
-    const uint32_t up[3] = { params->m_lz_dict_size, params->m_lz_literal_cost, params->m_endpoint_refinement };
-    arena& ws = ctx->scratch[5];
-    BU_TRY(ctx, ws.reserve(bu::uastc_rdo_workspace_bytes(n_blocks, total_jobs)));
-    BU_TRY(ctx, bu::launch_uastc_rdo_phase(ctx->stream, 0, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p));
-    if (!uastc_rdo_walks(ctx, up[2] != 0, [&](hipStream_t st, int phase) { return bu::launch_uastc_rdo_phase(st, phase, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p); })) return 0;
-    // the longest list a strip can have (every block of it modified): the launch does not wait for the walk to know better, surplus workgroups leave at once
-    const uint32_t strips = bu::uastc_rdo_strips(n_blocks, total_jobs);
-    const uint32_t longest = strips > 1 ? (total_jobs ? n_blocks / total_jobs : n_blocks) : n_blocks;
-    BU_TRY(ctx, bu::launch_uastc_rdo_finish(ctx->stream, d_blocks, d_px, n_blocks, fp, up, flags, total_jobs, ws.p, longest));
-    BU_TRY(ctx, hipMemcpyAsync(h_pinned_counters, bu::uastc_rdo_counters(ws.p, n_blocks, total_jobs), 16, hipMemcpyDeviceToHost, ctx->stream));
-    return 1;
+    const bu_uastc::rdo_params p = uastc_rdo_kernel_params(params);
+    const uint32_t s = L.recs.front().slice;
+    if (L.recs.back().slice != s) return uastc_rdo_run(ctx, d_blocks, d_px, L, p, flags, true, nullptr, 0, out_stats);
+    // ONE slice holds all the blocks (a bare image without mips; the slices in front of it are empty, so it begins where the call's arrays do): nothing to overlap,
+    // and the arithmetic builds of the walk were measured 0.4 - 0.9 % faster per block than the strip table's on a 4096^2 chain -- the call runs on the
+    // layout of that slice alone, launch for launch what bu_hip_k_uastc_rdo does with it
+    bu::rdo_slices_layout one;
+    bu::rdo_slice_layout_build(slice_blocks[s], total_jobs, one);   // fits: L does
+    return uastc_rdo_run(ctx, d_blocks, d_px, one, p, flags, false, nullptr, s, out_stats ? out_stats + 4 * (size_t)s : nullptr);
 }
 
 bu_uastc_pipeline* bu_hip_uastc_pipeline_create(bu_hip_context* ctx, uint32_t lanes, uint32_t max_blocks, uint32_t flags, uint32_t max_total_jobs) {
@@ -335,7 +318,9 @@ int bu_hip_uastc_pipeline_submit(bu_uastc_pipeline* p, const void* d_px, uint32_
     bu_hip_context* ctx = p->parent;
     if (!d_px || !d_out || !n_blocks) { set_error(ctx, "uastc_pipeline_submit: null pointer / no blocks"); return 0; }
     // every refusal comes before the first enqueue: a submission that fails here has left nothing in flight on its lane, which wait() would not know to wait for
-    const size_t need = std::max(bu::uastc_workspace_bytes(n_blocks, flags), rdo ? bu::uastc_rdo_workspace_bytes(n_blocks, total_jobs) : (size_t)0);
+    bu::rdo_slices_layout L;
+    if (rdo && !bu::rdo_slice_layout_build(n_blocks, total_jobs, L)) { set_error(ctx, "uastc_pipeline_submit: more than %u blocks", bu::RDO_SLICES_MAX_BLOCKS); return 0; }
+    const size_t need = std::max(bu::uastc_workspace_bytes(n_blocks, flags), L.total_bytes);
     if (need > p->ws_bytes) { set_error(ctx, "uastc_pipeline_submit: %u blocks / %u jobs exceed what the pipeline was created for", n_blocks, total_jobs); return 0; }
     if (rdo && !uastc_rdo_params_ok(ctx, rdo)) return 0;
     device_guard g(ctx->device);
@@ -347,8 +332,8 @@ int bu_hip_uastc_pipeline_submit(bu_uastc_pipeline* p, const void* d_px, uint32_
     BU_TRY(ctx, hipStreamWaitEvent(l.ctx->stream, l.input, 0));
     if (!bu_hip_k_encode_uastc_blocks(l.ctx, d_px, n_blocks, flags, d_out)) { set_error(ctx, "uastc_pipeline_submit: %s", bu_hip_last_error(l.ctx)); return 0; }
     l.with_rdo = rdo != nullptr;
-    l.strips = rdo ? bu::uastc_rdo_strips(n_blocks, total_jobs) : 0;
-    if (rdo && !uastc_rdo_enqueue(l.ctx, d_out, d_px, n_blocks, rdo, flags, total_jobs, l.stats)) { set_error(ctx, "uastc_pipeline_submit: %s", bu_hip_last_error(l.ctx)); return 0; }
+    l.strips = rdo ? L.slice_strips[0] : 0;
+    if (rdo && !uastc_rdo_run(l.ctx, d_out, d_px, L, uastc_rdo_kernel_params(rdo), flags, false, l.stats, -1, nullptr)) { set_error(ctx, "uastc_pipeline_submit: %s", bu_hip_last_error(l.ctx)); return 0; }
     BU_TRY(ctx, hipEventRecord(l.done, l.ctx->stream));
     l.busy = true; l.ticket = ticket;
     p->next_ticket++;

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "uastc_rdo_params.h"
+
 namespace bu {
 
 // Bytes of device workspace bu::launch_encode_uastc needs for n_blocks at the given pack flags (level in the low bits).
@@ -13,30 +15,20 @@ hipError_t launch_encode_uastc(hipStream_t st, const void* d_pixel_blocks, uint3
 // The four phases separately (profiling brackets in the C ABI layer).
 hipError_t launch_uastc_phase(hipStream_t st, int phase, const void* d_pixel_blocks, uint32_t n_blocks, uint32_t flags, void* d_workspace, void* d_out_blocks);
 
-// uastc_rdo (encoder/basisu_uastc_enc.h:139, uastc_enc.cpp:4095) in place over n_blocks resident UASTC blocks (uastc_rdo_kernels.hip).
-// fparams: lambda, max_allowed_rms_increase_ratio, skip_block_rms_thresh, max_smooth_block_std_dev, smooth_block_max_error_scale;
-// uparams: lz_dict_size, lz_literal_cost, endpoint_refinement. total_jobs splits into independent strips exactly as the reference does.
-// Phases: 0 prepare (parallel), 1 strips (serial per strip); then launch_uastc_rdo_finish (refit + hints of the modified blocks) with the
-// longest per-strip list length read back from uastc_rdo_strip_counts. Stream-ordered.
-size_t uastc_rdo_workspace_bytes(uint32_t n_blocks, uint32_t total_jobs);
-uint32_t uastc_rdo_strips(uint32_t n_blocks, uint32_t total_jobs);
-hipError_t launch_uastc_rdo_phase(hipStream_t st, int phase, void* d_blocks, const void* d_pixel_blocks, uint32_t n_blocks, const float* fparams,
-                                  const uint32_t* uparams, uint32_t flags, uint32_t total_jobs, void* d_workspace);
-hipError_t launch_uastc_rdo_finish(hipStream_t st, void* d_blocks, const void* d_pixel_blocks, uint32_t n_blocks, const float* fparams, const uint32_t* uparams,
-                                   uint32_t flags, uint32_t total_jobs, void* d_workspace, uint32_t longest_list);
-// device address of uastc_rdo_strips() x uint32: modified blocks per strip, valid after phase 1
-const void* uastc_rdo_strip_counts(void* d_workspace, uint32_t n_blocks, uint32_t total_jobs);
-// device address of 4 x uint32 {modified, failed, refined, skipped} inside the workspace, valid after phase 1 (refined: after the finish)
-const void* uastc_rdo_counters(void* d_workspace, uint32_t n_blocks, uint32_t total_jobs);
-
-// uastc_rdo over several slices that lie back to back, every slice cut into its own strips, in one pass: the kernels read a strip table (uastc_rdo_strips.h:
-// rdo_slices_layout_build gives the table and the workspace's carve). The caller copies L.recs to d_workspace + L.strips and L.order to d_workspace + L.order_at
-// first. Phases: 0 clear + prepare over all blocks, 1 the lean walk and 3 the walk with the refit in it, each over all strips of all slices, longest strips first;
-// then the finish for the longest per-strip list (strip counts at d_workspace + L.strip_counts, 4 counters per slice at d_workspace + L.counters).
+// uastc_rdo (encoder/basisu_uastc_enc.h:139, uastc_enc.cpp:4095) in place over resident UASTC blocks (uastc_rdo_kernels.hip): one slice, or several that lie back to
+// back, every slice cut into its own strips exactly as the reference cuts it (total_jobs). uastc_rdo_strips.h's rdo_slices_layout states the strips and the
+// workspace of a call; d_workspace holds L.total_bytes. Three launches, stream-ordered: prepare (clears [0, L.zero_bytes), then what depends on a block alone, in
+// parallel), the walk (serial per strip; fat = the build with the refit in it, for the strips the prepare pass flagged, beside the lean build for the others: both
+// cover all strips) and the finish (refit + hints of the modified blocks) for the longest per-strip list: the strip counts at d_workspace + L.strip_counts say it,
+// L.longest bounds it. Four counters {modified, failed, refined, skipped} per slice lie at d_workspace + L.counters.
+// table = false, the arithmetic form, for a layout of ONE slice: a strip's range follows from its index and the slice's per_job. table = true: every strip is read
+// from its record, workgroups take the longest strips first; the caller has copied L.recs to d_workspace + L.strips and L.order to d_workspace + L.order_at.
 struct rdo_slices_layout;
-hipError_t launch_uastc_rdo_slices_phase(hipStream_t st, int phase, void* d_blocks, const void* d_pixel_blocks, const rdo_slices_layout& L, const float* fparams,
-                                         const uint32_t* uparams, void* d_workspace);
-hipError_t launch_uastc_rdo_slices_finish(hipStream_t st, void* d_blocks, const void* d_pixel_blocks, const rdo_slices_layout& L, const float* fparams,
-                                          const uint32_t* uparams, uint32_t flags, void* d_workspace, uint32_t longest_list);
+hipError_t launch_uastc_rdo_prepare(hipStream_t st, void* d_blocks, const void* d_pixel_blocks, const rdo_slices_layout& L, const bu_uastc::rdo_params& p, void* d_workspace,
+                                    bool table);
+hipError_t launch_uastc_rdo_walk(hipStream_t st, bool fat, void* d_blocks, const void* d_pixel_blocks, const rdo_slices_layout& L, const bu_uastc::rdo_params& p,
+                                 void* d_workspace, bool table);
+hipError_t launch_uastc_rdo_finish(hipStream_t st, void* d_blocks, const void* d_pixel_blocks, const rdo_slices_layout& L, const bu_uastc::rdo_params& p, uint32_t flags,
+                                   void* d_workspace, bool table, uint32_t longest_list);
 
 } // namespace bu

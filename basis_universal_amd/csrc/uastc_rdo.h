@@ -5,19 +5,9 @@
 // g++ compiles it into the test-only host library that is diffed against the reference's uastc_rdo.
 #pragma once
 #include "uastc_core.h"
+#include "uastc_rdo_params.h"
 
 namespace bu_uastc {
-
-struct rdo_params {              // uastc_rdo_params, uastc_enc.h:94-134
-    float lambda;
-    float max_allowed_rms_increase_ratio;
-    float skip_block_rms_thresh;
-    float max_smooth_block_std_dev;
-    float smooth_block_max_error_scale;
-    uint32_t lz_dict_size;
-    uint32_t lz_literal_cost;
-    uint32_t endpoint_refinement;
-};
 
 // g_uastc_mode_selector_bits (uastc_enc.cpp:3728-3735): first bit and length of the weight field of every mode
 BU_TAB unsigned char ku_sel_first[19] = { 65, 69, 73, 89, 89, 68, 66, 89, 0, 97, 65, 66, 81, 94, 92, 62, 98, 61, 49 };

@@ -36,17 +36,6 @@ struct rdo_info4 { float ms_err, rms_err, scale; uint32_t meta, field, anchors, 
 struct hist_entry { uint64_t sel; uint32_t ofs1; uint32_t idx; };    // ofs1 = first selector bit + 1, 0 = empty
 constexpr uint32_t HIST_BUCKET = 4;  // entries per bucket = one 64-byte line, fetched with one round trip
 
-struct rdo_workspace {
-    rdo_info4* info; hist_entry* hist; uint32_t* mod_list; uint32_t* counters;  // counters: [0] modified, [1] failed, [2] refined, [3] skipped
-    uint32_t* strip_counts;  // modified blocks per strip
-    uint32_t* strip_flags;   // per strip: != 0 when it holds an active block of a sensitive mode (15 / 17 / 18) -- set by the prepare pass, decides which walk kernel takes the strip
-    uint8_t* state;    // per block: 0 untouched, 1 modified + refit pending, 2 modified
-    uint32_t* table;   // per block RDO_TABLE_WORDS
-    size_t zero_bytes; // counters + hist + state, contiguous
-};
-size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
-void strip_layout(uint32_t n, uint32_t total_jobs, uint32_t& per_job, uint32_t& n_strips, uint32_t& hist_cap) { rdo_strip_layout(n, total_jobs, per_job, n_strips, hist_cap); }
 static_assert(sizeof(rdo_info4) == RDO_INFO_BYTES && sizeof(hist_entry) == RDO_HIST_ENTRY_BYTES && RDO_TABLE_WORDS * 4 == RDO_TABLE_BYTES && sizeof(rdo_strip_rec) == 32, "uastc_rdo_strips.h");
 
 // The strip table form of the three kernels (TABLE builds of the walk and the finish, recs != nullptr in the prepare pass), for a call over several slices that lie
@@ -60,25 +49,6 @@ __device__ inline uint32_t strip_of_block(const rdo_strip_rec* __restrict__ recs
         if (recs[mid].first <= b) lo = mid; else hi = mid;
     }
     return lo;
-}
-
-rdo_workspace carve(void* base, uint32_t n, uint32_t total_jobs, size_t* total) {
-    uint32_t per_job, n_strips, cap;
-    strip_layout(n, total_jobs, per_job, n_strips, cap);
-    char* p = static_cast<char*>(base);
-    size_t o = 0;
-    rdo_workspace w;
-    w.counters = reinterpret_cast<uint32_t*>(p + o); o += 256;
-    w.strip_counts = reinterpret_cast<uint32_t*>(p + o); o += align_up((size_t)n_strips * 4);
-    w.strip_flags = reinterpret_cast<uint32_t*>(p + o); o += align_up((size_t)n_strips * 4);
-    w.hist = reinterpret_cast<hist_entry*>(p + o); o += align_up((size_t)n_strips * cap * sizeof(hist_entry));
-    w.state = reinterpret_cast<uint8_t*>(p + o); o += align_up(n);
-    w.zero_bytes = o;
-    w.info = reinterpret_cast<rdo_info4*>(p + o); o += align_up((size_t)n * sizeof(rdo_info4));
-    w.mod_list = reinterpret_cast<uint32_t*>(p + o); o += align_up((size_t)n * 4);
-    w.table = reinterpret_cast<uint32_t*>(p + o); o += align_up((size_t)n * RDO_TABLE_WORDS * 4);
-    if (total) *total = o;
-    return w;
 }
 
 __device__ inline void load_tile(const uint4* px, uint32_t b, rgba8* out) {
@@ -491,140 +461,65 @@ __global__ void __launch_bounds__(64, 2) k_rdo_finish(uint4* blocks, const uint4
     blocks[b] = *reinterpret_cast<const uint4*>(blk);
 }
 
-rdo_params to_params(const float* f, const uint32_t* u) {
-    rdo_params p;
-    p.lambda = f[0]; p.max_allowed_rms_increase_ratio = f[1]; p.skip_block_rms_thresh = f[2]; p.max_smooth_block_std_dev = f[3];
-    p.smooth_block_max_error_scale = f[4];
-    p.lz_dict_size = u[0]; p.lz_literal_cost = u[1]; p.endpoint_refinement = u[2];
-    return p;
-}
+// THE table of the kernels' builds, by form: [0] arithmetic, [1] strip table; of the walk one per (candidates from the LDS ring / from HBM, fat / lean). The compiler
+// emits an instantiation where it is first named, so this order is the order of the kernels in the code object.
+struct rdo_builds { decltype(&k_rdo_strips<true, true, true>) ring_fat, ring_lean, hbm_fat, hbm_lean; decltype(&k_rdo_finish<true>) finish; };
+constexpr rdo_builds RDO_BUILDS[2] = {
+    { k_rdo_strips<true, true, false>, k_rdo_strips<true, false, false>, k_rdo_strips<false, true, false>, k_rdo_strips<false, false, false>, k_rdo_finish<false> },
+    { k_rdo_strips<true, true, true>, k_rdo_strips<true, false, true>, k_rdo_strips<false, true, true>, k_rdo_strips<false, false, true>, k_rdo_finish<true> } };
+
+// The workspace as rdo_slices_layout (uastc_rdo_strips.h) carves it: counters (per slice: modified, failed, refined, skipped), strip_counts (modified blocks per strip),
+// strip_flags (per strip: != 0 when it holds an active block of a sensitive mode, 15 / 17 / 18 -- set by the prepare pass, decides which build of the walk takes the
+// strip), hist, state (per block: 0 untouched, 1 modified + refit pending, 2 modified), the uploaded strips and order, info, mod_list, table (RDO_TABLE_WORDS per block).
+template <class T>
+T* at(void* d_ws, size_t ofs) { return reinterpret_cast<T*>(static_cast<char*>(d_ws) + ofs); }
+
+// The arithmetic form's per_job, 0 = one strip: a slice alone is cut into strips of per_job blocks (the last one may be shorter), so record 0 says it.
+uint32_t per_job_of(const rdo_slices_layout& L) { return L.recs.size() > 1 ? L.recs[0].last - L.recs[0].first : 0u; }
 
 } // namespace
 
-size_t uastc_rdo_workspace_bytes(uint32_t n_blocks, uint32_t total_jobs) {
-    size_t total = 0;
-    carve(nullptr, n_blocks, total_jobs, &total);
-    return total;
-}
-
-uint32_t uastc_rdo_strips(uint32_t n_blocks, uint32_t total_jobs) {
-    uint32_t per_job, n_strips, cap;
-    strip_layout(n_blocks, total_jobs, per_job, n_strips, cap);
-    return n_strips;
-}
-
-hipError_t launch_uastc_rdo_phase(hipStream_t st, int phase, void* d_blocks, const void* d_px, uint32_t n, const float* fparams, const uint32_t* uparams,
-                                  uint32_t flags, uint32_t total_jobs, void* d_ws) {
+hipError_t launch_uastc_rdo_prepare(hipStream_t st, void* d_blocks, const void* d_px, const rdo_slices_layout& L, const rdo_params& p, void* d_ws, bool table) {
+    const uint32_t n = L.total_blocks;
     if (!n) return hipSuccess;
-    const rdo_workspace w = carve(d_ws, n, total_jobs, nullptr);
-    const rdo_params p = to_params(fparams, uparams);
-    uint32_t per_job, n_strips, cap;
-    strip_layout(n, total_jobs, per_job, n_strips, cap);
-    uint4* blocks = static_cast<uint4*>(d_blocks);
-    const uint4* px = static_cast<const uint4*>(d_px);
-    const uint32_t gx = (n + 63) / 64;
-    switch (phase) {
-    case 0: {
-        const hipError_t e = hipMemsetAsync(w.counters, 0, w.zero_bytes, st);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_rdo_prepare, dim3(gx), dim3(64), 0, st, blocks, px, n, p, w.info, w.table, w.counters, w.strip_flags, per_job, nullptr, 0u);
-        break;
-    }
-    case 1:     // the lean walk: strips without a sensitive block
-    case 3: {   // the walk with the refit in it: the flagged strips (the caller runs it on a second stream beside phase 1)
-        const uint32_t window = p.lz_dict_size / 16 > 1 ? p.lz_dict_size / 16 : 1;
-        uint32_t ring = 1;
-        while (ring < window) ring <<= 1;
-        if (ring > RDO_RING_MAX) ring = 0;
-        const bool fat = phase == 3;
-        if (ring && fat)
-            hipLaunchKernelGGL((k_rdo_strips<true, true, false>), dim3(n_strips), dim3(RDO_THREADS), (size_t)ring * 16, st, blocks, px, n, per_job, p, w.info, w.table, w.hist,
-                               cap, w.state, w.mod_list, w.strip_counts, w.counters, ring, w.strip_flags, nullptr, nullptr);
-        else if (ring)
-            hipLaunchKernelGGL((k_rdo_strips<true, false, false>), dim3(n_strips), dim3(RDO_THREADS), (size_t)ring * 16, st, blocks, px, n, per_job, p, w.info, w.table, w.hist,
-                               cap, w.state, w.mod_list, w.strip_counts, w.counters, ring, w.strip_flags, nullptr, nullptr);
-        else if (fat)
-            hipLaunchKernelGGL((k_rdo_strips<false, true, false>), dim3(n_strips), dim3(RDO_THREADS), 0, st, blocks, px, n, per_job, p, w.info, w.table, w.hist, cap, w.state,
-                               w.mod_list, w.strip_counts, w.counters, 1u, w.strip_flags, nullptr, nullptr);
-        else
-            hipLaunchKernelGGL((k_rdo_strips<false, false, false>), dim3(n_strips), dim3(RDO_THREADS), 0, st, blocks, px, n, per_job, p, w.info, w.table, w.hist, cap, w.state,
-                               w.mod_list, w.strip_counts, w.counters, 1u, w.strip_flags, nullptr, nullptr);
-        break;
-    }
-    default: {
-        // phase 2 takes the longest per-strip list length in `total_jobs`' place holder: see launch_uastc_rdo_finish
-        return hipErrorInvalidValue;
-    }
-    }
+    const hipError_t e = hipMemsetAsync(d_ws, 0, L.zero_bytes, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rdo_prepare, dim3((n + 63) / 64), dim3(64), 0, st, static_cast<const uint4*>(d_blocks), static_cast<const uint4*>(d_px), n, p,
+                       at<rdo_info4>(d_ws, L.info), at<uint32_t>(d_ws, L.table), at<uint32_t>(d_ws, L.counters), at<uint32_t>(d_ws, L.strip_flags), table ? 0u : per_job_of(L),
+                       table ? at<const rdo_strip_rec>(d_ws, L.strips) : nullptr, table ? (uint32_t)L.recs.size() : 0u);
     return hipGetLastError();
 }
 
-hipError_t launch_uastc_rdo_finish(hipStream_t st, void* d_blocks, const void* d_px, uint32_t n, const float* fparams, const uint32_t* uparams, uint32_t flags,
-                                   uint32_t total_jobs, void* d_ws, uint32_t longest_list) {
-    if (!n || !longest_list) return hipSuccess;
-    const rdo_workspace w = carve(d_ws, n, total_jobs, nullptr);
-    uint32_t per_job, n_strips, cap;
-    strip_layout(n, total_jobs, per_job, n_strips, cap);
-    enc_cfg e;
-    make_cfg(flags, e);
-    hipLaunchKernelGGL(k_rdo_finish<false>, dim3((longest_list + 63) / 64, n_strips), dim3(64), 0, st, static_cast<uint4*>(d_blocks), static_cast<const uint4*>(d_px), n,
-                       per_job, e, to_params(fparams, uparams), w.mod_list, w.strip_counts, w.state, w.counters, nullptr, 0u);
-    return hipGetLastError();
-}
-
-// ---- several slices in one pass: the strip table form. The caller has put L.recs at d_ws + L.strips and L.order at d_ws + L.order_at.
-
-hipError_t launch_uastc_rdo_slices_phase(hipStream_t st, int phase, void* d_blocks, const void* d_px, const rdo_slices_layout& L, const float* fparams,
-                                         const uint32_t* uparams, void* d_ws) {
-    const uint32_t n = L.total_blocks, n_strips = (uint32_t)L.recs.size();
-    if (!n) return hipSuccess;
-    char* ws = static_cast<char*>(d_ws);
-    const rdo_params p = to_params(fparams, uparams);
-    uint4* blocks = static_cast<uint4*>(d_blocks);
-    const uint4* px = static_cast<const uint4*>(d_px);
-    rdo_info4* info = reinterpret_cast<rdo_info4*>(ws + L.info);
-    uint32_t* table = reinterpret_cast<uint32_t*>(ws + L.table);
-    uint32_t* counters = reinterpret_cast<uint32_t*>(ws + L.counters);
-    uint32_t* strip_flags = reinterpret_cast<uint32_t*>(ws + L.strip_flags);
-    const rdo_strip_rec* recs = reinterpret_cast<const rdo_strip_rec*>(ws + L.strips);
-    if (phase == 0) {
-        const hipError_t e = hipMemsetAsync(ws, 0, L.zero_bytes, st);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_rdo_prepare, dim3((n + 63) / 64), dim3(64), 0, st, blocks, px, n, p, info, table, counters, strip_flags, 0u, recs, n_strips);
-        return hipGetLastError();
-    }
-    if (phase != 1 && phase != 3) return hipErrorInvalidValue;
+hipError_t launch_uastc_rdo_walk(hipStream_t st, bool fat, void* d_blocks, const void* d_px, const rdo_slices_layout& L, const rdo_params& p, void* d_ws, bool table) {
+    if (!L.total_blocks) return hipSuccess;
     const uint32_t window = p.lz_dict_size / 16 > 1 ? p.lz_dict_size / 16 : 1;
     uint32_t ring = 1;
     while (ring < window) ring <<= 1;
     if (ring > RDO_RING_MAX) ring = 0;
-    const bool fat = phase == 3;
-    auto* kernel = ring ? (fat ? k_rdo_strips<true, true, true> : k_rdo_strips<true, false, true>) : (fat ? k_rdo_strips<false, true, true> : k_rdo_strips<false, false, true>);
-    hipLaunchKernelGGL(kernel, dim3(n_strips), dim3(RDO_THREADS), (size_t)ring * 16, st, blocks, px, n, 0u, p, info, table, reinterpret_cast<hist_entry*>(ws + L.hist), 0u,
-                       reinterpret_cast<uint8_t*>(ws + L.state), reinterpret_cast<uint32_t*>(ws + L.mod_list), reinterpret_cast<uint32_t*>(ws + L.strip_counts), counters,
-                       ring ? ring : 1u, strip_flags, recs, reinterpret_cast<const uint32_t*>(ws + L.order_at));
+    const rdo_builds& b = RDO_BUILDS[table];
+    hipLaunchKernelGGL(ring ? (fat ? b.ring_fat : b.ring_lean) : (fat ? b.hbm_fat : b.hbm_lean), dim3((uint32_t)L.recs.size()), dim3(RDO_THREADS), (size_t)ring * 16, st, static_cast<uint4*>(d_blocks),
+                       static_cast<const uint4*>(d_px), L.total_blocks, table ? 0u : per_job_of(L), p, at<const rdo_info4>(d_ws, L.info), at<const uint32_t>(d_ws, L.table),
+                       at<hist_entry>(d_ws, L.hist), table ? 0u : L.recs[0].hist_cap, at<uint8_t>(d_ws, L.state), at<uint32_t>(d_ws, L.mod_list),
+                       at<uint32_t>(d_ws, L.strip_counts), at<uint32_t>(d_ws, L.counters), ring ? ring : 1u, at<const uint32_t>(d_ws, L.strip_flags),
+                       table ? at<const rdo_strip_rec>(d_ws, L.strips) : nullptr, table ? at<const uint32_t>(d_ws, L.order_at) : nullptr);
     return hipGetLastError();
 }
 
-hipError_t launch_uastc_rdo_slices_finish(hipStream_t st, void* d_blocks, const void* d_px, const rdo_slices_layout& L, const float* fparams, const uint32_t* uparams,
-                                          uint32_t flags, void* d_ws, uint32_t longest_list) {
+hipError_t launch_uastc_rdo_finish(hipStream_t st, void* d_blocks, const void* d_px, const rdo_slices_layout& L, const rdo_params& p, uint32_t flags, void* d_ws, bool table,
+                                   uint32_t longest_list) {
     const uint32_t n_strips = (uint32_t)L.recs.size();
     if (!L.total_blocks || !longest_list) return hipSuccess;
-    char* ws = static_cast<char*>(d_ws);
     enc_cfg e;
     make_cfg(flags, e);
     for (uint32_t base = 0; base < n_strips; base += 65535u) {   // a grid's y extent ends at 65535
-        hipLaunchKernelGGL(k_rdo_finish<true>, dim3((longest_list + 63) / 64, std::min(65535u, n_strips - base)), dim3(64), 0, st, static_cast<uint4*>(d_blocks),
-                           static_cast<const uint4*>(d_px), L.total_blocks, 0u, e, to_params(fparams, uparams), reinterpret_cast<const uint32_t*>(ws + L.mod_list),
-                           reinterpret_cast<const uint32_t*>(ws + L.strip_counts), reinterpret_cast<const uint8_t*>(ws + L.state),
-                           reinterpret_cast<uint32_t*>(ws + L.counters), reinterpret_cast<const rdo_strip_rec*>(ws + L.strips), base);
+        hipLaunchKernelGGL(RDO_BUILDS[table].finish, dim3((longest_list + 63) / 64, std::min(65535u, n_strips - base)), dim3(64), 0, st, static_cast<uint4*>(d_blocks),
+                           static_cast<const uint4*>(d_px), L.total_blocks, table ? 0u : per_job_of(L), e, p, at<const uint32_t>(d_ws, L.mod_list),
+                           at<const uint32_t>(d_ws, L.strip_counts), at<const uint8_t>(d_ws, L.state), at<uint32_t>(d_ws, L.counters),
+                           table ? at<const rdo_strip_rec>(d_ws, L.strips) : nullptr, base);
         const hipError_t err = hipGetLastError();
         if (err != hipSuccess) return err;
     }
     return hipSuccess;
 }
-
-const void* uastc_rdo_counters(void* d_ws, uint32_t n, uint32_t total_jobs) { return carve(d_ws, n, total_jobs, nullptr).counters; }
-const void* uastc_rdo_strip_counts(void* d_ws, uint32_t n, uint32_t total_jobs) { return carve(d_ws, n, total_jobs, nullptr).strip_counts; }
 
 } // namespace bu

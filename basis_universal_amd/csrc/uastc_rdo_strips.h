@@ -1,5 +1,6 @@
-// uastc_rdo_strips.h -- how uastc_rdo cuts a slice into strips, and the strip table of one call over several slices (bu_hip_k_uastc_rdo_slices). Plain host code:
-// uastc_rdo_kernels.hip builds the table with it before anything is enqueued, and tests/test_uastc_rdo_slices_host.py builds it into a stand-alone program.
+// uastc_rdo_strips.h -- how uastc_rdo cuts a slice into strips, and rdo_slices_layout: the strip table and THE statement of the device workspace of every RDO call,
+// over one slice (bu_hip_k_uastc_rdo, a pipeline submission) or several (bu_hip_k_uastc_rdo_slices). Plain host code: api_uastc.cpp builds the layout before anything
+// is enqueued, the launchers of uastc_rdo_kernels.hip read it, and tests/test_uastc_rdo_slices_host.py builds it into a stand-alone program.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -75,6 +76,15 @@ inline bool rdo_slices_layout_build(const uint32_t* slice_blocks, uint32_t n_sli
     L.table = o; o += up((size_t)L.total_blocks * RDO_TABLE_BYTES);
     L.total_bytes = o;
     return true;
+}
+
+// One slice alone. Its records are what the arithmetic form of the kernels computes from a strip's index (first = k * per_job, hist_ofs = k * hist_cap, one hist_cap),
+// so that form runs on this layout without the table on the device: the strips / order_at regions then lie unused.
+inline bool rdo_slice_layout_build(uint32_t n, uint32_t total_jobs, rdo_slices_layout& L) { return rdo_slices_layout_build(&n, 1, total_jobs, L); }
+// what bu_hip_k_uastc_rdo needs for n blocks; 0: more blocks than a call takes
+inline size_t uastc_rdo_workspace_bytes(uint32_t n, uint32_t total_jobs) {
+    rdo_slices_layout L;
+    return rdo_slice_layout_build(n, total_jobs, L) ? L.total_bytes : 0;
 }
 
 } // namespace bu

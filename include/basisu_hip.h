@@ -317,7 +317,9 @@ BU_HIP_API int bu_hip_k_find_optimal_selector_clusters(bu_hip_context*, const vo
 BU_HIP_API int bu_hip_k_encode_uastc_blocks(bu_hip_context*, const void* d_pixel_blocks, uint32_t n_blocks, uint32_t flags, void* d_out_uastc_blocks);
 /* Bytes of context workspace that call needs (27 candidate slots x 76 B per block at level 2; 170 at level 4). */
 BU_HIP_API size_t bu_hip_uastc_workspace_bytes(uint32_t n_blocks, uint32_t flags);
-/* ... and what bu_hip_k_uastc_rdo needs for the same blocks cut into total_jobs strips (the two calls share the one workspace; a UASTC pipeline sizes its lanes' for the larger of the two) */
+/* ... and what bu_hip_k_uastc_rdo needs for the same blocks cut into total_jobs strips (the two calls share the one workspace; a UASTC pipeline sizes its lanes' for the larger of the two).
+ * It is bu_hip_uastc_rdo_slices_workspace_bytes of that one slice: every RDO call has the one workspace layout, so the figure includes the two regions of the strip table
+ * (32 + 4 bytes per strip, each region rounded up to 256), which a single-slice call leaves unused. 0 for more than 2^31 - 1 blocks, which bu_hip_k_uastc_rdo refuses. */
 BU_HIP_API size_t bu_hip_uastc_rdo_workspace_bytes(uint32_t n_blocks, uint32_t total_jobs);
 
 /* a20 (SURVEY.md 8a "next" row f1): basisu::uastc_rdo (encoder/basisu_uastc_enc.h:139, uastc_enc.cpp:4095-4163) in place over n_blocks
@@ -326,7 +328,7 @@ BU_HIP_API size_t bu_hip_uastc_rdo_workspace_bytes(uint32_t n_blocks, uint32_t t
  * `total_jobs` has the reference's meaning: 0/1 = one strip, otherwise strips of n_blocks / total_jobs blocks that do not see each
  * other (comp.cpp:2076-2078 passes min(4, threads)). Output is bit-identical to the reference called with the same total_jobs.
  * Synchronises the context's stream; `out_stats` (optional) receives {modified, refined, skipped, strips}. Fails (0) like the reference
- * when a block does not unpack. */
+ * when a block does not unpack; refuses more than 2^31 - 1 blocks (the walk holds block indices in signed ints). */
 typedef struct bu_uastc_rdo_params {
     float m_lambda;
     float m_max_allowed_rms_increase_ratio;

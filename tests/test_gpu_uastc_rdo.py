@@ -60,13 +60,16 @@ def test_flagged_and_unflagged_strips_side_by_side(hip_ctx, golden):
             assert (got == helpers.host_uastc_rdo(pk, bl, 2, jobs, lam=3.0, refine=refine)).all(), (jobs, refine)
 
 
-@pytest.mark.parametrize("n", [0, 1, 2, 40, 257, 600])
+@pytest.mark.parametrize("n", [0, 1, 2, 35, 36, 37, 40, 257, 600])
 @pytest.mark.parametrize("jobs", [0, 4])
 def test_ragged_sizes(hip_ctx, golden, n, jobs):
+    """35, 36, 37 at four jobs: one strip (per_job 8), the smallest size that is split (four strips of 9), a fifth strip of one block"""
     packed, blocks = golden["packed_l2"][:n], golden["blocks"][:n]
     got, info = uastc.uastc_rdo(hip_ctx, packed, blocks, params(lam=4.0), 2, jobs)
     assert got.shape == (n, 16)
     assert (got == helpers.host_uastc_rdo(packed, blocks, 2, jobs, lam=4.0)).all()
+    if n in (35, 36, 37):
+        assert info["strips"] == ({35: 1, 36: 4, 37: 5}[n] if jobs == 4 else 1)
 
 
 def test_window_larger_than_the_lds_ring(hip_ctx, golden):

@@ -107,6 +107,18 @@ def test_one_slice_holds_all_blocks(hip_ctx, golden, sizes, jobs):
     junk[7, 0] = 0x45
     with pytest.raises(capi.HipError, match=f"slice {len(sizes) // 2} "):
         in_one_pass(hip_ctx, junk, blocks, sizes, params(), 2, jobs)
+    if len(sizes) == 3:
+        # the arithmetic builds took it (the decision of DESIGN 4l), not the strip table's: the single-slice entry's scopes, once each, and none of uastc_rdo_slices_*
+        ctx = capi.Context(0)   # its own context: profile_read names 32 scopes at the most
+        try:
+            ctx.profile_enable()
+            got, _ = in_one_pass(ctx, packed, blocks, sizes, params(lam=4.0), 2, jobs)
+            scopes = ctx.profile_read()
+            ctx.profile_enable(False)
+        finally:
+            ctx.close()
+        assert {k: v[1] for k, v in scopes.items() if k.startswith("uastc_rdo")} == {"uastc_rdo_prepare": 1, "uastc_rdo_strips": 1, "uastc_rdo_finish": 1}, scopes
+        assert (got == helpers.host_uastc_rdo(packed, blocks, 2, jobs, lam=4.0)).all()
 
 
 # ---- 2. nothing looks back across a slice boundary

@@ -14,6 +14,7 @@ ROOT = pathlib.Path(__file__).resolve().parent.parent
 SLICE_LISTS = ([600, 1, 40, 257, 9, 2, 36, 0, 64], [120, 120, 120], [4400, 300], [257, 40], [0], [0, 0, 5], [1], [1 << 20, 1 << 18, 1 << 16, 4096, 1024, 256, 64, 16, 4, 1, 1, 1, 1],
                [4096] * 64)
 JOBS = (0, 1, 3, 4, 64)
+ONE_SLICE = (1, 8, 35, 36, 37, 257, 1464, 4096)   # at four jobs 35: one strip (per_job 8), 36: four strips, 37: five, the last of one block
 INFO_BYTES, HIST_ENTRY_BYTES, TABLE_BYTES = 32, 16, 2048
 
 MAIN = r"""
@@ -123,6 +124,35 @@ def test_strip_table(program, slices, jobs):
     lengths = [recs[i][1] - recs[i][0] for i in order]
     assert all(a >= b for a, b in zip(lengths, lengths[1:]))
     assert all(i < j for (i, a), (j, b) in zip(zip(order, lengths), zip(order[1:], lengths[1:])) if a == b)
+
+
+def up256(v):
+    return (v + 255) & ~255
+
+
+@pytest.mark.parametrize("jobs", JOBS)
+@pytest.mark.parametrize("n", ONE_SLICE)
+def test_one_slice_is_the_arithmetic_form(program, n, jobs):
+    """The layout of ONE slice is what the arithmetic builds of the kernels (strip k: per_job and one history capacity, no table on the device) work on, and up to
+    zero_bytes what the single-slice entry carved before this layout became the only one; the regions of the table it does not upload are all it adds."""
+    L = program([n], jobs)
+    per_job, strips, cap = strip_layout(n, jobs)
+    assert L["ok"] and L["total_blocks"] == n and L["slice_strips"] == [strips] and len(L["recs"]) == strips
+    for k, (first, last, hist_cap, mod_ofs, hist_ofs, slice_) in enumerate(L["recs"]):
+        assert (first, last) == ((k * per_job, min(n, k * per_job + per_job)) if per_job else (0, n))
+        assert (hist_cap, mod_ofs, hist_ofs, slice_) == (cap, first, k * cap, 0)
+    assert L["longest"] == (per_job or n)
+    # the carve of the single-slice entry as it was: 256 bytes of counters, then strip counts, strip flags, histories and state, every region rounded up to 256
+    at, o = L["at"], 0
+    for name, size in (("counters", 256), ("strip_counts", 4 * strips), ("strip_flags", 4 * strips), ("hist", strips * cap * HIST_ENTRY_BYTES), ("state", n)):
+        assert at[name] == o, name
+        o += up256(size)
+    assert at["zero_bytes"] == o
+    was_total = o + up256(n * INFO_BYTES) + up256(4 * n) + up256(n * TABLE_BYTES)
+    assert at["total_bytes"] == was_total + up256(32 * strips) + up256(4 * strips)
+    if jobs == 4 and n in (35, 36, 37):
+        assert (strips, per_job) == {35: (1, 0), 36: (4, 9), 37: (5, 9)}[n]
+        assert L["recs"][-1][:2] == {35: [0, 35], 36: [27, 36], 37: [36, 37]}[n]
 
 
 def test_a_mip_level_does_not_reserve_level_0s_history(program):
