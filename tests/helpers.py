@@ -151,6 +151,140 @@ def etc1s_test_tiles():
     return np.concatenate([a, b, flat, to_pixel_blocks(grad)])
 
 
+ETC1_INTEN_TABLES = np.array([[-8, -2, 2, 8], [-17, -5, 5, 17], [-29, -9, 9, 29], [-42, -13, 13, 42], [-60, -18, 18, 60], [-80, -24, 24, 80], [-106, -33, 33, 106],
+                              [-183, -47, 47, 183]], np.int32)
+PLANT_CLASSES = ("inside", "low", "high", "both", "split")
+PLANT_TILES_PER_ENDPOINT = 12
+PLANT_NOISE = (0, 0, 1, 3)
+
+
+def etc1s_clamp_class(color5, table):
+    """How the outer colours of ETC1S endpoints (color5 (..., 3), table (...)) clamp: 0 = neither base - b nor base + b leaves 0..255 in any channel, 1 = only base - b
+    does (low), 2 = only base + b does (high), 3 = both do."""
+    c5 = np.asarray(color5, np.int32)
+    c8 = (c5 << 3) | (c5 >> 2)
+    b = ETC1_INTEN_TABLES[np.asarray(table, np.int64), 3]
+    return ((c8.min(axis=-1) - b < 0) * 1 + (c8.max(axis=-1) + b > 255) * 2).astype(np.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def _planted_tiles():
+    rng = np.random.default_rng(20241)
+    all5 = np.stack(np.meshgrid(np.arange(32), np.arange(32), np.arange(32), indexing="ij"), -1).reshape(-1, 3).astype(np.int32)
+    all8 = (all5 << 3) | (all5 >> 2)
+    mn, mx = all8.min(axis=1), all8.max(axis=1)
+    tiles, meta = [], []
+    endpoint = 0
+    for t in range(8):
+        b = int(ETC1_INTEN_TABLES[t, 3])
+        lo, hi = mn - b < 0, mx + b > 255
+        member = {"inside": ~lo & ~hi, "low": lo & ~hi, "high": ~lo & hi, "both": lo & hi & (mx - mn < 60), "split": lo & hi & (mx - mn >= 120)}
+        for ci, cls in enumerate(PLANT_CLASSES):
+            if not member[cls].any():   # no base of table 7 stays inside; only tables 6 and 7 clamp at both ends with channels that close
+                continue
+            picked = set()
+            while len(picked) < 6:      # rejection: draw colour5 values until six distinct members of the class have come up
+                c = int(rng.integers(0, 1 << 15))
+                if member[cls][c]:
+                    picked.add(c)
+            for c in sorted(picked):
+                for k in range(PLANT_TILES_PER_ENDPOINT):
+                    sel = rng.integers(0, 4, 16)
+                    sel[:4] = rng.permutation(4)
+                    a = PLANT_NOISE[k % len(PLANT_NOISE)]
+                    clean = np.clip(all8[c][None, :] + ETC1_INTEN_TABLES[t][sel][:, None], 0, 255)
+                    px = np.clip(clean + rng.integers(-a, a + 1, (16, 3)), 0, 255)
+                    tile = np.full((16, 4), 255, np.uint8)
+                    tile[:, :3] = px
+                    tiles.append(tile.reshape(4, 4, 4))
+                    meta.append((t, ci, endpoint, a, tuple(int(v) for v in all5[c])))
+                endpoint += 1
+    meta = np.array(meta, np.dtype([("table", np.uint8), ("cls", np.uint8), ("endpoint", np.uint32), ("noise", np.uint8), ("color5", np.uint8, 3)]))
+    tiles = np.ascontiguousarray(np.stack(tiles))
+    tiles.setflags(write=False); meta.setflags(write=False)
+    return tiles, meta
+
+
+def etc1s_planted_tiles():
+    """-> (tiles (n, 4, 4, 4) u8, meta): tiles drawn from the four colours of a PLANTED ETC1S endpoint, so that every intensity table wins somewhere and the winning
+    endpoint's outer colours clamp in every way they can. Per table 0..7 and per clamp class (PLANT_CLASSES; mn, mx the smallest and largest channel of the scaled base, b the
+    table's outer step: inside = nothing clamps, low = only mn - b < 0, high = only mx + b > 255, both = both with mx - mn < 60, split = both with mx - mn >= 120, one channel
+    clamping low while another clamps high) six base colours found by rejection, classes no base of the table falls in left out; per endpoint twelve tiles of sixteen random
+    selectors, the first four a permutation of 0..3, texel = clamp(base + delta[selector]) plus uniform noise of amplitude 0, 0, 1, 3 (in turn), clamped again. Alpha is 255.
+    meta (structured, one record per tile): table, cls (index into PLANT_CLASSES), endpoint (0.., ordered by table, then class), noise, color5. Read-only, seeded."""
+    return _planted_tiles()
+
+
+@functools.lru_cache(maxsize=None)
+def etc1s_spread_ladder():
+    """768 tiles: for every spread s in 0..255 and every channel c one tile whose channel c spans exactly [l0, l0 + s], both extremes present, the other two channels
+    spanning at most s -- the block's (and, as a cluster of its two sub-blocks, the cluster's) index into the per-spread intensity table mask is s. Read-only, seeded."""
+    rng = np.random.default_rng(20242)
+    tiles = np.full((768, 16, 4), 255, np.uint8)
+    for s in range(256):
+        for c in range(3):
+            t = tiles[s * 3 + c]
+            for ch in range(3):
+                span = s if ch == c else int(rng.integers(0, s + 1))
+                l0 = int(rng.integers(0, 256 - span))
+                t[:, ch] = rng.integers(l0, l0 + span + 1, 16)
+                if ch == c:
+                    where = rng.permutation(16)[:2]
+                    t[where[0], ch], t[where[1], ch] = l0, l0 + s
+    tiles = np.ascontiguousarray(tiles.reshape(768, 4, 4, 4))
+    tiles.setflags(write=False)
+    return tiles
+
+
+def etc1s_planted_test_tiles():
+    """The second tile set of the ETC1S kernel parity tests: the planted tiles followed by the spread ladder."""
+    return np.ascontiguousarray(np.concatenate([etc1s_planted_tiles()[0], etc1s_spread_ladder()]))
+
+
+def clusters_by_plant(meta):
+    """The endpoint clustering the planted tiles were made for, in clusters_by_luma's shape: cluster e = both sub-blocks of every tile of planted endpoint e."""
+    ep = np.asarray(meta["endpoint"], np.uint32)
+    lists = []
+    for e in range(int(ep.max()) + 1):
+        run = np.nonzero(ep == e)[0]
+        lists.append(np.stack([run * 2, run * 2 + 1], axis=1).reshape(-1).astype(np.uint32))
+    return lists, ep.copy()
+
+
+def planted_exact_clusters(meta, count=24):
+    """`count` clusters the cluster fit can reproduce exactly: the first two noise-free tiles of one planted endpoint each, endpoints spread evenly over the tables and clamp
+    classes (the clusters of clusters_by_plant hold the noisy tiles too, and none of them comes out with error 0)."""
+    n_ep = int(meta["endpoint"].max()) + 1
+    lists = []
+    for e in np.linspace(0, n_ep - 1, count).astype(np.int64):
+        run = np.nonzero((meta["endpoint"] == e) & (meta["noise"] == 0))[0][:2]
+        lists.append(np.stack([run * 2, run * 2 + 1], axis=1).reshape(-1).astype(np.uint32))
+    return lists
+
+
+def planted_endpoint_codebook(perceptual=1, level=1):
+    """-> fresh copies of (the oracle's fit of clusters_by_plant's clusters, about 200 x {r5, g5, b5, inten} with every table and clamp class present, the cluster of every tile of
+    etc1s_planted_test_tiles: its planted endpoint, and for a ladder tile the cluster whose colour5 is nearest to the tile's mean colour)"""
+    params, block_cluster = _planted_endpoint_codebook(int(perceptual), level)
+    return params.copy(), block_cluster.copy()
+
+
+@functools.lru_cache(maxsize=None)
+def _planted_endpoint_codebook(perceptual, level):
+    tiles, meta = etc1s_planted_tiles()
+    blocks = etc1s_planted_test_tiles()
+    lists, block_cluster = clusters_by_plant(meta)
+    k = len(lists)
+    offs, idx = csr_from_lists(lists)
+    params = np.zeros((k, 4), np.uint8); err = np.zeros(k, np.uint64); valid = np.zeros(k, np.uint8)
+    oracle().orc_generate_endpoint_codebook(ptr(blocks), k, ptr(offs, u32p), ptr(idx, u32p), level, perceptual, 0, ptr(params), ptr(err, u64p), ptr(valid))
+    assert valid.all()
+    ladder = blocks[tiles.shape[0]:, :, :, :3].reshape(-1, 16, 3).astype(np.float64).mean(axis=1)
+    base = ((params[:, :3].astype(np.int32) << 3) | (params[:, :3] >> 2)).astype(np.float64)
+    near = ((ladder[:, None, :] - base[None, :, :]) ** 2).sum(axis=2).argmin(axis=1).astype(np.uint32)
+    return params, np.ascontiguousarray(np.concatenate([block_cluster, near]))
+
+
 def clusters_by_luma(blocks, k, rng):
     """A plausible endpoint clustering: blocks sorted by mean luma cut into k uneven runs; both subblocks stay together."""
     n = blocks.shape[0]

@@ -10,10 +10,19 @@ import pytest
 
 from helpers import (oracle, ptr, u8p, u32p, u64p, f32p, synth, uniform_random, to_pixel_blocks, csr_from_lists)
 from helpers import etc1s_test_tiles as _images, clusters_by_luma as _clusters_by_luma, endpoint_codebook as _codebook
+from helpers import (etc1s_planted_tiles, etc1s_planted_test_tiles, clusters_by_plant, planted_exact_clusters, planted_endpoint_codebook, ETC1_INTEN_TABLES)
 
 pytestmark = pytest.mark.gpu
 
 VP = C.c_void_p
+
+
+# The tests that take `blocks` run on two tile sets. "images" (these module fixtures): a synthetic image, noise, flat tiles, a gradient. "planted" (class TestPlanted at
+# the end of the file, which overrides the three fixtures and runs the same test functions): helpers.etc1s_planted_test_tiles -- tiles drawn from planted endpoints of every
+# intensity table and clamp class, then one tile per spread and channel; what they reach that the images do not is held in test_etc1s_tile_coverage_host.py.
+@pytest.fixture(scope="module")
+def tileset():
+    return "images"
 
 
 @pytest.fixture(scope="module")
@@ -28,9 +37,17 @@ def d_blocks(hip_ctx, blocks):
     hip_ctx.free(p)
 
 
+def _tile_codebook(tileset, blocks, k, seed, perceptual=1):
+    """the endpoint codebook (and the cluster of every block) that the refine and selector tests work with: fitted by the oracle to a luma clustering of the images, to the
+    planted clustering of the planted tiles (about 200 entries whatever k: every table and clamp class among them)"""
+    if tileset == "planted":
+        return planted_endpoint_codebook(perceptual)
+    return _codebook(blocks, k, seed, perceptual=perceptual)
+
+
 @pytest.mark.parametrize("perceptual", [1, 0])
 @pytest.mark.parametrize("quality,level", [(0, 0), (1, 1), (2, 2), (3, 6)])
-def test_encode_etc1s_blocks(hip_ctx, blocks, d_blocks, quality, level, perceptual):
+def test_encode_etc1s_blocks(hip_ctx, tileset, blocks, d_blocks, quality, level, perceptual):
     n = blocks.shape[0]
     d_out = hip_ctx.alloc(n * 8)
     hip_ctx.check(hip_ctx.lib.k_encode_etc1s_blocks(hip_ctx.h, d_blocks, n, quality, perceptual, d_out), "k_encode")
@@ -39,7 +56,17 @@ def test_encode_etc1s_blocks(hip_ctx, blocks, d_blocks, quality, level, perceptu
     exp = np.zeros((n, 8), np.uint8)
     oracle().orc_encode_etc1s_blocks(ptr(blocks), n, level, perceptual, ptr(exp))
     bad = np.nonzero((got != exp).any(axis=1))[0]
-    assert bad.size == 0, f"{bad.size} of {n} blocks differ, first {bad[:5]}: got {got[bad[:2]]} exp {exp[bad[:2]]}"
+    assert bad.size == 0, f"{bad.size} of {n} blocks differ, first {bad[:5]} {_tile_origin(tileset, bad[:1])}: got {got[bad[:2]]} exp {exp[bad[:2]]}"
+
+
+def _tile_origin(tileset, which):
+    """what a tile of the planted set was made as (for a failure's message)"""
+    if tileset != "planted" or not len(which):
+        return ""
+    meta, i = etc1s_planted_tiles()[1], int(which[0])
+    if i >= meta.shape[0]:
+        return f"(ladder: spread {(i - meta.shape[0]) // 3}, channel {(i - meta.shape[0]) % 3})"
+    return f"(planted: {meta[i]})"
 
 
 def test_encode_ragged_tail(hip_ctx, blocks):
@@ -141,16 +168,23 @@ def test_endpoint_training_vectors(hip_ctx, blocks):
 @pytest.mark.parametrize("wide_min", [None, 8, 0])
 @pytest.mark.parametrize("perceptual", [1, 0])
 @pytest.mark.parametrize("quality,level", [(1, 1), (2, 2), (3, 6)])
-def test_generate_endpoint_codebook(hip_ctx, blocks, d_blocks, quality, level, perceptual, wide_min, request):
+def test_generate_endpoint_codebook(hip_ctx, tileset, blocks, d_blocks, quality, level, perceptual, wide_min, request):
     if wide_min is not None:
         request.addfinalizer(hip_ctx.set_tuning)
         hip_ctx.set_tuning(codebook_wide_min=wide_min)
     rng = np.random.default_rng(7)
-    k = 97
-    lists, _ = _clusters_by_luma(blocks, k, rng)
+    if tileset == "planted":
+        # the clusters the tiles were planted for (every table wins, winners of every clamp class), clusters of noise-free tiles that fit with error 0 (the early-out), one
+        # cluster per ladder tile (every spread: the per-spread table mask at quality 1), and clusters of a single sub-block
+        meta = etc1s_planted_tiles()[1]
+        lists = clusters_by_plant(meta)[0] + planted_exact_clusters(meta)
+        lists += [np.array([2 * b, 2 * b + 1], np.uint32) for b in range(meta.shape[0], blocks.shape[0])]
+        lists += [np.array([s], np.uint32) for s in rng.choice(blocks.shape[0] * 2, 16, replace=False)]
+    else:
+        lists, _ = _clusters_by_luma(blocks, 97, rng)
     # one giant cluster as well: exercises the multi-wave reduction with thousands of pixels
     lists.append(np.arange(blocks.shape[0] * 2, dtype=np.uint32))
-    k += 1
+    k = len(lists)
     offs, idx = csr_from_lists(lists)
     d_offs, d_idx = hip_ctx.upload(offs), hip_ctx.upload(idx)
     params = np.zeros((k, 4), np.uint8); err = np.zeros(k, np.uint64); valid = np.zeros(k, np.uint8)
@@ -164,7 +198,7 @@ def test_generate_endpoint_codebook(hip_ctx, blocks, d_blocks, quality, level, p
 
     got = run(0)
     oracle().orc_generate_endpoint_codebook(ptr(blocks), k, ptr(offs, u32p), ptr(idx, u32p), level, perceptual, 0, ptr(params), ptr(err, u64p), ptr(valid))
-    assert (got[0] == params).all() and (got[1] == err).all() and (got[2] == valid).all()
+    assert (got[0] == params).all() and (got[1] == err).all() and (got[2] == valid).all(), _first_cluster_off(got, (params, err, valid), lists)
 
     # step 1: perturb half of the previous parameters so that both "keep old" and "take new" branches run (frontend.cpp:1554-1605)
     params2 = params.copy()
@@ -176,9 +210,16 @@ def test_generate_endpoint_codebook(hip_ctx, blocks, d_blocks, quality, level, p
     got = run(1)
     err2 = err.copy()
     oracle().orc_generate_endpoint_codebook(ptr(blocks), k, ptr(offs, u32p), ptr(idx, u32p), level, perceptual, 1, ptr(params2), ptr(err2, u64p), ptr(valid2))
-    assert (got[0] == params2).all() and (got[1] == err2).all() and (got[2] == valid2).all()
+    assert (got[0] == params2).all() and (got[1] == err2).all() and (got[2] == valid2).all(), _first_cluster_off(got, (params2, err2, valid2), lists)
     for p in (d_offs, d_idx, d_params, d_err, d_valid):
         hip_ctx.free(p)
+
+
+def _first_cluster_off(got, exp, lists):
+    bad = np.nonzero((got[0] != exp[0]).any(axis=1) | (got[1] != exp[1]) | (got[2] != exp[2]))[0]
+    c = int(bad[0])
+    return (f"{bad.size} of {len(lists)} clusters differ, first {c} ({lists[c].size} sub-blocks, first {lists[c][:4].tolist()}): "
+            f"got {got[0][c].tolist()} err {int(got[1][c])} valid {int(got[2][c])}, expected {exp[0][c].tolist()} err {int(exp[1][c])} valid {int(exp[2][c])}")
 
 
 @pytest.mark.parametrize("kind", ["bright", "dark_then_bright", "solid"])
@@ -267,20 +308,26 @@ def test_ordered_colour_mean_of_clusters(hip_ctx, kind):
 @pytest.mark.parametrize("presorted", [True, False])
 @pytest.mark.parametrize("perceptual", [1, 0])
 @pytest.mark.parametrize("hier", [True, False, "foreign"])
-def test_refine_endpoint_clusterization(hip_ctx, blocks, d_blocks, hier, perceptual, presorted, request):
+def test_refine_endpoint_clusterization(hip_ctx, tileset, blocks, d_blocks, hier, perceptual, presorted, request):
     # presorted: the candidate lists re-sorted on the device by (clamping class, intensity table) first (k_refine_sort_lists + k_refine_sorted, the
     # default); otherwise the kernel that filters and classifies the lists as it reads them (kept for codebooks beyond 65,535 entries)
     if not presorted:
         hip_ctx.set_tuning(refine_unsorted=1)
         request.addfinalizer(hip_ctx.set_tuning)   # back to the process defaults
     n = blocks.shape[0]
-    k = 300
-    params, block_cluster = _codebook(blocks, k, 11, perceptual=perceptual)
+    params, block_cluster = _tile_codebook(tileset, blocks, 300, 11, perceptual)
+    k = params.shape[0]
     # duplicate a few codebook entries so that ties between distinct clusters occur
-    params[10] = params[11]; params[200] = params[150]
+    params[10] = params[11]; params[k * 2 // 3] = params[k // 2]
+    if tileset == "planted":
+        # every planted tile starts in the cluster that was fitted to it: move a seeded eighth of the blocks to a random other cluster, so that something has to move back
+        rng = np.random.default_rng(13)
+        moved = rng.choice(n, n // 8, replace=False)
+        block_cluster[moved] = (block_cluster[moved] + rng.integers(1, k, moved.size)) % k
     n_parents = 7 if hier else 0
     if hier:
-        # parents = contiguous ranges of clusters (luma ordered), candidate lists = clusters of that parent, sorted ascending like
+        # parents = contiguous ranges of clusters (luma ordered in the images; ordered by (table, clamp class) in the planted set, so every candidate list there is of few
+        # tables and "foreign" mixes them), candidate lists = clusters of that parent, sorted ascending like
         # compute_endpoint_clusters_within_each_parent_cluster (frontend.cpp:971-996)
         cluster_parent = (np.arange(k) * n_parents // k).astype(np.uint8)
         block_parent = cluster_parent[block_cluster]
@@ -299,16 +346,17 @@ def test_refine_endpoint_clusterization(hip_ctx, blocks, d_blocks, hier, percept
     d_out = hip_ctx.alloc(n * 4)
     hip_ctx.check(hip_ctx.lib.k_refine_endpoint_clusterization(hip_ctx.h, d_blocks, n, bufs[0], bufs[1], k, n_parents, bufs[2], bufs[3], bufs[4], perceptual, d_out), "k_refine")
     got = hip_ctx.download(d_out, (n,), np.uint32)
-    assert (got == exp).all(), f"{int((got != exp).sum())} of {n} differ"
+    bad = np.nonzero(got != exp)[0]
+    assert bad.size == 0, f"{bad.size} of {n} differ, first block {bad[:5]}: got {got[bad[:5]]} ({params[got[bad[:5]] % k].tolist()}) exp {exp[bad[:5]]} ({params[exp[bad[:5]]].tolist()})"
     assert (got != block_cluster).any(), "degenerate test: nothing moved"
     for p in bufs + [d_out]:
         hip_ctx.free(p)
 
 
 @pytest.mark.parametrize("perceptual", [1, 0])
-def test_determine_selectors(hip_ctx, blocks, d_blocks, perceptual):
+def test_determine_selectors(hip_ctx, tileset, blocks, d_blocks, perceptual):
     n = blocks.shape[0]
-    params, block_cluster = _codebook(blocks, 64, 3, perceptual=perceptual)
+    params, block_cluster = _tile_codebook(tileset, blocks, 64, 3, perceptual)
     per_block = np.ascontiguousarray(params[block_cluster])
     exp = np.zeros((n, 8), np.uint8)
     oracle().orc_determine_selectors(ptr(blocks), n, ptr(per_block), perceptual, ptr(exp))
@@ -326,18 +374,18 @@ def test_determine_selectors(hip_ctx, blocks, d_blocks, perceptual):
         hip_ctx.free(p)
 
 
-def _encoded(blocks, perceptual=1):
+def _encoded(blocks, perceptual=1, tileset="images"):
     n = blocks.shape[0]
-    params, block_cluster = _codebook(blocks, 64, 3, perceptual=perceptual)
+    params, block_cluster = _tile_codebook(tileset, blocks, 64, 3, perceptual)
     enc = np.zeros((n, 8), np.uint8)
     oracle().orc_determine_selectors(ptr(blocks), n, ptr(np.ascontiguousarray(params[block_cluster])), perceptual, ptr(enc))
     return enc
 
 
 @pytest.mark.parametrize("perceptual", [1, 0])
-def test_selector_training_vectors(hip_ctx, blocks, perceptual):
+def test_selector_training_vectors(hip_ctx, tileset, blocks, perceptual):
     n = blocks.shape[0]
-    enc = _encoded(blocks, perceptual)
+    enc = _encoded(blocks, perceptual, tileset)
     exp_v = np.zeros((n, 16), np.float32); exp_w = np.zeros(n, np.uint64)
     oracle().orc_selector_training_vectors(ptr(enc), n, perceptual, ptr(exp_v, f32p), ptr(exp_w, u64p))
     d_enc = hip_ctx.upload(enc); d_v = hip_ctx.alloc(n * 64); d_w = hip_ctx.alloc(n * 8)
@@ -360,10 +408,10 @@ def _check_groups(n, u, keys_np, got_keys, got_offsets, got_idx, weights=None, g
 
 
 @pytest.mark.parametrize("n", [0, 1, 2, 257, 3072])
-def test_unique_selector_vectors(hip_ctx, blocks, n):
+def test_unique_selector_vectors(hip_ctx, tileset, blocks, n):
     """bu_hip_k_unique_selector_vectors against the oracle's selector training vectors + numpy: the key is the vector's 16 values, first in the
     top two bits (the reference's std::map<vec16F> order); all-equal and all-distinct inputs included through the block sample."""
-    enc_all = _encoded(blocks, 1)
+    enc_all = _encoded(blocks, 1, tileset)
     enc = np.ascontiguousarray(np.concatenate([enc_all, enc_all[:64]])[:n])   # duplicates guaranteed
     vec = np.zeros((n, 16), np.float32); w = np.zeros(n, np.uint64)
     if n:
@@ -405,6 +453,35 @@ def test_unique_endpoint_vectors(hip_ctx, blocks, n):
         hip_ctx.free(p_)
 
 
+def test_unique_endpoint_vectors_of_every_code(hip_ctx):
+    """One ETC1S block per (colour5, intensity table) code, all 2^18 in a seeded order, then the first 64 of them again: the blocks are sorted by the RANK of their code's key
+    in a table made once per device, and codes whose clamped low and high colours coincide share a rank -- which encoder output at a few thousand blocks hardly ever shows.
+    The expected keys are numpy's, by the format's definition: clamp(base - b) and clamp(base + b) of the three channels as one 48-bit number. 236,235 groups: the ceiling
+    test_host_logic.py::test_endpoint_codebook_can_never_reach_the_threaded_gate derives."""
+    rng = np.random.default_rng(18)
+    code = rng.permutation(1 << 18)
+    code = np.concatenate([code, code[:64]])
+    n = code.size
+    c5 = np.stack([(code >> 13) & 31, (code >> 8) & 31, (code >> 3) & 31], axis=1)
+    table = code & 7
+    etc = np.zeros((n, 8), np.uint8)     # differential, zero deltas, both tables the same, flipped (etc_block::is_etc1s); selector bits zero
+    etc[:, 0:3] = c5 << 3
+    etc[:, 3] = (table << 5) | (table << 2) | 3
+    base = (c5 << 3) | (c5 >> 2)
+    b = ETC1_INTEN_TABLES[table, 3].astype(np.int64)[:, None]
+    six = np.concatenate([np.clip(base - b, 0, 255), np.clip(base + b, 0, 255)], axis=1).astype(np.uint64)
+    keys = (six << (8 * (5 - np.arange(6, dtype=np.uint64)))).sum(axis=1).astype(np.uint64)
+    d_etc = hip_ctx.upload(etc)
+    d_idx, d_keys, d_ofs = hip_ctx.alloc(n * 4 + 4), hip_ctx.alloc(n * 8 + 8), hip_ctx.alloc(n * 4 + 8)
+    u = C.c_uint32(12345)
+    hip_ctx.check(hip_ctx.lib.k_unique_endpoint_vectors(hip_ctx.h, d_etc, n, d_idx, d_keys, d_ofs, C.byref(u)), "k_unique_endpoint_vectors")
+    got = hip_ctx.download(d_keys, (n,), np.uint64), hip_ctx.download(d_ofs, (n + 1,), np.uint32), hip_ctx.download(d_idx, (n,), np.uint32)
+    for p_ in (d_etc, d_idx, d_keys, d_ofs):
+        hip_ctx.free(p_)
+    assert u.value == 236235
+    _check_groups(n, u.value, keys, *got)
+
+
 def _selector_clusters(enc, k, rng):
     n = enc.shape[0]
     key = enc[:, 4:].astype(np.uint32) @ np.array([1, 256, 65536, 16777216], np.uint32)
@@ -416,8 +493,8 @@ def _selector_clusters(enc, k, rng):
 
 
 @pytest.mark.parametrize("perceptual", [1, 0])
-def test_create_optimized_selector_codebook(hip_ctx, blocks, d_blocks, perceptual):
-    enc = _encoded(blocks, perceptual)
+def test_create_optimized_selector_codebook(hip_ctx, tileset, blocks, d_blocks, perceptual):
+    enc = _encoded(blocks, perceptual, tileset)
     rng = np.random.default_rng(5)
     k = 120
     lists = _selector_clusters(enc, k, rng)
@@ -435,13 +512,13 @@ def test_create_optimized_selector_codebook(hip_ctx, blocks, d_blocks, perceptua
 
 @pytest.mark.parametrize("perceptual", [1, 0])
 @pytest.mark.parametrize("hier", [True, False])
-def test_find_optimal_selector_clusters(hip_ctx, blocks, hier, perceptual):
+def test_find_optimal_selector_clusters(hip_ctx, tileset, blocks, hier, perceptual):
     # make runs of identical tiles that straddle a job boundary (chunk) so the shortcut of frontend.cpp:2557-2564 is exercised
     blocks = blocks.copy()
     blocks[100:110] = blocks[100]
     blocks[2040:2060] = blocks[2040]
     n = blocks.shape[0]
-    enc = _encoded(blocks, perceptual)
+    enc = _encoded(blocks, perceptual, tileset)
     enc[105, :3] ^= 0x18  # identical tiles with DIFFERENT endpoints: the copied choice must still be the run head's
     rng = np.random.default_rng(9)
     k = 200
@@ -531,3 +608,29 @@ def test_error_convention(hip_ctx):
     assert lib.k_encode_uastc_blocks(hip_ctx.h, None, 16, 2, None) == 0 and b"null" in lib.dll.bu_hip_last_error(hip_ctx.h)
     assert lib.encode_uastc_blocks(None, None, 2) == 0
     assert lib.k_generate_endpoint_codebook_part(hip_ctx.h, None, 4, None, None, None, 1, 1, 0, None, None, None, 3, 2) == 0
+
+
+class TestPlanted:
+    """The tests above that take `blocks`, once more on the planted tiles followed by the spread ladder (3,144 tiles): the same functions, with these fixtures in place of
+    the module's. What differs per test is written where it reads `tileset`."""
+
+    @pytest.fixture(scope="class")
+    def tileset(self):
+        return "planted"
+
+    @pytest.fixture(scope="class")
+    def blocks(self):
+        return etc1s_planted_test_tiles()
+
+    @pytest.fixture(scope="class")
+    def d_blocks(self, hip_ctx, blocks):
+        p = hip_ctx.upload(blocks)
+        yield p
+        hip_ctx.free(p)
+
+
+for _test in (test_encode_etc1s_blocks, test_encode_ragged_tail, test_generate_endpoint_codebook, test_refine_endpoint_clusterization, test_determine_selectors,
+              test_selector_training_vectors, test_unique_selector_vectors, test_unique_endpoint_vectors, test_create_optimized_selector_codebook,
+              test_find_optimal_selector_clusters):
+    setattr(TestPlanted, _test.__name__, staticmethod(_test))
+del _test

@@ -6,14 +6,19 @@ import numpy as np
 import pytest
 
 from helpers import (oracle, ref, have_ref, ref_harness_version, RefFrontend, ptr, u32p, u64p, f32p, synth, uniform_random, to_pixel_blocks,
-                     csr_from_lists, ROOT)
+                     csr_from_lists, etc1s_planted_tiles, etc1s_spread_ladder, PLANT_TILES_PER_ENDPOINT, ROOT)
 
 pytestmark = pytest.mark.skipif(not have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 
 
 def _inputs():
     return {"synth": to_pixel_blocks(synth(256, 192, 1234)), "noise": to_pixel_blocks(uniform_random(96, 64, 42)),
-            "kodim03": to_pixel_blocks(np.load(ROOT / "tests" / "golden" / "kodim03.npz")["rgba"])}   # the reference's test_files/kodim03.png
+            "kodim03": to_pixel_blocks(np.load(ROOT / "tests" / "golden" / "kodim03.npz")["rgba"]),   # the reference's test_files/kodim03.png
+            # generated: every intensity table and clamp class as the winner, every spread (test_etc1s_tile_coverage_host.py)
+            "planted": etc1s_planted_tiles()[0], "ladder": etc1s_spread_ladder()}
+
+
+GENERATED = ("planted", "ladder")   # small: never truncated
 
 
 INPUTS = _inputs()
@@ -23,7 +28,7 @@ INPUTS = _inputs()
 @pytest.mark.parametrize("level,perceptual", [(0, 1), (1, 1), (1, 0), (2, 1), (6, 0)])
 def test_block_encode(name, level, perceptual):
     blocks = INPUTS[name]
-    if level >= 2:
+    if level >= 2 and name not in GENERATED:
         blocks = blocks[:2048]
     n = blocks.shape[0]
     a = np.zeros((n, 8), np.uint8); b = np.zeros((n, 8), np.uint8)
@@ -63,6 +68,33 @@ def test_cluster_optimizer(n, quality):
         assert oracle().orc_etc1_optimize(ptr(rgba), n, quality, perceptual, ptr(ca), ptr(ia, u32p), ptr(ea, u64p), ptr(sa)) == 1
         assert ref().ref_etc1_optimize(ptr(rgba), n, quality, perceptual, ptr(cb), ptr(ib, u32p), ptr(eb, u64p), ptr(sb)) == 1
         assert (ca == cb).all() and ia[0] == ib[0] and ea[0] == eb[0] and (sa == sb).all()
+
+
+def _planted_pixel_lists():
+    """the texels of every third planted endpoint's twelve tiles (192 each), and every fifth ladder tile on its own (16 texels)"""
+    tiles, meta = etc1s_planted_tiles()
+    n_ep = int(meta["endpoint"].max()) + 1
+    lists = [tiles[meta["endpoint"] == e].reshape(-1, 4) for e in range(0, n_ep, 3)]
+    assert all(l.shape[0] == 16 * PLANT_TILES_PER_ENDPOINT for l in lists)
+    return lists + [t.reshape(16, 4) for t in etc1s_spread_ladder()[::5]]
+
+
+@pytest.mark.ref
+@pytest.mark.parametrize("perceptual", [1, 0])
+@pytest.mark.parametrize("quality", [1, 2, 3])
+def test_cluster_optimizer_planted(quality, perceptual):
+    """etc1_optimizer on the generated inputs of the kernel parity tests: lists whose best table is each of the eight and whose best endpoint clamps low, high, at both
+    ends, and 16-texel lists of every fifth spread (the per-spread table mask at quality 1)."""
+    for i, rgba in enumerate(_planted_pixel_lists()):
+        rgba = np.ascontiguousarray(rgba)
+        n = rgba.shape[0]
+        ca = np.zeros(3, np.uint8); cb = np.zeros(3, np.uint8)
+        ia = np.zeros(1, np.uint32); ib = np.zeros(1, np.uint32)
+        ea = np.zeros(1, np.uint64); eb = np.zeros(1, np.uint64)
+        sa = np.zeros(n, np.uint8); sb = np.zeros(n, np.uint8)
+        assert oracle().orc_etc1_optimize(ptr(rgba), n, quality, perceptual, ptr(ca), ptr(ia, u32p), ptr(ea, u64p), ptr(sa)) == 1
+        assert ref().ref_etc1_optimize(ptr(rgba), n, quality, perceptual, ptr(cb), ptr(ib, u32p), ptr(eb, u64p), ptr(sb)) == 1
+        assert (ca == cb).all() and ia[0] == ib[0] and ea[0] == eb[0] and (sa == sb).all(), (i, n, ca, cb, ia, ib, ea, eb)
 
 
 # the pins below need entry points an oracle/_ref/ built from an earlier revision's harness does not have; where the reference lies, build() rebuilds the harness
