@@ -117,4 +117,35 @@ int bu_hip_k_transcode_etc1s(bu_hip_context* ctx, const void* d_ep_pal, uint32_t
     return 1;
 }
 
+// every image of a file in one launch: the table's checks, upload and read-back are api_transcode_slices.cpp's
+int bu_hip_k_transcode_etc1s_slices(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
+                                    uint64_t n_indices, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target, void* d_out, size_t out_bytes,
+                                    uint32_t* out_invalid_per_slice) {
+    if (!ctx) return 0;
+    static const char* const fn = "transcode_etc1s_slices";
+    if (!bu::etc1s_transcode_unit_bytes(target)) {
+        set_error(ctx, "transcode_etc1s: target %u (%s) is not supported (supported: %s)", target, transcoder_format_name(target), kEtc1sTargets);
+        return 0;
+    }
+    if (!d_ep_pal || !d_sel_pal || !d_ep_idx || !d_sel_idx) { set_error(ctx, "%s: null pointer", fn); return 0; }
+    if (!n_ep || !n_sel || n_ep > 65535u || n_sel > 65535u) { set_error(ctx, "%s: palettes of %u endpoints and %u selectors (1..65535 each)", fn, n_ep, n_sel); return 0; }
+    transcode_slice_table table;
+    if (!table.check(ctx, fn, slices, n_slices, n_indices, target, true, d_out, out_bytes)) return 0;
+    device_guard g(ctx->device);
+    const uint32_t* bc1 = nullptr;
+    if (target == bu::ETF_BC1_RGB) {
+        if (!ensure_bc1_tables(ctx)) return 0;
+        bc1 = static_cast<const uint32_t*>(ctx->etc1s_bc1_tables.p);
+    }
+    if (!table.upload(ctx)) return 0;
+    const bu::etc1s_transcode_slices_args a = { static_cast<const uint32_t*>(d_ep_pal), static_cast<const uint32_t*>(d_sel_pal), static_cast<const uint16_t*>(d_ep_idx),
+                                                static_cast<const uint16_t*>(d_sel_idx), static_cast<uint8_t*>(d_out), table.d_counters, bc1, table.d_slices, table.d_prefix,
+                                                n_ep, n_sel, table.n, table.total_blocks };
+    {
+        prof_scope ps(ctx, fn);
+        BU_TRY(ctx, bu::launch_transcode_etc1s_slices(ctx->stream, a, target));
+    }
+    return out_invalid_per_slice ? table.read_counters(ctx, out_invalid_per_slice) : 1;
+}
+
 } // extern "C"

@@ -109,6 +109,20 @@ inline const char* transcoder_format_name(uint32_t format) {
     return format < sizeof(names) / sizeof(names[0]) ? names[format] : "unknown";
 }
 
+// The slice table of the whole-file transcoders (api_transcode_slices.cpp): check() is every refusal the two entries share -- nothing is touched when it returns 0 --
+// and packs what upload() sends in one stream-ordered copy into scratch[4]: the records with their zero sizes filled in, the prefix table of their block counts, and
+// behind them the per-slice counters the launcher clears.
+struct transcode_slice_table {
+    std::vector<uint8_t> pack;
+    size_t prefix_at = 0, counters_at = 0;
+    uint32_t n = 0, total_blocks = 0;
+    const bu_hip_transcode_slice* d_slices = nullptr; const uint32_t* d_prefix = nullptr; uint32_t* d_counters = nullptr;   // set by upload()
+    int check(bu_hip_context* ctx, const char* fn, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint64_t n_inputs, uint32_t target, bool etc1s, const void* d_out,
+              size_t out_bytes);
+    int upload(bu_hip_context* ctx);
+    int read_counters(bu_hip_context* ctx, uint32_t* out_per_slice);   // one copy, one stream wait
+};
+
 struct device_guard {
     int prev = -1; bool ok = false;
     explicit device_guard(int dev) {

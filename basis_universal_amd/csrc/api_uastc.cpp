@@ -52,6 +52,8 @@ int bu_hip_encode_uastc_blocks(bu_hip_context* ctx, bu_uastc_block* out, uint32_
 
 // ---------------------------------------------------------------- UASTC transcode (uastc_transcode_kernels.hip)
 
+static const char* const kUastcTargetRefused = "transcode_uastc: target %u is not supported (RGBA32, ASTC 4x4, BC1, BC3, BC4, BC5, BC7 are)";   // both entries' text
+
 size_t bu_hip_transcode_output_bytes(uint32_t nbx, uint32_t nby, uint32_t orig_width, uint32_t orig_height, uint32_t target) {
     return bu::transcode_output_bytes(nbx, nby, orig_width, orig_height, target);
 }
@@ -61,7 +63,7 @@ int bu_hip_k_transcode_uastc(bu_hip_context* ctx, const void* d_blocks, uint32_t
                              uint32_t* out_invalid_blocks) {
     if (!ctx) return 0;
     if (out_invalid_blocks) *out_invalid_blocks = 0;
-    if (!bu::transcode_output_bytes(1, 1, 0, 0, target)) { set_error(ctx, "transcode_uastc: target %u is not supported (RGBA32, ASTC 4x4, BC1, BC3, BC4, BC5, BC7 are)", target); return 0; }
+    if (!bu::transcode_output_bytes(1, 1, 0, 0, target)) { set_error(ctx, kUastcTargetRefused, target); return 0; }
     if (!d_blocks || !d_out) { set_error(ctx, "transcode_uastc: null device pointer"); return 0; }
     if ((uint64_t)nbx * nby > 0x7FFFFFFFull) { set_error(ctx, "transcode_uastc: %u x %u blocks is too many", nbx, nby); return 0; }
     const uint32_t width = orig_width ? orig_width : nbx * 4, height = orig_height ? orig_height : nby * 4;
@@ -82,6 +84,28 @@ int bu_hip_k_transcode_uastc(bu_hip_context* ctx, const void* d_blocks, uint32_t
     BU_TRY(ctx, stream_wait(ctx, ctx->stream));
     if (out_invalid_blocks) *out_invalid_blocks = invalid;
     return 1;
+}
+
+// every image of a file in one launch: the table's checks, upload and read-back are api_transcode_slices.cpp's
+int bu_hip_k_transcode_uastc_slices(bu_hip_context* ctx, const void* d_blocks, uint64_t n_blocks, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target,
+                                    uint32_t decode_flags, int32_t channel0, int32_t channel1, void* d_out, size_t out_bytes, uint32_t* out_invalid_per_slice) {
+    if (!ctx) return 0;
+    static const char* const fn = "transcode_uastc_slices";
+    if (!bu::transcode_output_bytes(1, 1, 0, 0, target)) { set_error(ctx, kUastcTargetRefused, target); return 0; }
+    if (!d_blocks) { set_error(ctx, "%s: null pointer", fn); return 0; }
+    if ((uintptr_t)d_blocks & 15u) { set_error(ctx, "%s: the blocks are not 16-byte aligned", fn); return 0; }
+    if (channel0 > 3 || channel1 > 3) { set_error(ctx, "%s: channel out of range", fn); return 0; }
+    transcode_slice_table table;
+    if (!table.check(ctx, fn, slices, n_slices, n_blocks, target, false, d_out, out_bytes)) return 0;
+    device_guard g(ctx->device);
+    if (!table.upload(ctx)) return 0;
+    {
+        prof_scope ps(ctx, fn);
+        BU_TRY(ctx, bu::launch_transcode_uastc_slices(ctx->stream, d_blocks, table.d_slices, table.d_prefix, table.n, table.total_blocks, target,
+                                                      (decode_flags & 32u) != 0 /* cDecodeFlagsHighQuality */, channel0 < 0 ? 0u : (uint32_t)channel0,
+                                                      channel1 < 0 ? 3u : (uint32_t)channel1, d_out, table.d_counters));
+    }
+    return out_invalid_per_slice ? table.read_counters(ctx, out_invalid_per_slice) : 1;
 }
 
 void bu_hip_uastc_rdo_default_params(bu_uastc_rdo_params* p) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/basisu_hip.h"
 
 namespace bu {
 
@@ -19,10 +20,24 @@ struct etc1s_transcode_args {
     uint32_t n_endpoints, n_selectors, nbx, nby, width, height, pitch, rows;
 };
 
+// every image of a file in one launch: the file's two whole index arrays, and a table that says which ranges of them are whose
+struct etc1s_transcode_slices_args {
+    const uint32_t *endpoint_palette, *selector_palette;
+    const uint16_t *endpoint_idx, *selector_idx;   // slice s reads [first_block, first_block + nbx * nby) of both, its alpha slice the same from alpha_first_block
+    uint8_t* out;                                  // slice s writes at out + out_offset
+    uint32_t* invalid;                             // n_slices device counters
+    const uint32_t* bc1_endpoints;
+    const bu_hip_transcode_slice* slices;          // device copies of the records, every zero size replaced by what it stands for
+    const uint32_t* prefix;                        // n_slices + 1 entries: where each slice's blocks begin among the total_blocks of the call
+    uint32_t n_endpoints, n_selectors, n_slices, total_blocks;
+};
+
 uint32_t etc1s_transcode_unit_bytes(uint32_t target);   // per block for block targets, per pixel for pixel targets; 0 = the target does not exist here
 bool etc1s_transcode_is_pixel_target(uint32_t target);
 // one launch; d_invalid is cleared first and afterwards holds how many blocks had an index past its palette (their output is zero-filled)
 hipError_t launch_transcode_etc1s(hipStream_t st, const etc1s_transcode_args& a, uint32_t target);
+// one launch over every slice of the table; invalid[n_slices] is cleared first and afterwards holds the per-slice counts
+hipError_t launch_transcode_etc1s_slices(hipStream_t st, const etc1s_transcode_slices_args& a, uint32_t target);
 // fills d_tables[2 * kBc1TableEntries] with the ETC1S -> BC1 endpoint tables (5-bit, then 6-bit)
 hipError_t launch_etc1s_build_bc1_tables(hipStream_t st, uint32_t* d_tables);
 // counts the entries of idx[n] that are >= limit into *d_count (cleared first)

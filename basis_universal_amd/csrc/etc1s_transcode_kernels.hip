@@ -3,10 +3,12 @@
 // A lane reads its two u16 indices (four with an alpha slice), gathers the palette entries (4 bytes each) and builds its output in registers: block targets store
 // one uint2 per block, consecutive lanes on consecutive blocks; pixel targets store the four rows of the tile into the caller's raster, cropped to the image, as
 // one 16-byte (RGBA32) or 8-byte (16-bit formats) word per row where the row is whole and aligned. An index past its palette never reaches a gather: the block is
-// zero-filled and counted with a vector atomic, and it does not stop the others.
+// zero-filled and counted with a vector atomic, and it does not stop the others. Two kernels share that per-block work: one image per launch, and every image of
+// a file in one launch through a slice table (transcode_slices.h), counted per slice.
 #include <hip/hip_runtime.h>
 #include "etc1s_device.h"
 #include "etc1s_transcode_kernels.h"
+#include "transcode_slices.h"
 
 #define BU_TAB static __device__ const
 #include "etc1s_transcode_tables.inc"
@@ -115,21 +117,30 @@ __device__ __forceinline__ uint32_t pack_pixel(uint32_t c, uint32_t a) {
     return (mul_8(r, 15) << 12) | (mul_8(g, 15) << 8) | (mul_8(b, 15) << 4) | mul_8(a, 15);   // RGBA4444
 }
 
+// what every block of a launch reads besides its own indices
+struct etc1s_palettes {
+    const uint32_t *endpoint_palette, *selector_palette, *bc1_endpoints;
+    uint32_t n_endpoints, n_selectors;
+};
+
+// One block: the range check, the gathers, the target's conversion, the store. The four index pointers are the IMAGE's (alpha: both null = opaque), `out` is where
+// the image's output begins, `i` the block's place in the image's raster order. Block targets write one uint2 at out[i]; pixel targets the four rows of the tile
+// cropped to width x min(height, rows), a row as one word where it is whole and its address aligned. false = an index was past its palette and zeros were written.
+// Both kernels below are this function behind their own indexing.
 template <uint32_t TARGET>
-__global__ __launch_bounds__(256) void transcode_etc1s_kernel(etc1s_transcode_args a) {
-    const uint32_t n = a.nbx * a.nby, i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
+__device__ __forceinline__ bool transcode_etc1s_block(const etc1s_palettes& a, const uint16_t* endpoint_idx, const uint16_t* selector_idx, const uint16_t* alpha_endpoint_idx,
+                                                      const uint16_t* alpha_selector_idx, void* out, uint32_t i, uint32_t nbx, uint32_t width, uint32_t height, uint32_t pitch,
+                                                      uint32_t rows) {
     constexpr bool kPixels = TARGET == ETF_RGBA32 || TARGET == ETF_RGB565 || TARGET == ETF_BGR565 || TARGET == ETF_RGBA4444;
     constexpr bool kAlpha = TARGET == ETF_RGBA32 || TARGET == ETF_RGBA4444;
-    const uint32_t ei = a.endpoint_idx[i], si = a.selector_idx[i];
+    const uint32_t ei = endpoint_idx[i], si = selector_idx[i];
     bool ok = ei < a.n_endpoints && si < a.n_selectors;
     uint32_t aei = 0, asi = 0;
-    const bool has_alpha = kAlpha && a.alpha_endpoint_idx != nullptr;
+    const bool has_alpha = kAlpha && alpha_endpoint_idx != nullptr;
     if (has_alpha) {
-        aei = a.alpha_endpoint_idx[i]; asi = a.alpha_selector_idx[i];
+        aei = alpha_endpoint_idx[i]; asi = alpha_selector_idx[i];
         ok = ok && aei < a.n_endpoints && asi < a.n_selectors;
     }
-    if (!ok) atomicAdd(a.invalid, 1u);
     if (!kPixels) {
         uint2 o = make_uint2(0u, 0u);
         if (ok) {
@@ -137,8 +148,8 @@ __global__ __launch_bounds__(256) void transcode_etc1s_kernel(etc1s_transcode_ar
             const uint32_t sel = a.selector_palette[si];
             o = TARGET == ETF_ETC1_RGB ? to_etc1(e, sel) : to_bc1(e, sel, a.bc1_endpoints, a.bc1_endpoints + kBc1TableEntries);
         }
-        ((uint2*)a.out)[i] = o;
-        return;
+        ((uint2*)out)[i] = o;
+        return ok;
     }
     uint32_t colors[4] = { 0, 0, 0, 0 }, alphas[4] = { 255u, 255u, 255u, 255u }, sel = 0, asel = 0;
     if (ok) {
@@ -154,35 +165,58 @@ __global__ __launch_bounds__(256) void transcode_etc1s_kernel(etc1s_transcode_ar
     } else {
         alphas[0] = alphas[1] = alphas[2] = alphas[3] = 0;
     }
-    const uint32_t bx = i % a.nbx, by = i / a.nbx;
-    const bool whole = bx * 4u + 4u <= a.width;
+    const uint32_t bx = i % nbx, by = i / nbx;
+    const bool whole = bx * 4u + 4u <= width;
 #pragma unroll
     for (uint32_t y = 0; y < 4; y++) {
         const uint32_t row = by * 4u + y;
-        if (row >= a.height || row >= a.rows) break;
+        if (row >= height || row >= rows) break;
         uint32_t v[4];
 #pragma unroll
         for (uint32_t x = 0; x < 4; x++) {
             const uint32_t px = pack_pixel<TARGET>(pick4(colors, texel_selector(sel, x, y)), has_alpha ? pick4(alphas, texel_selector(asel, x, y)) : alphas[0]);
             v[x] = ok ? px : 0u;
         }
-        const size_t at = (size_t)row * a.pitch + bx * 4u;
+        const size_t at = (size_t)row * pitch + bx * 4u;
         if (TARGET == ETF_RGBA32) {
-            uint32_t* dst = (uint32_t*)a.out + at;
+            uint32_t* dst = (uint32_t*)out + at;
             if (whole && (((uintptr_t)dst & 15u) == 0)) *(uint4*)dst = make_uint4(v[0], v[1], v[2], v[3]);
             else {
 #pragma unroll
-                for (uint32_t x = 0; x < 4; x++) if (bx * 4u + x < a.width) dst[x] = v[x];
+                for (uint32_t x = 0; x < 4; x++) if (bx * 4u + x < width) dst[x] = v[x];
             }
         } else {
-            uint16_t* dst = (uint16_t*)a.out + at;
+            uint16_t* dst = (uint16_t*)out + at;
             if (whole && (((uintptr_t)dst & 7u) == 0)) *(uint2*)dst = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
             else {
 #pragma unroll
-                for (uint32_t x = 0; x < 4; x++) if (bx * 4u + x < a.width) dst[x] = (uint16_t)v[x];
+                for (uint32_t x = 0; x < 4; x++) if (bx * 4u + x < width) dst[x] = (uint16_t)v[x];
             }
         }
     }
+    return ok;
+}
+
+template <uint32_t TARGET>
+__global__ __launch_bounds__(256) void transcode_etc1s_kernel(etc1s_transcode_args a) {
+    const uint32_t n = a.nbx * a.nby, i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const etc1s_palettes p = { a.endpoint_palette, a.selector_palette, a.bc1_endpoints, a.n_endpoints, a.n_selectors };
+    if (!transcode_etc1s_block<TARGET>(p, a.endpoint_idx, a.selector_idx, a.alpha_endpoint_idx, a.alpha_selector_idx, a.out, i, a.nbx, a.width, a.height, a.pitch, a.rows))
+        atomicAdd(a.invalid, 1u);
+}
+
+// every image of a file in one launch (bu_hip_k_transcode_etc1s_slices): the lookup of transcode_slices.h in front of the same block function. The colour and the
+// alpha slice of an image are two ranges of the same two index arrays.
+template <uint32_t TARGET>
+__global__ __launch_bounds__(256) void transcode_etc1s_slices_kernel(etc1s_transcode_slices_args a) {
+    transcode_slice_view v;
+    if (!find_transcode_slice(a.slices, a.prefix, a.n_slices, a.total_blocks, blockIdx.x * 256u + threadIdx.x, v)) return;
+    const etc1s_palettes p = { a.endpoint_palette, a.selector_palette, a.bc1_endpoints, a.n_endpoints, a.n_selectors };
+    const bool alpha = v.alpha_first_block != BU_HIP_NO_ALPHA_SLICE;
+    if (!transcode_etc1s_block<TARGET>(p, a.endpoint_idx + v.first_block, a.selector_idx + v.first_block, alpha ? a.endpoint_idx + v.alpha_first_block : nullptr,
+                                       alpha ? a.selector_idx + v.alpha_first_block : nullptr, a.out + v.out_offset, v.local, v.nbx, v.width, v.height, v.pitch, v.rows))
+        atomicAdd(a.invalid + v.slice, 1u);
 }
 
 // The two endpoint tables of to_bc1, [intensity table][base5][range][mapping] -> lo | hi << 8 | squared error << 16 for 5-bit (first kBc1TableEntries words) and 6-bit
@@ -231,6 +265,26 @@ static hipError_t launch(hipStream_t st, const etc1s_transcode_args& a) {
     hipLaunchKernelGGL((transcode_etc1s_kernel<TARGET>), dim3((n + 255) / 256), dim3(256), 0, st, a);
     return hipGetLastError();
 }
+template <uint32_t TARGET>
+static hipError_t launch(hipStream_t st, const etc1s_transcode_slices_args& a) {
+    hipLaunchKernelGGL((transcode_etc1s_slices_kernel<TARGET>), dim3((a.total_blocks + 255) / 256), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+// the instance of either kernel for the target
+template <class Args>
+static hipError_t launch_for_target(hipStream_t st, const Args& a, uint32_t target) {
+    if (target == ETF_BC1_RGB && !a.bc1_endpoints) return hipErrorInvalidValue;
+    switch (target) {
+    case ETF_ETC1_RGB: return launch<ETF_ETC1_RGB>(st, a);
+    case ETF_BC1_RGB: return launch<ETF_BC1_RGB>(st, a);
+    case ETF_RGBA32: return launch<ETF_RGBA32>(st, a);
+    case ETF_RGB565: return launch<ETF_RGB565>(st, a);
+    case ETF_BGR565: return launch<ETF_BGR565>(st, a);
+    case ETF_RGBA4444: return launch<ETF_RGBA4444>(st, a);
+    default: return hipErrorInvalidValue;
+    }
+}
 
 uint32_t etc1s_transcode_unit_bytes(uint32_t target) {
     switch (target) {
@@ -245,16 +299,13 @@ bool etc1s_transcode_is_pixel_target(uint32_t target) { return target == ETF_RGB
 hipError_t launch_transcode_etc1s(hipStream_t st, const etc1s_transcode_args& a, uint32_t target) {
     hipError_t e = hipMemsetAsync(a.invalid, 0, sizeof(uint32_t), st);
     if (e != hipSuccess || !a.nbx || !a.nby) return e;
-    if (target == ETF_BC1_RGB && !a.bc1_endpoints) return hipErrorInvalidValue;
-    switch (target) {
-    case ETF_ETC1_RGB: return launch<ETF_ETC1_RGB>(st, a);
-    case ETF_BC1_RGB: return launch<ETF_BC1_RGB>(st, a);
-    case ETF_RGBA32: return launch<ETF_RGBA32>(st, a);
-    case ETF_RGB565: return launch<ETF_RGB565>(st, a);
-    case ETF_BGR565: return launch<ETF_BGR565>(st, a);
-    case ETF_RGBA4444: return launch<ETF_RGBA4444>(st, a);
-    default: return hipErrorInvalidValue;
-    }
+    return launch_for_target(st, a, target);
+}
+
+hipError_t launch_transcode_etc1s_slices(hipStream_t st, const etc1s_transcode_slices_args& a, uint32_t target) {
+    hipError_t e = hipMemsetAsync(a.invalid, 0, (size_t)a.n_slices * sizeof(uint32_t), st);
+    if (e != hipSuccess || !a.n_slices || !a.total_blocks) return e;
+    return launch_for_target(st, a, target);
 }
 
 hipError_t launch_etc1s_build_bc1_tables(hipStream_t st, uint32_t* d_tables) {

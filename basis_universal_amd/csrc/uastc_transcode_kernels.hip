@@ -2,10 +2,12 @@
 // blocks: one lane per 16-byte block, the target a template parameter so that each instance carries only its own path (uastc_transcode.h). A block
 // is loaded as one uint4 and its result stored as whole uint2 / uint4 words, consecutive lanes on consecutive blocks; RGBA32 writes the four 16-byte
 // rows of its tile into the caller's raster, cropped to the image. A block the core refuses (mode code that matches nothing, pattern index out of
-// range) gets zeros and is counted with a vector atomic; it never stops the others.
+// range) gets zeros and is counted with a vector atomic; it never stops the others. Two kernels share that per-block work: one image per launch, and every
+// image of a file in one launch through a slice table (transcode_slices.h), counted per slice.
 #include <hip/hip_runtime.h>
 #include "uastc_transcode.h"
 #include "uastc_transcode_kernels.h"
+#include "transcode_slices.h"
 
 namespace bu {
 using namespace bu_uastc;
@@ -17,11 +19,12 @@ struct transcode_args {
     uint32_t nbx, nby, width, height, pitch, rows, chan0, chan1;
 };
 
+// One block: unpack, the target's conversion, the store. `out` is where the image's output begins, `i` the block's place in the image's raster order. RGBA32
+// writes the four rows of the tile cropped to width x min(height, rows), a row as one 16-byte word where it is whole and its address aligned; every other target
+// one uint2 / uint4 at out[i]. false = the block did not unpack and zeros were written. Both kernels below are this function behind their own indexing.
 template <uint32_t TARGET, bool HQ>
-__global__ __launch_bounds__(256) void transcode_uastc_kernel(transcode_args a) {
-    const uint32_t n = a.nbx * a.nby, i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const uint4 in = a.blocks[i];
+__device__ __forceinline__ bool transcode_uastc_block(const uint4 in, void* out, uint32_t i, uint32_t nbx, uint32_t width, uint32_t height, uint32_t pitch, uint32_t rows,
+                                                      uint32_t chan0, uint32_t chan1) {
     uint8_t blk[16];
     const uint32_t words[4] = { in.x, in.y, in.z, in.w };
     BU_UNROLL
@@ -30,19 +33,19 @@ __global__ __launch_bounds__(256) void transcode_uastc_kernel(transcode_args a) 
     if (TARGET == TF_RGBA32) {
         rgba8 px[16];
         ok = transcode_rgba32(blk, px);
-        const uint32_t bx = i % a.nbx, by = i / a.nbx;
+        const uint32_t bx = i % nbx, by = i / nbx;
         BU_UNROLL
         for (uint32_t y = 0; y < 4; y++) {
             const uint32_t row = by * 4 + y;
-            if (row >= a.height || row >= a.rows) break;
-            uint32_t* dst = (uint32_t*)a.out + (size_t)row * a.pitch + bx * 4;
+            if (row >= height || row >= rows) break;
+            uint32_t* dst = (uint32_t*)out + (size_t)row * pitch + bx * 4;
             uint32_t v[4];
             BU_UNROLL
             for (uint32_t x = 0; x < 4; x++) v[x] = ok ? pack_px(px[y * 4 + x].c) : 0u;
-            if (bx * 4 + 4 <= a.width && ((a.pitch & 3u) == 0)) *(uint4*)dst = make_uint4(v[0], v[1], v[2], v[3]);   // rows of a tile are 16-byte aligned when the pitch is
+            if (bx * 4 + 4 <= width && (((uintptr_t)dst & 15u) == 0)) *(uint4*)dst = make_uint4(v[0], v[1], v[2], v[3]);
             else {
                 BU_UNROLL
-                for (uint32_t x = 0; x < 4; x++) if (bx * 4 + x < a.width) dst[x] = v[x];
+                for (uint32_t x = 0; x < 4; x++) if (bx * 4 + x < width) dst[x] = v[x];
             }
         }
     } else if (TARGET == TF_ASTC_4x4_RGBA || TARGET == TF_BC7_RGBA) {
@@ -53,15 +56,40 @@ __global__ __launch_bounds__(256) void transcode_uastc_kernel(transcode_args a) 
             BU_UNROLL
             for (int k = 0; k < 16; k++) w[k >> 2] |= (uint32_t)o[k] << (8 * (k & 3));
         }
-        ((uint4*)a.out)[i] = make_uint4(w[0], w[1], w[2], w[3]);
+        ((uint4*)out)[i] = make_uint4(w[0], w[1], w[2], w[3]);
     } else {
         uint64_t w[2] = { 0, 0 };
-        ok = transcode_bcn(blk, TARGET, HQ, a.chan0, a.chan1, w);
+        ok = transcode_bcn(blk, TARGET, HQ, chan0, chan1, w);
         if (!ok) w[0] = w[1] = 0;
-        if (TARGET == TF_BC1_RGB || TARGET == TF_BC4_R) ((uint2*)a.out)[i] = make_uint2((uint32_t)w[0], (uint32_t)(w[0] >> 32));
-        else ((uint4*)a.out)[i] = make_uint4((uint32_t)w[0], (uint32_t)(w[0] >> 32), (uint32_t)w[1], (uint32_t)(w[1] >> 32));
+        if (TARGET == TF_BC1_RGB || TARGET == TF_BC4_R) ((uint2*)out)[i] = make_uint2((uint32_t)w[0], (uint32_t)(w[0] >> 32));
+        else ((uint4*)out)[i] = make_uint4((uint32_t)w[0], (uint32_t)(w[0] >> 32), (uint32_t)w[1], (uint32_t)(w[1] >> 32));
     }
-    if (!ok) atomicAdd(a.invalid, 1u);
+    return ok;
+}
+
+template <uint32_t TARGET, bool HQ>
+__global__ __launch_bounds__(256) void transcode_uastc_kernel(transcode_args a) {
+    const uint32_t n = a.nbx * a.nby, i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    if (!transcode_uastc_block<TARGET, HQ>(a.blocks[i], a.out, i, a.nbx, a.width, a.height, a.pitch, a.rows, a.chan0, a.chan1)) atomicAdd(a.invalid, 1u);
+}
+
+// every image of a file in one launch (bu_hip_k_transcode_uastc_slices): the lookup of transcode_slices.h in front of the same block function
+struct transcode_slices_args {
+    const uint4* blocks;
+    uint8_t* out;
+    uint32_t* invalid;                      // n_slices counters
+    const bu_hip_transcode_slice* slices;   // as the entry normalised them
+    const uint32_t* prefix;
+    uint32_t n_slices, total_blocks, chan0, chan1;
+};
+
+template <uint32_t TARGET, bool HQ>
+__global__ __launch_bounds__(256) void transcode_uastc_slices_kernel(transcode_slices_args a) {
+    transcode_slice_view v;
+    if (!find_transcode_slice(a.slices, a.prefix, a.n_slices, a.total_blocks, blockIdx.x * 256u + threadIdx.x, v)) return;
+    if (!transcode_uastc_block<TARGET, HQ>(a.blocks[v.first_block + v.local], a.out + v.out_offset, v.local, v.nbx, v.width, v.height, v.pitch, v.rows, a.chan0, a.chan1))
+        atomicAdd(a.invalid + v.slice, 1u);
 }
 
 template <uint32_t TARGET, bool HQ>
@@ -69,6 +97,26 @@ static hipError_t launch(hipStream_t st, const transcode_args& a) {
     const uint32_t n = a.nbx * a.nby;
     hipLaunchKernelGGL((transcode_uastc_kernel<TARGET, HQ>), dim3((n + 255) / 256), dim3(256), 0, st, a);
     return hipGetLastError();
+}
+template <uint32_t TARGET, bool HQ>
+static hipError_t launch(hipStream_t st, const transcode_slices_args& a) {
+    hipLaunchKernelGGL((transcode_uastc_slices_kernel<TARGET, HQ>), dim3((a.total_blocks + 255) / 256), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+// the instance of either kernel for (target, high_quality)
+template <class Args>
+static hipError_t launch_for_target(hipStream_t st, const Args& a, uint32_t target, bool high_quality) {
+    switch (target) {
+    case TF_RGBA32: return launch<TF_RGBA32, false>(st, a);
+    case TF_ASTC_4x4_RGBA: return launch<TF_ASTC_4x4_RGBA, false>(st, a);
+    case TF_BC7_RGBA: return launch<TF_BC7_RGBA, false>(st, a);
+    case TF_BC1_RGB: return high_quality ? launch<TF_BC1_RGB, true>(st, a) : launch<TF_BC1_RGB, false>(st, a);
+    case TF_BC3_RGBA: return high_quality ? launch<TF_BC3_RGBA, true>(st, a) : launch<TF_BC3_RGBA, false>(st, a);
+    case TF_BC4_R: return launch<TF_BC4_R, false>(st, a);
+    case TF_BC5_RG: return launch<TF_BC5_RG, false>(st, a);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 size_t transcode_output_bytes(uint32_t nbx, uint32_t nby, uint32_t width, uint32_t height, uint32_t target) {
@@ -83,16 +131,15 @@ hipError_t launch_transcode_uastc(hipStream_t st, const void* d_blocks, uint32_t
     transcode_args a = { (const uint4*)d_blocks, d_out, d_invalid, nbx, nby, width, height, pitch, rows, chan0, chan1 };
     hipError_t e = hipMemsetAsync(d_invalid, 0, sizeof(uint32_t), st);
     if (e != hipSuccess || !nbx || !nby) return e;
-    switch (target) {
-    case TF_RGBA32: return launch<TF_RGBA32, false>(st, a);
-    case TF_ASTC_4x4_RGBA: return launch<TF_ASTC_4x4_RGBA, false>(st, a);
-    case TF_BC7_RGBA: return launch<TF_BC7_RGBA, false>(st, a);
-    case TF_BC1_RGB: return high_quality ? launch<TF_BC1_RGB, true>(st, a) : launch<TF_BC1_RGB, false>(st, a);
-    case TF_BC3_RGBA: return high_quality ? launch<TF_BC3_RGBA, true>(st, a) : launch<TF_BC3_RGBA, false>(st, a);
-    case TF_BC4_R: return launch<TF_BC4_R, false>(st, a);
-    case TF_BC5_RG: return launch<TF_BC5_RG, false>(st, a);
-    default: return hipErrorInvalidValue;
-    }
+    return launch_for_target(st, a, target, high_quality);
+}
+
+hipError_t launch_transcode_uastc_slices(hipStream_t st, const void* d_blocks, const bu_hip_transcode_slice* d_slices, const uint32_t* d_prefix, uint32_t n_slices,
+                                         uint32_t total_blocks, uint32_t target, bool high_quality, uint32_t chan0, uint32_t chan1, void* d_out, uint32_t* d_invalid) {
+    transcode_slices_args a = { (const uint4*)d_blocks, (uint8_t*)d_out, d_invalid, d_slices, d_prefix, n_slices, total_blocks, chan0, chan1 };
+    hipError_t e = hipMemsetAsync(d_invalid, 0, (size_t)n_slices * sizeof(uint32_t), st);
+    if (e != hipSuccess || !n_slices || !total_blocks) return e;
+    return launch_for_target(st, a, target, high_quality);
 }
 
 } // namespace bu

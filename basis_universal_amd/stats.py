@@ -241,25 +241,36 @@ def _stats_from_slices(ctx, raw, slice_sources, hvs=False, bc7=False, ssim=False
     if _is_etc1s(raw):
         if bc7:
             raise ValueError(BC7_REFUSAL)
-        decoded = transcode.decode_etc1s_file(raw)
-        for k in _slice_order(decoded["images"]):
-            im = decoded["images"][k]
-            w, h = im["width"], im["height"]
-            # the alpha slice is decoded as a colour image from the alpha indices, as the reference unpacks every slice on its own
-            parts = [dict(im, alpha_endpoint_indices=None, alpha_selector_indices=None)]
-            if im["has_alpha"]:
-                parts.append(dict(im, endpoint_indices=im["alpha_endpoint_indices"], selector_indices=im["alpha_selector_indices"], alpha_endpoint_indices=None,
-                                  alpha_selector_indices=None))
-            sources = slice_sources(im["level"], im["layer"], im["face"], len(parts))
-            d_out = ctx.alloc(w * h * 4)
-            try:
-                for part, src in zip(parts, sources):
-                    transcode.transcode_etc1s_image(ctx, decoded, part, transcode.RGBA32, out_device=d_out)
-                    out.append(_slice_stats(ctx, src, (d_out, w, h, w), hvs, ssim))
-            finally:
-                ctx.free(d_out)
+        # every slice of the file decoded by ONE whole-file call into one allocation. The alpha slice is decoded as a colour image from the alpha indices, as the
+        # reference unpacks every slice on its own: a record of its own whose first_block is the alpha range, without an alpha slice
+        decoded = transcode._decode_etc1s(raw, False, whole=True)
+        order = _slice_order(decoded["images"])
+        slices = [(decoded["images"][k], first) for k in order for first in (["_first", "_alpha_first"] if decoded["images"][k]["has_alpha"] else ["_first"])]
+        layout, total = transcode.image_layout([im for im, _ in slices], transcode.RGBA32, etc1s=True)
+        d_out = ctx.alloc(max(total, 1))
+        try:
+            transcode._transcode_etc1s_slices(ctx, decoded, [im for im, _ in slices], [im[first] for im, first in slices], None, transcode.RGBA32, d_out)
+            at = iter(layout)
+            for k in order:
+                im = decoded["images"][k]
+                for src in slice_sources(im["level"], im["layer"], im["face"], 2 if im["has_alpha"] else 1):
+                    out.append(_slice_stats(ctx, src, (d_out + next(at)["offset"], im["width"], im["height"], im["width"]), hvs, ssim))
+        finally:
+            ctx.free(d_out)
         return out
     info = transcode.read_uastc_file(raw)
+    if not bc7:   # the same for UASTC; the bc7 path below stays slice by slice (unpack_blocks has no table form)
+        layout, total = transcode.image_layout(info["images"], transcode.RGBA32, etc1s=False)
+        d_out = ctx.alloc(max(total, 1))
+        try:
+            transcode.transcode_file_images(ctx, raw, transcode.RGBA32, out_device=d_out)
+            for k in _slice_order(info["images"]):
+                im = info["images"][k]
+                (src,) = slice_sources(im["level"], im["layer"], im["face"], 1)
+                out.append(_slice_stats(ctx, src, (d_out + layout[k]["offset"], im["width"], im["height"], im["width"]), hvs, ssim))
+        finally:
+            ctx.free(d_out)
+        return out
     for k in _slice_order(info["images"]):
         im = info["images"][k]
         w, h = im["width"], im["height"]
@@ -267,10 +278,6 @@ def _stats_from_slices(ctx, raw, slice_sources, hvs=False, bc7=False, ssim=False
         (src,) = slice_sources(im["level"], im["layer"], im["face"], 1)
         d_out = ctx.alloc(w * h * 4)
         try:
-            if not bc7:
-                transcode.transcode_uastc_blocks(ctx, blocks, im["num_blocks_x"], im["num_blocks_y"], transcode.RGBA32, width=w, height=h, out_device=d_out)
-                out.append(_slice_stats(ctx, src, (d_out, w, h, w), hvs, ssim))
-                continue
             # the blocks go up once; the BC7 texture and both rasters stay on the device
             d_blocks, d_bc7 = ctx.upload(blocks), ctx.alloc(blocks.shape[0] * 16)
             try:
@@ -292,8 +299,8 @@ def file_stats(ctx, data, images, hvs=False, bc7=False, ssim=False):
     """The reference's m_stats for a .basis / .ktx2 file of this package (UASTC LDR 4x4 or ETC1S): one image_metrics dict per slice, in the compressor's slice order
     (source image outermost, then its levels; an ETC1S image with alpha has a colour slice and then an alpha slice, each with its own stats).
     images: the source of every image the file holds -- {(level, layer, face): image} or, for a file of one layer and face, a list by level; an image is an
-    (h, w, 4) u8 array or a resident (device pointer, width, height, pitch) tuple. The file is decoded on the device to RGBA32 (transcode_uastc_blocks /
-    decode_etc1s_file + transcode_etc1s_image), cropped to each slice's original size, and compared there. A colour slice of an ETC1S file with alpha is compared
+    (h, w, 4) u8 array or a resident (device pointer, width, height, pitch) tuple. The file is decoded on the device to RGBA32 -- every slice by one whole-file
+    transcode call into one allocation (transcode_file_images / the ETC1S slice table; with bc7 slice by slice) --, cropped to each slice's original size, and compared there. A colour slice of an ETC1S file with alpha is compared
     against (r, g, b, 255), its alpha slice -- decoded as a colour image -- against (a, a, a, 255).
     hvs: every slice dict gains "hvs", psnr_hvs of the same source against the same resident decode (m_psnr_hvs_m_stats, which the tool sets with -stats). A source
     that is padded beyond the slice's size (the compressor's level rasters) must be padded with duplicated borders, as the compressor's are: a block's coordinates

@@ -8,6 +8,9 @@ without the HIP library and a GPU `transcode_uastc_blocks` raises.
 ETC1S files have their own three functions at the end of this module (`read_etc1s_file`, `decode_etc1s_file`, `transcode_etc1s_file`) and their own target list
 (ETC1S_BYTES_PER_BLOCK / ETC1S_BYTES_PER_PIXEL): the serial half -- containers, Huffman tables, palettes, the per-slice symbol walk -- is host code in
 libbasisu_frontend.so (csrc/host/etc1s_decode.cpp, needs no GPU), the texel half is one HIP kernel launch per image (csrc/etc1s_transcode_kernels.hip).
+
+`transcode_file_images` and `transcode_etc1s_file_images` (the last section) are the whole-file forms: every image of a file -- levels x layers x faces -- by ONE
+launch over a slice table, into one allocation whose layout `image_layout` gives.
 """
 import contextlib
 import ctypes as C
@@ -23,11 +26,14 @@ DECODE_FLAGS_HIGH_QUALITY = 32   # cDecodeFlagsHighQuality
 
 
 class InvalidBlocksError(ValueError):
-    """Some blocks did not unpack as UASTC -- or, from unpack_blocks, as BC7 -- (their output was zero-filled). `count` is how many."""
+    """Some blocks did not unpack as UASTC -- or, from unpack_blocks, as BC7 -- (their output was zero-filled). `count` is how many. From the whole-file calls
+    (transcode_file_images, transcode_etc1s_file_images) `per_slice` is the count of every slice in table order and `slice` the lowest slice that has any."""
 
-    def __init__(self, count, total, what="UASTC LDR 4x4"):
-        super().__init__(f"{count} of {total} blocks are not valid {what} blocks")
-        self.count = count
+    def __init__(self, count, total, what="UASTC LDR 4x4", per_slice=None):
+        self.count, self.per_slice = count, None if per_slice is None else [int(c) for c in per_slice]
+        self.slice = None if per_slice is None else next(s for s, c in enumerate(self.per_slice) if c)
+        where = "" if per_slice is None else f", the first in slice {self.slice} (per slice: {self.per_slice})"
+        super().__init__(f"{count} of {total} blocks are not valid {what} blocks{where}")
 
 
 @contextlib.contextmanager
@@ -45,23 +51,33 @@ def _output(ctx, out_device, out_row_pitch, out_rows, nbytes):
         ctx.free(d_out)
 
 
+def _check_uastc_target(target):
+    target = int(target)
+    if target not in BYTES_PER_BLOCK:
+        raise ValueError(f"transcode target {target} is not supported (supported: {sorted(BYTES_PER_BLOCK)})")
+    return target
+
+
+def _channel_pair(channels):
+    """channels=(c,) / (c0, c1) / None -> the C ABI's two values, -1 = the reference's default"""
+    ch = tuple(channels) if channels is not None else ()
+    if len(ch) > 2 or any(not 0 <= int(c) <= 3 for c in ch):
+        raise ValueError("channels: up to two values in 0..3")
+    return (int(ch[0]) if len(ch) > 0 else -1), (int(ch[1]) if len(ch) > 1 else -1)
+
+
 def transcode_uastc_blocks(ctx, blocks, nbx, nby, target, *, width=None, height=None, high_quality=False, channels=None, out_device=None,
                            out_row_pitch=0, out_rows=0):
     """blocks: (nby * nbx, 16) uint8 array in raster order (uploaded once) or a device pointer (int) to that many resident blocks.
     Returns (nby * nbx, bytes_per_block) uint8, for RGBA32 the (height, width, 4) raster, or None when out_device (a device pointer with room for
     bu_hip_transcode_output_bytes, or for out_rows x out_row_pitch pixels when those are given) receives the output. width / height default to the padded size;
     channels: BC4's (c,) or BC5's (c0, c1), default (0,) / (0, 3). Raises InvalidBlocksError when a block does not unpack."""
-    nbx, nby, target = int(nbx), int(nby), int(target)
-    if target not in BYTES_PER_BLOCK:
-        raise ValueError(f"transcode target {target} is not supported (supported: {sorted(BYTES_PER_BLOCK)})")
+    nbx, nby, target = int(nbx), int(nby), _check_uastc_target(target)
     n = nbx * nby
     width, height = int(width or nbx * 4), int(height or nby * 4)
     if not (0 < width <= nbx * 4 and 0 < height <= nby * 4) and n:
         raise ValueError(f"{width} x {height} pixels do not fit {nbx} x {nby} blocks")
-    ch = tuple(channels) if channels is not None else ()
-    if len(ch) > 2 or any(not 0 <= int(c) <= 3 for c in ch):
-        raise ValueError("channels: up to two values in 0..3")
-    c0, c1 = (int(ch[0]) if len(ch) > 0 else -1), (int(ch[1]) if len(ch) > 1 else -1)
+    c0, c1 = _channel_pair(channels)
     own = None
     try:
         if isinstance(blocks, np.ndarray):
@@ -248,7 +264,9 @@ class _Etc1sImage(C.Structure):      # = bu_etc1s_image
                                                                                                                                       ("alpha_first_block", C.c_uint64)]
 
 
-def _decode_etc1s(data, header_only):
+def _decode_etc1s(data, header_only, whole=False):
+    """whole (transcode_etc1s_file_images' private route): also the file's two whole index arrays, as "_endpoint_indices" / "_selector_indices", and per image where
+    its slices begin in them, "_first" / "_alpha_first" -- what read_etc1s_file and decode_etc1s_file return does not have them"""
     raw = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
     L = load_frontend_library()
     err = C.create_string_buffer(512)
@@ -279,8 +297,12 @@ def _decode_etc1s(data, header_only):
         info["endpoint_palette"] = take("endpoint_palette", fi.num_endpoints * 4, np.uint8).reshape(-1, 4)
         info["selector_palette"] = take("selector_palette", fi.num_selectors, np.uint32)
         ep, sel = take("endpoint_indices", fi.total_blocks, np.uint16), take("selector_indices", fi.total_blocks, np.uint16)
+        if whole:
+            info["_endpoint_indices"], info["_selector_indices"] = ep, sel
         for im in images:
-            n, a, b = im["num_blocks_x"] * im["num_blocks_y"], im.pop("_first"), im.pop("_alpha_first")
+            n, a, b = im["num_blocks_x"] * im["num_blocks_y"], im["_first"], im["_alpha_first"]
+            if not whole:
+                del im["_first"], im["_alpha_first"]
             shape = (im["num_blocks_y"], im["num_blocks_x"])
             im["endpoint_indices"], im["selector_indices"] = ep[a:a + n].reshape(shape), sel[a:a + n].reshape(shape)
             im["alpha_endpoint_indices"], im["alpha_selector_indices"] = (ep[b:b + n].reshape(shape), sel[b:b + n].reshape(shape)) if im["has_alpha"] else (None, None)
@@ -352,3 +374,137 @@ def transcode_etc1s_file(ctx, data, target, *, level=0, layer=0, face=0):
         if (im["level"], im["layer"], im["face"]) == (level, layer, face):
             return transcode_etc1s_image(ctx, decoded, im, target)
     raise ValueError(f"the file has no image at level {level}, layer {layer}, face {face}")
+
+
+# ---------------------------------------------------------------- every image of a file in one launch
+
+NO_ALPHA_SLICE = 2 ** 64 - 1   # BU_HIP_NO_ALPHA_SLICE
+
+
+class TranscodeSlice(C.Structure):   # = bu_hip_transcode_slice, include/basisu_hip.h
+    _fields_ = [("first_block", C.c_uint64), ("alpha_first_block", C.c_uint64), ("out_offset", C.c_uint64)] + \
+               [(n, C.c_uint32) for n in ("num_blocks_x", "num_blocks_y", "orig_width", "orig_height", "out_row_pitch_pixels", "out_rows_pixels")]
+
+
+def image_layout(images, target, *, etc1s):
+    """Where the whole-file calls put each image of a file: `images` is the "images" list of read_uastc_file (etc1s=False) or of read_etc1s_file / decode_etc1s_file
+    (etc1s=True). -> ([{"offset", "nbytes", "shape", "dtype"} per image, in the list's order], total_bytes): the images packed in order, each rounded up to 16
+    bytes. A block target is (blocks, bytes per block) u8; a pixel target the tight raster of the image's own size, (height, width, 4) u8 for RGBA32 and
+    (height, width) u16 for ETC1S' 16-bit formats. Host only."""
+    target = _check_etc1s_target(target) if etc1s else _check_uastc_target(target)
+    layout, at = [], 0
+    for im in images:
+        n, w, h = im["num_blocks_x"] * im["num_blocks_y"], im["width"], im["height"]
+        if etc1s and target in ETC1S_BYTES_PER_PIXEL:
+            shape, dtype = ((h, w, 4), np.uint8) if target == RGBA32 else ((h, w), np.uint16)
+            nbytes = w * h * ETC1S_BYTES_PER_PIXEL[target]
+        elif not etc1s and target == RGBA32:
+            shape, dtype, nbytes = (h, w, 4), np.uint8, w * h * 4
+        else:
+            unit = ETC1S_BYTES_PER_BLOCK[target] if etc1s else BYTES_PER_BLOCK[target]
+            shape, dtype, nbytes = (n, unit), np.uint8, n * unit
+        layout.append({"offset": at, "nbytes": nbytes, "shape": shape, "dtype": dtype})
+        at += (nbytes + 15) & ~15
+    return layout, at
+
+
+def _slice_table(images, layout, firsts, alpha_firsts=None):
+    """the records of one call: image k reads from firsts[k] (alpha_firsts[k], None = no alpha slice) and writes its tight output at layout[k]["offset"]"""
+    recs = (TranscodeSlice * len(images))()
+    for k, im in enumerate(images):
+        alpha = NO_ALPHA_SLICE if alpha_firsts is None or alpha_firsts[k] is None else int(alpha_firsts[k])
+        recs[k] = TranscodeSlice(int(firsts[k]), alpha, layout[k]["offset"], im["num_blocks_x"], im["num_blocks_y"], im["width"], im["height"], 0, 0)
+    return recs
+
+
+def _upload_async(ctx, arr):
+    """a buffer of our own holding `arr`, the copy ordered on the context's stream: nobody waits for it"""
+    p = ctx.alloc(max(arr.nbytes, 1))
+    try:
+        if arr.nbytes:
+            ctx.memcpy_h2d_async(p, np.ascontiguousarray(arr))
+    except Exception:
+        ctx.free(p)
+        raise
+    return p
+
+
+def _run_slices(ctx, call, images, layout, total, out_device, what):
+    """the half both whole-file calls share: the output (ours or the caller's), the one call, the per-slice counts, one download"""
+    with _output(ctx, out_device, 0, 0, lambda: total) as d_out:
+        invalid = (C.c_uint32 * len(images))()
+        call(C.c_void_p(d_out), total, invalid)
+        if any(invalid):
+            raise InvalidBlocksError(sum(invalid), sum(im["num_blocks_x"] * im["num_blocks_y"] for im in images), what, per_slice=list(invalid))
+        if out_device is not None:
+            return layout, total
+        raw = ctx.download(d_out, (total,), np.uint8)
+        return [raw[e["offset"]:e["offset"] + e["nbytes"]].view(e["dtype"]).reshape(e["shape"]) for e in layout]
+
+
+def _uastc_block_span(raw, images):
+    """The blocks of a UASTC file's images as ONE host array for one upload -> (u8 array, [each image's first block in it]). Both containers write the images back to
+    back, so this is normally the file's own bytes from the first image's to the last one's, not a copy (the table takes inputs in any order; only the device
+    buffer needs the 16-byte alignment that a .basis payload does not have in the file). Where an image does not lie a multiple of 16 bytes from the first, or the
+    span holds more than twice the images' bytes, the blocks are gathered in image order instead."""
+    lo, hi = min(im["offset"] for im in images), max(im["offset"] + im["length"] for im in images)
+    if all((im["offset"] - lo) % 16 == 0 for im in images) and hi - lo <= 2 * sum(im["length"] for im in images):
+        return np.frombuffer(raw, np.uint8, hi - lo, lo), [(im["offset"] - lo) // 16 for im in images]
+    firsts = np.concatenate([[0], np.cumsum([im["length"] // 16 for im in images])])
+    return np.concatenate([np.frombuffer(raw, np.uint8, im["length"], im["offset"]) for im in images]), [int(f) for f in firsts[:-1]]
+
+
+def transcode_file_images(ctx, data, target, *, high_quality=False, channels=None, out_device=None):
+    """EVERY image of a UASTC .basis / .ktx2 file (read_uastc_file) transcoded by one launch (bu_hip_k_transcode_uastc_slices): the images' blocks go up
+    as one array in one upload (_uastc_block_span: the file's own span of them, or a gather), and one call writes them all. Returns a list of arrays,
+    one per image in the order of read_uastc_file's "images", each what transcode_file returns for it (views of one download). With out_device (a device pointer
+    with room for image_layout's total_bytes) the output stays there and image_layout(images, target, etc1s=False) is returned. Raises InvalidBlocksError, with
+    the per-slice counts and the lowest slice that has any, when a block does not unpack."""
+    raw = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
+    images = read_uastc_file(raw)["images"]
+    layout, total = image_layout(images, target, etc1s=False)
+    target, (c0, c1) = int(target), _channel_pair(channels)
+    blocks, firsts = _uastc_block_span(raw, images)
+    recs = _slice_table(images, layout, firsts)
+    d_blocks = _upload_async(ctx, blocks)
+    try:
+        def call(d_out, out_bytes, invalid):
+            ctx.check(ctx.lib.k_transcode_uastc_slices(ctx.h, C.c_void_p(d_blocks), blocks.size // 16, recs, len(images), target, DECODE_FLAGS_HIGH_QUALITY if high_quality else 0,
+                                                       c0, c1, d_out, out_bytes, invalid), "transcode_uastc_slices")
+        return _run_slices(ctx, call, images, layout, total, out_device, "UASTC LDR 4x4")
+    finally:
+        ctx.free(d_blocks)
+
+
+def transcode_etc1s_file_images(ctx, data, target, *, out_device=None):
+    """EVERY image of an ETC1S .basis / .ktx2 file transcoded by one launch (bu_hip_k_transcode_etc1s_slices): one host decode, both palettes and the file's two
+    whole index arrays uploaded once, one call; an image's alpha slice is a second range of the same arrays. Returns a list of arrays, one per image in the order
+    of read_etc1s_file's "images", each what transcode_etc1s_file returns for it (views of one download). With out_device (room for image_layout's total_bytes)
+    the output stays there and image_layout(images, target, etc1s=True) is returned. Raises InvalidBlocksError, with the per-slice counts and the lowest slice
+    that has any, when a block has an index past its palette."""
+    target = _check_etc1s_target(target)
+    decoded = _decode_etc1s(data, False, whole=True)
+    images = decoded["images"]
+    return _transcode_etc1s_slices(ctx, decoded, images, [im["_first"] for im in images], [im["_alpha_first"] if im["has_alpha"] else None for im in images], target, out_device)
+
+
+def _transcode_etc1s_slices(ctx, decoded, images, firsts, alpha_firsts, target, out_device):
+    """transcode_etc1s_file_images behind the decode (_decode_etc1s with whole=True): `images` (sizes) with where each one's indices begin in the file's whole
+    arrays. stats.py decodes an alpha slice as a colour image of its own this way."""
+    layout, total = image_layout(images, target, etc1s=True)
+    recs = _slice_table(images, layout, firsts, alpha_firsts)
+    ep_pal = np.ascontiguousarray(decoded["endpoint_palette"], np.uint8).reshape(-1, 4)
+    sel_pal = np.ascontiguousarray(decoded["selector_palette"], np.uint32).reshape(-1)
+    ep_idx, sel_idx = decoded["_endpoint_indices"], decoded["_selector_indices"]
+    held = []
+    try:
+        for a in (ep_pal, sel_pal, ep_idx, sel_idx):
+            held.append(_upload_async(ctx, a))
+
+        def call(d_out, out_bytes, invalid):
+            ctx.check(ctx.lib.k_transcode_etc1s_slices(ctx.h, C.c_void_p(held[0]), ep_pal.shape[0], C.c_void_p(held[1]), sel_pal.size, C.c_void_p(held[2]), C.c_void_p(held[3]),
+                                                       ep_idx.size, recs, len(images), target, d_out, out_bytes, invalid), "transcode_etc1s_slices")
+        return _run_slices(ctx, call, images, layout, total, out_device, "ETC1S")
+    finally:
+        for p in held:
+            ctx.free(p)

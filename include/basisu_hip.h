@@ -411,7 +411,42 @@ BU_HIP_API int bu_hip_etc1s_bc1_endpoint_tables(bu_hip_context*, uint32_t* h_out
 BU_HIP_API size_t bu_hip_etc1s_transcode_output_bytes(uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height, uint32_t target,
         uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
 
-/* gpu_image::unpack (encoder/basisu_gpu_texture.cpp:1218-1266) over resident blocks: what a GPU samples from a BC1 / BC3 / BC4 / BC5 / BC7 texture, as RGBA8.
+/* Both transcoders over EVERY image of a file in one launch: what reading back a texture array, a cubemap or a mip chain (levels x layers x faces, for ETC1S with
+ * alpha a second slice per image) would otherwise pay a launch, a stream wait and, for ETC1S, the uploads per image for. One record per image serves both codecs.
+ * `slices` is a HOST array of n_slices records. Slice s reads num_blocks_x * num_blocks_y inputs in raster order from first_block on -- UASTC: 16-byte blocks counted
+ * from d_uastc_blocks (n_blocks of them, 16-byte aligned); ETC1S: entries of d_endpoint_idx / d_selector_idx (n_indices uint16 each: the file's whole index
+ * arrays, bu_etc1s_file_endpoint_indices / _selector_indices), its alpha slice the same two arrays from alpha_first_block on -- and writes at d_out + out_offset
+ * byte for byte what bu_hip_k_transcode_uastc / bu_hip_k_transcode_etc1s_counted write for the same inputs, size, pitch, rows, target, flags and channels. A pixel
+ * target (RGBA32; ETC1S also the 16-bit formats) writes only orig_width x min(orig_height, rows) pixels: padding, and the gaps between slices, are not touched.
+ * bu_hip_transcode_slice_extent is the room a record takes from its out_offset: blocks x bytes per block, or pitch x rows x bytes per pixel.
+ * The records and the table of their block counts go up in one stream-ordered copy; `slices` may be released on return. ONE transcode launch on the context's
+ * stream (plus, once per context, the build of the ETC1S -> BC1 tables). A UASTC block that does not unpack, or an ETC1S block with an index past its palette, is
+ * zero-filled and counted for its slice. With out_invalid_per_slice non-NULL the n_slices counts are read back behind one stream wait, however many slices there
+ * are; with NULL nothing is read back and the call does not synchronise.
+ * Fails -- nothing copied, nothing launched, nothing written, the reason by name in bu_hip_last_error -- on a null pointer or n_slices == 0; a target the codec's
+ * one-image entry refuses (same text); a record with zero blocks or more than 16384 blocks either way; pixels that do not fit the blocks; a pitch below the width;
+ * pitch or rows set for a block target; alpha_first_block set for UASTC; an input range (or alpha range) that ends past n_blocks / n_indices; d_out,
+ * d_uastc_blocks or an out_offset that is not 16-byte aligned (the RGBA32 rows are stored as 16-byte words where their address allows); an extent that ends past
+ * out_bytes; an out_offset before the end of the record before it (outputs ascend in table order and may not overlap, gaps are allowed; inputs may be in any
+ * order and may repeat, they are only read); more than 2^30 blocks in all; ETC1S palettes outside 1..65535; a UASTC channel above 3. */
+#define BU_HIP_NO_ALPHA_SLICE UINT64_MAX
+typedef struct bu_hip_transcode_slice {
+    uint64_t first_block;        /* UASTC: the image's first block, counted in 16-byte blocks from d_uastc_blocks. ETC1S: the image's first entry in d_ep_idx / d_sel_idx */
+    uint64_t alpha_first_block;  /* ETC1S: first entry of the image's alpha slice, or BU_HIP_NO_ALPHA_SLICE; read only by RGBA32 / RGBA4444. UASTC: must be BU_HIP_NO_ALPHA_SLICE */
+    uint64_t out_offset;         /* bytes from d_out where this image's output begins; a multiple of 16 */
+    uint32_t num_blocks_x, num_blocks_y;              /* both >= 1 */
+    uint32_t orig_width, orig_height;                 /* 0 = 4 * num_blocks */
+    uint32_t out_row_pitch_pixels, out_rows_pixels;   /* pixel targets: 0 = orig size; block targets: must be 0 */
+} bu_hip_transcode_slice;
+BU_HIP_API int bu_hip_k_transcode_uastc_slices(bu_hip_context*, const void* d_uastc_blocks, uint64_t n_blocks, const bu_hip_transcode_slice* slices, uint32_t n_slices,
+        uint32_t target, uint32_t decode_flags, int32_t channel0, int32_t channel1, void* d_out, size_t out_bytes, uint32_t* out_invalid_per_slice);
+BU_HIP_API int bu_hip_k_transcode_etc1s_slices(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette, uint32_t n_selectors,
+        const void* d_endpoint_idx, const void* d_selector_idx, uint64_t n_indices, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target,
+        void* d_out, size_t out_bytes, uint32_t* out_invalid_per_slice);
+/* bytes one record occupies from its out_offset for `target` (0 = target not supported by that codec) */
+BU_HIP_API size_t bu_hip_transcode_slice_extent(const bu_hip_transcode_slice*, uint32_t target, int etc1s);
+
+/* gpu_image::unpack(encoder/basisu_gpu_texture.cpp:1218-1266) over resident blocks: what a GPU samples from a BC1 / BC3 / BC4 / BC5 / BC7 texture, as RGBA8.
  * format: the transcoder_texture_format value the transcoders above take as a target -- cTFBC1_RGB (2), cTFBC3_RGBA (3), cTFBC4_R (4), cTFBC5_RG (5), cTFBC7_RGBA (6);
  * any other fails with an error that names it. d_blocks: num_blocks_x * num_blocks_y blocks of 8 (BC1, BC4) or 16 bytes in raster order, aligned to their size;
  * d_out: 4-byte aligned, room for bu_hip_unpack_output_bytes. orig_width / orig_height: 0 = the padded size; row_pitch / rows: in pixels, 0 = orig size.
