@@ -460,6 +460,30 @@ BU_HIP_API int bu_hip_k_unpack_blocks(bu_hip_context*, const void* d_blocks, uin
 BU_HIP_API size_t bu_hip_unpack_output_bytes(uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height,
         uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
 
+/* The payload of a DX10 .dds file from the resident tile array (64 B per tile: RGBA8, rows of four texels, borders duplicated -- what bu_hip_k_extract_slices
+ * writes): pack_slice of the reference tool's `-dds` mode (encoder/basisu_dds_export.cpp:151-267). format: the tool's dds_output_format value, in the order of its
+ * -dds_format tokens. BC1 is basist::encode_bc1 with cEncodeBC1HighQuality, BC4 basist::encode_bc4; BC2 = explicit 4-bit alpha + BC1, BC3 = BC4 of alpha + BC1,
+ * BC5 = BC4 of red + BC4 of green. The raw formats truncate the channels to their bits (r >> 3, a >= 128, a >> 4), they never round.
+ *   bu_hip_k_pack_dds_blocks (BC1-BC5): tile i -> 8 (BC1, BC4) or 16 bytes at d_out + i * that, i < n_tiles. The tile array is in slice order (image outermost,
+ *     then level), which is DDS subresource order (layer, face, level): the whole file's payload is this one launch, and there is no slice table.
+ *   bu_hip_k_pack_dds_pixels (the seven raw formats): `slices` is a HOST array of n_slices records as the whole-file transcoders take them. Slice s reads its
+ *     num_blocks_x * num_blocks_y tiles in raster order from tile first_block on and writes exactly orig_width x orig_height pixels in tight rows at d_out +
+ *     out_offset: the padding of the last tiles is cropped and nothing between or behind the slices is written. One launch for all slices.
+ *   bu_hip_dds_payload_bytes: what the slices' subresources take, back to back (blocks x bytes per block, or pixels x bytes per pixel); 0 for a format that is
+ *     refused or a null / empty table.
+ * Both kernels are stream-ordered and neither call synchronises. Both fail -- nothing copied, nothing launched, nothing written, the reason by name in
+ * bu_hip_last_error -- on BU_HIP_DDS_BC7 (neither of the reference's two BC7 packers, bc7f and bc7e_scalar, is implemented here); on a format value that is no
+ * format; on a raw format given to _blocks or a block format given to _pixels; on a null pointer; on d_tiles or d_out that is not 16-byte aligned; on more than
+ * 2^30 tiles. _pixels also fails on n_slices == 0; a record with zero blocks or more than 16384 either way; pixels that do not fit the blocks; a pitch or row count
+ * (rows are tight) or an alpha_first_block that is set; tiles that end past n_tiles; an out_offset that is no multiple of the pixel size, lies before the end of the
+ * record before it, or whose subresource ends past out_bytes. */
+enum { BU_HIP_DDS_BC1 = 0, BU_HIP_DDS_BC2 = 1, BU_HIP_DDS_BC3 = 2, BU_HIP_DDS_BC4 = 3, BU_HIP_DDS_BC5 = 4, BU_HIP_DDS_BC7 = 5, BU_HIP_DDS_A8R8G8B8 = 6,
+       BU_HIP_DDS_A8B8G8R8 = 7, BU_HIP_DDS_R8 = 8, BU_HIP_DDS_R8G8 = 9, BU_HIP_DDS_R5G6B5 = 10, BU_HIP_DDS_A1R5G5B5 = 11, BU_HIP_DDS_A4R4G4B4 = 12 };
+BU_HIP_API int bu_hip_k_pack_dds_blocks(bu_hip_context*, const void* d_tiles, uint64_t n_tiles, uint32_t format, void* d_out);
+BU_HIP_API int bu_hip_k_pack_dds_pixels(bu_hip_context*, const void* d_tiles, uint64_t n_tiles, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t format,
+        void* d_out, size_t out_bytes);
+BU_HIP_API size_t bu_hip_dds_payload_bytes(const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t format);
+
 /* The counting half of image_metrics::calc (encoder/basisu_enc.cpp:2155-2226) for all eight lines basis_compressor's m_compute_stats stage reports per slice
  * (comp.cpp:4195-4253), in one pass over two resident RGBA8 rasters (4 bytes per pixel, 4-byte aligned; a row pitch in pixels, 0 = the width; each raster reaches
  * to pixel (height - 1) * pitch + width). The region compared is min(width_a, width_b) x min(height_a, height_b), as calc crops; at most 16384 each way.
