@@ -340,6 +340,68 @@ def test_find_optimal_selector_clusters_for_each_block(seam, perceptual):
     assert tie[1] not in got[info["first_selector"] == 0], "of two identical selector blocks in one window the lower position wins"
 
 
+FOSC_LONG_WINDOWS = (383, 384, 385, 700)   # either side of the kernel's quad-table threshold (384 candidates), and well past it
+
+
+@functools.lru_cache(maxsize=None)
+def _fosc_long_case(perceptual):
+    """Windows of 383 / 384 / 385 / 700 selectors: the seam entry hands the kernel no candidate words, so this is the way to its quad tables (and, in the first window, its
+    pair tables) reading the selector blocks through the list. The flat list holds a seeded codebook of 1,100 words (candidate_list_cases.selector_codebook_words over this
+    file's tiles) dealt to the windows by permutations, so selector_cluster_indices is no identity; in every window, where blocks find their minimum, the same word again
+    1, 64 and 320 positions on (neighbouring lanes; the same lane one and five iterations later) and in the last position a copy of the first: the lower position wins.
+    The oracle runs in POSITION space (one selector block per flat position, windows as candidate lists of positions); the answer is selector_cluster_indices of it."""
+    import candidate_list_cases as CL
+    t = _tiles()
+    n = t.shape[0]
+    c5i, enc = _ds_case(perceptual)
+    rng = np.random.default_rng(29)
+    words = np.concatenate(CL.selector_codebook_words(t, enc, perceptual, rng))
+    members = [rng.permutation(words.size)[:m] for m in FOSC_LONG_WINDOWS]
+    flat = np.concatenate(members).astype(np.int64)
+    first = np.concatenate([[0], np.cumsum(FOSC_LONG_WINDOWS)])
+    packed_bits = words[flat].copy()                                    # selector word of every flat position (etc_block bit planes)
+    block_win = rng.choice(len(members), n, p=[1 / 6, 1 / 6, 1 / 6, 1 / 2])        # half of the blocks under the long window
+    err = CL.fosc_errors(t, enc, packed_bits, perceptual)
+    later = []                                                          # flat positions that hold a copy of an earlier position of their window
+    for w, m in enumerate(FOSC_LONG_WINDOWS):
+        f = int(first[w])
+        blocks = np.nonzero(block_win == w)[0]
+        votes = np.bincount(err[np.ix_(blocks, np.arange(f, f + m))].argmin(axis=1), minlength=m)
+        used, spacing = {0, m - 1}, 0
+        packed_bits[f + m - 1] = packed_bits[f]; later.append(f + m - 1)
+        for k in np.argsort(-votes, kind="stable")[:40]:
+            k, d = int(k), (1, 64, 320)[spacing % 3]
+            if votes[k] and k not in used and k + d < m and k + d not in used:
+                used.update((k, k + d)); spacing += 1
+                packed_bits[f + k + d] = packed_bits[f + k]; later.append(f + k + d)
+    sel_pos = CL._words_to_blocks(packed_bits)                          # (positions, 8) etc_blocks for the oracle
+    packed = (CL.word_selectors(packed_bits).astype(np.uint32) << (2 * np.arange(16, dtype=np.uint32))).sum(axis=1).astype(np.uint32)   # fosc_selector_struct
+    selectors = np.zeros(flat.size, BU_FOSC_SELECTOR)
+    selectors["packed_selectors"] = packed
+    info = np.zeros(n, BU_FOSC_BLOCK)
+    for i, ch in enumerate("rgba"):
+        info["etc_color5_inten"][ch] = c5i[:, i]
+    info["first_selector"] = first[block_win]
+    info["num_selectors"] = np.asarray(FOSC_LONG_WINDOWS)[block_win]
+    cluster_indices = np.ascontiguousarray(flat.astype(np.uint32))
+    coffs, cidx = csr_from_lists([np.arange(first[w], first[w + 1], dtype=np.uint32) for w in range(len(members))])
+    exp_pos = np.zeros(n, np.uint32)
+    enc_copy = enc.copy()
+    oracle().orc_find_optimal_selector_clusters(ptr(t), ptr(enc_copy), n, ptr(sel_pos), flat.size, len(members), ptr(coffs, u32p), ptr(cidx, u32p),
+                                                ptr(block_win.astype(np.uint8)), perceptual, 1, ptr(exp_pos, u32p))
+    assert not np.isin(exp_pos, later).any()                            # of equal words the lower position wins
+    return info, selectors, cluster_indices, cluster_indices[exp_pos], exp_pos - first[block_win], len(later)
+
+
+@pytest.mark.parametrize("perceptual", [1, 0])
+def test_find_optimal_selector_clusters_long_windows(seam, perceptual):
+    info, selectors, cluster_indices, exp, exp_at, n_copies = _fosc_long_case(perceptual)
+    got = seam.fosc(info, selectors, cluster_indices, perceptual)
+    bad = np.nonzero(got != exp)[0]
+    assert bad.size == 0, f"{bad.size} of {exp.size} differ, first {bad[:8]} (windows of {info['num_selectors'][bad[:8]]}): got {got[bad[:8]]} expected {exp[bad[:8]]}"
+    assert n_copies >= 4 * 10 and (exp_at >= 384).sum() >= 50 and np.unique(exp).size > 200, "degenerate test: hardly a winner past position 384, or hardly any cluster chosen"
+
+
 # ----------------------------------------------------------------------------- encode_etc1s_pixel_clusters
 
 def _cluster_texels(t, tv):
