@@ -7,8 +7,7 @@ static const char* const kUnpackFormats = "BC1_RGB (2), BC3_RGBA (3), BC4_R (4),
 extern "C" {
 
 size_t bu_hip_unpack_output_bytes(uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t pitch_px, uint32_t rows_px) {
-    const size_t width = orig_w ? orig_w : (size_t)nbx * 4, height = orig_h ? orig_h : (size_t)nby * 4;
-    return (pitch_px ? pitch_px : width) * (rows_px ? rows_px : height) * 4;
+    return bu::raster_output_bytes(bu::tile_geometry{ nbx, nby, orig_w, orig_h, pitch_px, rows_px }, 4, true);
 }
 
 int bu_hip_k_unpack_blocks(bu_hip_context* ctx, const void* d_blocks, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t format, void* d_out,
@@ -25,22 +24,18 @@ int bu_hip_k_unpack_blocks(bu_hip_context* ctx, const void* d_blocks, uint32_t n
         set_error(ctx, "unpack_blocks: %s blocks must be %u-byte aligned and the raster 4-byte aligned", transcoder_format_name(format), unit);
         return 0;
     }
-    if (nbx > 16384u || nby > 16384u) { set_error(ctx, "unpack_blocks: %u x %u blocks is too many (16384 each way at the most)", nbx, nby); return 0; }
-    const uint32_t width = orig_w ? orig_w : nbx * 4, height = orig_h ? orig_h : nby * 4;
-    if (width > nbx * 4 || height > nby * 4) { set_error(ctx, "unpack_blocks: %u x %u pixels do not fit %u x %u blocks", width, height, nbx, nby); return 0; }
-    const uint32_t pitch = pitch_px ? pitch_px : width, rows = rows_px ? rows_px : height;
-    if (pitch < width) { set_error(ctx, "unpack_blocks: row pitch %u is less than the width %u", pitch, width); return 0; }
+    bu::tile_geometry geo;
+    if (!checked(ctx, [&](bu::err_text e) { return bu::resolve_geometry("unpack_blocks", nbx, nby, orig_w, orig_h, pitch_px, rows_px, bu::kEachWay16384, &geo, e); })) return 0;
     device_guard g(ctx->device);
     arena& counter = ctx->scratch[4];
     BU_TRY(ctx, counter.reserve(sizeof(uint32_t)));
-    const bu::block_unpack_args a = { d_blocks, static_cast<uint32_t*>(d_out), static_cast<uint32_t*>(counter.p), nbx, nby, width, height, pitch, rows };
+    const bu::block_unpack_args a = { d_blocks, static_cast<uint32_t*>(d_out), static_cast<uint32_t*>(counter.p), geo };
     {
         prof_scope ps(ctx, "unpack_blocks");
         BU_TRY(ctx, bu::launch_unpack_blocks(ctx->stream, a, format));
     }
     uint32_t invalid = 0;
-    BU_TRY(ctx, d2h_pageable(ctx, &invalid, counter.p, sizeof(uint32_t)));
-    BU_TRY(ctx, stream_wait(ctx, ctx->stream));
+    if (!read_back(ctx, &invalid, counter.p, sizeof(invalid))) return 0;
     if (out_invalid_blocks) *out_invalid_blocks = invalid;
     return 1;
 }

@@ -328,38 +328,14 @@ int bu_hip_k_extract_blocks(bu_hip_context* ctx, const void* d_rgba, uint32_t wi
 int bu_hip_k_extract_slices(bu_hip_context* ctx, const bu_hip_slice_source* slices, uint32_t n, void* d_out) {
     if (!ctx) return 0;
     static const char* const fn = "extract_slices";
-    static_assert(sizeof(bu_hip_slice_source) == 32, "the kernel reads a record as two 16-byte words");
-    if (!n) { set_error(ctx, "%s: no slices (n == 0)", fn); return 0; }
-    if (!slices || !d_out) { set_error(ctx, "%s: null pointer", fn); return 0; }
-    if ((uintptr_t)d_out & 15u) { set_error(ctx, "%s: the output is not 16-byte aligned", fn); return 0; }
     // the records as they are, then the table of where each slice's tiles begin among the tiles of the call
-    const size_t table_at = (size_t)n * sizeof(bu_hip_slice_source), bytes = table_at + ((size_t)n + 1) * sizeof(uint32_t);
-    std::vector<uint8_t> pack(bytes);
-    uint32_t* prefix = reinterpret_cast<uint32_t*>(pack.data() + table_at);
-    uint64_t total = 0, end = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        const bu_hip_slice_source& s = slices[i];
-        if (!s.d_raster) { set_error(ctx, "%s: slice %u: null raster", fn, i); return 0; }
-        if (!s.width || !s.height) { set_error(ctx, "%s: slice %u: zero size (%u x %u)", fn, i, s.width, s.height); return 0; }
-        if (s.width > 0x7fffffffu || s.height > 0x7fffffffu) { set_error(ctx, "%s: slice %u: %u x %u pixels is too large", fn, i, s.width, s.height); return 0; }
-        if ((uint64_t)s.pitch_bytes < (uint64_t)s.width * 4u) { set_error(ctx, "%s: slice %u: row pitch %u bytes is less than 4 * width = %llu", fn, i, s.pitch_bytes, (unsigned long long)s.width * 4u); return 0; }
-        if (s.mode > BU_HIP_SLICE_ALPHA) { set_error(ctx, "%s: slice %u: unknown mode %u", fn, i, s.mode); return 0; }
-        if (s.first_block < end) { set_error(ctx, "%s: slice %u: first_block %llu lies before the end of slice %u's blocks (%llu): ranges must ascend without overlap", fn, i, (unsigned long long)s.first_block, i ? i - 1 : 0, (unsigned long long)end); return 0; }
-        const uint64_t tiles = (((uint64_t)s.width + 3u) / 4u) * (((uint64_t)s.height + 3u) / 4u);
-        prefix[i] = (uint32_t)total;
-        total += tiles;
-        if (tiles > ((uint64_t)1 << 30) || total > ((uint64_t)1 << 30)) { set_error(ctx, "%s: more than 2^30 tiles in one call (at slice %u)", fn, i); return 0; }
-        end = s.first_block + tiles;
-    }
-    prefix[n] = (uint32_t)total;
-    std::memcpy(pack.data(), slices, table_at);
+    bu::slice_table table;
+    if (!checked(ctx, [&](bu::err_text e) { return bu::build_source_slices(table, fn, slices, n, d_out, e); })) return 0;
     device_guard g(ctx->device);
-    arena& table = ctx->scratch[4];
-    BU_TRY(ctx, table.reserve(bytes));
-    BU_TRY(ctx, h2d(ctx, table.p, pack.data(), bytes));
+    uploaded_slices d;
+    if (!upload_slice_table(ctx, table, d)) return 0;
     prof_scope ps(ctx, fn);
-    BU_TRY(ctx, bu::launch_extract_slices(ctx->stream, static_cast<const bu_hip_slice_source*>(table.p), reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(table.p) + table_at),
-                                          n, (uint32_t)total, d_out));
+    BU_TRY(ctx, bu::launch_extract_slices(ctx->stream, static_cast<const bu_hip_slice_source*>(d.records), d.prefix, n, table.total, d_out));
     return 1;
 }
 

@@ -15,14 +15,11 @@ static int etc1s_transcode_args_from(bu_hip_context* ctx, const void* d_ep_pal, 
     if (!d_ep_pal || !d_sel_pal || !d_ep_idx || !d_sel_idx || !d_out) { set_error(ctx, "transcode_etc1s: null device pointer"); return 0; }
     if ((d_a_ep_idx == nullptr) != (d_a_sel_idx == nullptr)) { set_error(ctx, "transcode_etc1s: an alpha slice needs both of its index arrays"); return 0; }
     if (!n_ep || !n_sel || n_ep > 65535u || n_sel > 65535u) { set_error(ctx, "transcode_etc1s: palettes of %u endpoints and %u selectors (1..65535 each)", n_ep, n_sel); return 0; }
-    if (nbx > 16384u || nby > 16384u) { set_error(ctx, "transcode_etc1s: %u x %u blocks is too many (16384 each way at the most)", nbx, nby); return 0; }
-    const uint32_t width = orig_w ? orig_w : nbx * 4, height = orig_h ? orig_h : nby * 4;
-    if (width > nbx * 4 || height > nby * 4) { set_error(ctx, "transcode_etc1s: %u x %u pixels do not fit %u x %u blocks", width, height, nbx, nby); return 0; }
-    const uint32_t pitch = pitch_px ? pitch_px : width, rows = rows_px ? rows_px : height;
-    if (pitch < width) { set_error(ctx, "transcode_etc1s: row pitch %u is less than the width %u", pitch, width); return 0; }
+    bu::tile_geometry geo;
+    if (!checked(ctx, [&](bu::err_text e) { return bu::resolve_geometry("transcode_etc1s", nbx, nby, orig_w, orig_h, pitch_px, rows_px, bu::kEachWay16384, &geo, e); })) return 0;
     a = bu::etc1s_transcode_args{ static_cast<const uint32_t*>(d_ep_pal), static_cast<const uint32_t*>(d_sel_pal), static_cast<const uint16_t*>(d_ep_idx),
                                   static_cast<const uint16_t*>(d_sel_idx), static_cast<const uint16_t*>(d_a_ep_idx), static_cast<const uint16_t*>(d_a_sel_idx), d_out, nullptr, nullptr,
-                                  n_ep, n_sel, nbx, nby, width, height, pitch, rows };
+                                  n_ep, n_sel, geo };
     return 1;
 }
 
@@ -35,20 +32,11 @@ static int ensure_bc1_tables(bu_hip_context* ctx) {
     return 1;
 }
 
-static int read_counter(bu_hip_context* ctx, const void* d_counter, uint32_t* out) {
-    BU_TRY(ctx, d2h_pageable(ctx, out, d_counter, sizeof(uint32_t)));
-    BU_TRY(ctx, stream_wait(ctx, ctx->stream));
-    return 1;
-}
-
 extern "C" {
 
 size_t bu_hip_etc1s_transcode_output_bytes(uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, uint32_t pitch_px, uint32_t rows_px) {
-    const size_t unit = bu::etc1s_transcode_unit_bytes(target);
-    if (!unit) return 0;
-    if (!bu::etc1s_transcode_is_pixel_target(target)) return (size_t)nbx * nby * unit;
-    const size_t width = orig_w ? orig_w : nbx * 4, height = orig_h ? orig_h : nby * 4;
-    return (pitch_px ? pitch_px : width) * (rows_px ? rows_px : height) * unit;
+    return bu::raster_output_bytes(bu::tile_geometry{ nbx, nby, orig_w, orig_h, pitch_px, rows_px }, bu::etc1s_transcode_unit_bytes(target),
+                                   bu::etc1s_transcode_is_pixel_target(target));
 }
 
 int bu_hip_etc1s_bc1_endpoint_tables(bu_hip_context* ctx, uint32_t* h_out5, uint32_t* h_out6) {
@@ -80,7 +68,7 @@ int bu_hip_k_transcode_etc1s_counted(bu_hip_context* ctx, const void* d_ep_pal, 
         BU_TRY(ctx, bu::launch_transcode_etc1s(ctx->stream, a, target));
     }
     uint32_t invalid = 0;
-    if (!read_counter(ctx, counter.p, &invalid)) return 0;
+    if (!read_back(ctx, &invalid, counter.p, sizeof(invalid))) return 0;
     if (out_invalid_blocks) *out_invalid_blocks = invalid;
     return 1;
 }
@@ -108,7 +96,7 @@ int bu_hip_k_transcode_etc1s(bu_hip_context* ctx, const void* d_ep_pal, uint32_t
         }
     }
     uint32_t past = 0;
-    if (!read_counter(ctx, d_count, &past)) return 0;
+    if (!read_back(ctx, &past, d_count, sizeof(past))) return 0;
     if (past) { set_error(ctx, "transcode_etc1s: %u indices are past their palette (%u endpoints, %u selectors): nothing was transcoded", past, n_ep, n_sel); return 0; }
     uint32_t invalid = 0;
     if (!bu_hip_k_transcode_etc1s_counted(ctx, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out, pitch_px, rows_px,
@@ -117,7 +105,7 @@ int bu_hip_k_transcode_etc1s(bu_hip_context* ctx, const void* d_ep_pal, uint32_t
     return 1;
 }
 
-// every image of a file in one launch: the table's checks, upload and read-back are api_transcode_slices.cpp's
+// every image of a file in one launch: the table's checks and pack are tile_geometry_check.h's behind transcode_slices_check, upload and read-back api_internal.h's
 int bu_hip_k_transcode_etc1s_slices(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
                                     uint64_t n_indices, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target, void* d_out, size_t out_bytes,
                                     uint32_t* out_invalid_per_slice) {
@@ -129,23 +117,24 @@ int bu_hip_k_transcode_etc1s_slices(bu_hip_context* ctx, const void* d_ep_pal, u
     }
     if (!d_ep_pal || !d_sel_pal || !d_ep_idx || !d_sel_idx) { set_error(ctx, "%s: null pointer", fn); return 0; }
     if (!n_ep || !n_sel || n_ep > 65535u || n_sel > 65535u) { set_error(ctx, "%s: palettes of %u endpoints and %u selectors (1..65535 each)", fn, n_ep, n_sel); return 0; }
-    transcode_slice_table table;
-    if (!table.check(ctx, fn, slices, n_slices, n_indices, target, true, d_out, out_bytes)) return 0;
+    bu::slice_table table;
+    if (!transcode_slices_check(ctx, table, fn, slices, n_slices, n_indices, target, true, d_out, out_bytes)) return 0;
     device_guard g(ctx->device);
     const uint32_t* bc1 = nullptr;
     if (target == bu::ETF_BC1_RGB) {
         if (!ensure_bc1_tables(ctx)) return 0;
         bc1 = static_cast<const uint32_t*>(ctx->etc1s_bc1_tables.p);
     }
-    if (!table.upload(ctx)) return 0;
+    uploaded_slices d;
+    if (!upload_slice_table(ctx, table, d)) return 0;
     const bu::etc1s_transcode_slices_args a = { static_cast<const uint32_t*>(d_ep_pal), static_cast<const uint32_t*>(d_sel_pal), static_cast<const uint16_t*>(d_ep_idx),
-                                                static_cast<const uint16_t*>(d_sel_idx), static_cast<uint8_t*>(d_out), table.d_counters, bc1, table.d_slices, table.d_prefix,
-                                                n_ep, n_sel, table.n, table.total_blocks };
+                                                static_cast<const uint16_t*>(d_sel_idx), static_cast<uint8_t*>(d_out), d.counters, bc1,
+                                                static_cast<const bu_hip_transcode_slice*>(d.records), d.prefix, n_ep, n_sel, table.n, table.total };
     {
         prof_scope ps(ctx, fn);
         BU_TRY(ctx, bu::launch_transcode_etc1s_slices(ctx->stream, a, target));
     }
-    return out_invalid_per_slice ? table.read_counters(ctx, out_invalid_per_slice) : 1;
+    return out_invalid_per_slice ? read_back(ctx, out_invalid_per_slice, d.counters, (size_t)table.n * sizeof(uint32_t)) : 1;
 }
 
 } // extern "C"

@@ -12,15 +12,8 @@ int bu_hip_k_image_metrics(bu_hip_context* ctx, const void* d_a, uint32_t wa, ui
     if (!ctx) return 0;
     if (!d_a || !d_b || !h_out) { set_error(ctx, "image_metrics: null pointer"); return 0; }
     if (h_out->struct_bytes < sizeof(uint32_t)) { set_error(ctx, "image_metrics: struct_bytes is not set"); return 0; }
-    if ((reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_b)) & 3u) { set_error(ctx, "image_metrics: a raster is not 4-byte aligned"); return 0; }
-    const uint32_t pa = pitch_a ? pitch_a : wa, pb = pitch_b ? pitch_b : wb;
-    if (pa < wa) { set_error(ctx, "image_metrics: row pitch %u of the first raster is less than its width %u", pa, wa); return 0; }
-    if (pb < wb) { set_error(ctx, "image_metrics: row pitch %u of the second raster is less than its width %u", pb, wb); return 0; }
-    const uint32_t w = std::min(wa, wb), h = std::min(ha, hb);
-    if (w > bu::kImageMetricsMaxDim || h > bu::kImageMetricsMaxDim) {
-        set_error(ctx, "image_metrics: a region of %u x %u pixels is too large (%u each way at the most)", w, h, (uint32_t)bu::kImageMetricsMaxDim);
-        return 0;
-    }
+    uint32_t pa = pitch_a, pb = pitch_b, w, h;
+    if (!checked(ctx, [&](bu::err_text e) { return bu::raster_pair_region("image_metrics", d_a, wa, ha, &pa, d_b, wb, hb, &pb, &w, &h, bu::kImageMetricsMaxDim, e); })) return 0;
     device_guard g(ctx->device);
     arena& dev = ctx->scratch[4];
     BU_TRY(ctx, dev.reserve(sizeof(bu::image_metrics_device_counts)));
@@ -30,8 +23,7 @@ int bu_hip_k_image_metrics(bu_hip_context* ctx, const void* d_a, uint32_t wa, ui
                                              static_cast<bu::image_metrics_device_counts*>(dev.p)));
     }
     bu_image_metrics_counts full;
-    BU_TRY(ctx, d2h_pageable(ctx, full.hist, dev.p, sizeof(bu::image_metrics_device_counts)));
-    BU_TRY(ctx, stream_wait(ctx, ctx->stream));
+    if (!read_back(ctx, full.hist, dev.p, sizeof(bu::image_metrics_device_counts))) return 0;
     full.struct_bytes = h_out->struct_bytes;
     full.width = w; full.height = h; full.reserved = 0;
     memcpy(h_out, &full, std::min<size_t>(h_out->struct_bytes, sizeof(full)));

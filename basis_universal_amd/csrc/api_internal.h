@@ -15,6 +15,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/basisu_hip.h"
+#include "tile_geometry_check.h"
 
 // A grow-only device buffer: the per-call temporaries of the blocking layer live here so that repeated calls
 // (one per frontend stage, several per refinement iteration) do not hit hipMalloc/hipFree.
@@ -109,19 +110,36 @@ inline const char* transcoder_format_name(uint32_t format) {
     return format < sizeof(names) / sizeof(names[0]) ? names[format] : "unknown";
 }
 
-// The slice table of the whole-file transcoders (api_transcode_slices.cpp): check() is every refusal the two entries share -- nothing is touched when it returns 0 --
-// and packs what upload() sends in one stream-ordered copy into scratch[4]: the records with their zero sizes filled in, the prefix table of their block counts, and
-// behind them the per-slice counters the launcher clears.
-struct transcode_slice_table {
-    std::vector<uint8_t> pack;
-    size_t prefix_at = 0, counters_at = 0;
-    uint32_t n = 0, total_blocks = 0;
-    const bu_hip_transcode_slice* d_slices = nullptr; const uint32_t* d_prefix = nullptr; uint32_t* d_counters = nullptr;   // set by upload()
-    int check(bu_hip_context* ctx, const char* fn, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint64_t n_inputs, uint32_t target, bool etc1s, const void* d_out,
-              size_t out_bytes);
-    int upload(bu_hip_context* ctx);
-    int read_counters(bu_hip_context* ctx, uint32_t* out_per_slice);   // one copy, one stream wait
-};
+// A check of tile_geometry_check.h with its refusal as the context's error: checked(ctx, [&](bu::err_text e) { return bu::resolve_geometry(..., e); })
+template <class Check>
+inline int checked(bu_hip_context* ctx, Check check) {
+    char text[512];
+    if (check(bu::err_text{ text, sizeof(text) })) return 1;
+    set_error(ctx, "%s", text);
+    return 0;
+}
+
+// a small result copied back and waited for; not the mailbox path of fetch()
+inline int read_back(bu_hip_context* ctx, void* h, const void* d, size_t bytes) {
+    BU_TRY(ctx, d2h_pageable(ctx, h, d, bytes));
+    BU_TRY(ctx, stream_wait(ctx, ctx->stream));
+    return 1;
+}
+
+// A slice_table (tile_geometry_check.h) in scratch[4], sent in one stream-ordered copy: where its three parts are on the device. The counters, where the table has
+// them, are not part of the copy: the launcher clears them.
+struct uploaded_slices { const void* records; const uint32_t* prefix; uint32_t* counters; };
+inline int upload_slice_table(bu_hip_context* ctx, const bu::slice_table& t, uploaded_slices& d) {
+    arena& table = ctx->scratch[4];
+    BU_TRY(ctx, table.reserve(t.pack.size()));
+    BU_TRY(ctx, h2d(ctx, table.p, t.pack.data(), t.upload_bytes()));
+    uint8_t* base = static_cast<uint8_t*>(table.p);
+    d = uploaded_slices{ base, reinterpret_cast<const uint32_t*>(base + t.prefix_at), reinterpret_cast<uint32_t*>(base + t.counters_at) };
+    return 1;
+}
+// every refusal the two whole-file transcoders share (api_transcode_slices.cpp): nothing is touched when it returns 0
+int transcode_slices_check(bu_hip_context* ctx, bu::slice_table& t, const char* fn, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint64_t n_inputs, uint32_t target,
+                           bool etc1s, const void* d_out, size_t out_bytes);
 
 struct device_guard {
     int prev = -1; bool ok = false;

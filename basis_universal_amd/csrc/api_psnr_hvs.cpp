@@ -10,16 +10,7 @@ static_assert(sizeof(bu_psnr_hvs_sums) - offsetof(bu_psnr_hvs_sums, sum_hvs) == 
 // the checks both entry points share -> the region, or 0 with the error set
 static int psnr_hvs_region(bu_hip_context* ctx, const void* d_a, uint32_t wa, uint32_t ha, uint32_t& pa, const void* d_b, uint32_t wb, uint32_t hb, uint32_t& pb, uint32_t& w,
                            uint32_t& h) {
-    if ((reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_b)) & 3u) { set_error(ctx, "psnr_hvs: a raster is not 4-byte aligned"); return 0; }
-    pa = pa ? pa : wa; pb = pb ? pb : wb;
-    if (pa < wa) { set_error(ctx, "psnr_hvs: row pitch %u of the first raster is less than its width %u", pa, wa); return 0; }
-    if (pb < wb) { set_error(ctx, "psnr_hvs: row pitch %u of the second raster is less than its width %u", pb, wb); return 0; }
-    w = std::min(wa, wb); h = std::min(ha, hb);
-    if (w > bu::kImageMetricsMaxDim || h > bu::kImageMetricsMaxDim) {
-        set_error(ctx, "psnr_hvs: a region of %u x %u pixels is too large (%u each way at the most)", w, h, (uint32_t)bu::kImageMetricsMaxDim);
-        return 0;
-    }
-    return 1;
+    return checked(ctx, [&](bu::err_text e) { return bu::raster_pair_region("psnr_hvs", d_a, wa, ha, &pa, d_b, wb, hb, &pb, &w, &h, bu::kImageMetricsMaxDim, e); });
 }
 
 // launches into scratch[4] (sums, then partials) and, with per_block, scratch[5]; the sums are on the host and the stream idle when it returns 1
@@ -37,9 +28,7 @@ static int psnr_hvs_run(bu_hip_context* ctx, const void* d_a, uint32_t wa, uint3
                                         reinterpret_cast<double*>(static_cast<char*>(dev.p) + head), static_cast<bu::psnr_hvs_device_sums*>(dev.p),
                                         per_block ? static_cast<double*>(ctx->scratch[5].p) : nullptr, mode));
     }
-    BU_TRY(ctx, d2h_pageable(ctx, full.sum_hvs, dev.p, sizeof(bu::psnr_hvs_device_sums)));
-    BU_TRY(ctx, stream_wait(ctx, ctx->stream));
-    return 1;
+    return read_back(ctx, full.sum_hvs, dev.p, sizeof(bu::psnr_hvs_device_sums));
 }
 
 extern "C" {
@@ -70,10 +59,7 @@ int bu_hip_k_psnr_hvs_blocks(bu_hip_context* ctx, const void* d_a, uint32_t wa, 
     if (blocks > capacity_blocks) { set_error(ctx, "psnr_hvs_blocks: %u blocks, room for %u", blocks, capacity_blocks); return 0; }
     bu_psnr_hvs_sums full;
     if (!psnr_hvs_run(ctx, d_a, wa, ha, pitch_a, d_b, wb, hb, pitch_b, blocks, true, mode, full)) return 0;
-    if (blocks) {
-        BU_TRY(ctx, d2h_pageable(ctx, h_out_blocks, ctx->scratch[5].p, (size_t)blocks * 2 * sizeof(double)));
-        BU_TRY(ctx, stream_wait(ctx, ctx->stream));
-    }
+    if (blocks && !read_back(ctx, h_out_blocks, ctx->scratch[5].p, (size_t)blocks * 2 * sizeof(double))) return 0;
     if (out_blocks) *out_blocks = blocks;
     return 1;
 }

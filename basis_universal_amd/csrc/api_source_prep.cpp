@@ -29,8 +29,7 @@ static int prepare(bu_hip_context* ctx, const char* fn, const bu::source_prep_ar
     }
     if (out_any_below_255) {
         uint32_t any = 0;
-        BU_TRY(ctx, d2h_pageable(ctx, &any, word.p, sizeof(uint32_t)));
-        BU_TRY(ctx, stream_wait(ctx, ctx->stream));
+        if (!read_back(ctx, &any, word.p, sizeof(any))) return 0;
         *out_any_below_255 = any & 1u;
     }
     return 1;

@@ -11,11 +11,8 @@ static constexpr size_t kSsimKeepBytes = (size_t)64 << 20;
 // the checks both entry points share -> the region, or 0 with the error set
 static int ssim_region(bu_hip_context* ctx, const char* who, const void* d_a, uint32_t wa, uint32_t ha, uint32_t& pa, const void* d_b, uint32_t wb, uint32_t hb, uint32_t& pb,
                        uint32_t& w, uint32_t& h) {
-    if ((reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_b)) & 3u) { set_error(ctx, "%s: a raster is not 4-byte aligned", who); return 0; }
-    pa = pa ? pa : wa; pb = pb ? pb : wb;
-    if (pa < wa) { set_error(ctx, "%s: row pitch %u of the first raster is less than its width %u", who, pa, wa); return 0; }
-    if (pb < wb) { set_error(ctx, "%s: row pitch %u of the second raster is less than its width %u", who, pb, wb); return 0; }
-    w = std::min(wa, wb); h = std::min(ha, hb);
+    // the size limit is this file's own sentence (it names the pixel cap too), after the empty region's: none is given to the shared check
+    if (!checked(ctx, [&](bu::err_text e) { return bu::raster_pair_region(who, d_a, wa, ha, &pa, d_b, wb, hb, &pb, &w, &h, UINT32_MAX, e); })) return 0;
     if (!w || !h) { set_error(ctx, "%s: an empty region (%u x %u pixels): there is no mean over no pixels", who, w, h); return 0; }
     if (w > bu::kImageMetricsMaxDim || h > bu::kImageMetricsMaxDim || (uint64_t)w * h > bu::kSsimMaxPixels) {
         set_error(ctx, "%s: a region of %u x %u pixels is too large (%u each way and %u pixels at the most: the context holds six float planes of the region)", who, w, h,
@@ -51,11 +48,7 @@ int bu_hip_k_ssim(bu_hip_context* ctx, const void* d_a, uint32_t wa, uint32_t ha
     const uint32_t n = w * h;
     bu::ssim_device_result dev;
     int ok = ssim_run(ctx, d_a, wa, ha, pitch_a, d_b, wb, hb, pitch_b, n, true);
-    if (ok) {
-        hipError_t e = d2h_pageable(ctx, &dev, static_cast<char*>(ctx->scratch[5].p) + bu::ssim_result_offset(n), sizeof(dev));
-        if (e == hipSuccess) e = stream_wait(ctx, ctx->stream);
-        if (e != hipSuccess) { set_error(ctx, "ssim: %s", hipGetErrorString(e)); ok = 0; }
-    }
+    if (ok) ok = read_back(ctx, &dev, static_cast<char*>(ctx->scratch[5].p) + bu::ssim_result_offset(n), sizeof(dev));
     ssim_done(ctx);
     if (!ok) return 0;
     bu_ssim_result full;
@@ -85,19 +78,15 @@ int bu_hip_k_ssim_map(bu_hip_context* ctx, const void* d_a, uint32_t wa, uint32_
     int ok = ssim_run(ctx, d_a, wa, ha, pitch_a, d_b, wb, hb, pitch_b, n, false);
     if (ok) {
         const float* planes = static_cast<const float*>(ctx->scratch[5].p);
-        hipError_t e = hipSuccess;
         if (mode == bu::SSIM_RGBA) {
             std::vector<float> planar((size_t)n * 4);
-            e = d2h_pageable(ctx, planar.data(), planes, planar.size() * sizeof(float));
-            if (e == hipSuccess) e = stream_wait(ctx, ctx->stream);
-            if (e == hipSuccess)
+            ok = read_back(ctx, planar.data(), planes, planar.size() * sizeof(float));
+            if (ok)
                 for (size_t i = 0; i < n; i++)
                     for (uint32_t c = 0; c < 4; c++) h_out[i * 4 + c] = planar[(size_t)c * n + i];
         } else {
-            e = d2h_pageable(ctx, h_out, planes + (size_t)(mode == bu::SSIM_LUMA_709 ? bu::SSIM_PLANE_709 : bu::SSIM_PLANE_601) * n, (size_t)n * sizeof(float));
-            if (e == hipSuccess) e = stream_wait(ctx, ctx->stream);
+            ok = read_back(ctx, h_out, planes + (size_t)(mode == bu::SSIM_LUMA_709 ? bu::SSIM_PLANE_709 : bu::SSIM_PLANE_601) * n, (size_t)n * sizeof(float));
         }
-        if (e != hipSuccess) { set_error(ctx, "ssim_map: %s", hipGetErrorString(e)); ok = 0; }
     }
     ssim_done(ctx);
     if (!ok) return 0;

@@ -65,28 +65,26 @@ int bu_hip_k_transcode_uastc(bu_hip_context* ctx, const void* d_blocks, uint32_t
     if (out_invalid_blocks) *out_invalid_blocks = 0;
     if (!bu::transcode_output_bytes(1, 1, 0, 0, target)) { set_error(ctx, kUastcTargetRefused, target); return 0; }
     if (!d_blocks || !d_out) { set_error(ctx, "transcode_uastc: null device pointer"); return 0; }
-    if ((uint64_t)nbx * nby > 0x7FFFFFFFull) { set_error(ctx, "transcode_uastc: %u x %u blocks is too many", nbx, nby); return 0; }
-    const uint32_t width = orig_width ? orig_width : nbx * 4, height = orig_height ? orig_height : nby * 4;
-    if (width > nbx * 4 || height > nby * 4) { set_error(ctx, "transcode_uastc: %u x %u pixels do not fit %u x %u blocks", width, height, nbx, nby); return 0; }
-    const uint32_t pitch = out_row_pitch_pixels ? out_row_pitch_pixels : width, rows = out_rows_pixels ? out_rows_pixels : height;
-    if (pitch < width) { set_error(ctx, "transcode_uastc: row pitch %u is less than the width %u", pitch, width); return 0; }
+    bu::tile_geometry geo;
+    if (!checked(ctx, [&](bu::err_text e) {
+            return bu::resolve_geometry("transcode_uastc", nbx, nby, orig_width, orig_height, out_row_pitch_pixels, out_rows_pixels, bu::kUastcOneImage, &geo, e);
+        })) return 0;
     if (channel0 > 3 || channel1 > 3) { set_error(ctx, "transcode_uastc: channel out of range"); return 0; }
     device_guard g(ctx->device);
     arena& counter = ctx->scratch[4];
     BU_TRY(ctx, counter.reserve(sizeof(uint32_t)));
     {
         prof_scope ps(ctx, "uastc_transcode");
-        BU_TRY(ctx, bu::launch_transcode_uastc(ctx->stream, d_blocks, nbx, nby, width, height, target, (decode_flags & 32u) != 0 /* cDecodeFlagsHighQuality */,
-                                               channel0 < 0 ? 0u : (uint32_t)channel0, channel1 < 0 ? 3u : (uint32_t)channel1, d_out, pitch, rows, static_cast<uint32_t*>(counter.p)));
+        BU_TRY(ctx, bu::launch_transcode_uastc(ctx->stream, d_blocks, geo, target, (decode_flags & 32u) != 0 /* cDecodeFlagsHighQuality */,
+                                               channel0 < 0 ? 0u : (uint32_t)channel0, channel1 < 0 ? 3u : (uint32_t)channel1, d_out, static_cast<uint32_t*>(counter.p)));
     }
     uint32_t invalid = 0;
-    BU_TRY(ctx, d2h_pageable(ctx, &invalid, counter.p, sizeof(invalid)));
-    BU_TRY(ctx, stream_wait(ctx, ctx->stream));
+    if (!read_back(ctx, &invalid, counter.p, sizeof(invalid))) return 0;
     if (out_invalid_blocks) *out_invalid_blocks = invalid;
     return 1;
 }
 
-// every image of a file in one launch: the table's checks, upload and read-back are api_transcode_slices.cpp's
+// every image of a file in one launch: the table's checks and pack are tile_geometry_check.h's behind transcode_slices_check, upload and read-back api_internal.h's
 int bu_hip_k_transcode_uastc_slices(bu_hip_context* ctx, const void* d_blocks, uint64_t n_blocks, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target,
                                     uint32_t decode_flags, int32_t channel0, int32_t channel1, void* d_out, size_t out_bytes, uint32_t* out_invalid_per_slice) {
     if (!ctx) return 0;
@@ -95,17 +93,18 @@ int bu_hip_k_transcode_uastc_slices(bu_hip_context* ctx, const void* d_blocks, u
     if (!d_blocks) { set_error(ctx, "%s: null pointer", fn); return 0; }
     if ((uintptr_t)d_blocks & 15u) { set_error(ctx, "%s: the blocks are not 16-byte aligned", fn); return 0; }
     if (channel0 > 3 || channel1 > 3) { set_error(ctx, "%s: channel out of range", fn); return 0; }
-    transcode_slice_table table;
-    if (!table.check(ctx, fn, slices, n_slices, n_blocks, target, false, d_out, out_bytes)) return 0;
+    bu::slice_table table;
+    if (!transcode_slices_check(ctx, table, fn, slices, n_slices, n_blocks, target, false, d_out, out_bytes)) return 0;
     device_guard g(ctx->device);
-    if (!table.upload(ctx)) return 0;
+    uploaded_slices d;
+    if (!upload_slice_table(ctx, table, d)) return 0;
     {
         prof_scope ps(ctx, fn);
-        BU_TRY(ctx, bu::launch_transcode_uastc_slices(ctx->stream, d_blocks, table.d_slices, table.d_prefix, table.n, table.total_blocks, target,
+        BU_TRY(ctx, bu::launch_transcode_uastc_slices(ctx->stream, d_blocks, static_cast<const bu_hip_transcode_slice*>(d.records), d.prefix, table.n, table.total, target,
                                                       (decode_flags & 32u) != 0 /* cDecodeFlagsHighQuality */, channel0 < 0 ? 0u : (uint32_t)channel0,
-                                                      channel1 < 0 ? 3u : (uint32_t)channel1, d_out, table.d_counters));
+                                                      channel1 < 0 ? 3u : (uint32_t)channel1, d_out, d.counters));
     }
-    return out_invalid_per_slice ? table.read_counters(ctx, out_invalid_per_slice) : 1;
+    return out_invalid_per_slice ? read_back(ctx, out_invalid_per_slice, d.counters, (size_t)table.n * sizeof(uint32_t)) : 1;
 }
 
 void bu_hip_uastc_rdo_default_params(bu_uastc_rdo_params* p) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "tile_raster.h"
 
 namespace bu {
 
@@ -9,7 +10,7 @@ struct block_unpack_args {
     const void* blocks;    // nbx * nby blocks of 8 (BC1, BC4) or 16 bytes, raster order, aligned to their size
     uint32_t* out;         // RGBA8 raster, 4-byte aligned
     uint32_t* invalid;     // device counter
-    uint32_t nbx, nby, width, height, pitch, rows;   // width x height pixels are written (rows cut at `rows`); pitch in pixels
+    tile_geometry g;       // width x height pixels are written (rows cut at `rows`); pitch in pixels
 };
 
 uint32_t block_unpack_bytes_per_block(uint32_t format);   // 0 = the format does not unpack here

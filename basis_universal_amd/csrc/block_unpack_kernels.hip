@@ -14,7 +14,8 @@ using namespace bu_unpack;
 
 template <uint32_t FORMAT>
 __global__ __launch_bounds__(256) void unpack_blocks_kernel(block_unpack_args a) {
-    const uint32_t n = a.nbx * a.nby, b = blockIdx.x * 16u + (threadIdx.x >> 4), i = threadIdx.x & 15u;   // n <= 2^28: no overflow
+    const tile_geometry& g = a.g;
+    const uint32_t n = g.nbx * g.nby, b = blockIdx.x * 16u + (threadIdx.x >> 4), i = threadIdx.x & 15u;   // n <= 2^28: no overflow
     if (b >= n) return;
     uint64_t lo, hi = 0;
     if (unpack_bytes_per_block(FORMAT) == 8u) {
@@ -28,13 +29,13 @@ __global__ __launch_bounds__(256) void unpack_blocks_kernel(block_unpack_args a)
     bool ok;
     const uint32_t px = unpack_texel<FORMAT>(lo, hi, i, &ok);
     if (FORMAT == UF_BC7 && !ok && i == 0u) atomicAdd(a.invalid, 1u);
-    const uint32_t bx = b % a.nbx, by = b / a.nbx, x = bx * 4u + (i & 3u), y = by * 4u + (i >> 2);
-    if (x < a.width && y < a.height && y < a.rows) a.out[(size_t)y * a.pitch + x] = px;
+    const uint32_t bx = b % g.nbx, by = b / g.nbx, x = bx * 4u + (i & 3u), y = by * 4u + (i >> 2);
+    if (x < g.width && y < g.height && y < g.rows) a.out[(size_t)y * g.pitch + x] = px;
 }
 
 template <uint32_t FORMAT>
 static hipError_t launch(hipStream_t st, const block_unpack_args& a) {
-    const uint32_t n = a.nbx * a.nby;
+    const uint32_t n = a.g.nbx * a.g.nby;
     hipLaunchKernelGGL((unpack_blocks_kernel<FORMAT>), dim3((n + 15u) / 16u), dim3(256), 0, st, a);
     return hipGetLastError();
 }
@@ -43,7 +44,7 @@ uint32_t block_unpack_bytes_per_block(uint32_t format) { return unpack_bytes_per
 
 hipError_t launch_unpack_blocks(hipStream_t st, const block_unpack_args& a, uint32_t format) {
     hipError_t e = hipMemsetAsync(a.invalid, 0, sizeof(uint32_t), st);
-    if (e != hipSuccess || !a.nbx || !a.nby) return e;
+    if (e != hipSuccess || !a.g.nbx || !a.g.nby) return e;
     switch (format) {
     case UF_BC1: return launch<UF_BC1>(st, a);
     case UF_BC3: return launch<UF_BC3>(st, a);

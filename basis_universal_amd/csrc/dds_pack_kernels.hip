@@ -2,13 +2,13 @@
 // each instance carries only its own path. A tile is loaded as four 16-byte words, consecutive lanes on consecutive tiles.
 //   k_dds_pack_blocks : BC1-BC5. The tile array is in slice order -- image outermost, then level -- which is DDS subresource order (layer, face, level), and a block
 //                       format's subresource is its tiles in raster order: the whole file's payload is tile i -> out[i], one uint2 / uint4 store, no slice table.
-//   k_dds_pack_pixels : the seven raw formats. Rows are tight (exactly width x height pixels per subresource), so a lane needs its slice: the lookup of
-//                       transcode_slices.h. A tile's row is cropped to the slice's width and stored as one 16 / 8 / 4-byte word where it is whole and its address
-//                       allows, else texel by texel; rows past the slice's height are not written.
+//   k_dds_pack_pixels : the seven raw formats. Rows are tight (exactly width x height pixels per subresource), so a lane needs its slice: find_transcode_slice of
+//                       tile_raster.h. A tile's row is cropped to the slice's width and stored by store_tile_row: one 16 / 8 / 4-byte word where it is whole and
+//                       its address allows, else texel by texel; rows past the slice's height are not written.
 #include <hip/hip_runtime.h>
 #include "dds_pack.h"
 #include "dds_pack_kernels.h"
-#include "transcode_slices.h"
+#include "tile_raster.h"
 
 namespace bu {
 using namespace bu_dds;
@@ -29,8 +29,7 @@ __global__ __launch_bounds__(256) void k_dds_pack_blocks(const uint4* __restrict
     load_tile(tiles + (size_t)i * 4, px);
     uint64_t w[2] = { 0, 0 };
     pack_block(px, FMT, w);
-    if (FMT == FMT_BC1 || FMT == FMT_BC4) ((uint2*)out)[i] = make_uint2((uint32_t)w[0], (uint32_t)(w[0] >> 32));
-    else ((uint4*)out)[i] = make_uint4((uint32_t)w[0], (uint32_t)(w[0] >> 32), (uint32_t)w[1], (uint32_t)(w[1] >> 32));
+    store_block_words(out, i, w, !(FMT == FMT_BC1 || FMT == FMT_BC4));
 }
 
 struct dds_pixels_args {
@@ -48,35 +47,15 @@ __global__ __launch_bounds__(256) void k_dds_pack_pixels(dds_pixels_args a) {
     uint32_t px[16];
     load_tile(a.tiles + (size_t)(v.first_block + v.local) * 4, px);
     const uint32_t unit = unit_bytes(FMT);
-    const uint32_t bx = v.local % v.nbx, by = v.local / v.nbx;
-    const bool whole = bx * 4u + 4u <= v.width;
+    const uint32_t bx = v.local % v.g.nbx, by = v.local / v.g.nbx;
     BU_UNROLL
     for (uint32_t y = 0; y < 4; y++) {
         const uint32_t row = by * 4u + y;
-        if (row >= v.height) break;
+        if (row >= v.g.height) break;
         uint32_t p[4];
         BU_UNROLL
         for (uint32_t x = 0; x < 4; x++) p[x] = pack_pixel(px[y * 4 + x], FMT);
-        uint8_t* dst = a.out + v.out_offset + ((size_t)row * v.width + bx * 4u) * unit;
-        if (unit == 4) {
-            if (whole && ((uintptr_t)dst & 15u) == 0) *(uint4*)dst = make_uint4(p[0], p[1], p[2], p[3]);
-            else {
-                BU_UNROLL
-                for (uint32_t x = 0; x < 4; x++) if (bx * 4u + x < v.width) ((uint32_t*)dst)[x] = p[x];
-            }
-        } else if (unit == 2) {
-            if (whole && ((uintptr_t)dst & 7u) == 0) *(uint2*)dst = make_uint2(p[0] | (p[1] << 16), p[2] | (p[3] << 16));
-            else {
-                BU_UNROLL
-                for (uint32_t x = 0; x < 4; x++) if (bx * 4u + x < v.width) ((uint16_t*)dst)[x] = (uint16_t)p[x];
-            }
-        } else {
-            if (whole && ((uintptr_t)dst & 3u) == 0) *(uint32_t*)dst = p[0] | (p[1] << 8) | (p[2] << 16) | (p[3] << 24);
-            else {
-                BU_UNROLL
-                for (uint32_t x = 0; x < 4; x++) if (bx * 4u + x < v.width) dst[x] = (uint8_t)p[x];
-            }
-        }
+        store_tile_row(unit, a.out + v.out_offset + ((size_t)row * v.g.width + bx * 4u) * unit, bx, v.g.width, p);
     }
 }
 

@@ -5,6 +5,7 @@
 #include "etc1s_device.h"
 #include "etc1s_kernels.h"
 #include "launch_dispatch.h"
+#include "tile_raster.h"
 
 namespace bu {
 
@@ -135,22 +136,7 @@ __global__ __launch_bounds__(256) void k_extract_blocks(const uint8_t* __restric
     const uint32_t block = t >> 2, row = t & 3u;
     if (block >= n_blocks) return;
     const uint32_t bx = block % blocks_x, by = block / blocks_x;
-    const uint32_t y = min(by * 4u + row, height - 1u);
-    const uint8_t* line = rgba + (size_t)y * pitch;
-    uint4 v;
-    if (bx * 4u + 3u < width && ((pitch | (uint32_t)(uintptr_t)rgba) & 15u) == 0) {
-        v = *reinterpret_cast<const uint4*>(line + (size_t)bx * 16u);
-    } else {
-        uint32_t p[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t x = min(bx * 4u + (uint32_t)k, width - 1u);
-            const uint8_t* q = line + (size_t)x * 4u;
-            p[k] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-        }
-        v = make_uint4(p[0], p[1], p[2], p[3]);
-    }
-    out[(size_t)block * 4u + row] = v;
+    out[(size_t)block * 4u + row] = load_tile_row_clamped(rgba, pitch, width, height, bx, by * 4u + row);
 }
 
 hipError_t launch_extract_blocks(hipStream_t st, const void* d_rgba, uint32_t width, uint32_t height, uint32_t pitch_bytes, void* d_out_blocks) {
@@ -165,44 +151,22 @@ hipError_t launch_extract_blocks(hipStream_t st, const void* d_rgba, uint32_t wi
 // The same for every slice of a call in ONE launch (bu_hip_k_extract_slices): a multi-image call -- array layers, cubemap faces, video frames, each with its levels,
 // for ETC1S with alpha a colour and an alpha slice per level -- has hundreds of slices of a few blocks, and a launch pair per slice costs more than the tiling.
 // One lane per block row over the tiles of all slices in call order; `prefix` (n_slices + 1 entries, strictly ascending, prefix[n_slices] = total_tiles) says where
-// each slice's tiles begin in that order. A wave's lanes are 16 consecutive tiles: the slice of its first tile is found once per wave by bisection at wave-uniform
-// addresses (scalar loads through the scalar cache), and each lane steps on from there -- at most 15 steps, where a wave straddles slices of one block.
+// each slice's tiles begin in that order. A wave's lanes are 16 consecutive tiles: find_slice (tile_raster.h) with item = tile, so a lane steps on from the wave's
+// first slice at most 15 times, where a wave straddles slices of one block.
 // mode 1 / 2 are the ETC1S colour / alpha slices read straight from the RGBA raster (comp.cpp:2883-2903), so no split plane is ever materialised.
 __global__ __launch_bounds__(256) void k_extract_slices(const bu_hip_slice_source* __restrict__ slices, const uint32_t* __restrict__ prefix, uint32_t n_slices,
                                                         uint32_t total_tiles, uint4* __restrict__ out) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;   // total_tiles <= 2^30 (the launcher's caller refuses more)
     const uint32_t tile = t >> 2, row = t & 3u;
-    const uint32_t wave_first = __builtin_amdgcn_readfirstlane(tile);
-    uint32_t lo = 0, hi = n_slices;                       // prefix[lo] <= wave_first < prefix[hi] while the wave has any tile at all
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (prefix[mid] <= wave_first) lo = mid; else hi = mid;
-    }
-    if (tile >= total_tiles) return;
-    uint32_t s = lo;
-    while (tile >= prefix[s + 1u]) s++;                   // ends: tile < total_tiles = prefix[n_slices]
+    uint32_t s, local;
+    if (!find_slice(prefix, n_slices, total_tiles, tile, s, local)) return;   // every lane of the wave gets here
     const uint4* rec = reinterpret_cast<const uint4*>(slices + s);
     const uint4 r0 = rec[0], r1 = rec[1];                 // { raster lo, hi, width, height } { pitch, mode, first_block lo, hi }
     const uint8_t* rgba = reinterpret_cast<const uint8_t*>((uintptr_t)r0.x | ((uintptr_t)r0.y << 32));
     const uint32_t width = r0.z, height = r0.w, pitch = r1.x, mode = r1.y;
     const uint64_t first_block = (uint64_t)r1.z | ((uint64_t)r1.w << 32);
-    const uint32_t local = tile - prefix[s], blocks_x = (width + 3u) >> 2;
-    const uint32_t bx = local % blocks_x, by = local / blocks_x;
-    const uint32_t y = min(by * 4u + row, height - 1u);
-    const uint8_t* line = rgba + (size_t)y * pitch;
-    uint4 v;
-    if (bx * 4u + 3u < width && ((pitch | (uint32_t)(uintptr_t)rgba) & 15u) == 0) {
-        v = *reinterpret_cast<const uint4*>(line + (size_t)bx * 16u);
-    } else {
-        uint32_t p[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t x = min(bx * 4u + (uint32_t)k, width - 1u);
-            const uint8_t* q = line + (size_t)x * 4u;
-            p[k] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-        }
-        v = make_uint4(p[0], p[1], p[2], p[3]);
-    }
+    const uint32_t blocks_x = (width + 3u) >> 2, bx = local % blocks_x, by = local / blocks_x;
+    uint4 v = load_tile_row_clamped(rgba, pitch, width, height, bx, by * 4u + row);
     if (mode == BU_HIP_SLICE_RGB) {
         v.x |= 0xff000000u; v.y |= 0xff000000u; v.z |= 0xff000000u; v.w |= 0xff000000u;
     } else if (mode == BU_HIP_SLICE_ALPHA) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/basisu_hip.h"
+#include "tile_raster.h"
 
 namespace bu {
 
@@ -17,7 +18,8 @@ struct etc1s_transcode_args {
     void* out;
     uint32_t* invalid;                  // device counter
     const uint32_t* bc1_endpoints;      // BC1 only: 2 * kBc1TableEntries words from launch_etc1s_build_bc1_tables
-    uint32_t n_endpoints, n_selectors, nbx, nby, width, height, pitch, rows;
+    uint32_t n_endpoints, n_selectors;
+    tile_geometry g;
 };
 
 // every image of a file in one launch: the file's two whole index arrays, and a table that says which ranges of them are whose

@@ -4,11 +4,11 @@
 // one uint2 per block, consecutive lanes on consecutive blocks; pixel targets store the four rows of the tile into the caller's raster, cropped to the image, as
 // one 16-byte (RGBA32) or 8-byte (16-bit formats) word per row where the row is whole and aligned. An index past its palette never reaches a gather: the block is
 // zero-filled and counted with a vector atomic, and it does not stop the others. Two kernels share that per-block work: one image per launch, and every image of
-// a file in one launch through a slice table (transcode_slices.h), counted per slice.
+// a file in one launch through a slice table (tile_raster.h), counted per slice.
 #include <hip/hip_runtime.h>
 #include "etc1s_device.h"
 #include "etc1s_transcode_kernels.h"
-#include "transcode_slices.h"
+#include "tile_raster.h"
 
 #define BU_TAB static __device__ const
 #include "etc1s_transcode_tables.inc"
@@ -125,12 +125,11 @@ struct etc1s_palettes {
 
 // One block: the range check, the gathers, the target's conversion, the store. The four index pointers are the IMAGE's (alpha: both null = opaque), `out` is where
 // the image's output begins, `i` the block's place in the image's raster order. Block targets write one uint2 at out[i]; pixel targets the four rows of the tile
-// cropped to width x min(height, rows), a row as one word where it is whole and its address aligned. false = an index was past its palette and zeros were written.
+// cropped to width x min(height, rows) (store_tile_row, tile_raster.h). false = an index was past its palette and zeros were written.
 // Both kernels below are this function behind their own indexing.
 template <uint32_t TARGET>
 __device__ __forceinline__ bool transcode_etc1s_block(const etc1s_palettes& a, const uint16_t* endpoint_idx, const uint16_t* selector_idx, const uint16_t* alpha_endpoint_idx,
-                                                      const uint16_t* alpha_selector_idx, void* out, uint32_t i, uint32_t nbx, uint32_t width, uint32_t height, uint32_t pitch,
-                                                      uint32_t rows) {
+                                                      const uint16_t* alpha_selector_idx, void* out, uint32_t i, const tile_geometry& g) {
     constexpr bool kPixels = TARGET == ETF_RGBA32 || TARGET == ETF_RGB565 || TARGET == ETF_BGR565 || TARGET == ETF_RGBA4444;
     constexpr bool kAlpha = TARGET == ETF_RGBA32 || TARGET == ETF_RGBA4444;
     const uint32_t ei = endpoint_idx[i], si = selector_idx[i];
@@ -165,48 +164,32 @@ __device__ __forceinline__ bool transcode_etc1s_block(const etc1s_palettes& a, c
     } else {
         alphas[0] = alphas[1] = alphas[2] = alphas[3] = 0;
     }
-    const uint32_t bx = i % nbx, by = i / nbx;
-    const bool whole = bx * 4u + 4u <= width;
+    constexpr uint32_t kUnit = TARGET == ETF_RGBA32 ? 4u : 2u;
+    const uint32_t bx = i % g.nbx, by = i / g.nbx;
 #pragma unroll
     for (uint32_t y = 0; y < 4; y++) {
         const uint32_t row = by * 4u + y;
-        if (row >= height || row >= rows) break;
+        if (row >= g.height || row >= g.rows) break;
         uint32_t v[4];
 #pragma unroll
         for (uint32_t x = 0; x < 4; x++) {
             const uint32_t px = pack_pixel<TARGET>(pick4(colors, texel_selector(sel, x, y)), has_alpha ? pick4(alphas, texel_selector(asel, x, y)) : alphas[0]);
             v[x] = ok ? px : 0u;
         }
-        const size_t at = (size_t)row * pitch + bx * 4u;
-        if (TARGET == ETF_RGBA32) {
-            uint32_t* dst = (uint32_t*)out + at;
-            if (whole && (((uintptr_t)dst & 15u) == 0)) *(uint4*)dst = make_uint4(v[0], v[1], v[2], v[3]);
-            else {
-#pragma unroll
-                for (uint32_t x = 0; x < 4; x++) if (bx * 4u + x < width) dst[x] = v[x];
-            }
-        } else {
-            uint16_t* dst = (uint16_t*)out + at;
-            if (whole && (((uintptr_t)dst & 7u) == 0)) *(uint2*)dst = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
-            else {
-#pragma unroll
-                for (uint32_t x = 0; x < 4; x++) if (bx * 4u + x < width) dst[x] = (uint16_t)v[x];
-            }
-        }
+        store_tile_row(kUnit, (uint8_t*)out + ((size_t)row * g.pitch + bx * 4u) * kUnit, bx, g.width, v);
     }
     return ok;
 }
 
 template <uint32_t TARGET>
 __global__ __launch_bounds__(256) void transcode_etc1s_kernel(etc1s_transcode_args a) {
-    const uint32_t n = a.nbx * a.nby, i = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t n = a.g.nbx * a.g.nby, i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const etc1s_palettes p = { a.endpoint_palette, a.selector_palette, a.bc1_endpoints, a.n_endpoints, a.n_selectors };
-    if (!transcode_etc1s_block<TARGET>(p, a.endpoint_idx, a.selector_idx, a.alpha_endpoint_idx, a.alpha_selector_idx, a.out, i, a.nbx, a.width, a.height, a.pitch, a.rows))
-        atomicAdd(a.invalid, 1u);
+    if (!transcode_etc1s_block<TARGET>(p, a.endpoint_idx, a.selector_idx, a.alpha_endpoint_idx, a.alpha_selector_idx, a.out, i, a.g)) atomicAdd(a.invalid, 1u);
 }
 
-// every image of a file in one launch (bu_hip_k_transcode_etc1s_slices): the lookup of transcode_slices.h in front of the same block function. The colour and the
+// every image of a file in one launch (bu_hip_k_transcode_etc1s_slices): find_transcode_slice (tile_raster.h) in front of the same block function. The colour and the
 // alpha slice of an image are two ranges of the same two index arrays.
 template <uint32_t TARGET>
 __global__ __launch_bounds__(256) void transcode_etc1s_slices_kernel(etc1s_transcode_slices_args a) {
@@ -215,7 +198,7 @@ __global__ __launch_bounds__(256) void transcode_etc1s_slices_kernel(etc1s_trans
     const etc1s_palettes p = { a.endpoint_palette, a.selector_palette, a.bc1_endpoints, a.n_endpoints, a.n_selectors };
     const bool alpha = v.alpha_first_block != BU_HIP_NO_ALPHA_SLICE;
     if (!transcode_etc1s_block<TARGET>(p, a.endpoint_idx + v.first_block, a.selector_idx + v.first_block, alpha ? a.endpoint_idx + v.alpha_first_block : nullptr,
-                                       alpha ? a.selector_idx + v.alpha_first_block : nullptr, a.out + v.out_offset, v.local, v.nbx, v.width, v.height, v.pitch, v.rows))
+                                       alpha ? a.selector_idx + v.alpha_first_block : nullptr, a.out + v.out_offset, v.local, v.g))
         atomicAdd(a.invalid + v.slice, 1u);
 }
 
@@ -261,7 +244,7 @@ __global__ __launch_bounds__(256) void etc1s_count_indices_past_kernel(const uin
 
 template <uint32_t TARGET>
 static hipError_t launch(hipStream_t st, const etc1s_transcode_args& a) {
-    const uint32_t n = a.nbx * a.nby;
+    const uint32_t n = a.g.nbx * a.g.nby;
     hipLaunchKernelGGL((transcode_etc1s_kernel<TARGET>), dim3((n + 255) / 256), dim3(256), 0, st, a);
     return hipGetLastError();
 }
@@ -298,7 +281,7 @@ bool etc1s_transcode_is_pixel_target(uint32_t target) { return target == ETF_RGB
 
 hipError_t launch_transcode_etc1s(hipStream_t st, const etc1s_transcode_args& a, uint32_t target) {
     hipError_t e = hipMemsetAsync(a.invalid, 0, sizeof(uint32_t), st);
-    if (e != hipSuccess || !a.nbx || !a.nby) return e;
+    if (e != hipSuccess || !a.g.nbx || !a.g.nby) return e;
     return launch_for_target(st, a, target);
 }
 

@@ -3,16 +3,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/basisu_hip.h"
+#include "tile_raster.h"
 
 namespace bu {
 
 // Bytes the transcode of an nbx x nby grid writes for `target` (a transcoder_texture_format value); RGBA32: the tight width x height raster (0 = the
 // padded size). 0 for a target that is not supported.
 size_t transcode_output_bytes(uint32_t nbx, uint32_t nby, uint32_t width, uint32_t height, uint32_t target);
-// One launch over the grid, stream-ordered. width / height: the image's size (<= the grid's); pitch / rows: the RGBA32 raster's row pitch and row
-// count in pixels; chan0 / chan1: BC4's channel, BC5's two. *d_invalid (device) receives the number of blocks that did not unpack (zero-filled).
-hipError_t launch_transcode_uastc(hipStream_t st, const void* d_blocks, uint32_t nbx, uint32_t nby, uint32_t width, uint32_t height, uint32_t target, bool high_quality,
-                                  uint32_t chan0, uint32_t chan1, void* d_out, uint32_t pitch, uint32_t rows, uint32_t* d_invalid);
+// One launch over the grid, stream-ordered. g: the grid, the image's size (<= the grid's) and the RGBA32 raster's row pitch and row count in pixels, no zeros
+// left; chan0 / chan1: BC4's channel, BC5's two. *d_invalid (device) receives the number of blocks that did not unpack (zero-filled).
+hipError_t launch_transcode_uastc(hipStream_t st, const void* d_blocks, const tile_geometry& g, uint32_t target, bool high_quality, uint32_t chan0, uint32_t chan1,
+                                  void* d_out, uint32_t* d_invalid);
 // The same for every slice of a table in ONE launch (bu_hip_k_transcode_uastc_slices): d_slices are device copies of the records with every zero size replaced by what
 // it stands for, d_prefix[n_slices + 1] where each slice's blocks begin among the total_blocks of the call (strictly ascending). Slice s reads its blocks from
 // d_blocks + 16 * first_block and writes at d_out + out_offset; d_invalid[n_slices] is cleared first and receives the per-slice counts.

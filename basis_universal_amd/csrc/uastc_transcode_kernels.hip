@@ -3,11 +3,12 @@
 // is loaded as one uint4 and its result stored as whole uint2 / uint4 words, consecutive lanes on consecutive blocks; RGBA32 writes the four 16-byte
 // rows of its tile into the caller's raster, cropped to the image. A block the core refuses (mode code that matches nothing, pattern index out of
 // range) gets zeros and is counted with a vector atomic; it never stops the others. Two kernels share that per-block work: one image per launch, and every
-// image of a file in one launch through a slice table (transcode_slices.h), counted per slice.
+// image of a file in one launch through a slice table (tile_raster.h), counted per slice.
 #include <hip/hip_runtime.h>
 #include "uastc_transcode.h"
 #include "uastc_transcode_kernels.h"
-#include "transcode_slices.h"
+#include "tile_raster.h"
+#include "tile_geometry_check.h"
 
 namespace bu {
 using namespace bu_uastc;
@@ -16,15 +17,15 @@ struct transcode_args {
     const uint4* blocks;
     void* out;
     uint32_t* invalid;
-    uint32_t nbx, nby, width, height, pitch, rows, chan0, chan1;
+    tile_geometry g;
+    uint32_t chan0, chan1;
 };
 
 // One block: unpack, the target's conversion, the store. `out` is where the image's output begins, `i` the block's place in the image's raster order. RGBA32
-// writes the four rows of the tile cropped to width x min(height, rows), a row as one 16-byte word where it is whole and its address aligned; every other target
-// one uint2 / uint4 at out[i]. false = the block did not unpack and zeros were written. Both kernels below are this function behind their own indexing.
+// writes the four rows of the tile cropped to width x min(height, rows) (store_tile_row); every other target one uint2 / uint4 at out[i] (store_block_words).
+// false = the block did not unpack and zeros were written. Both kernels below are this function behind their own indexing.
 template <uint32_t TARGET, bool HQ>
-__device__ __forceinline__ bool transcode_uastc_block(const uint4 in, void* out, uint32_t i, uint32_t nbx, uint32_t width, uint32_t height, uint32_t pitch, uint32_t rows,
-                                                      uint32_t chan0, uint32_t chan1) {
+__device__ __forceinline__ bool transcode_uastc_block(const uint4 in, void* out, uint32_t i, const tile_geometry& g, uint32_t chan0, uint32_t chan1) {
     uint8_t blk[16];
     const uint32_t words[4] = { in.x, in.y, in.z, in.w };
     BU_UNROLL
@@ -33,20 +34,15 @@ __device__ __forceinline__ bool transcode_uastc_block(const uint4 in, void* out,
     if (TARGET == TF_RGBA32) {
         rgba8 px[16];
         ok = transcode_rgba32(blk, px);
-        const uint32_t bx = i % nbx, by = i / nbx;
+        const uint32_t bx = i % g.nbx, by = i / g.nbx;
         BU_UNROLL
         for (uint32_t y = 0; y < 4; y++) {
             const uint32_t row = by * 4 + y;
-            if (row >= height || row >= rows) break;
-            uint32_t* dst = (uint32_t*)out + (size_t)row * pitch + bx * 4;
+            if (row >= g.height || row >= g.rows) break;
             uint32_t v[4];
             BU_UNROLL
             for (uint32_t x = 0; x < 4; x++) v[x] = ok ? pack_px(px[y * 4 + x].c) : 0u;
-            if (bx * 4 + 4 <= width && (((uintptr_t)dst & 15u) == 0)) *(uint4*)dst = make_uint4(v[0], v[1], v[2], v[3]);
-            else {
-                BU_UNROLL
-                for (uint32_t x = 0; x < 4; x++) if (bx * 4 + x < width) dst[x] = v[x];
-            }
+            store_tile_row(4, (uint32_t*)out + (size_t)row * g.pitch + bx * 4, bx, g.width, v);
         }
     } else if (TARGET == TF_ASTC_4x4_RGBA || TARGET == TF_BC7_RGBA) {
         uint8_t o[16];
@@ -61,20 +57,19 @@ __device__ __forceinline__ bool transcode_uastc_block(const uint4 in, void* out,
         uint64_t w[2] = { 0, 0 };
         ok = transcode_bcn(blk, TARGET, HQ, chan0, chan1, w);
         if (!ok) w[0] = w[1] = 0;
-        if (TARGET == TF_BC1_RGB || TARGET == TF_BC4_R) ((uint2*)out)[i] = make_uint2((uint32_t)w[0], (uint32_t)(w[0] >> 32));
-        else ((uint4*)out)[i] = make_uint4((uint32_t)w[0], (uint32_t)(w[0] >> 32), (uint32_t)w[1], (uint32_t)(w[1] >> 32));
+        store_block_words(out, i, w, !(TARGET == TF_BC1_RGB || TARGET == TF_BC4_R));
     }
     return ok;
 }
 
 template <uint32_t TARGET, bool HQ>
 __global__ __launch_bounds__(256) void transcode_uastc_kernel(transcode_args a) {
-    const uint32_t n = a.nbx * a.nby, i = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t n = a.g.nbx * a.g.nby, i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    if (!transcode_uastc_block<TARGET, HQ>(a.blocks[i], a.out, i, a.nbx, a.width, a.height, a.pitch, a.rows, a.chan0, a.chan1)) atomicAdd(a.invalid, 1u);
+    if (!transcode_uastc_block<TARGET, HQ>(a.blocks[i], a.out, i, a.g, a.chan0, a.chan1)) atomicAdd(a.invalid, 1u);
 }
 
-// every image of a file in one launch (bu_hip_k_transcode_uastc_slices): the lookup of transcode_slices.h in front of the same block function
+// every image of a file in one launch (bu_hip_k_transcode_uastc_slices): find_transcode_slice (tile_raster.h) in front of the same block function
 struct transcode_slices_args {
     const uint4* blocks;
     uint8_t* out;
@@ -88,13 +83,12 @@ template <uint32_t TARGET, bool HQ>
 __global__ __launch_bounds__(256) void transcode_uastc_slices_kernel(transcode_slices_args a) {
     transcode_slice_view v;
     if (!find_transcode_slice(a.slices, a.prefix, a.n_slices, a.total_blocks, blockIdx.x * 256u + threadIdx.x, v)) return;
-    if (!transcode_uastc_block<TARGET, HQ>(a.blocks[v.first_block + v.local], a.out + v.out_offset, v.local, v.nbx, v.width, v.height, v.pitch, v.rows, a.chan0, a.chan1))
-        atomicAdd(a.invalid + v.slice, 1u);
+    if (!transcode_uastc_block<TARGET, HQ>(a.blocks[v.first_block + v.local], a.out + v.out_offset, v.local, v.g, a.chan0, a.chan1)) atomicAdd(a.invalid + v.slice, 1u);
 }
 
 template <uint32_t TARGET, bool HQ>
 static hipError_t launch(hipStream_t st, const transcode_args& a) {
-    const uint32_t n = a.nbx * a.nby;
+    const uint32_t n = a.g.nbx * a.g.nby;
     hipLaunchKernelGGL((transcode_uastc_kernel<TARGET, HQ>), dim3((n + 255) / 256), dim3(256), 0, st, a);
     return hipGetLastError();
 }
@@ -122,15 +116,15 @@ static hipError_t launch_for_target(hipStream_t st, const Args& a, uint32_t targ
 size_t transcode_output_bytes(uint32_t nbx, uint32_t nby, uint32_t width, uint32_t height, uint32_t target) {
     const uint32_t bpb = transcode_bytes_per_block(target);
     if (!bpb) return 0;
-    if (target == TF_RGBA32) return (size_t)(width ? width : nbx * 4) * (height ? height : nby * 4) * 4;
-    return (size_t)nbx * nby * bpb;
+    const bool pixels = target == TF_RGBA32;   // bpb is per block: 16 pixels of 4 bytes
+    return raster_output_bytes(tile_geometry{ nbx, nby, width, height, 0, 0 }, pixels ? 4 : bpb, pixels);
 }
 
-hipError_t launch_transcode_uastc(hipStream_t st, const void* d_blocks, uint32_t nbx, uint32_t nby, uint32_t width, uint32_t height, uint32_t target, bool high_quality,
-                                  uint32_t chan0, uint32_t chan1, void* d_out, uint32_t pitch, uint32_t rows, uint32_t* d_invalid) {
-    transcode_args a = { (const uint4*)d_blocks, d_out, d_invalid, nbx, nby, width, height, pitch, rows, chan0, chan1 };
+hipError_t launch_transcode_uastc(hipStream_t st, const void* d_blocks, const tile_geometry& g, uint32_t target, bool high_quality, uint32_t chan0, uint32_t chan1,
+                                  void* d_out, uint32_t* d_invalid) {
+    transcode_args a = { (const uint4*)d_blocks, d_out, d_invalid, g, chan0, chan1 };
     hipError_t e = hipMemsetAsync(d_invalid, 0, sizeof(uint32_t), st);
-    if (e != hipSuccess || !nbx || !nby) return e;
+    if (e != hipSuccess || !g.nbx || !g.nby) return e;
     return launch_for_target(st, a, target, high_quality);
 }
 

@@ -28,7 +28,7 @@ COMPILE = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", 
 #   "prebuilt"  never built by a test: oracle/Makefile makes it where the reference is, elsewhere it travels as a binary (and may be of an older revision)
 CHECKERS = {name: (NATIVE / f"lib{name}.so", NATIVE / f"{name}.cpp", "HOST_API", "g++")
             for name in ("uastc_host", "fsum_host", "tt_exact_host", "tsvq_node_host", "seam_translate_host", "block_metric_host", "transcode_host", "image_metrics_host",
-                         "psnr_hvs_host", "block_unpack_host")}
+                         "psnr_hvs_host", "block_unpack_host", "tile_geometry_host")}
 CHECKERS["oracle"] = (ORACLE / "liboracle_etc1s.so", ORACLE / "etc1s_oracle.h", "ORC_API", "make")
 CHECKERS["ref"] = (ORACLE / "_ref" / "libref_harness.so", ORACLE / "ref_harness.cpp", "REF_API", "prebuilt")
 
