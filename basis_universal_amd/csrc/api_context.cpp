@@ -427,6 +427,7 @@ int bu_hip_set_stream(bu_hip_context* ctx, void* s) {
 }
 void* bu_hip_get_stream(bu_hip_context* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 const char* bu_hip_last_error(const bu_hip_context* ctx) { return ctx ? ctx->error.c_str() : g_global_error.c_str(); }
+void bu_hip_set_last_error(bu_hip_context* ctx, const char* text) { set_error(ctx, "%s", text ? text : ""); }
 
 void bu_hip_get_tuning(const bu_hip_context* ctx, bu_hip_tuning* out, uint32_t struct_bytes) {
     if (!out || struct_bytes < 8) return;

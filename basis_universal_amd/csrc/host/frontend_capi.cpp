@@ -244,11 +244,25 @@ int bu_device_tsvq_mt(bu_hip_context* ctx, uint32_t dim, const float* rows, cons
     return 1;
 } BU_CATCH(0)
 
-// comp.cpp:3310-3379, float arithmetic in the reference's order
+// A refused resampling plan leaves "<call>: <reason>" for bu_hip_last_error (of the context, or the global text without one) and for bu_host_last_exception
+static int plan_refused(bu_hip_context* ctx, const char* call, const std::string& why) {
+    g_last_exception = std::string(call) + ": " + why;
+    bu_hip_set_last_error(ctx, g_last_exception.c_str());
+    return 0;
+}
+
 int bu_generate_mipmap_level(bu_hip_context* ctx, const void* d_src, uint32_t src_w, uint32_t src_h, void* d_dst, uint32_t dst_w, uint32_t dst_h, int srgb,
                              const char* filter, float filter_scale, int wrapping, uint32_t num_comps) try {
+    static const char* const fn = "bu_generate_mipmap_level";
     bu::mip::plan p;
-    if (!ctx || !filter || !bu::mip::make_plan(p, src_w, src_h, dst_w, dst_h, srgb != 0, filter, filter_scale, wrapping != 0)) return 0;
+    std::string why;
+    if (!filter) return plan_refused(ctx, fn, "null filter name");
+    if (!bu::mip::make_plan(p, src_w, src_h, dst_w, dst_h, srgb != 0, filter, filter_scale, wrapping != 0, &why)) return plan_refused(ctx, fn, why);
+    if (!ctx) return plan_refused(ctx, fn, "null context");
+    if (p.identity) {  // dst = src, all four channels whatever num_comps says; the component count is checked as for any other call
+        if (!d_src || !d_dst || num_comps < 3 || num_comps > 4) return plan_refused(ctx, fn, "bad arguments");
+        return bu_hip_memcpy_d2d(ctx, d_dst, d_src, (size_t)src_w * src_h * 4);
+    }
     return bu_hip_k_resample_rgba8(ctx, d_src, src_w, src_h, d_dst, dst_w, dst_h, p.x.first.data(), p.x.pixel.data(), p.x.weight.data(), p.y.first.data(), p.y.pixel.data(),
                                    p.y.weight.data(), p.x_after_y, srgb, p.srgb_to_linear, p.linear_to_srgb, num_comps);
 } BU_CATCH(0)
@@ -261,9 +275,12 @@ uint32_t bu_mipmap_level_sizes(uint32_t w, uint32_t h, uint32_t smallest_dimensi
 
 int bu_mipmap_plan(uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h, int srgb, const char* filter, float filter_scale, int wrapping, uint32_t* out_counts,
                    uint32_t* x_first, uint16_t* x_pixel, float* x_weight, uint32_t* y_first, uint16_t* y_pixel, float* y_weight, float* to_linear, uint8_t* to_srgb) try {
+    static const char* const fn = "bu_mipmap_plan";
     bu::mip::plan p;
-    if (!filter || !out_counts || !bu::mip::make_plan(p, src_w, src_h, dst_w, dst_h, srgb != 0, filter, filter_scale, wrapping != 0)) return 0;
-    out_counts[0] = p.x.ops(); out_counts[1] = p.y.ops(); out_counts[2] = p.x_after_y; out_counts[3] = 0;
+    std::string why;
+    if (!filter || !out_counts) return plan_refused(nullptr, fn, "null filter name or counts");
+    if (!bu::mip::make_plan(p, src_w, src_h, dst_w, dst_h, srgb != 0, filter, filter_scale, wrapping != 0, &why)) return plan_refused(nullptr, fn, why);
+    out_counts[0] = p.x.ops(); out_counts[1] = p.y.ops(); out_counts[2] = p.x_after_y; out_counts[3] = p.identity;
     auto copy = [](auto* dst, const auto& v) { if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
     copy(x_first, p.x.first); copy(x_pixel, p.x.pixel); copy(x_weight, p.x.weight); copy(y_first, p.y.first); copy(y_pixel, p.y.pixel); copy(y_weight, p.y.weight);
     if (to_linear) std::memcpy(to_linear, p.srgb_to_linear, sizeof(p.srgb_to_linear));

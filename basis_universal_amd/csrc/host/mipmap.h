@@ -117,13 +117,32 @@ inline bool make_contributors(contributors& out, int src_n, int dst_n, bool wrap
 struct plan {
     contributors x, y;
     bool x_after_y = false;            // Resampler's m_delay_x_resample: the cheaper order by its operation count (resampler.cpp:773-789)
-    float srgb_to_linear[256];
-    uint8_t linear_to_srgb[8192];
+    bool identity = false;             // equal sizes at filter scale 1: image_resample returns dst = src (basisu_enc.cpp:1053-1059), no filter runs, the lists are empty
+    float srgb_to_linear[256] = {};    // both tables stay zero in an identity plan
+    uint8_t linear_to_srgb[8192] = {};
 };
-inline bool make_plan(plan& p, uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h, bool srgb, const char* filter_name, float filter_scale, bool wrap) {
+const uint32_t kMaxDimension = 16384;  // BASISU_RESAMPLER_MAX_DIMENSION, both of the source and of the destination (basisu_enc.cpp:1035, 1047)
+// false: refused as image_resample refuses it, with the reason in `why` (when given)
+inline bool make_plan(plan& p, uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h, bool srgb, const char* filter_name, float filter_scale, bool wrap,
+                      std::string* why = nullptr) {
+    auto refuse = [&](const std::string& text) { if (why) *why = text; return false; };
+    auto size_text = [](const char* what, uint32_t w, uint32_t h) { return std::string(what) + " size " + std::to_string(w) + "x" + std::to_string(h) + " is outside 1..16384"; };
+    p.identity = false;
+    if (!src_w || !src_h || src_w > kMaxDimension || src_h > kMaxDimension) return refuse(size_text("source", src_w, src_h));
+    if (!dst_w || !dst_h || dst_w > kMaxDimension || dst_h > kMaxDimension) return refuse(size_text("destination", dst_w, dst_h));
+    if (src_w == dst_w && src_h == dst_h && filter_scale == 1.0f) {  // before the filter is looked up, as there
+        p.identity = true;
+        p.x_after_y = false;
+        for (contributors* c : {&p.x, &p.y}) { c->first.clear(); c->pixel.clear(); c->weight.clear(); }
+        return true;
+    }
     const filter* flt = find_filter(filter_name);
-    if (!flt || !src_w || !src_h || !dst_w || !dst_h || src_w > 16384 || src_h > 16384) return false;
-    if (!make_contributors(p.x, (int)src_w, (int)dst_w, wrap, *flt, filter_scale) || !make_contributors(p.y, (int)src_h, (int)dst_h, wrap, *flt, filter_scale)) return false;
+    if (!flt) return refuse(std::string("unknown filter \"") + filter_name + "\"");
+    auto axis_text = [&](const char* axis, uint32_t s, uint32_t d) {
+        return std::string("filter scale ") + std::to_string(filter_scale) + " leaves a destination sample without contributors along " + axis + " (" + std::to_string(s) + " -> " + std::to_string(d) + ")";
+    };
+    if (!make_contributors(p.x, (int)src_w, (int)dst_w, wrap, *flt, filter_scale)) return refuse(axis_text("x", src_w, dst_w));
+    if (!make_contributors(p.y, (int)src_h, (int)dst_h, wrap, *flt, filter_scale)) return refuse(axis_text("y", src_h, dst_h));
     const int x_ops = (int)p.x.ops(), y_ops = (int)p.y.ops();
     const int xy_ops = x_ops * (int)src_h + (4 * y_ops * (int)dst_w) / 3, yx_ops = (4 * y_ops * (int)src_w) / 3 + x_ops * (int)dst_h;
     p.x_after_y = (xy_ops > yx_ops) || (xy_ops == yx_ops && src_w < dst_w);

@@ -1,6 +1,6 @@
 """Mip generation on the device: basis_compressor::generate_mipmaps (encoder/basisu_comp.cpp:2146-2230) as a chain of
 bu_generate_mipmap_level calls -- contributor lists on the host exactly as the reference's Resampler builds them, pixels resampled by the HIP
-kernels of mipmap_kernels.hip. Byte-identical to image_resample."""
+kernels of mipmap_kernels.hip. Byte-identical to image_resample, its shortcut included: equal sizes at filter scale 1 copy the source, all four channels."""
 import ctypes as C
 
 import numpy as np

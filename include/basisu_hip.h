@@ -156,6 +156,9 @@ BU_HIP_API int  bu_hip_set_tuning(bu_hip_context*, const bu_hip_tuning* /* NULL:
 typedef void (*bu_hip_wait_fn)(void* user);
 BU_HIP_API int   bu_hip_set_wait_hook(bu_hip_context*, bu_hip_wait_fn fn, void* user);
 BU_HIP_API const char* bu_hip_last_error(const bu_hip_context*); /* NULL context -> last global (init) error */
+/* For the libraries layered on this one (libbasisu_frontend.so refuses a resampling plan on the host, before any call here): the text a failed call of theirs leaves
+ * for bu_hip_last_error, cut at 511 characters. NULL context -> the global text. */
+BU_HIP_API void bu_hip_set_last_error(bu_hip_context*, const char* text);
 
 /* Per-kernel timing with HIP events recorded on the launch stream around every section-2 kernel. enable(1) resets the totals and times every region; enable(2) only
  * the regions that are ONE kernel launch each (per-block and per-cluster kernels) -- the regions of many launches (codebook builders' rounds, de-duplication, list

@@ -139,12 +139,16 @@ BU_HIP_API void bu_etc1s_quality_to_clusters(int quality_level, uint32_t total_b
  *     wrapping, 0, num_comps) on a resident RGBA8 raster. The filter's contributor lists and tables are built here on the host exactly as
  *     Resampler does (basis_universal_amd/csrc/host/mipmap.h), the pixels are resampled by bu_hip_k_resample_rgba8. filter: "kaiser" (the
  *     compressor's default), "box", "tent", "bell", "mitchell", "catmullrom", "blackman", "lanczos3|4|6|12". The compressor's defaults:
- *     srgb 1, scale 1, wrapping 1, and each level made from the previous one (m_mip_fast) down to 1x1. */
+ *     srgb 1, scale 1, wrapping 1, and each level made from the previous one (m_mip_fast) down to 1x1.
+ *     Equal sizes at filter scale 1 copy the source raster, all four channels, whatever filter and num_comps say (basisu_enc.cpp:1053-1059): stream-ordered, no wait.
+ *     Refused (0, "bu_generate_mipmap_level: <reason>" in bu_hip_last_error, nothing launched): an unknown filter, a source or destination size outside 1..16384, a
+ *     filter scale that leaves a destination sample without contributors; num_comps other than 3 or 4. */
 BU_HIP_API int bu_generate_mipmap_level(bu_hip_context* ctx, const void* d_src, uint32_t src_w, uint32_t src_h, void* d_dst, uint32_t dst_w, uint32_t dst_h,
                                         int srgb, const char* filter, float filter_scale, int wrapping, uint32_t num_comps);
 /* The sizes of the levels below w x h (comp.cpp:2153-2160): writes up to cap (w, h) pairs, returns the count. */
 BU_HIP_API uint32_t bu_mipmap_level_sizes(uint32_t w, uint32_t h, uint32_t smallest_dimension, uint32_t* out_wh, uint32_t cap);
-/* Test hook: the plan of one resampling step as flat arrays (counts via out_counts[4] = {x taps, y taps, x_after_y, 0}); buffers may be NULL. */
+/* Test hook: the plan of one resampling step as flat arrays (counts via out_counts[4] = {x taps, y taps, x_after_y, identity}); buffers may be NULL. identity = 1: the
+ * step is a copy and both lists are empty. 0 = refused, "bu_mipmap_plan: <reason>" in bu_hip_last_error(NULL). */
 BU_HIP_API int bu_mipmap_plan(uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h, int srgb, const char* filter, float filter_scale, int wrapping,
                               uint32_t* out_counts, uint32_t* x_first, uint16_t* x_pixel, float* x_weight, uint32_t* y_first, uint16_t* y_pixel, float* y_weight,
                               float* srgb_to_linear_256, uint8_t* linear_to_srgb_8192);

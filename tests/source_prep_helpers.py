@@ -111,7 +111,17 @@ def case_list():
     add("combo_no_alpha_uastc_basis", "alpha", (20, 28), True, "basis", ["-no_alpha"])
     add("combo_force_alpha_uastc_basis", "opaque", (20, 28), True, "basis", ["-force_alpha", "-y_flip"])
     add("combo_force_and_no_alpha", "alpha", (21, 13), False, "basis", ["-no_alpha", "-force_alpha"])
+    # -resample where it does not shrink both axes: above the source size, one axis up and one down, the source's own size (image_resample's shortcut: a copy), a
+    # factor above 1 -- the resampler's y-first pass order and its magnification lists. After everything above, so that the seeds of the older cases stay.
+    for name, flags in _RESAMPLE_UPWARDS:
+        for uastc, source in ((False, "alpha"), (True, "opaque")):
+            for ext in ("basis", "ktx2"):
+                add(f"{'uastc' if uastc else 'etc1s'}_{name}_{ext}", source, (21, 13), uastc, ext, flags)
     return out
+
+
+_RESAMPLE_UPWARDS = [("resample_up", ["-resample", "40", "30"]), ("resample_mixed", ["-resample", "30", "9"]), ("resample_same", ["-resample", "21", "13"]),
+                     ("resample_factor_up", ["-resample_factor", "1.7"])]
 
 
 # flag -> (how many values follow it, what it sets). THE table: the generator passes the flags to the tool, the tests pass what this gives to compress().

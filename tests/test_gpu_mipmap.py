@@ -37,6 +37,98 @@ def test_mip_chain_matches_reference(hip_ctx, w, h, alpha):
         assert (g == e).all(), (level, np.argwhere(g != e)[:5])
 
 
+GUARD = 0xA5
+
+
+def _resample_between_guards(ctx, src, case):
+    """bu_generate_mipmap_level into the middle of a buffer filled with GUARD, more than a destination row of it in front and behind -> (the raster, the guards intact)"""
+    from basis_universal_amd import mipmap
+    sw, sh, dw, dh, srgb, flt, scale, wrap, comps = case
+    lead, tail = dw + 3, dw + 5
+    fill = np.full((lead + dw * dh + tail, 4), GUARD, np.uint8)
+    d_src, d_buf = ctx.upload(src), ctx.upload(fill)
+    try:
+        ctx.check(mipmap._lib().bu_generate_mipmap_level(ctx.h, d_src, sw, sh, d_buf + 4 * lead, dw, dh, int(srgb), flt.encode(), scale, int(wrap), comps), "bu_generate_mipmap_level")
+        out = ctx.download(d_buf, fill.shape, np.uint8)
+    finally:
+        ctx.free(d_src); ctx.free(d_buf)
+    return out[lead:lead + dw * dh].reshape(dh, dw, 4), bool((out[:lead] == GUARD).all() and (out[lead + dw * dh:] == GUARD).all())
+
+
+def _wide_and_magnify():
+    from test_mipmap_host import WIDE_AND_MAGNIFY
+    return WIDE_AND_MAGNIFY
+
+
+@pytest.mark.parametrize("case", _wide_and_magnify(), ids=lambda c: "-".join(str(v) for v in c))
+def test_resample_matches_the_committed_reference_bytes(hip_ctx, case):
+    """the y-first kernels past one workgroup along x, magnification, lists of thousands of taps and the identity copy against tests/golden/resample_vectors.npz (what
+    ref_image_resample wrote: needs no oracle/_ref), through mipmap.resample and, between guards, through the C entry point"""
+    from basis_universal_amd import mipmap
+    from test_mipmap_host import golden, rgba, seeds_of
+    sw, sh, dw, dh, srgb, flt, scale, wrap, comps = case
+    for seed, noise in seeds_of(case):
+        src, exp = rgba(sw, sh, seed, noise), golden()[case, seed]
+        got = mipmap.resample(hip_ctx, src, dw, dh, srgb, flt, scale, wrap, comps)
+        assert got.shape == exp.shape and (got == exp).all(), (seed, np.argwhere(got != exp)[:5])
+        raster, guards_intact = _resample_between_guards(hip_ctx, src, case)
+        assert (raster == exp).all(), (seed, np.argwhere(raster != exp)[:5])
+        assert guards_intact, seed
+
+
+def test_resample_scratch_is_reused_across_sizes():
+    """the packed lists and the float4 intermediate live in two arenas of the context that grow and are never cleared: the largest case, the smallest, the largest again,
+    on a context of their own"""
+    from basis_universal_amd import capi, mipmap
+    from test_mipmap_host import SEEDS, golden, rgba
+    cases = _wide_and_magnify()
+    largest = max(cases, key=lambda c: max(c[2] * c[1], c[0] * c[3]))   # the intermediate's pixels, as the launcher sizes it
+    smallest = (1, 1, 5, 3, True, "box", 1.0, False, 4)
+    assert smallest in cases and largest != smallest
+    ctx = capi.Context()
+    try:
+        for case in (largest, smallest, largest):
+            sw, sh, dw, dh, srgb, flt, scale, wrap, comps = case
+            for seed, noise in SEEDS:
+                got = mipmap.resample(ctx, rgba(sw, sh, seed, noise), dw, dh, srgb, flt, scale, wrap, comps)
+                assert (got == golden()[case, seed]).all(), (case, seed)
+    finally:
+        ctx.close()
+
+
+def test_mip_slow_chain_matches_the_emulation_from_level_0(hip_ctx):
+    """-mip_slow: every level of 260x9 is made from level 0 (lists up to 260 x 6 taps long, y first for the upper levels), and has to equal the float32 emulation of the
+    plan applied to level 0 -- and, where oracle/_ref is there, image_resample applied to level 0. test_backend_host._ref_mip_chain offers no slow mode (it makes each
+    level from the one before), so it is not what this chain is compared with."""
+    from basis_universal_amd import mipmap
+    from test_mipmap_host import emulate, plan, reference, rgba
+    img = rgba(260, 9, 2, True)
+    sizes = mipmap.level_sizes(260, 9)
+    assert sizes == [(130, 4), (65, 2), (32, 1), (16, 1), (8, 1), (4, 1), (2, 1), (1, 1)]
+    got = mipmap.generate_mipmaps(hip_ctx, img, has_alpha=True, fast=False)
+    assert [g.shape for g in got] == [(lh, lw, 4) for lw, lh in sizes]
+    for level, (g, (lw, lh)) in enumerate(zip(got, sizes), 1):
+        exp = emulate(img, lw, lh, plan(260, 9, lw, lh, True, "kaiser", 1.0, True), True, 4)
+        assert (g == exp).all(), (level, np.argwhere(g != exp)[:5])
+        if have_ref():
+            assert (g == reference(img, lw, lh, True, "kaiser", 1.0, True, 4)).all(), level
+
+
+def test_a_refused_resample_raises_with_the_reason(hip_ctx):
+    """the text is this call's, not what an earlier failure left in the context; an unknown filter is not looked at where the sizes are equal at scale 1 (a copy)"""
+    from basis_universal_amd import capi, mipmap
+    from test_mipmap_host import REFUSED, rgba
+    src = rgba(8, 2, 1)
+    with pytest.raises(capi.HipError, match='bu_generate_mipmap_level: unknown filter "gauss"'):
+        mipmap.resample(hip_ctx, src, 4, 1, filter="gauss")
+    with pytest.raises(capi.HipError, match="bu_generate_mipmap_level: destination size 16385x2 is outside 1..16384"):
+        mipmap.resample(hip_ctx, src, 16385, 2, filter="box")
+    sw, sh, dw, dh, srgb, flt, scale, wrap, comps = REFUSED
+    with pytest.raises(capi.HipError, match="bu_generate_mipmap_level: filter scale .* without contributors"):
+        mipmap.resample(hip_ctx, rgba(sw, sh, 1), dw, dh, srgb, flt, scale, wrap, comps)
+    assert (mipmap.resample(hip_ctx, src, 8, 2, filter="gauss", num_comps=3) == src).all()
+
+
 @pytest.mark.skipif(not have_ref_cli(), reason="oracle/_ref/basisu not present")
 @pytest.mark.parametrize("w,h,alpha", [(256, 192, False), (100, 60, True)])
 def test_mipmapped_encode_matches_reference_command_line(hip_ctx, tmp_path, w, h, alpha):

@@ -97,6 +97,12 @@ if __name__ == "__main__":
         meta["cases"].append(dict(case, slices=len(rasters), sizes=sizes, has_alpha=has_alpha))
         print(case["name"], data.size, "bytes,", len(rasters), "slices", sizes, "has alpha", has_alpha, flush=True)
     arrays["meta"] = np.frombuffer(json.dumps(meta, sort_keys=True).encode(), np.uint8)
+    if H.GOLDEN.exists():   # cases are only ever added: what the committed file holds comes out as it is, before anything is overwritten
+        committed, committed_meta = H.native_libs.load_npz_golden(H.GOLDEN)
+        for key, value in committed.items():
+            assert key == "meta" or (key in arrays and arrays[key].shape == value.shape and (arrays[key] == value).all()), f"{key}: not what the committed fixture holds"
+        assert json.loads(json.dumps(meta["cases"]))[:len(committed_meta["cases"])] == committed_meta["cases"], "a committed case's description changed"
+        print("all", len(committed) - 1, "committed members and", len(committed_meta["cases"]), "committed cases unchanged")
     S.save(H.GOLDEN, arrays)
     assert H.GOLDEN.stat().st_size <= 1 << 20, H.GOLDEN.stat().st_size
     print("wrote", H.GOLDEN, H.GOLDEN.stat().st_size, "bytes,", len(arrays), "members")
