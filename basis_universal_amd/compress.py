@@ -1,7 +1,7 @@
 """One call from an image to a file: the C-style entry of the reference (`basis_compress`, encoder/basisu_comp.cpp:5561-5900 ->
 basis_compressor::process, comp.cpp:619-1040) for the two hot paths of this package, every stage in its MI355X-native form:
 
-    raster in HBM -> source-image options (source_prep_kernels.hip; source.py) -> mip levels (mipmap_kernels.hip) -> 4x4 tiles of every slice in one launch (bu_hip_k_extract_slices)
+    raster in HBM -> source-image options (source_prep_kernels.hip; source.py) -> mip levels (mipmap_kernels.hip; the caller's own or a .dds file's: mip_levels_kernels.hip) -> 4x4 tiles of every slice in one launch (bu_hip_k_extract_slices)
       ETC1S : resident frontend (etc1s.Etc1sFrontend) -> host backend (backend.Etc1sBackend) -> .basis / .ktx2
       UASTC : encode_uastc kernels (-> uastc_rdo kernels) -> .basis / .ktx2 (KTX2_SS_NONE: what the reference's library default,
               comp.h:323, and `basisu -ktx2_no_zstandard` write; Zstandard supercompression of the levels is not part of this package)
@@ -52,7 +52,7 @@ def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=
              ktx2=False, srgb=True, key_values=(), max_threads=0, stats=None, stats_hvs=False, stats_bc7=False, stats_ssim=False,
              renormalize=False, swizzle=None, check_for_alpha=True, force_alpha=False, y_flip=False, resample=None,
              mip_filter="kaiser", mip_scale=1.0, mip_wrapping=True, mip_srgb=None, mip_renormalize=False, mip_fast=True, mip_smallest_dimension=1,
-             no_selector_rdo=False, no_endpoint_rdo=False, tex_type="2d", us_per_frame=0, userdata=(0, 0), ktx2_animdata=(1, 15, 0)):
+             no_selector_rdo=False, no_endpoint_rdo=False, tex_type="2d", us_per_frame=0, userdata=(0, 0), ktx2_animdata=(1, 15, 0), mip_levels=None):
     """image: (h, w, 4) uint8 RGBA, or a sequence of such arrays (below). Returns the file as a uint8 array.
     ETC1S: quality 1-255 (`-q`), comp_level 0-6 (`-comp_level`). UASTC: uastc_level 0-4, uastc_rdo_lambda (`-uastc_rdo_l`; None = no post-pass, any float
     incl. 0.0 = post-pass on, as m_rdo_uastc_ldr_4x4 + its scalar), uastc_rdo_jobs = the strips of the post-pass (the reference: min(4, pool threads) when
@@ -93,23 +93,52 @@ def compress(ctx, image, *, uastc=False, quality=128, comp_level=1, uastc_level=
       stats: one dict per slice in slice order; ETC1S video with stats raises ValueError before any work (the ETC1S reader does not read video files).
       ValueError before ctx is touched: several images with tex_type "2d", a cubemap whose image count is not a multiple of 6, images of different sizes (after
       `resample`) in anything but "2d", more slices than BASISU_MAX_SLICES, an empty sequence.
-    A single array is a sequence of one: the same stages, the same launches, the same bytes."""
+    A single array is a sequence of one: the same stages, the same launches, the same bytes.
+    mip_levels: the levels below level 0 as the caller made them (basis_compressor_params::m_source_mipmap_images, comp.cpp:2737-2818) -- for a bare image a sequence
+      of (h, w, 4) uint8 arrays, levels 1..n; for a sequence of images one such sequence per image. Level k is max(1, w >> k) x max(1, h >> k) pixels; a chain may stop
+      early. None, an empty sequence or empty sequences throughout: the call is what it is without the argument, and nothing new is launched. Supplied levels win over
+      `mipmaps` (the reference generates only where none are given, comp.cpp:2849), and of the source options only `swizzle` touches them (comp.cpp:2796-2817):
+      renormalize, y_flip and the alpha policy are level 0's. All levels of all images go up as one payload and become rasters in ONE launch (source.resident_levels).
+      has_alpha is level 0's answer OR any supplied level with an alpha value that is not 255 after the swizzle (comp.cpp:2746-2766) -- so with check_for_alpha=False,
+      which clears level 0 only, alpha in a lower level still gives an ETC1S file alpha slices for every level; a UASTC slice carries its own level's flag. `stats`
+      compares level k with the supplied level k.
+      ValueError before ctx is touched: a level of another size, more levels than the full chain, chains of unequal length, a flat sequence where one per image is
+      needed or the reverse, a level that is not an (h, w, 4) uint8 array, `resample` together with mip_levels, too many slices.
+    dds.compress_dds gives the same for .dds sources (image is then a source.DdsSources and mip_levels must stay None)."""
     if stats_bc7 and not uastc:
         from .stats import BC7_REFUSAL
         raise ValueError(BC7_REFUSAL)
-    bare = not (isinstance(image, (list, tuple)) and (not len(image) or np.ndim(image[0]) == 3) or (isinstance(image, np.ndarray) and image.ndim == 4))
+    dds = image if isinstance(image, _source.DdsSources) else None
+    if dds is not None:
+        if mip_levels is not None:
+            raise ValueError("mip_levels with .dds sources: the levels below level 0 are the file's")
+        bare, (images, levels) = dds.bare, dds.arrays()
+    else:
+        bare = not (isinstance(image, (list, tuple)) and (not len(image) or np.ndim(image[0]) == 3) or (isinstance(image, np.ndarray) and image.ndim == 4))
+        images = [image] if bare else list(image)
+        levels = _mip_level_arrays(mip_levels, len(images), bare)
     prepare_options = dict(renormalize=renormalize, swizzle=swizzle, check_for_alpha=check_for_alpha, force_alpha=force_alpha, y_flip=y_flip)
     imgs, level_sizes, type_index, host_alpha, key_values = _checked(
-        [image] if bare else list(image), bare, prepare_options, uastc=uastc, mipmaps=mipmaps, ktx2=ktx2, key_values=key_values, stats=stats, resample=resample,
+        images, bare, prepare_options, uastc=uastc, mipmaps=mipmaps, ktx2=ktx2, key_values=key_values, stats=stats, resample=resample,
         mip_filter=mip_filter, mip_scale=mip_scale, mip_smallest_dimension=mip_smallest_dimension, tex_type=tex_type, us_per_frame=us_per_frame, userdata=userdata,
-        ktx2_animdata=ktx2_animdata)
+        ktx2_animdata=ktx2_animdata, mip_levels=levels, host_alpha=dds is None)
     owned = []
     try:
-        level0, image_alpha, has_alpha = _resident_level0(ctx, owned, imgs, level_sizes, host_alpha, prepare_options, resample=resample, srgb=srgb)
+        if dds is not None:
+            level0, image_alpha, has_alpha, lower, level_alpha = _resident_dds(ctx, owned, dds, level_sizes, prepare_options, resample=resample, srgb=srgb)
+        else:
+            level0, image_alpha, has_alpha = _resident_level0(ctx, owned, imgs, level_sizes, host_alpha, prepare_options, resample=resample, srgb=srgb)
+            lower, level_alpha = _resident_supplied_levels(ctx, owned, levels, swizzle) if levels is not None else (None, None)
+        if lower is not None:   # comp.cpp:2746-2766: any supplied level with alpha gives the file alpha; a UASTC slice is marked by its own pixels (comp.cpp:2932)
+            has_alpha = has_alpha or any(any(flags) for flags in level_alpha)
+            image_alpha = [[own, *flags] for own, flags in zip(image_alpha, level_alpha)]
         _source.check_slice_count(len(imgs), len(level_sizes[0]), has_alpha and not uastc)
-        # each image's own chain (generate_mipmaps with m_any_source_image_has_alpha: four components for every image when any has alpha)
-        rasters = [mipmap.resident_chain(ctx, owned, d, sizes, srgb=srgb if mip_srgb is None else mip_srgb, filter=mip_filter, filter_scale=mip_scale, wrapping=mip_wrapping,
-                                         num_comps=4 if has_alpha else 3, fast=mip_fast, renormalize=mip_renormalize) for d, sizes in zip(level0, level_sizes)]
+        if lower is not None:
+            rasters = [[d, *below] for d, below in zip(level0, lower)]
+        else:
+            # each image's own chain (generate_mipmaps with m_any_source_image_has_alpha: four components for every image when any has alpha)
+            rasters = [mipmap.resident_chain(ctx, owned, d, sizes, srgb=srgb if mip_srgb is None else mip_srgb, filter=mip_filter, filter_scale=mip_scale, wrapping=mip_wrapping,
+                                             num_comps=4 if has_alpha else 3, fast=mip_fast, renormalize=mip_renormalize) for d, sizes in zip(level0, level_sizes)]
         d_all, slices, planes = _tiles(ctx, owned, rasters, level_sizes, tex_type=tex_type, uastc=uastc, has_alpha=has_alpha, image_alpha=image_alpha,
                                        video=tex_type == "video", with_planes=stats is not None)
         data = _encode(ctx, owned, d_all, slices, has_alpha, uastc=uastc, quality=quality, comp_level=comp_level, uastc_level=uastc_level, uastc_rdo_lambda=uastc_rdo_lambda,
@@ -129,10 +158,40 @@ VIDEO_STATS_REFUSAL = ("stats of an ETC1S video file: video files are not suppor
                        "does not keep (csrc/host/etc1s_decode.cpp)")
 
 
+def _mip_level_arrays(mip_levels, n_images, bare):
+    """compress()'s mip_levels -> per image the list of its levels as (h, w, 4) uint8 arrays, or None where there are none (None, empty, or empty for every image).
+    ValueError for a flat sequence where one per image is needed or the reverse, a count that is not the images', and for what is no (h, w, 4) uint8 array."""
+    if mip_levels is None or not len(mip_levels):
+        return None
+
+    def is_level(x):
+        return isinstance(x, np.ndarray) and x.ndim <= 3
+
+    if bare:
+        if not all(is_level(x) for x in mip_levels):
+            raise ValueError("mip_levels of a single image is a flat sequence of (h, w, 4) uint8 arrays, levels 1..n; a sequence per image goes with a sequence of images")
+        chains = [list(mip_levels)]
+    else:
+        if any(is_level(x) for x in mip_levels):
+            raise ValueError("mip_levels of a sequence of images is one sequence of levels per image (nested), not a flat sequence of arrays")
+        if len(mip_levels) != n_images:
+            raise ValueError(f"mip_levels holds the levels of {len(mip_levels)} images, and there are {n_images} images")
+        chains = [list(chain) for chain in mip_levels]
+    for k, chain in enumerate(chains):
+        for i, level in enumerate(chain, 1):
+            if not isinstance(level, np.ndarray) or level.dtype != np.uint8 or level.ndim != 3 or level.shape[2] != 4:
+                what = f"{level.dtype} {level.shape}" if isinstance(level, np.ndarray) else type(level).__name__
+                raise ValueError(f"mip level {i}{'' if bare else f' of image {k}'} must be an (h, w, 4) uint8 array, not {what}")
+    if not any(chains):
+        return None
+    return [[np.ascontiguousarray(level) for level in chain] for chain in chains]
+
+
 def _checked(images, bare, prepare_options, *, uastc, mipmaps, ktx2, key_values, stats, resample, mip_filter, mip_scale, mip_smallest_dimension, tex_type, us_per_frame,
-             userdata, ktx2_animdata):
+             userdata, ktx2_animdata, mip_levels=None, host_alpha=True):
     """Everything that can be refused, before ctx is touched. -> the images as uint8 arrays, per image the (width, height) of its levels (level 0: after `resample`), the
-    basis_texture_type number, per image image::has_alpha decided on the host (None where the prepare kernel decides it), and key_values with a video .ktx2's KTXanimData."""
+    basis_texture_type number, per image image::has_alpha decided on the host (None where the prepare kernel decides it, or without `host_alpha`), and key_values with a
+    video .ktx2's KTXanimData. mip_levels: None, or per image its supplied levels as arrays (_mip_level_arrays): their sizes are then the levels' sizes."""
     imgs = []
     for k, image in enumerate(images):
         name = "image" if bare else f"image {k}"
@@ -152,8 +211,19 @@ def _checked(images, bare, prepare_options, *, uastc, mipmaps, ktx2, key_values,
         raise ValueError(VIDEO_STATS_REFUSAL)
     if len(tuple(userdata)) != 2 or len(tuple(ktx2_animdata)) != 3 or any(not 0 <= int(v) < 2 ** 32 for v in (*userdata, *ktx2_animdata, us_per_frame)):
         raise ValueError("userdata is two, ktx2_animdata three and us_per_frame one unsigned 32-bit value")
-    level_sizes = [[size] + (mipmap.level_sizes(size[0], size[1], int(mip_smallest_dimension)) if mipmaps else []) for size in sizes]
-    host_alpha = [bool((img[..., 3] != 255).any()) for img in imgs] if not prepare else None      # image::has_alpha of an image that is not prepared
+    if mip_levels is not None:
+        if resample is not None:
+            raise ValueError("resample together with mip_levels: the supplied levels are halvings of the source's size and the reference resamples level 0 only "
+                             "(its file would hold levels that do not follow from level 0); resample the levels yourself, or let compress() generate them")
+        if any(len(chain) != len(mip_levels[0]) for chain in mip_levels):
+            raise ValueError(f"the images' mip chains are of unequal length ({', '.join(str(len(chain)) for chain in mip_levels)} levels): every image of a file "
+                             "has the same levels")
+        for k, (size, chain) in enumerate(zip(sizes, mip_levels)):
+            _source.check_supplied_levels("image" if bare else f"image {k}", size[0], size[1], [(level.shape[1], level.shape[0]) for level in chain])
+        level_sizes = [[size] + [(level.shape[1], level.shape[0]) for level in chain] for size, chain in zip(sizes, mip_levels)]
+    else:
+        level_sizes = [[size] + (mipmap.level_sizes(size[0], size[1], int(mip_smallest_dimension)) if mipmaps else []) for size in sizes]
+    host_alpha = [bool((img[..., 3] != 255).any()) for img in imgs] if not prepare and host_alpha else None      # image::has_alpha of an image that is not prepared
     # the alpha slices double the count; where only the device can say whether there are any (the prepare kernel's flag), the count is checked again once it has
     alpha_known = bool(prepare_options["force_alpha"]) or (host_alpha is not None and any(host_alpha))
     _source.check_slice_count(len(imgs), len(level_sizes[0]), not uastc and alpha_known)
@@ -167,22 +237,58 @@ def _resident_level0(ctx, owned, imgs, level_sizes, host_alpha, prepare_options,
     level0, image_alpha, has_alpha = [], [], False
     for k, img in enumerate(imgs):
         h, w = img.shape[:2]
-        d_level0 = d_src = ctx.upload(img)
+        d_src = ctx.upload(img)
         owned.append(d_src)
-        if host_alpha is None:
-            if prepare_options["y_flip"]:                                 # the flip reads another row than it writes: not in place
-                d_level0 = ctx.alloc(w * h * 4)
-                owned.append(d_level0)
-            one_has, one_any = _source.prepare_resident(ctx, d_src, w, h, d_level0, **prepare_options)
-        else:
-            one_has = one_any = host_alpha[k]
-        if resample is not None:   # has_alpha is decided before the resample, as the reference decides it
-            d_level0 = _source.resample_resident(ctx, d_level0, w, h, *level_sizes[k][0], srgb)
-            owned.append(d_level0)
+        d_level0, one_has, one_any = _prepared(ctx, owned, d_src, w, h, None if host_alpha is None else host_alpha[k], prepare_options, resample=resample,
+                                               new_size=level_sizes[k][0], srgb=srgb)
         level0.append(d_level0)
         image_alpha.append(one_any)
         has_alpha = has_alpha or one_has
     return level0, image_alpha, has_alpha
+
+
+def _prepared(ctx, owned, d_src, w, h, alpha, prepare_options, *, resample, new_size, srgb):
+    """One resident source image (ours: prepared in place) -> (its level-0 raster, has_alpha, any prepared alpha below 255). alpha: image::has_alpha of an image that
+    needs no preparing, None where the prepare kernel runs and decides it."""
+    d_level0 = d_src
+    if alpha is None:
+        if prepare_options["y_flip"]:                                 # the flip reads another row than it writes: not in place
+            d_level0 = ctx.alloc(w * h * 4)
+            owned.append(d_level0)
+        one_has, one_any = _source.prepare_resident(ctx, d_src, w, h, d_level0, **prepare_options)
+    else:
+        one_has = one_any = alpha
+    if resample is not None:   # has_alpha is decided before the resample, as the reference decides it
+        d_level0 = _source.resample_resident(ctx, d_level0, w, h, *new_size, srgb)
+        owned.append(d_level0)
+    return d_level0, one_has, one_any
+
+
+def _resident_supplied_levels(ctx, owned, levels, swizzle):
+    """The supplied levels of every image as one payload, one launch -> (per image its level rasters, per image the levels' alpha flags)"""
+    parts = [level.reshape(-1) for chain in levels for level in chain]
+    selector = _source.level_selector("rgba", swizzle)
+    rasters, flags = _source.resident_levels(ctx, owned, parts, [(i, 0, level.shape[1], level.shape[0], selector) for i, level in enumerate(lv for chain in levels for lv in chain)])
+    n = len(levels[0])
+    return [rasters[k * n:(k + 1) * n] for k in range(len(levels))], [flags[k * n:(k + 1) * n] for k in range(len(levels))]
+
+
+def _resident_dds(ctx, owned, dds, level_sizes, prepare_options, *, resample, srgb):
+    """.dds sources: every file's payload uploaded once and ONE launch for level 0's byte order and the lower levels; level 0 then goes through the source options as an
+    image does. -> (level-0 rasters, per image any alpha below 255, has_alpha, per image the lower levels' rasters or None, their flags or None)"""
+    identity = _source.is_identity(**prepare_options)
+    level0, image_alpha, has_alpha, lower, level_alpha = [], [], False, [], []
+    for k, ((rasters, flags), f) in enumerate(zip(dds.resident(ctx, owned, prepare_options["swizzle"]), dds.files)):
+        d_level0, one_has, one_any = _prepared(ctx, owned, rasters[0], f["width"], f["height"], flags[0] if identity else None, prepare_options, resample=resample,
+                                               new_size=level_sizes[k][0], srgb=srgb)
+        level0.append(d_level0)
+        image_alpha.append(one_any)
+        has_alpha = has_alpha or one_has
+        lower.append(rasters[1:])
+        level_alpha.append(flags[1:])
+    if not any(lower):
+        lower = level_alpha = None
+    return level0, image_alpha, has_alpha, lower, level_alpha
 
 
 def _tiles(ctx, owned, rasters, level_sizes, *, tex_type, uastc, has_alpha, image_alpha, video, with_planes):

@@ -7,6 +7,10 @@ encoder/basisu_dds_export.cpp) -- with mips, arrays and cubemaps, BC1-BC5 or one
 `fmt` is the tool's `-dds_format` token. The block encoders are the reference's (basist::encode_bc1 with cEncodeBC1HighQuality, basist::encode_bc4), restated
 for the device in csrc/uastc_core.h / uastc_transcode.h; the raw formats truncate to their bits. BC7 is refused: neither of the reference's two BC7 packers is
 implemented here. There is no CPU implementation: without the HIP library and a GPU `export_dds` and `pack_dds_blocks` raise. `dds_header` and `read_dds` are host code.
+
+The other direction, .dds files as SOURCES of the compressor (the tool's `.dds` input files, comp.cpp:2310-2439): `read_dds_source` (host code) reads a 2D texture of
+32-bit RGBA or BGRA pixels with its mip chain, and `compress_dds` hands level 0 and the file's own lower levels to compress()'s pipeline -- each file's payload
+uploaded once, one launch of mip_levels_kernels.hip for all levels.
 """
 import ctypes as C
 import struct
@@ -191,6 +195,96 @@ def pack_dds_pixels(ctx, tiles, sizes, fmt, *, out_device=None):
     finally:
         if own:
             ctx.free(own)
+
+
+LEGACY_HEADER_BYTES = 128   # "DDS ", DDS_HEADER (124)
+_DDPF_ALPHA, _DDPF_RGB, _DDSCAPS2_CUBEMAP, _DDSCAPS2_VOLUME, _TEXTURE3D = 0x2, 0x40, 0x200, 0x200000, 4
+_SOURCE_DXGI = {28: ("rgba", False), 29: ("rgba", True), 87: ("bgra", False), 91: ("bgra", True)}   # R8G8B8A8_UNORM / _SRGB, B8G8R8A8_UNORM / _SRGB
+_SOURCE_MASKS = {(0x000000FF, 0x0000FF00, 0x00FF0000, 0xFF000000): "rgba",     # D3DFMT_A8B8G8R8
+                 (0x00FF0000, 0x0000FF00, 0x000000FF, 0xFF000000): "bgra"}     # D3DFMT_A8R8G8B8
+_DXGI_KINDS = [("a block-compressed format", (*range(70, 85), *range(94, 100))), ("a float format", (2, 6, 10, 16, 34, 41, 54)),
+               ("a 16-bit format", (*range(11, 15), *range(35, 39), *range(56, 60), 85, 86, 115))]
+_FOURCC_KINDS = [("a block-compressed format", tuple(int.from_bytes(t, "little") for t in (b"DXT1", b"DXT2", b"DXT3", b"DXT4", b"DXT5", b"ATI1", b"ATI2", b"BC4U", b"BC4S",
+                                                                                           b"BC5U", b"BC5S"))),
+                 ("a float format", (111, 112, 113, 114, 115, 116)), ("a 16-bit format", (34, 36, 110))]
+
+
+def _kind(code, kinds):
+    return next((kind for kind, codes in kinds if code in codes), None)
+
+
+def read_dds_source(data):
+    """A .dds file as a SOURCE of compress_dds: what the reference tool reads as one (read_uncompressed_dds_file, encoder/basisu_gpu_texture.cpp:2025-2210, through
+    tinydds) for the LDR compressor -- a 2D texture of 32-bit RGBA or BGRA pixels with its mip chain: a DX10 header with DXGI format 28, 29 (R8G8B8A8 UNORM / SRGB),
+    87 or 91 (B8G8R8A8 UNORM / SRGB), or a legacy header whose bit masks are those of A8B8G8R8 or A8R8G8B8. The chain may stop early; a mip count of 0 is one level and a
+    count past the full chain is cut to it, as the tool's reader does. Bytes behind the last level are ignored.
+    -> {"width", "height", "byte_order" ("rgba" | "bgra"), "srgb", "dx10", "levels": per level {"level", "width", "height", "offset" (into "payload"), "nbytes"},
+        "payload": the levels' bytes, a uint8 view of `data`}. Every size is checked against the buffer before anything is listed.
+    ValueError, naming the reason: a truncated file; texture arrays, cubemaps, volumes and 1D textures (a height of 1 is one to the tool); block-compressed, 16-bit and
+    float formats (HDR .dds sources belong to codecs this package does not have) and every other pixel format; a size outside 1..16384."""
+    raw = np.frombuffer(data.tobytes() if isinstance(data, np.ndarray) else bytes(data), np.uint8)
+    if raw.size < LEGACY_HEADER_BYTES:
+        raise ValueError(f"truncated .dds file: the header needs {LEGACY_HEADER_BYTES} bytes, {raw.size} are here")
+    magic, size, _flags, height, width, _pitch, depth, levels = struct.unpack_from("<4s7I", raw, 0)
+    pf_size, pf_flags, fourcc, bits, *masks = struct.unpack_from("<8I", raw, 76)
+    _caps, caps2 = struct.unpack_from("<2I", raw, 108)
+    if magic != b"DDS " or size != 124 or pf_size != 32:
+        raise ValueError("not a .dds file (magic or header sizes)")
+    dx10 = bool(pf_flags & _DDPF_FOURCC) and fourcc == _DX10
+    header, dimension, misc, array_size = LEGACY_HEADER_BYTES, _TEXTURE2D, 0, 1
+    if dx10:
+        header = HEADER_BYTES
+        if raw.size < header:
+            raise ValueError(f"truncated .dds file: the DX10 header needs {header} bytes, {raw.size} are here")
+        dxgi, dimension, misc, array_size, _misc2 = struct.unpack_from("<5I", raw, 128)
+    if array_size > 1:
+        raise ValueError(f"a texture array of {array_size} layers: the tool reads 2D textures only as sources; compress the layers as several files (tex_type '2darray')")
+    if caps2 & _DDSCAPS2_CUBEMAP or misc & _MISC_TEXTURECUBE:
+        raise ValueError("a cubemap: the tool reads 2D textures only as sources; compress the faces as six files (tex_type 'cubemap')")
+    if depth > 1 or caps2 & _DDSCAPS2_VOLUME or dimension == _TEXTURE3D:
+        raise ValueError("a volume texture: the tool reads 2D textures only as sources")
+    if dx10:
+        if dxgi not in _SOURCE_DXGI:
+            raise ValueError(f"DXGI format {dxgi} is {_kind(dxgi, _DXGI_KINDS) or 'another pixel format'}: a .dds source is 32-bit R8G8B8A8 or B8G8R8A8, "
+                             "UNORM or SRGB (DXGI 28, 29, 87, 91)")
+        byte_order, srgb = _SOURCE_DXGI[dxgi]
+    elif pf_flags & _DDPF_FOURCC:
+        kind = _kind(fourcc, _FOURCC_KINDS)
+        raise ValueError(f"FourCC {fourcc:#x} is {kind or 'another pixel format'}: a .dds source is 32-bit RGBA or BGRA")
+    else:
+        if bits == 16:
+            raise ValueError("a 16-bit format (legacy header, 16 bits per pixel): a .dds source is 32-bit RGBA or BGRA")
+        if not pf_flags & (_DDPF_RGB | _DDPF_ALPHA) or bits != 32 or tuple(masks) not in _SOURCE_MASKS:
+            raise ValueError(f"a legacy header of {bits} bits per pixel with masks {', '.join(f'{m:#010x}' for m in masks)}: only those of A8B8G8R8 and A8R8G8B8 are read")
+        byte_order, srgb = _SOURCE_MASKS[tuple(masks)], False
+    if not 1 <= width <= _source.MAX_DIMENSION or not 1 <= height <= _source.MAX_DIMENSION:
+        raise ValueError(f"{width} x {height} pixels: 1..{_source.MAX_DIMENSION} each way")
+    if height == 1:
+        raise ValueError(f"{width} x 1 pixels: a height of 1 is a 1D texture to the tool, which reads 2D textures only as sources")
+    levels = min(max(levels, 1), max(width, height).bit_length())
+    listed, at = [], 0
+    for level in range(levels):
+        w, h = max(1, width >> level), max(1, height >> level)
+        listed.append({"level": level, "width": w, "height": h, "offset": at, "nbytes": w * h * 4})
+        at += w * h * 4
+    if header + at > raw.size:
+        raise ValueError(f"truncated .dds file: {levels} levels of {width} x {height} 32-bit pixels are {at} bytes behind {header} header bytes, and {raw.size} bytes are here")
+    return {"width": width, "height": height, "byte_order": byte_order, "srgb": srgb, "dx10": dx10, "levels": listed, "payload": raw[header:header + at]}
+
+
+def compress_dds(ctx, data, **options):
+    """.dds sources to a .basis / .ktx2 file: what the reference tool does with `.dds` input files (basis_compressor::read_dds_source_images, comp.cpp:2310-2439).
+    data: the bytes of one .dds file (bytes or a uint8 array), or a sequence of them with tex_type "2darray", "cubemap", "video" or "volume". options: compress()'s
+    keyword arguments, except mip_levels. Level 0 of a file is the source image and goes through every source option; the levels below it are used as they are
+    (compress()'s mip_levels: the swizzle alone touches them, they win over `mipmaps`, alpha in any of them gives the file alpha); a file of one level is a plain image.
+    Each file's payload is uploaded once, as it is; ONE launch makes RGBA rasters of level 0 (the file's byte order) and of all lower levels (byte order and swizzle);
+    the rest is compress()'s pipeline. ValueError before ctx is touched: whatever read_dds_source refuses, files whose level counts or sizes differ, `resample` with a
+    file that has lower levels, and everything else compress() refuses."""
+    bare = isinstance(data, (bytes, bytearray, memoryview)) or (isinstance(data, np.ndarray) and data.ndim == 1)
+    if "mip_levels" in options:
+        raise ValueError("mip_levels with .dds sources: the levels below level 0 are the file's")
+    from .compress import compress
+    return compress(ctx, _source.DdsSources([read_dds_source(d) for d in ([data] if bare else data)], bare), **options)
 
 
 def read_dds(data):

@@ -3,6 +3,8 @@ first block is cut -- `basisu -renorm`, `-swizzle` / `-separate_rg_to_color_alph
 (the per-pixel rules: csrc/source_prep.h), then `-resample` / `-resample_factor` through the mip generator's resampler -- and the argument checks compress() shares.
 For several source images per call (texture arrays, cubemaps, video, volumes): the texture-type rules of basis_compressor::validate_texture_type_constraints, the
 slice table of read_source_images (both pure functions), and the one-launch tiling of every slice (bu_hip_k_extract_slices).
+For mip levels the caller made (m_source_mipmap_images; the levels of a .dds source): the selector word of a level, and every level of a call from one resident payload
+into tight rasters by one launch (bu_hip_k_prepare_mip_levels).
 Nothing here has a CPU implementation."""
 import ctypes
 import math
@@ -188,7 +190,7 @@ def slice_table(level_sizes, *, uastc, any_alpha, image_alpha=None, video=False)
     """The slices basis_compressor::read_source_images makes (comp.cpp:2773-3044), in its order: source image outermost, then level, then -- ETC1S with
     m_any_source_image_has_alpha -- the colour and the alpha slice.
     level_sizes: per source image the (width, height) of its levels; any_alpha: m_any_source_image_has_alpha; image_alpha: per image whether its raster has an alpha
-    value below 255 (UASTC: the slice's own flag, image::has_alpha of the slice; without any_alpha no slice has one).
+    value below 255 (UASTC: the slice's own flag, image::has_alpha of the slice; without any_alpha no slice has one), or per image a list with a flag per level.
     -> (slices, sources): slices[i] = (first_block, num_blocks_x, num_blocks_y, width, height, image, level, alpha, iframe) as backend.slice_descs takes them;
     sources[i] = (image, level, mode) with mode one of SLICE_AS_IS / SLICE_RGB / SLICE_ALPHA: what the slice's tiles are cut from.
     video: ETC1S -- the slices of image 0 are i-frames; UASTC -- every slice is (comp.cpp:3016-3030)."""
@@ -197,7 +199,10 @@ def slice_table(level_sizes, *, uastc, any_alpha, image_alpha=None, video=False)
         for level, (w, h) in enumerate(levels):
             nbx, nby = (w + 3) // 4, (h + 3) // 4
             if uastc:
-                parts = [(SLICE_AS_IS, int(bool(any_alpha and image_alpha is not None and image_alpha[image])))]
+                own = image_alpha[image] if image_alpha is not None else False
+                if isinstance(own, (list, tuple)):       # a flag per level: caller-supplied levels, each image::has_alpha of its own pixels
+                    own = own[level]
+                parts = [(SLICE_AS_IS, int(bool(any_alpha and own)))]
             else:
                 parts = [(SLICE_RGB, 0), (SLICE_ALPHA, 1)] if any_alpha else [(SLICE_AS_IS, 0)]
             for mode, alpha in parts:
@@ -219,3 +224,94 @@ def extract_slices_resident(ctx, entries, d_out_blocks):
     for i, (d, w, h, pitch, mode, first) in enumerate(entries):
         arr[i] = SliceSource(d, w, h, pitch or w * 4, mode, first)
     ctx.check(ctx.lib.k_extract_slices(ctx.h, arr, len(entries), ctypes.c_void_p(d_out_blocks)), "k_extract_slices")
+
+
+# ---- mip levels the caller made (basis_compressor_params::m_source_mipmap_images; the levels of a .dds source)
+
+BYTE_ORDERS = {"rgba": (0, 1, 2, 3), "bgra": (2, 1, 0, 3)}   # where a pixel's r, g, b, a lie in memory: DXGI R8G8B8A8 and B8G8R8A8
+
+
+class MipLevelRecord(ctypes.Structure):   # = bu_hip_mip_level_record, include/basisu_hip.h
+    _fields_ = [("src_offset", ctypes.c_uint64), ("dst_offset", ctypes.c_uint64), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("selector", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+def level_selector(byte_order="rgba", swizzle=None):
+    """The selector word of a level's record: the source's byte order composed with the compressor's swizzle -- output channel i is the reader's channel swizzle[i],
+    which lies at byte byte_order[swizzle[i]] of the source pixel. That is all the reference applies to a supplied level (comp.cpp:2796-2817)."""
+    order = BYTE_ORDERS[byte_order]
+    return sum(order[s] << (8 * i) for i, s in enumerate(packed_entries(parse_swizzle(swizzle))))
+
+
+def full_chain_levels(w, h):
+    """how many levels lie below level 0 of a full chain (down to 1 x 1)"""
+    return max(int(w), int(h)).bit_length() - 1
+
+
+def check_supplied_levels(name, w, h, sizes):
+    """sizes: the (width, height) of the levels supplied below a w x h level 0; each must be the next halving, and the chain may stop early"""
+    if len(sizes) > full_chain_levels(w, h):
+        raise ValueError(f"{name}: {len(sizes)} mip levels below {w} x {h} pixels, whose full chain has {full_chain_levels(w, h)}")
+    for k, size in enumerate(sizes, 1):
+        want = (max(1, w >> k), max(1, h >> k))
+        if tuple(size) != want:
+            raise ValueError(f"{name}: mip level {k} is {size[0]} x {size[1]} pixels; level {k} of {w} x {h} is {want[0]} x {want[1]} (max(1, size >> level))")
+
+
+def prepare_mip_levels_resident(ctx, d_payload, payload_bytes, records, d_out, out_bytes, d_flags):
+    """bu_hip_k_prepare_mip_levels: records = [(src_offset, dst_offset, width, height, selector)], every level of the call in ONE launch; no synchronisation"""
+    arr = (MipLevelRecord * max(len(records), 1))()
+    for i, (src, dst, w, h, selector) in enumerate(records):
+        arr[i] = MipLevelRecord(src, dst, w, h, selector, 0)
+    ctx.check(ctx.lib.k_prepare_mip_levels(ctx.h, ctypes.c_void_p(d_payload), payload_bytes, arr, len(records), ctypes.c_void_p(d_out), out_bytes, ctypes.c_void_p(d_flags)),
+              "k_prepare_mip_levels")
+
+
+def resident_levels(ctx, owned, parts, levels):
+    """parts: host uint8 arrays (C-contiguous, sizes multiples of 4), uploaded once each, back to back, into ONE resident payload; levels = [(part, byte offset within
+    the part, width, height, selector)]. ONE prepare_mip_levels launch writes every level as a tight RGBA8 raster (each begins on a 16-byte line, so that the tiler
+    reads whole rows) -> ([device address per level], [per level: is any written alpha not 255]). The call waits once, for the flags. What is allocated goes into the
+    caller's `owned`."""
+    starts, payload_bytes = [], 0
+    for part in parts:
+        starts.append(payload_bytes)
+        payload_bytes += part.nbytes
+    records, out_bytes = [], 0
+    for part, offset, w, h, selector in levels:
+        records.append((starts[part] + offset, out_bytes, w, h, selector))
+        out_bytes += (w * h * 4 + 15) & ~15
+    d_payload, d_out, d_flags = ctx.alloc(max(payload_bytes, 4)), ctx.alloc(max(out_bytes, 4)), ctx.alloc(4 * max(len(levels), 1))
+    owned.extend((d_payload, d_out, d_flags))
+    for part, at in zip(parts, starts):
+        if part.nbytes:
+            ctx.memcpy_h2d_async(d_payload + at, part)
+    prepare_mip_levels_resident(ctx, d_payload, payload_bytes, records, d_out, out_bytes, d_flags)
+    flags = ctx.download(d_flags, (max(len(levels), 1),), np.uint32)
+    return [d_out + r[1] for r in records], [bool(f) for f in flags[:len(levels)]]
+
+
+class DdsSources:
+    """The source images of compress() as parsed .dds files (dds.read_dds_source): what dds.compress_dds hands to compress() in place of arrays. Level 0 and the lower
+    levels stay in the file's bytes; `arrays` gives views of them for the argument checks, `resident` brings every level of every file to the device."""
+
+    def __init__(self, files, bare):
+        self.files, self.bare = list(files), bool(bare)
+
+    def arrays(self):
+        """-> (level-0 views, per file the views of its lower levels or None where no file has any): the file's bytes as they are, whatever the byte order"""
+        views = [[f["payload"][lv["offset"]:lv["offset"] + lv["nbytes"]].reshape(lv["height"], lv["width"], 4) for lv in f["levels"]] for f in self.files]
+        lower = [v[1:] for v in views]
+        return [v[0] for v in views], (lower if any(lower) else None)
+
+    def resident(self, ctx, owned, swizzle):
+        """every file's payload uploaded once, ONE launch for level 0's byte order and the lower levels' byte order and swizzle
+        -> per file ([level rasters], [the flag of each])"""
+        levels = [(k, lv["offset"], lv["width"], lv["height"], level_selector(f["byte_order"], swizzle if i else None))
+                  for k, f in enumerate(self.files) for i, lv in enumerate(f["levels"])]
+        rasters, flags = resident_levels(ctx, owned, [f["payload"] for f in self.files], levels)
+        out, at = [], 0
+        for f in self.files:
+            n = len(f["levels"])
+            out.append((rasters[at:at + n], flags[at:at + n]))
+            at += n
+        return out

@@ -233,6 +233,27 @@ BU_HIP_API int bu_hip_k_renormalize_normal_map(bu_hip_context*, void* d_rgba, ui
 BU_HIP_API int bu_hip_k_split_alpha(bu_hip_context*, const void* d_rgba, uint32_t width, uint32_t height, uint32_t pitch_bytes, void* d_out_rgb, uint32_t rgb_pitch_bytes,
         void* d_out_alpha, uint32_t alpha_pitch_bytes);
 
+/* Mip levels the caller made (basis_compressor_params::m_source_mipmap_images, comp.cpp:2737-2818; the levels of a .dds source, comp.cpp:2310-2439) into tight
+ * RGBA8 rasters: every level of every image of a call from ONE resident payload -- the levels' bytes back to back, or a .dds file's payload as it was uploaded -- in
+ * ONE launch. `records` is a HOST array of n records. Level i's width x height pixels are read as tight 32-bit pixels from d_payload + src_offset, each pixel's
+ * bytes permuted by `selector` -- byte k of the word names the source byte 0..3 of output channel k: 0x03020100 copies, 0x03000102 reads B8G8R8A8, and the host
+ * composes the byte order with the compressor's swizzle, which is all the reference applies to a supplied level -- and written as a tight raster to
+ * d_out + dst_offset. d_flags[i] (n device words, cleared by the call) becomes 1 where a written alpha value of level i is not 255: image::has_alpha of the level
+ * as written. The rasters must not overlap each other or the payload. The records and the table of their pixel counts go up in one stream-ordered copy; `records`
+ * may be released on return. One launch on the context's stream, no synchronisation: the flags are read after bu_hip_sync or by a blocking copy.
+ * n == 0 succeeds and does nothing. Fails -- nothing copied, nothing launched, nothing written, the reason by name in bu_hip_last_error -- on a null pointer, a
+ * payload, output or flags pointer or an offset that is not 4-byte aligned, a level that ends past payload_bytes or past out_bytes, a size outside 1..16384, a
+ * selector entry above 3, more than 0xFFFFFF records (BASISU_MAX_SLICES), or more than 2^30 pixels in all. */
+typedef struct bu_hip_mip_level_record {
+    uint64_t src_offset;         /* bytes from d_payload, a multiple of 4 */
+    uint64_t dst_offset;         /* bytes from d_out, a multiple of 4 */
+    uint32_t width, height;      /* pixels, 1..16384 */
+    uint32_t selector;           /* s0 | s1 << 8 | s2 << 16 | s3 << 24, each 0..3 */
+    uint32_t reserved;           /* 0 */
+} bu_hip_mip_level_record;
+BU_HIP_API int bu_hip_k_prepare_mip_levels(bu_hip_context*, const void* d_payload, size_t payload_bytes, const bu_hip_mip_level_record* records, uint32_t n,
+        void* d_out, size_t out_bytes, uint32_t* d_flags);
+
 /* etc1_optimizer quality (basis_etc_quality, basisu_etc.h:794-801) */
 enum { BU_ETC_QUALITY_FAST = 0, BU_ETC_QUALITY_MEDIUM = 1, BU_ETC_QUALITY_SLOW = 2, BU_ETC_QUALITY_UBER = 3 };
 
