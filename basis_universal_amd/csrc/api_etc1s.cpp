@@ -21,6 +21,13 @@ unsigned upload_threads() {
     }();
     return t;
 }
+// The de-duplication and block-ranking sorts hand their item count to hipCUB as an int and size their grids in 32 bits: more than 2^30 items is refused by name, before
+// any workspace is reserved and before any output is touched.
+bool sort_size_ok(bu_hip_context* ctx, const char* fn, uint32_t n) {
+    if (n <= (1u << 30)) return true;
+    set_error(ctx, "%s: %u blocks: more than 2^30 in one call", fn, n);
+    return false;
+}
 }
 
 extern "C" {
@@ -437,6 +444,7 @@ int bu_hip_k_map_blocks_from_groups(bu_hip_context* ctx, const uint32_t* d_goffs
 int bu_hip_k_map_rank_blocks(bu_hip_context* ctx, const uint32_t* d_cluster, uint32_t n, uint32_t k, uint32_t* d_sizes, uint32_t* d_offsets, uint32_t* d_sorted, uint32_t* d_pos) {
     if (!ctx) return 0;
     if (n && (!d_cluster || !d_sizes || !d_offsets || !d_sorted)) { set_error(ctx, "map_rank_blocks: null pointer"); return 0; }
+    if (!sort_size_ok(ctx, "map_rank_blocks", n)) return 0;
     device_guard g(ctx->device);
     arena& ws = ctx->scratch[4];
     BU_TRY(ctx, ws.reserve(bu::rank_blocks_workspace_bytes(n, k)));
@@ -618,6 +626,7 @@ int bu_hip_k_unique_endpoint_vectors(bu_hip_context* ctx, const void* d_etc1_blo
     if (!out_unique || (n_blocks && (!d_etc1_blocks || !d_sorted_block_idx || !d_unique_keys || !d_group_offsets))) { set_error(ctx, "unique_endpoint_vectors: null pointer"); return 0; }
     *out_unique = 0;
     if (!n_blocks) return 1;
+    if (!sort_size_ok(ctx, "unique_endpoint_vectors", n_blocks)) return 0;
     device_guard g(ctx->device);
     arena& ws = ctx->scratch[4];
     BU_TRY(ctx, ws.reserve(bu::unique_endpoint_vectors_workspace_bytes(n_blocks)));
@@ -639,6 +648,7 @@ int bu_hip_k_unique_selector_vectors(bu_hip_context* ctx, const void* d_enc_bloc
     }
     *out_unique = 0;
     if (!n_blocks) return 1;
+    if (!sort_size_ok(ctx, "unique_selector_vectors", n_blocks)) return 0;
     device_guard g(ctx->device);
     arena& ws = ctx->scratch[4];
     BU_TRY(ctx, ws.reserve(bu::unique_selector_vectors_workspace_bytes(n_blocks)));

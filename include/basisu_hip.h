@@ -586,7 +586,8 @@ BU_HIP_API int bu_hip_k_ssim_map(bu_hip_context*, const void* d_a, uint32_t widt
  *     distinct vector u gets cluster d_leaf_of_unique[u], position d_first_pos[u] + its rank inside the group, parent d_parent_of_unique[u]
  *     (d_first_pos / d_out_pos and d_parent_of_unique / d_out_parent may be NULL).
  *   map_rank_blocks (frontend.cpp:1921-1942, lists rebuilt in block order): d_out_sizes[k + 1] (last entry 0), d_out_offsets[k + 1] (exclusive
- *     sum), d_out_sorted_blocks[n] = block ids grouped by cluster, ascending inside a cluster, d_out_pos[n] (may be NULL) = rank of every block. */
+ *     sum), d_out_sorted_blocks[n] = block ids grouped by cluster, ascending inside a cluster, d_out_pos[n] (may be NULL) = rank of every block.
+ *     More than 2^30 blocks returns 0 with "more than 2^30 in one call" before anything is reserved or written. */
 BU_HIP_API int bu_hip_k_map_blocks_from_groups(bu_hip_context*, const uint32_t* d_group_offsets, const uint32_t* d_sorted_block_idx, uint32_t n_blocks, uint32_t u_total,
     const uint32_t* d_leaf_of_unique, const uint32_t* d_first_pos, const uint32_t* d_parent_of_unique, uint32_t* d_out_cluster, uint32_t* d_out_pos, uint8_t* d_out_parent);
 BU_HIP_API int bu_hip_k_map_rank_blocks(bu_hip_context*, const uint32_t* d_block_cluster, uint32_t n_blocks, uint32_t n_clusters, uint32_t* d_out_sizes,
@@ -655,7 +656,8 @@ BU_HIP_API bu_tsvq* bu_hip_tsvq_create_endpoint_device(bu_hip_context*, const ui
 /* a7 + its de-duplication (frontend.cpp:825-866, enc.h:2218-2290) for n resident ETC1S blocks: distinct (low rgb, high rgb) block-colour vectors as
  * 48-bit keys (low r,g,b in bits 47..24, high r,g,b in bits 23..0; divide the bytes by 255 for the reference's vec6F) in ascending order, and the
  * blocks of every distinct vector (ascending) as d_sorted_block_idx[d_group_offsets[u] .. d_group_offsets[u+1]). Each block stands for its two
- * sub-block training vectors (ids 2b and 2b+1, weight 1 each). Outputs: device arrays of n_blocks (offsets: n_blocks + 1) entries. Synchronises. */
+ * sub-block training vectors (ids 2b and 2b+1, weight 1 each). Outputs: device arrays of n_blocks (offsets: n_blocks + 1) entries. Synchronises.
+ * Both refuse n_blocks > 2^30: they return 0 with "more than 2^30 in one call" and *out_unique = 0, before any workspace is reserved or any output written. */
 BU_HIP_API int bu_hip_k_unique_endpoint_vectors(bu_hip_context*, const void* d_etc1_blocks, uint32_t n_blocks, uint32_t* d_sorted_block_idx, uint64_t* d_unique_keys,
                                                 uint32_t* d_group_offsets, uint32_t* out_unique);
 BU_HIP_API int bu_hip_k_unique_selector_vectors(bu_hip_context*, const void* d_enc_blocks, const uint64_t* d_weights, uint32_t n_blocks, uint32_t* d_sorted_block_idx,

@@ -11,6 +11,7 @@ import pytest
 from helpers import (oracle, ptr, u8p, u32p, u64p, f32p, synth, uniform_random, to_pixel_blocks, csr_from_lists)
 from helpers import etc1s_test_tiles as _images, clusters_by_luma as _clusters_by_luma, endpoint_codebook as _codebook
 from helpers import (etc1s_planted_tiles, etc1s_planted_test_tiles, clusters_by_plant, planted_exact_clusters, planted_endpoint_codebook, ETC1_INTEN_TABLES)
+from dedup_sort_cases import check_groups as _check_groups   # distinct keys ascending; blocks of every distinct vector ascending and complete; summed weights
 
 pytestmark = pytest.mark.gpu
 
@@ -394,17 +395,6 @@ def test_selector_training_vectors(hip_ctx, tileset, blocks, perceptual):
     assert (hip_ctx.download(d_w, (n,), np.uint64) == exp_w).all()
     for p in (d_enc, d_v, d_w):
         hip_ctx.free(p)
-
-
-def _check_groups(n, u, keys_np, got_keys, got_offsets, got_idx, weights=None, got_weights=None):
-    """distinct keys ascending; blocks of every distinct vector ascending and complete; summed weights"""
-    uniq, inverse = np.unique(keys_np, return_inverse=True)
-    assert u == uniq.size and (got_keys[:u] == uniq).all()
-    assert got_offsets[0] == 0 and got_offsets[u] == n and (np.diff(got_offsets[:u + 1].astype(np.int64)) > 0).all()
-    order = np.argsort(keys_np, kind="stable")        # stable: ascending block index inside a key
-    assert (got_idx == order).all()
-    if weights is not None:
-        assert (got_weights[:u] == np.array([weights[order[got_offsets[i]:got_offsets[i + 1]]].sum() for i in range(u)], np.uint64)).all()
 
 
 @pytest.mark.parametrize("n", [0, 1, 2, 257, 3072])

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from helpers import oracle, ptr, u32p, u64p, csr_from_lists, decode_etc1s_blocks
+from dedup_sort_cases import rank_reference as _rank_reference   # sizes, offsets, stable order and positions of a clustering, by numpy
 import test_gpu_etc1s_kernels as K
 
 pytestmark = pytest.mark.gpu
@@ -389,15 +390,6 @@ def test_backend_block_errors(hip_ctx, mix, nbx, nby, perceptual, with_neighbour
 
 
 # ----------------------------------------------------------------------------- bookkeeping maps, against numpy
-
-def _rank_reference(cluster, k):
-    n = cluster.size
-    order = np.argsort(cluster, kind="stable").astype(np.uint32)             # block ids grouped by cluster, ascending inside a cluster
-    sizes = np.zeros(k + 1, np.uint32); sizes[:k] = np.bincount(cluster, minlength=k)
-    offsets = np.zeros(k + 1, np.uint32); offsets[1:] = np.cumsum(sizes[:k])
-    pos = np.zeros(n, np.uint32); pos[order] = np.arange(n, dtype=np.uint32) - offsets[cluster[order]]
-    return sizes, offsets, order, pos
-
 
 def _cluster_maps():
     rng = np.random.default_rng(2024)

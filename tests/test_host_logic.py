@@ -119,6 +119,8 @@ def test_every_checker_function_is_exported_and_bound():
     import re
     import helpers
     import native_libs
+    import ssim_helpers, source_prep_helpers, dds_export_helpers  # noqa: F401,E401  (each registers its checker with native_libs at import: without them this test
+    #                                                               passes only behind a test module that happens to import all three)
     sources = [source for _, source, _, _ in native_libs.CHECKERS.values()]
     assert sorted(s for s in sources if s.parent == native_libs.NATIVE) == sorted(native_libs.NATIVE.glob("*.cpp")), "every tests/native/*.cpp is one checker"
     assert len(set(sources)) == len(sources)
