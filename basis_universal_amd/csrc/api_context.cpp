@@ -305,6 +305,7 @@ static void context_release(bu_hip_context* ctx) {   // the real teardown
     for (auto& a : ctx->scratch) a.release();
     ctx->refine_lists.release();
     ctx->etc1s_bc1_tables.release();
+    ctx->etc1s_bc7_tables.release();
     if (ctx->tsvq_pinned) (void)hipHostFree(ctx->tsvq_pinned);
     for (auto& b : ctx->pool_free) (void)hipFree(b.p);
     for (auto& b : ctx->pool_live) (void)hipFree(b.p);

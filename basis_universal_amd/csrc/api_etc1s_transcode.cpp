@@ -3,23 +3,43 @@
 #include "etc1s_transcode_kernels.h"
 
 static const char* const kEtc1sTargets = "ETC1_RGB (0), BC1_RGB (2), RGBA32 (13), RGB565 (14), BGR565 (15), RGBA4444 (16)";
+static const char* const kEtc1sTextureTargets = "ETC1_RGB (0), ETC2_RGBA (1), BC1_RGB (2), BC7_RGBA (6), RGBA32 (13), RGB565 (14), BGR565 (15), RGBA4444 (16)";
+static const uint32_t kNoChromaFiltering = 64;   // cDecodeFlagsNoETC1SChromaFiltering, the one flag of the bu_hip_k_transcode_etc1s_image* entries
 
-// the checks both entry points share; fills the launch arguments
-static int etc1s_transcode_args_from(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
-                                     const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, void* d_out,
-                                     uint32_t pitch_px, uint32_t rows_px, bu::etc1s_transcode_args& a) {
-    if (!bu::etc1s_transcode_unit_bytes(target)) {
-        set_error(ctx, "transcode_etc1s: target %u (%s) is not supported (supported: %s)", target, transcoder_format_name(target), kEtc1sTargets);
+// Which entry family a call came through. The first (bu_hip_k_transcode_etc1s*) has six targets and no flags; the second (bu_hip_k_transcode_etc1s_image*) adds the
+// 16-byte targets and decode_flags. Both run the same code below: the family decides the target list, the flags and the name in a refusal.
+struct etc1s_family { const char* fn; bool texture; };
+static const etc1s_family kFirstFamily = { "transcode_etc1s", false }, kImageFamily = { "transcode_etc1s_image", true };
+
+static uint32_t family_unit_bytes(const etc1s_family& f, uint32_t target) { return f.texture ? bu::etc1s_texture_unit_bytes(target) : bu::etc1s_transcode_unit_bytes(target); }
+static bool reads_alpha(uint32_t target) { return target == bu::ETF_RGBA32 || target == bu::ETF_RGBA4444 || target == bu::ETF_ETC2_RGBA || target == bu::ETF_BC7_RGBA; }
+// the target and the flags of a call; the refusal names what is wrong
+static int etc1s_target_ok(bu_hip_context* ctx, const etc1s_family& f, uint32_t target, uint32_t decode_flags) {
+    if (!family_unit_bytes(f, target)) {
+        set_error(ctx, "%s: target %u (%s) is not supported (supported: %s)", f.fn, target, transcoder_format_name(target), f.texture ? kEtc1sTextureTargets : kEtc1sTargets);
         return 0;
     }
-    if (!d_ep_pal || !d_sel_pal || !d_ep_idx || !d_sel_idx || !d_out) { set_error(ctx, "transcode_etc1s: null device pointer"); return 0; }
-    if ((d_a_ep_idx == nullptr) != (d_a_sel_idx == nullptr)) { set_error(ctx, "transcode_etc1s: an alpha slice needs both of its index arrays"); return 0; }
-    if (!n_ep || !n_sel || n_ep > 65535u || n_sel > 65535u) { set_error(ctx, "transcode_etc1s: palettes of %u endpoints and %u selectors (1..65535 each)", n_ep, n_sel); return 0; }
+    if (decode_flags & ~kNoChromaFiltering) {
+        set_error(ctx, "%s: decode_flags 0x%x: bits 0x%x are not supported (supported: 64, cDecodeFlagsNoETC1SChromaFiltering)", f.fn, decode_flags, decode_flags & ~kNoChromaFiltering);
+        return 0;
+    }
+    return 1;
+}
+
+// the checks both entry points share; fills the launch arguments
+static int etc1s_transcode_args_from(bu_hip_context* ctx, const etc1s_family& f, uint32_t decode_flags, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
+                                     const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, void* d_out,
+                                     uint32_t pitch_px, uint32_t rows_px, bu::etc1s_transcode_args& a) {
+    if (!etc1s_target_ok(ctx, f, target, decode_flags)) return 0;
+    if (!d_ep_pal || !d_sel_pal || !d_ep_idx || !d_sel_idx || !d_out) { set_error(ctx, "%s: null device pointer", f.fn); return 0; }
+    if ((d_a_ep_idx == nullptr) != (d_a_sel_idx == nullptr)) { set_error(ctx, "%s: an alpha slice needs both of its index arrays", f.fn); return 0; }
+    if (!n_ep || !n_sel || n_ep > 65535u || n_sel > 65535u) { set_error(ctx, "%s: palettes of %u endpoints and %u selectors (1..65535 each)", f.fn, n_ep, n_sel); return 0; }
+    if (family_unit_bytes(f, target) == 16 && (reinterpret_cast<uintptr_t>(d_out) & 15u)) { set_error(ctx, "%s: the output of a 16-byte target must be 16-byte aligned", f.fn); return 0; }
     bu::tile_geometry geo;
-    if (!checked(ctx, [&](bu::err_text e) { return bu::resolve_geometry("transcode_etc1s", nbx, nby, orig_w, orig_h, pitch_px, rows_px, bu::kEachWay16384, &geo, e); })) return 0;
+    if (!checked(ctx, [&](bu::err_text e) { return bu::resolve_geometry(f.fn, nbx, nby, orig_w, orig_h, pitch_px, rows_px, bu::kEachWay16384, &geo, e); })) return 0;
     a = bu::etc1s_transcode_args{ static_cast<const uint32_t*>(d_ep_pal), static_cast<const uint32_t*>(d_sel_pal), static_cast<const uint16_t*>(d_ep_idx),
                                   static_cast<const uint16_t*>(d_sel_idx), static_cast<const uint16_t*>(d_a_ep_idx), static_cast<const uint16_t*>(d_a_sel_idx), d_out, nullptr, nullptr,
-                                  n_ep, n_sel, geo };
+                                  nullptr, n_ep, n_sel, geo };
     return 1;
 }
 
@@ -30,6 +50,109 @@ static int ensure_bc1_tables(bu_hip_context* ctx) {
     hipError_t e = bu::launch_etc1s_build_bc1_tables(ctx->stream, static_cast<uint32_t*>(ctx->etc1s_bc1_tables.p));
     if (e != hipSuccess) { ctx->etc1s_bc1_tables.release(); set_error(ctx, "etc1s_build_bc1_tables: %s", hipGetErrorString(e)); return 0; }
     return 1;
+}
+
+// the ETC1S -> BC7 colour look-up and the encoder's midpoints, the same way: built by the first BC7 transcode, released with the context
+static int ensure_bc7_tables(bu_hip_context* ctx) {
+    if (ctx->etc1s_bc7_tables.p) return 1;
+    BU_TRY(ctx, ctx->etc1s_bc7_tables.reserve(bu::kEtc1sBc7TableWords * sizeof(uint32_t)));
+    hipError_t e = bu::launch_etc1s_build_bc7_tables(ctx->stream, static_cast<uint32_t*>(ctx->etc1s_bc7_tables.p));
+    if (e != hipSuccess) { ctx->etc1s_bc7_tables.release(); set_error(ctx, "etc1s_build_bc7_tables: %s", hipGetErrorString(e)); return 0; }
+    return 1;
+}
+// only what the target needs
+static int ensure_target_tables(bu_hip_context* ctx, uint32_t target, const uint32_t*& bc1, const uint32_t*& bc7) {
+    if (target == bu::ETF_BC1_RGB) {
+        if (!ensure_bc1_tables(ctx)) return 0;
+        bc1 = static_cast<const uint32_t*>(ctx->etc1s_bc1_tables.p);
+    }
+    if (target == bu::ETF_BC7_RGBA) {
+        if (!ensure_bc7_tables(ctx)) return 0;
+        bc7 = static_cast<const uint32_t*>(ctx->etc1s_bc7_tables.p);
+    }
+    return 1;
+}
+
+// one image, counted: both families' *_counted entries
+static int transcode_image_counted(bu_hip_context* ctx, const etc1s_family& f, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx,
+                                   const void* d_sel_idx, const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target,
+                                   void* d_out, uint32_t pitch_px, uint32_t rows_px, uint32_t decode_flags, uint32_t* out_invalid_blocks) {
+    if (!ctx) return 0;
+    if (out_invalid_blocks) *out_invalid_blocks = 0;
+    bu::etc1s_transcode_args a;
+    if (!etc1s_transcode_args_from(ctx, f, decode_flags, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out, pitch_px,
+                                   rows_px, a)) return 0;
+    device_guard g(ctx->device);
+    arena& counter = ctx->scratch[4];
+    BU_TRY(ctx, counter.reserve(sizeof(uint32_t)));
+    a.invalid = static_cast<uint32_t*>(counter.p);
+    if (!ensure_target_tables(ctx, target, a.bc1_endpoints, a.bc7_tables)) return 0;
+    {
+        prof_scope ps(ctx, "etc1s_transcode");
+        BU_TRY(ctx, bu::launch_transcode_etc1s(ctx->stream, a, target, !(decode_flags & kNoChromaFiltering)));
+    }
+    uint32_t invalid = 0;
+    if (!read_back(ctx, &invalid, counter.p, sizeof(invalid))) return 0;
+    if (out_invalid_blocks) *out_invalid_blocks = invalid;
+    return 1;
+}
+
+// one image behind a range check of every index the target reads: both families' plain entries
+static int transcode_image_checked(bu_hip_context* ctx, const etc1s_family& f, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx,
+                                   const void* d_sel_idx, const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target,
+                                   void* d_out, uint32_t pitch_px, uint32_t rows_px, uint32_t decode_flags) {
+    if (!ctx) return 0;
+    bu::etc1s_transcode_args a;
+    if (!etc1s_transcode_args_from(ctx, f, decode_flags, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out, pitch_px,
+                                   rows_px, a)) return 0;
+    device_guard g(ctx->device);
+    arena& counter = ctx->scratch[4];
+    BU_TRY(ctx, counter.reserve(sizeof(uint32_t)));
+    uint32_t* d_count = static_cast<uint32_t*>(counter.p);
+    const uint32_t n = nbx * nby;
+    // the indices are resident, so the range check that has to come before the launch is a pass over them on the device: 2-4 bytes per block read, one word back
+    {
+        prof_scope ps(ctx, "etc1s_transcode_check");
+        BU_TRY(ctx, bu::launch_etc1s_count_indices_past(ctx->stream, a.endpoint_idx, n, n_ep, d_count, true));
+        BU_TRY(ctx, bu::launch_etc1s_count_indices_past(ctx->stream, a.selector_idx, n, n_sel, d_count, false));
+        if (a.alpha_endpoint_idx && reads_alpha(target)) {
+            BU_TRY(ctx, bu::launch_etc1s_count_indices_past(ctx->stream, a.alpha_endpoint_idx, n, n_ep, d_count, false));
+            BU_TRY(ctx, bu::launch_etc1s_count_indices_past(ctx->stream, a.alpha_selector_idx, n, n_sel, d_count, false));
+        }
+    }
+    uint32_t past = 0;
+    if (!read_back(ctx, &past, d_count, sizeof(past))) return 0;
+    if (past) { set_error(ctx, "%s: %u indices are past their palette (%u endpoints, %u selectors): nothing was transcoded", f.fn, past, n_ep, n_sel); return 0; }
+    uint32_t invalid = 0;
+    if (!transcode_image_counted(ctx, f, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out, pitch_px, rows_px, decode_flags,
+                                 &invalid)) return 0;
+    if (invalid) { set_error(ctx, "%s: %u blocks had an index past its palette", f.fn, invalid); return 0; }
+    return 1;
+}
+
+// every image of a file in one launch: the table's checks and pack are tile_geometry_check.h's behind etc1s_slices_check, upload and read-back api_internal.h's
+static int transcode_images(bu_hip_context* ctx, const etc1s_family& f, const char* fn, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx,
+                            const void* d_sel_idx, uint64_t n_indices, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target, uint32_t decode_flags, void* d_out,
+                            size_t out_bytes, uint32_t* out_invalid_per_slice) {
+    if (!ctx) return 0;
+    if (!etc1s_target_ok(ctx, f, target, decode_flags)) return 0;
+    if (!d_ep_pal || !d_sel_pal || !d_ep_idx || !d_sel_idx) { set_error(ctx, "%s: null pointer", fn); return 0; }
+    if (!n_ep || !n_sel || n_ep > 65535u || n_sel > 65535u) { set_error(ctx, "%s: palettes of %u endpoints and %u selectors (1..65535 each)", fn, n_ep, n_sel); return 0; }
+    bu::slice_table table;
+    if (!etc1s_slices_check(ctx, table, fn, slices, n_slices, n_indices, target, f.texture, d_out, out_bytes)) return 0;
+    device_guard g(ctx->device);
+    const uint32_t *bc1 = nullptr, *bc7 = nullptr;
+    if (!ensure_target_tables(ctx, target, bc1, bc7)) return 0;
+    uploaded_slices d;
+    if (!upload_slice_table(ctx, table, d)) return 0;
+    const bu::etc1s_transcode_slices_args a = { static_cast<const uint32_t*>(d_ep_pal), static_cast<const uint32_t*>(d_sel_pal), static_cast<const uint16_t*>(d_ep_idx),
+                                                static_cast<const uint16_t*>(d_sel_idx), static_cast<uint8_t*>(d_out), d.counters, bc1, bc7,
+                                                static_cast<const bu_hip_transcode_slice*>(d.records), d.prefix, n_ep, n_sel, table.n, table.total };
+    {
+        prof_scope ps(ctx, fn);
+        BU_TRY(ctx, bu::launch_transcode_etc1s_slices(ctx->stream, a, target, !(decode_flags & kNoChromaFiltering)));
+    }
+    return out_invalid_per_slice ? read_back(ctx, out_invalid_per_slice, d.counters, (size_t)table.n * sizeof(uint32_t)) : 1;
 }
 
 extern "C" {
@@ -51,90 +174,58 @@ int bu_hip_etc1s_bc1_endpoint_tables(bu_hip_context* ctx, uint32_t* h_out5, uint
 int bu_hip_k_transcode_etc1s_counted(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
                                      const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, void* d_out,
                                      uint32_t pitch_px, uint32_t rows_px, uint32_t* out_invalid_blocks) {
-    if (!ctx) return 0;
-    if (out_invalid_blocks) *out_invalid_blocks = 0;
-    bu::etc1s_transcode_args a;
-    if (!etc1s_transcode_args_from(ctx, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out, pitch_px, rows_px, a)) return 0;
-    device_guard g(ctx->device);
-    arena& counter = ctx->scratch[4];
-    BU_TRY(ctx, counter.reserve(sizeof(uint32_t)));
-    a.invalid = static_cast<uint32_t*>(counter.p);
-    if (target == bu::ETF_BC1_RGB) {
-        if (!ensure_bc1_tables(ctx)) return 0;
-        a.bc1_endpoints = static_cast<const uint32_t*>(ctx->etc1s_bc1_tables.p);
-    }
-    {
-        prof_scope ps(ctx, "etc1s_transcode");
-        BU_TRY(ctx, bu::launch_transcode_etc1s(ctx->stream, a, target));
-    }
-    uint32_t invalid = 0;
-    if (!read_back(ctx, &invalid, counter.p, sizeof(invalid))) return 0;
-    if (out_invalid_blocks) *out_invalid_blocks = invalid;
-    return 1;
+    return transcode_image_counted(ctx, kFirstFamily, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out, pitch_px,
+                                   rows_px, 0, out_invalid_blocks);
 }
 
 int bu_hip_k_transcode_etc1s(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
                              const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, void* d_out,
                              uint32_t pitch_px, uint32_t rows_px) {
-    if (!ctx) return 0;
-    bu::etc1s_transcode_args a;
-    if (!etc1s_transcode_args_from(ctx, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out, pitch_px, rows_px, a)) return 0;
-    device_guard g(ctx->device);
-    arena& counter = ctx->scratch[4];
-    BU_TRY(ctx, counter.reserve(sizeof(uint32_t)));
-    uint32_t* d_count = static_cast<uint32_t*>(counter.p);
-    const uint32_t n = nbx * nby;
-    // the indices are resident, so the range check that has to come before the launch is a pass over them on the device: 2-4 bytes per block read, one word back
-    {
-        prof_scope ps(ctx, "etc1s_transcode_check");
-        BU_TRY(ctx, bu::launch_etc1s_count_indices_past(ctx->stream, a.endpoint_idx, n, n_ep, d_count, true));
-        BU_TRY(ctx, bu::launch_etc1s_count_indices_past(ctx->stream, a.selector_idx, n, n_sel, d_count, false));
-        const bool alpha_read = a.alpha_endpoint_idx && (target == bu::ETF_RGBA32 || target == bu::ETF_RGBA4444);
-        if (alpha_read) {
-            BU_TRY(ctx, bu::launch_etc1s_count_indices_past(ctx->stream, a.alpha_endpoint_idx, n, n_ep, d_count, false));
-            BU_TRY(ctx, bu::launch_etc1s_count_indices_past(ctx->stream, a.alpha_selector_idx, n, n_sel, d_count, false));
-        }
-    }
-    uint32_t past = 0;
-    if (!read_back(ctx, &past, d_count, sizeof(past))) return 0;
-    if (past) { set_error(ctx, "transcode_etc1s: %u indices are past their palette (%u endpoints, %u selectors): nothing was transcoded", past, n_ep, n_sel); return 0; }
-    uint32_t invalid = 0;
-    if (!bu_hip_k_transcode_etc1s_counted(ctx, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out, pitch_px, rows_px,
-                                          &invalid)) return 0;
-    if (invalid) { set_error(ctx, "transcode_etc1s: %u blocks had an index past its palette", invalid); return 0; }
-    return 1;
+    return transcode_image_checked(ctx, kFirstFamily, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out, pitch_px,
+                                   rows_px, 0);
 }
 
-// every image of a file in one launch: the table's checks and pack are tile_geometry_check.h's behind transcode_slices_check, upload and read-back api_internal.h's
 int bu_hip_k_transcode_etc1s_slices(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
                                     uint64_t n_indices, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target, void* d_out, size_t out_bytes,
                                     uint32_t* out_invalid_per_slice) {
-    if (!ctx) return 0;
-    static const char* const fn = "transcode_etc1s_slices";
-    if (!bu::etc1s_transcode_unit_bytes(target)) {
-        set_error(ctx, "transcode_etc1s: target %u (%s) is not supported (supported: %s)", target, transcoder_format_name(target), kEtc1sTargets);
-        return 0;
-    }
-    if (!d_ep_pal || !d_sel_pal || !d_ep_idx || !d_sel_idx) { set_error(ctx, "%s: null pointer", fn); return 0; }
-    if (!n_ep || !n_sel || n_ep > 65535u || n_sel > 65535u) { set_error(ctx, "%s: palettes of %u endpoints and %u selectors (1..65535 each)", fn, n_ep, n_sel); return 0; }
-    bu::slice_table table;
-    if (!transcode_slices_check(ctx, table, fn, slices, n_slices, n_indices, target, true, d_out, out_bytes)) return 0;
+    return transcode_images(ctx, kFirstFamily, "transcode_etc1s_slices", d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, n_indices, slices, n_slices, target, 0, d_out, out_bytes,
+                            out_invalid_per_slice);
+}
+
+// ---- the second family: the first one's arguments plus decode_flags, all eight targets
+
+size_t bu_hip_etc1s_image_output_bytes(uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, uint32_t pitch_px, uint32_t rows_px) {
+    return bu::raster_output_bytes(bu::tile_geometry{ nbx, nby, orig_w, orig_h, pitch_px, rows_px }, bu::etc1s_texture_unit_bytes(target), bu::etc1s_transcode_is_pixel_target(target));
+}
+
+int bu_hip_etc1s_bc7_color_table(bu_hip_context* ctx, uint32_t* h_out, uint32_t* h_midpoints) {
+    if (!ctx || !h_out || !h_midpoints) { if (ctx) set_error(ctx, "etc1s_bc7_color_table: null pointer"); return 0; }
     device_guard g(ctx->device);
-    const uint32_t* bc1 = nullptr;
-    if (target == bu::ETF_BC1_RGB) {
-        if (!ensure_bc1_tables(ctx)) return 0;
-        bc1 = static_cast<const uint32_t*>(ctx->etc1s_bc1_tables.p);
-    }
-    uploaded_slices d;
-    if (!upload_slice_table(ctx, table, d)) return 0;
-    const bu::etc1s_transcode_slices_args a = { static_cast<const uint32_t*>(d_ep_pal), static_cast<const uint32_t*>(d_sel_pal), static_cast<const uint16_t*>(d_ep_idx),
-                                                static_cast<const uint16_t*>(d_sel_idx), static_cast<uint8_t*>(d_out), d.counters, bc1,
-                                                static_cast<const bu_hip_transcode_slice*>(d.records), d.prefix, n_ep, n_sel, table.n, table.total };
-    {
-        prof_scope ps(ctx, fn);
-        BU_TRY(ctx, bu::launch_transcode_etc1s_slices(ctx->stream, a, target));
-    }
-    return out_invalid_per_slice ? read_back(ctx, out_invalid_per_slice, d.counters, (size_t)table.n * sizeof(uint32_t)) : 1;
+    if (!ensure_bc7_tables(ctx)) return 0;
+    const uint32_t* d = static_cast<const uint32_t*>(ctx->etc1s_bc7_tables.p);
+    const size_t n = bu::kEtc1sBc7TableWords - 128;
+    return fetch(ctx, h_out, d, n * sizeof(uint32_t)) && fetch(ctx, h_midpoints, d + n, 128 * sizeof(uint32_t)) ? 1 : 0;
+}
+
+int bu_hip_k_transcode_etc1s_image_counted(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
+                                           const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, void* d_out,
+                                           uint32_t pitch_px, uint32_t rows_px, uint32_t decode_flags, uint32_t* out_invalid_blocks) {
+    return transcode_image_counted(ctx, kImageFamily, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out, pitch_px,
+                                   rows_px, decode_flags, out_invalid_blocks);
+}
+
+int bu_hip_k_transcode_etc1s_image(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
+                                   const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, void* d_out,
+                                   uint32_t pitch_px, uint32_t rows_px, uint32_t decode_flags) {
+    return transcode_image_checked(ctx, kImageFamily, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out, pitch_px,
+                                   rows_px, decode_flags);
+}
+
+int bu_hip_k_transcode_etc1s_images(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
+                                    uint64_t n_indices, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target, uint32_t decode_flags, void* d_out, size_t out_bytes,
+                                    uint32_t* out_invalid_per_slice) {
+    return transcode_images(ctx, kImageFamily, "transcode_etc1s_images", d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, n_indices, slices, n_slices, target, decode_flags, d_out,
+                            out_bytes, out_invalid_per_slice);
 }
 
 } // extern "C"

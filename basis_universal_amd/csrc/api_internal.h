@@ -48,6 +48,7 @@ struct bu_hip_context {
     hipStream_t walk_stream = nullptr; hipEvent_t walk_join = nullptr; uint32_t walk_cus = 0;
     arena refine_lists;                   // the sorted candidate lists of refine_endpoint_clusterization (etc1s_refine_kernels.hip, k_refine_sort_lists)
     arena etc1s_bc1_tables;               // the ETC1S -> BC1 endpoint tables (api_etc1s_transcode.cpp), built by the first BC1 transcode of the context
+    arena etc1s_bc7_tables;               // the ETC1S -> BC7 colour look-up and the mode-5 encoder's midpoints, built by the first BC7 transcode
     const void* d_pixel_blocks = nullptr; // resident tiles (a1): 64 B per block
     size_t total_blocks = 0;
     arena pixel_arena;                    // owns the tiles when they were uploaded through bu_hip_set_pixel_blocks
@@ -140,6 +141,9 @@ inline int upload_slice_table(bu_hip_context* ctx, const bu::slice_table& t, upl
 // every refusal the two whole-file transcoders share (api_transcode_slices.cpp): nothing is touched when it returns 0
 int transcode_slices_check(bu_hip_context* ctx, bu::slice_table& t, const char* fn, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint64_t n_inputs, uint32_t target,
                            bool etc1s, const void* d_out, size_t out_bytes);
+// the same for an ETC1S table under the eight targets of bu_hip_k_transcode_etc1s_images (texture) or the six of bu_hip_k_transcode_etc1s_slices
+int etc1s_slices_check(bu_hip_context* ctx, bu::slice_table& t, const char* fn, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint64_t n_inputs, uint32_t target,
+                       bool texture, const void* d_out, size_t out_bytes);
 
 struct device_guard {
     int prev = -1; bool ok = false;

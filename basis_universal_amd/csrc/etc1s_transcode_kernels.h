@@ -9,7 +9,8 @@ namespace bu {
 
 enum : uint32_t { kBc1TableEntries = 8 * 32 * 6 * 10 };   // per endpoint width: intensity tables x 5-bit base values x selector ranges x selector mappings
 // the reference's transcoder_texture_format values of the targets that exist here
-enum : uint32_t { ETF_ETC1_RGB = 0, ETF_BC1_RGB = 2, ETF_RGBA32 = 13, ETF_RGB565 = 14, ETF_BGR565 = 15, ETF_RGBA4444 = 16 };
+enum : uint32_t { ETF_ETC1_RGB = 0, ETF_ETC2_RGBA = 1, ETF_BC1_RGB = 2, ETF_BC7_RGBA = 6, ETF_RGBA32 = 13, ETF_RGB565 = 14, ETF_BGR565 = 15, ETF_RGBA4444 = 16 };
+enum : uint32_t { kEtc1sBc7TableWords = 8 * 32 * 6 * 10 + 128 };   // the ETC1S -> BC7 colour look-up and the mode-5 encoder's midpoints (etc1s_texture_targets.h)
 
 struct etc1s_transcode_args {
     const uint32_t* endpoint_palette;   // r5 | g5 << 8 | b5 << 16 | intensity table << 24
@@ -18,6 +19,7 @@ struct etc1s_transcode_args {
     void* out;
     uint32_t* invalid;                  // device counter
     const uint32_t* bc1_endpoints;      // BC1 only: 2 * kBc1TableEntries words from launch_etc1s_build_bc1_tables
+    const uint32_t* bc7_tables;         // BC7 only: kEtc1sBc7TableWords words from launch_etc1s_build_bc7_tables
     uint32_t n_endpoints, n_selectors;
     tile_geometry g;
 };
@@ -28,20 +30,24 @@ struct etc1s_transcode_slices_args {
     const uint16_t *endpoint_idx, *selector_idx;   // slice s reads [first_block, first_block + nbx * nby) of both, its alpha slice the same from alpha_first_block
     uint8_t* out;                                  // slice s writes at out + out_offset
     uint32_t* invalid;                             // n_slices device counters
-    const uint32_t* bc1_endpoints;
+    const uint32_t *bc1_endpoints, *bc7_tables;
     const bu_hip_transcode_slice* slices;          // device copies of the records, every zero size replaced by what it stands for
     const uint32_t* prefix;                        // n_slices + 1 entries: where each slice's blocks begin among the total_blocks of the call
     uint32_t n_endpoints, n_selectors, n_slices, total_blocks;
 };
 
-uint32_t etc1s_transcode_unit_bytes(uint32_t target);   // per block for block targets, per pixel for pixel targets; 0 = the target does not exist here
+uint32_t etc1s_transcode_unit_bytes(uint32_t target);   // per block for block targets, per pixel for pixel targets; 0 = not a target of the first six (ETC1, BC1, pixels)
+uint32_t etc1s_texture_unit_bytes(uint32_t target);     // the same over all eight targets: also 16 for ETC2 RGBA and BC7 RGBA
 bool etc1s_transcode_is_pixel_target(uint32_t target);
 // one launch; d_invalid is cleared first and afterwards holds how many blocks had an index past its palette (their output is zero-filled)
-hipError_t launch_transcode_etc1s(hipStream_t st, const etc1s_transcode_args& a, uint32_t target);
+// chroma_filter: BC7 only, the reference's default
+hipError_t launch_transcode_etc1s(hipStream_t st, const etc1s_transcode_args& a, uint32_t target, bool chroma_filter = false);
 // one launch over every slice of the table; invalid[n_slices] is cleared first and afterwards holds the per-slice counts
-hipError_t launch_transcode_etc1s_slices(hipStream_t st, const etc1s_transcode_slices_args& a, uint32_t target);
+hipError_t launch_transcode_etc1s_slices(hipStream_t st, const etc1s_transcode_slices_args& a, uint32_t target, bool chroma_filter = false);
 // fills d_tables[2 * kBc1TableEntries] with the ETC1S -> BC1 endpoint tables (5-bit, then 6-bit)
 hipError_t launch_etc1s_build_bc1_tables(hipStream_t st, uint32_t* d_tables);
+// fills d_tables[kEtc1sBc7TableWords]
+hipError_t launch_etc1s_build_bc7_tables(hipStream_t st, uint32_t* d_tables);
 // counts the entries of idx[n] that are >= limit into *d_count (cleared first)
 hipError_t launch_etc1s_count_indices_past(hipStream_t st, const uint16_t* idx, uint32_t n, uint32_t limit, uint32_t* d_count, bool clear);
 

@@ -5,6 +5,8 @@
 // one 16-byte (RGBA32) or 8-byte (16-bit formats) word per row where the row is whole and aligned. An index past its palette never reaches a gather: the block is
 // zero-filled and counted with a vector atomic, and it does not stop the others. Two kernels share that per-block work: one image per launch, and every image of
 // a file in one launch through a slice table (tile_raster.h), counted per slice.
+// The 16-byte targets (ETC2 RGBA, BC7 mode 5) store one uint4 per block; their conversions are etc1s_texture_targets.h's. BC7's chroma filter is a second template
+// parameter, so the unfiltered instance carries none of the encoder.
 #include <hip/hip_runtime.h>
 #include "etc1s_device.h"
 #include "etc1s_transcode_kernels.h"
@@ -107,6 +109,11 @@ __device__ __forceinline__ uint2 to_bc1(const etc1s_entry& e, uint32_t sel, cons
     return make_uint2(l | (h << 16), bits);
 }
 
+}  // namespace bu
+#include "etc1s_texture_targets.h"
+namespace bu {
+static_assert(kBc7TableWords == kEtc1sBc7TableWords, "the header's size of the BC7 tables");
+
 // one pixel of a pixel target from the block colour (r | g << 8 | b << 16) and the alpha value (transcoder.cpp:9155-9332; the 4444 colour pass ORs onto the alpha pass)
 template <uint32_t TARGET>
 __device__ __forceinline__ uint32_t pack_pixel(uint32_t c, uint32_t a) {
@@ -119,19 +126,20 @@ __device__ __forceinline__ uint32_t pack_pixel(uint32_t c, uint32_t a) {
 
 // what every block of a launch reads besides its own indices
 struct etc1s_palettes {
-    const uint32_t *endpoint_palette, *selector_palette, *bc1_endpoints;
+    const uint32_t *endpoint_palette, *selector_palette, *bc1_endpoints, *bc7_tables;
     uint32_t n_endpoints, n_selectors;
 };
 
 // One block: the range check, the gathers, the target's conversion, the store. The four index pointers are the IMAGE's (alpha: both null = opaque), `out` is where
 // the image's output begins, `i` the block's place in the image's raster order. Block targets write one uint2 at out[i]; pixel targets the four rows of the tile
 // cropped to width x min(height, rows) (store_tile_row, tile_raster.h). false = an index was past its palette and zeros were written.
-// Both kernels below are this function behind their own indexing.
-template <uint32_t TARGET>
+// Both kernels below are this function behind their own indexing. FILTER: BC7's chroma filter.
+template <uint32_t TARGET, bool FILTER>
 __device__ __forceinline__ bool transcode_etc1s_block(const etc1s_palettes& a, const uint16_t* endpoint_idx, const uint16_t* selector_idx, const uint16_t* alpha_endpoint_idx,
                                                       const uint16_t* alpha_selector_idx, void* out, uint32_t i, const tile_geometry& g) {
     constexpr bool kPixels = TARGET == ETF_RGBA32 || TARGET == ETF_RGB565 || TARGET == ETF_BGR565 || TARGET == ETF_RGBA4444;
-    constexpr bool kAlpha = TARGET == ETF_RGBA32 || TARGET == ETF_RGBA4444;
+    constexpr bool kWide = TARGET == ETF_ETC2_RGBA || TARGET == ETF_BC7_RGBA;   // 16 bytes per block: bytes 0-7 from the alpha slice (BC7: its alpha fields)
+    constexpr bool kAlpha = TARGET == ETF_RGBA32 || TARGET == ETF_RGBA4444 || kWide;
     const uint32_t ei = endpoint_idx[i], si = selector_idx[i];
     bool ok = ei < a.n_endpoints && si < a.n_selectors;
     uint32_t aei = 0, asi = 0;
@@ -139,6 +147,26 @@ __device__ __forceinline__ bool transcode_etc1s_block(const etc1s_palettes& a, c
     if (has_alpha) {
         aei = alpha_endpoint_idx[i]; asi = alpha_selector_idx[i];
         ok = ok && aei < a.n_endpoints && asi < a.n_selectors;
+    }
+    if (kWide) {
+        uint4 o = make_uint4(0u, 0u, 0u, 0u);
+        if (ok) {
+            const uint32_t entry = a.endpoint_palette[ei], sel = a.selector_palette[si];
+            const etc1s_entry e = unpack_entry(entry);
+            if (TARGET == ETF_ETC2_RGBA) {
+                const uint2 alpha = has_alpha ? to_eac_a8(unpack_entry(a.endpoint_palette[aei]), a.selector_palette[asi]) : opaque_eac_a8(), rgb = to_etc1(e, sel);
+                o = make_uint4(alpha.x, alpha.y, rgb.x, rgb.y);
+            } else {
+                bc7_m5 b = to_bc7_m5_color(e, sel, a.bc7_tables);
+                if (FILTER)
+                    b = bc7_chroma_filter(b, a.endpoint_palette, a.n_endpoints, endpoint_idx, entry, i % g.nbx, i / g.nbx, g.nbx, g.nby,
+                                          reinterpret_cast<const float*>(a.bc7_tables + kBc7ColorEntries));
+                if (has_alpha) bc7_m5_alpha(b, unpack_entry(a.endpoint_palette[aei]), a.selector_palette[asi]);
+                o = make_uint4((uint32_t)b.lo, (uint32_t)(b.lo >> 32), (uint32_t)b.hi, (uint32_t)(b.hi >> 32));
+            }
+        }
+        ((uint4*)out)[i] = o;
+        return ok;
     }
     if (!kPixels) {
         uint2 o = make_uint2(0u, 0u);
@@ -181,24 +209,24 @@ __device__ __forceinline__ bool transcode_etc1s_block(const etc1s_palettes& a, c
     return ok;
 }
 
-template <uint32_t TARGET>
+template <uint32_t TARGET, bool FILTER>
 __global__ __launch_bounds__(256) void transcode_etc1s_kernel(etc1s_transcode_args a) {
     const uint32_t n = a.g.nbx * a.g.nby, i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const etc1s_palettes p = { a.endpoint_palette, a.selector_palette, a.bc1_endpoints, a.n_endpoints, a.n_selectors };
-    if (!transcode_etc1s_block<TARGET>(p, a.endpoint_idx, a.selector_idx, a.alpha_endpoint_idx, a.alpha_selector_idx, a.out, i, a.g)) atomicAdd(a.invalid, 1u);
+    const etc1s_palettes p = { a.endpoint_palette, a.selector_palette, a.bc1_endpoints, a.bc7_tables, a.n_endpoints, a.n_selectors };
+    if (!transcode_etc1s_block<TARGET, FILTER>(p, a.endpoint_idx, a.selector_idx, a.alpha_endpoint_idx, a.alpha_selector_idx, a.out, i, a.g)) atomicAdd(a.invalid, 1u);
 }
 
 // every image of a file in one launch (bu_hip_k_transcode_etc1s_slices): find_transcode_slice (tile_raster.h) in front of the same block function. The colour and the
 // alpha slice of an image are two ranges of the same two index arrays.
-template <uint32_t TARGET>
+template <uint32_t TARGET, bool FILTER>
 __global__ __launch_bounds__(256) void transcode_etc1s_slices_kernel(etc1s_transcode_slices_args a) {
     transcode_slice_view v;
     if (!find_transcode_slice(a.slices, a.prefix, a.n_slices, a.total_blocks, blockIdx.x * 256u + threadIdx.x, v)) return;
-    const etc1s_palettes p = { a.endpoint_palette, a.selector_palette, a.bc1_endpoints, a.n_endpoints, a.n_selectors };
+    const etc1s_palettes p = { a.endpoint_palette, a.selector_palette, a.bc1_endpoints, a.bc7_tables, a.n_endpoints, a.n_selectors };
     const bool alpha = v.alpha_first_block != BU_HIP_NO_ALPHA_SLICE;
-    if (!transcode_etc1s_block<TARGET>(p, a.endpoint_idx + v.first_block, a.selector_idx + v.first_block, alpha ? a.endpoint_idx + v.alpha_first_block : nullptr,
-                                       alpha ? a.selector_idx + v.alpha_first_block : nullptr, a.out + v.out_offset, v.local, v.g))
+    if (!transcode_etc1s_block<TARGET, FILTER>(p, a.endpoint_idx + v.first_block, a.selector_idx + v.first_block, alpha ? a.endpoint_idx + v.alpha_first_block : nullptr,
+                                               alpha ? a.selector_idx + v.alpha_first_block : nullptr, a.out + v.out_offset, v.local, v.g))
         atomicAdd(a.invalid + v.slice, 1u);
 }
 
@@ -237,28 +265,66 @@ __global__ __launch_bounds__(256) void etc1s_build_bc1_tables_kernel(uint32_t* t
     tables[idx] = best_lo | (best_hi << 8) | (best_err << 16);
 }
 
+// The colour look-up of to_bc7_m5_color, [intensity table][base5][range][mapping] -> lo | hi << 8 | min(error, 65535) << 16 over 7-bit endpoints, and behind it the
+// encoder's 128 midpoints. The search is the BC1 tables' (hi outermost, lo innermost, first minimum; bc7_color_table() of the tool on the host), over BC7's four
+// colours (weights 0, 21, 43, 64 of 64, rounded), and with the errors of selectors 0 and 3 counted five times for the widest intensity table over the whole range.
+__global__ __launch_bounds__(256) void etc1s_build_bc7_tables_kernel(uint32_t* tables) {
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= kBc7TableWords) return;
+    if (idx >= kBc7ColorEntries) { tables[idx] = __float_as_uint(mode5_midpoint(idx - kBc7ColorEntries)); return; }
+    const uint32_t m = idx % 10u, r = (idx / 10u) % 6u, g = (idx / 60u) % 32u, t = idx / 1920u;
+    const int base = scale5((int)g);
+    int block[4];
+#pragma unroll
+    for (int s = 0; s < 4; s++) block[s] = clamp255(base + inten_delta((int)t, s));
+    const uint32_t s0 = ke_bc1_ranges[r * 2], s1 = ke_bc1_ranges[r * 2 + 1];
+    const uint32_t m0 = ke_bc1_mappings[m * 4], m1 = ke_bc1_mappings[m * 4 + 1], m2 = ke_bc1_mappings[m * 4 + 2], m3 = ke_bc1_mappings[m * 4 + 3];
+    const uint32_t ends_weight = (t == 7u && s0 == 0u && s1 == 3u) ? 5u : 1u;
+    uint32_t best_err = 0xFFFFFFFFu, best_lo = 0, best_hi = 0;
+    for (uint32_t hi = 0; hi < 128u; hi++)
+        for (uint32_t lo = 0; lo < 128u; lo++) {
+            uint32_t c[4];
+            c[0] = from_7(lo);
+            c[3] = from_7(hi);
+            c[1] = (c[0] * 43u + c[3] * 21u + 32u) / 64u;
+            c[2] = (c[0] * 21u + c[3] * 43u + 32u) / 64u;
+            const uint32_t mapped[4] = { pick4(c, m0), pick4(c, m1), pick4(c, m2), pick4(c, m3) };
+            uint32_t err = 0;
+#pragma unroll
+            for (uint32_t s = 0; s < 4; s++) {
+                const int d = block[s] - (int)mapped[s];
+                if (s >= s0 && s <= s1) err += (uint32_t)(d * d) * ((s == 0u || s == 3u) ? ends_weight : 1u);
+            }
+            if (err < best_err) { best_err = err; best_lo = lo; best_hi = hi; }
+        }
+    tables[idx] = best_lo | (best_hi << 8) | ((best_err < 0xFFFFu ? best_err : 0xFFFFu) << 16);
+}
+
 __global__ __launch_bounds__(256) void etc1s_count_indices_past_kernel(const uint16_t* idx, uint32_t n, uint32_t limit, uint32_t* count) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i < n && idx[i] >= limit) atomicAdd(count, 1u);
 }
 
-template <uint32_t TARGET>
+template <uint32_t TARGET, bool FILTER = false>
 static hipError_t launch(hipStream_t st, const etc1s_transcode_args& a) {
     const uint32_t n = a.g.nbx * a.g.nby;
-    hipLaunchKernelGGL((transcode_etc1s_kernel<TARGET>), dim3((n + 255) / 256), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((transcode_etc1s_kernel<TARGET, FILTER>), dim3((n + 255) / 256), dim3(256), 0, st, a);
     return hipGetLastError();
 }
-template <uint32_t TARGET>
+template <uint32_t TARGET, bool FILTER = false>
 static hipError_t launch(hipStream_t st, const etc1s_transcode_slices_args& a) {
-    hipLaunchKernelGGL((transcode_etc1s_slices_kernel<TARGET>), dim3((a.total_blocks + 255) / 256), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((transcode_etc1s_slices_kernel<TARGET, FILTER>), dim3((a.total_blocks + 255) / 256), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
 // the instance of either kernel for the target
 template <class Args>
-static hipError_t launch_for_target(hipStream_t st, const Args& a, uint32_t target) {
+static hipError_t launch_for_target(hipStream_t st, const Args& a, uint32_t target, bool chroma_filter) {
     if (target == ETF_BC1_RGB && !a.bc1_endpoints) return hipErrorInvalidValue;
+    if (target == ETF_BC7_RGBA && !a.bc7_tables) return hipErrorInvalidValue;
     switch (target) {
+    case ETF_ETC2_RGBA: return launch<ETF_ETC2_RGBA>(st, a);
+    case ETF_BC7_RGBA: return chroma_filter ? launch<ETF_BC7_RGBA, true>(st, a) : launch<ETF_BC7_RGBA, false>(st, a);
     case ETF_ETC1_RGB: return launch<ETF_ETC1_RGB>(st, a);
     case ETF_BC1_RGB: return launch<ETF_BC1_RGB>(st, a);
     case ETF_RGBA32: return launch<ETF_RGBA32>(st, a);
@@ -277,22 +343,28 @@ uint32_t etc1s_transcode_unit_bytes(uint32_t target) {
     default: return 0;
     }
 }
+uint32_t etc1s_texture_unit_bytes(uint32_t target) { return target == ETF_ETC2_RGBA || target == ETF_BC7_RGBA ? 16u : etc1s_transcode_unit_bytes(target); }
 bool etc1s_transcode_is_pixel_target(uint32_t target) { return target == ETF_RGBA32 || target == ETF_RGB565 || target == ETF_BGR565 || target == ETF_RGBA4444; }
 
-hipError_t launch_transcode_etc1s(hipStream_t st, const etc1s_transcode_args& a, uint32_t target) {
+hipError_t launch_transcode_etc1s(hipStream_t st, const etc1s_transcode_args& a, uint32_t target, bool chroma_filter) {
     hipError_t e = hipMemsetAsync(a.invalid, 0, sizeof(uint32_t), st);
     if (e != hipSuccess || !a.g.nbx || !a.g.nby) return e;
-    return launch_for_target(st, a, target);
+    return launch_for_target(st, a, target, chroma_filter);
 }
 
-hipError_t launch_transcode_etc1s_slices(hipStream_t st, const etc1s_transcode_slices_args& a, uint32_t target) {
+hipError_t launch_transcode_etc1s_slices(hipStream_t st, const etc1s_transcode_slices_args& a, uint32_t target, bool chroma_filter) {
     hipError_t e = hipMemsetAsync(a.invalid, 0, (size_t)a.n_slices * sizeof(uint32_t), st);
     if (e != hipSuccess || !a.n_slices || !a.total_blocks) return e;
-    return launch_for_target(st, a, target);
+    return launch_for_target(st, a, target, chroma_filter);
 }
 
 hipError_t launch_etc1s_build_bc1_tables(hipStream_t st, uint32_t* d_tables) {
     hipLaunchKernelGGL(etc1s_build_bc1_tables_kernel, dim3((2u * kBc1TableEntries + 255) / 256), dim3(256), 0, st, d_tables);
+    return hipGetLastError();
+}
+
+hipError_t launch_etc1s_build_bc7_tables(hipStream_t st, uint32_t* d_tables) {
+    hipLaunchKernelGGL(etc1s_build_bc7_tables_kernel, dim3((kBc7TableWords + 255) / 256), dim3(256), 0, st, d_tables);
     return hipGetLastError();
 }
 

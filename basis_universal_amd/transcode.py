@@ -9,6 +9,9 @@ ETC1S files have their own three functions at the end of this module (`read_etc1
 (ETC1S_BYTES_PER_BLOCK / ETC1S_BYTES_PER_PIXEL): the serial half -- containers, Huffman tables, palettes, the per-slice symbol walk -- is host code in
 libbasisu_frontend.so (csrc/host/etc1s_decode.cpp, needs no GPU), the texel half is one HIP kernel launch per image (csrc/etc1s_transcode_kernels.hip).
 
+`transcode_etc1s_texture`, `transcode_etc1s_textures` and `etc1s_texture_layout` are a parallel ETC1S family with two more targets, ETC2 RGBA and BC7 RGBA (16 bytes
+per block, ETC1S_TEXTURE_BYTES_PER_BLOCK), and BC7's chroma filter as an option; the three functions above keep their six targets and their refusals.
+
 `transcode_file_images` and `transcode_etc1s_file_images` (the last section) are the whole-file forms: every image of a file -- levels x layers x faces -- by ONE
 launch over a slice table, into one allocation whose layout `image_layout` gives.
 """
@@ -250,6 +253,9 @@ def transcode_file(ctx, data, target, *, level=0, layer=0, face=0, high_quality=
 ETC1_RGB, RGB565, BGR565, RGBA4444 = 0, 14, 15, 16   # with BC1_RGB and RGBA32 above: the ETC1S transcoder's targets (transcoder_texture_format values)
 ETC1S_BYTES_PER_BLOCK = {ETC1_RGB: 8, BC1_RGB: 8}
 ETC1S_BYTES_PER_PIXEL = {RGBA32: 4, RGB565: 2, BGR565: 2, RGBA4444: 2}
+ETC2_RGBA = 1
+ETC1S_TEXTURE_BYTES_PER_BLOCK = {ETC1_RGB: 8, BC1_RGB: 8, ETC2_RGBA: 16, BC7_RGBA: 16}   # the targets of transcode_etc1s_texture*; the pixel targets are ETC1S_BYTES_PER_PIXEL's
+DECODE_FLAGS_NO_ETC1S_CHROMA_FILTERING = 64   # cDecodeFlagsNoETC1SChromaFiltering: the one decode flag of the ETC1S texture entries
 _TARGET_NAMES = ["ETC1_RGB", "ETC2_RGBA", "BC1_RGB", "BC3_RGBA", "BC4_R", "BC5_RG", "BC7_RGBA", "BC7_ALT", "PVRTC1_4_RGB", "PVRTC1_4_RGBA", "ASTC_4x4_RGBA", "ATC_RGB", "ATC_RGBA",
                  "RGBA32", "RGB565", "BGR565", "RGBA4444", "FXT1_RGB", "PVRTC2_4_RGB", "PVRTC2_4_RGBA", "ETC2_EAC_R11", "ETC2_EAC_RG11"]
 
@@ -338,28 +344,37 @@ def transcode_etc1s_image(ctx, decoded, image, target, *, out_device=None, out_r
     """One image of decode_etc1s_file's result on the GPU. Block targets (ETC1S_BYTES_PER_BLOCK) return (num_blocks, 8) u8, pixel targets (ETC1S_BYTES_PER_PIXEL)
     the (height, width, 4) u8 raster for RGBA32 and the (height, width) u16 raster for the 16-bit formats; with out_device (room for out_rows x out_row_pitch
     pixels when those are given) the output stays there and None is returned."""
-    target = _check_etc1s_target(target)
+    return _transcode_etc1s_image(ctx, decoded, image, _check_etc1s_target(target), None, out_device, out_row_pitch, out_rows)
+
+
+def _transcode_etc1s_image(ctx, decoded, image, target, decode_flags, out_device, out_row_pitch, out_rows):
+    """transcode_etc1s_image (decode_flags None: bu_hip_k_transcode_etc1s_counted) and transcode_etc1s_texture_image (bu_hip_k_transcode_etc1s_image_counted)"""
+    texture = decode_flags is not None
     nbx, nby, w, h = image["num_blocks_x"], image["num_blocks_y"], image["width"], image["height"]
     ep_pal = np.ascontiguousarray(decoded["endpoint_palette"], np.uint8).reshape(-1, 4)
     sel_pal = np.ascontiguousarray(decoded["selector_palette"], np.uint32).reshape(-1)
-    with_alpha = image["alpha_endpoint_indices"] is not None and target in (RGBA32, RGBA4444)
+    with_alpha = image["alpha_endpoint_indices"] is not None and target in (RGBA32, RGBA4444, ETC2_RGBA, BC7_RGBA)
     names = ["endpoint_indices", "selector_indices"] + (["alpha_endpoint_indices", "alpha_selector_indices"] if with_alpha else [])
+    output_bytes = ctx.lib.etc1s_image_output_bytes if texture else ctx.lib.etc1s_transcode_output_bytes
     held = []
-    with _output(ctx, out_device, out_row_pitch, out_rows, lambda: ctx.lib.etc1s_transcode_output_bytes(nbx, nby, w, h, target, 0, 0)) as d_out:
+    with _output(ctx, out_device, out_row_pitch, out_rows, lambda: output_bytes(nbx, nby, w, h, target, 0, 0)) as d_out:
         try:
             for a in [ep_pal, sel_pal] + [np.ascontiguousarray(image[k], np.uint16).reshape(-1) for k in names]:
                 held.append(ctx.upload(a))
             d_alpha = (held[4], held[5]) if with_alpha else (None, None)
             invalid = C.c_uint32(0)
-            ctx.check(ctx.lib.k_transcode_etc1s_counted(ctx.h, C.c_void_p(held[0]), ep_pal.shape[0], C.c_void_p(held[1]), sel_pal.size, C.c_void_p(held[2]), C.c_void_p(held[3]),
-                                                        C.c_void_p(d_alpha[0]), C.c_void_p(d_alpha[1]), nbx, nby, w, h, target, C.c_void_p(d_out), int(out_row_pitch),
-                                                        int(out_rows), C.byref(invalid)), "transcode_etc1s")
+            args = (ctx.h, C.c_void_p(held[0]), ep_pal.shape[0], C.c_void_p(held[1]), sel_pal.size, C.c_void_p(held[2]), C.c_void_p(held[3]), C.c_void_p(d_alpha[0]),
+                    C.c_void_p(d_alpha[1]), nbx, nby, w, h, target, C.c_void_p(d_out), int(out_row_pitch), int(out_rows))
+            if texture:
+                ctx.check(ctx.lib.k_transcode_etc1s_image_counted(*args, int(decode_flags), C.byref(invalid)), "transcode_etc1s_image")
+            else:
+                ctx.check(ctx.lib.k_transcode_etc1s_counted(*args, C.byref(invalid)), "transcode_etc1s")
             if invalid.value:
                 raise ValueError(f"{invalid.value} of {nbx * nby} blocks have an index past its palette")
             if out_device is not None:
                 return None
-            if target in ETC1S_BYTES_PER_BLOCK:
-                return ctx.download(d_out, (nbx * nby, 8), np.uint8)
+            if target in ETC1S_TEXTURE_BYTES_PER_BLOCK:
+                return ctx.download(d_out, (nbx * nby, ETC1S_TEXTURE_BYTES_PER_BLOCK[target]), np.uint8)
             return ctx.download(d_out, (h, w, 4), np.uint8) if target == RGBA32 else ctx.download(d_out, (h, w), np.uint16)
         finally:
             for p in held:
@@ -376,6 +391,42 @@ def transcode_etc1s_file(ctx, data, target, *, level=0, layer=0, face=0):
     raise ValueError(f"the file has no image at level {level}, layer {layer}, face {face}")
 
 
+# ---------------------------------------------------------------- the ETC1S texture family: also ETC2 RGBA and BC7 RGBA
+
+def _check_etc1s_texture_target(target):
+    target = int(target)
+    if target not in ETC1S_TEXTURE_BYTES_PER_BLOCK and target not in ETC1S_BYTES_PER_PIXEL:
+        name = _TARGET_NAMES[target] if 0 <= target < len(_TARGET_NAMES) else "unknown"
+        raise ValueError(f"ETC1S texture target {target} ({name}) is not supported (supported: {sorted(list(ETC1S_TEXTURE_BYTES_PER_BLOCK) + list(ETC1S_BYTES_PER_PIXEL))})")
+    return target
+
+
+def etc1s_decode_flags(*, chroma_filtering=True, decode_flags=None):
+    """the decode_flags word of the ETC1S texture entries: 64 (no chroma filtering) is the only bit there is; an explicit decode_flags with any other bit raises"""
+    flags = (0 if chroma_filtering else DECODE_FLAGS_NO_ETC1S_CHROMA_FILTERING) if decode_flags is None else int(decode_flags)
+    if flags & ~DECODE_FLAGS_NO_ETC1S_CHROMA_FILTERING:
+        raise ValueError(f"ETC1S decode flags 0x{flags:x}: bits 0x{flags & ~DECODE_FLAGS_NO_ETC1S_CHROMA_FILTERING:x} are not supported (supported: 64, "
+                         "cDecodeFlagsNoETC1SChromaFiltering)")
+    return flags
+
+
+def transcode_etc1s_texture_image(ctx, decoded, image, target, *, chroma_filtering=True, out_device=None, out_row_pitch=0, out_rows=0):
+    """transcode_etc1s_image over the texture family's targets: the six of transcode_etc1s_image, byte for byte the same, plus ETC2_RGBA -- the EAC A8 block of the
+    alpha slice, then the ETC1 block of the colour slice -- and BC7_RGBA -- one mode-5 block, by default behind the reference's chroma filter (chroma_filtering=False
+    is its -no_etc1s_chroma_filtering). Block targets return (num_blocks, 8 | 16) u8; an image without an alpha slice gets the opaque alpha half."""
+    return _transcode_etc1s_image(ctx, decoded, image, _check_etc1s_texture_target(target), etc1s_decode_flags(chroma_filtering=chroma_filtering), out_device, out_row_pitch, out_rows)
+
+
+def transcode_etc1s_texture(ctx, data, target, *, level=0, layer=0, face=0, chroma_filtering=True):
+    """One image of an ETC1S .basis / .ktx2 file as a texture of the family's targets (transcode_etc1s_texture_image): decoded on the host, transcoded on the GPU."""
+    target, flags = _check_etc1s_texture_target(target), etc1s_decode_flags(chroma_filtering=chroma_filtering)
+    decoded = decode_etc1s_file(data)
+    for im in decoded["images"]:
+        if (im["level"], im["layer"], im["face"]) == (level, layer, face):
+            return _transcode_etc1s_image(ctx, decoded, im, target, flags, None, 0, 0)
+    raise ValueError(f"the file has no image at level {level}, layer {layer}, face {face}")
+
+
 # ---------------------------------------------------------------- every image of a file in one launch
 
 NO_ALPHA_SLICE = 2 ** 64 - 1   # BU_HIP_NO_ALPHA_SLICE
@@ -386,12 +437,21 @@ class TranscodeSlice(C.Structure):   # = bu_hip_transcode_slice, include/basisu_
                [(n, C.c_uint32) for n in ("num_blocks_x", "num_blocks_y", "orig_width", "orig_height", "out_row_pitch_pixels", "out_rows_pixels")]
 
 
+def etc1s_texture_layout(images, target):
+    """image_layout for the ETC1S texture family (transcode_etc1s_textures): block targets are (blocks, 8 | 16) u8 by ETC1S_TEXTURE_BYTES_PER_BLOCK. Host only."""
+    return _layout(images, _check_etc1s_texture_target(target), ETC1S_TEXTURE_BYTES_PER_BLOCK, True)
+
+
 def image_layout(images, target, *, etc1s):
     """Where the whole-file calls put each image of a file: `images` is the "images" list of read_uastc_file (etc1s=False) or of read_etc1s_file / decode_etc1s_file
     (etc1s=True). -> ([{"offset", "nbytes", "shape", "dtype"} per image, in the list's order], total_bytes): the images packed in order, each rounded up to 16
     bytes. A block target is (blocks, bytes per block) u8; a pixel target the tight raster of the image's own size, (height, width, 4) u8 for RGBA32 and
     (height, width) u16 for ETC1S' 16-bit formats. Host only."""
     target = _check_etc1s_target(target) if etc1s else _check_uastc_target(target)
+    return _layout(images, target, ETC1S_BYTES_PER_BLOCK if etc1s else BYTES_PER_BLOCK, etc1s)
+
+
+def _layout(images, target, bytes_per_block, etc1s):
     layout, at = [], 0
     for im in images:
         n, w, h = im["num_blocks_x"] * im["num_blocks_y"], im["width"], im["height"]
@@ -401,7 +461,7 @@ def image_layout(images, target, *, etc1s):
         elif not etc1s and target == RGBA32:
             shape, dtype, nbytes = (h, w, 4), np.uint8, w * h * 4
         else:
-            unit = ETC1S_BYTES_PER_BLOCK[target] if etc1s else BYTES_PER_BLOCK[target]
+            unit = bytes_per_block[target]
             shape, dtype, nbytes = (n, unit), np.uint8, n * unit
         layout.append({"offset": at, "nbytes": nbytes, "shape": shape, "dtype": dtype})
         at += (nbytes + 15) & ~15
@@ -488,10 +548,21 @@ def transcode_etc1s_file_images(ctx, data, target, *, out_device=None):
     return _transcode_etc1s_slices(ctx, decoded, images, [im["_first"] for im in images], [im["_alpha_first"] if im["has_alpha"] else None for im in images], target, out_device)
 
 
-def _transcode_etc1s_slices(ctx, decoded, images, firsts, alpha_firsts, target, out_device):
+def transcode_etc1s_textures(ctx, data, target, *, chroma_filtering=True, out_device=None):
+    """transcode_etc1s_file_images over the texture family's targets (bu_hip_k_transcode_etc1s_images): every image of the file in one launch, each what
+    transcode_etc1s_texture returns for it. With out_device (room for etc1s_texture_layout's total_bytes) the output stays there -- a block target's part of it goes
+    straight into unpack_blocks -- and etc1s_texture_layout(images, target) is returned."""
+    target, flags = _check_etc1s_texture_target(target), etc1s_decode_flags(chroma_filtering=chroma_filtering)
+    decoded = _decode_etc1s(data, False, whole=True)
+    images = decoded["images"]
+    return _transcode_etc1s_slices(ctx, decoded, images, [im["_first"] for im in images], [im["_alpha_first"] if im["has_alpha"] else None for im in images], target, out_device,
+                                   flags)
+
+
+def _transcode_etc1s_slices(ctx, decoded, images, firsts, alpha_firsts, target, out_device, decode_flags=None):
     """transcode_etc1s_file_images behind the decode (_decode_etc1s with whole=True): `images` (sizes) with where each one's indices begin in the file's whole
-    arrays. stats.py decodes an alpha slice as a colour image of its own this way."""
-    layout, total = image_layout(images, target, etc1s=True)
+    arrays. stats.py decodes an alpha slice as a colour image of its own this way. decode_flags not None: the texture family's entry and layout."""
+    layout, total = image_layout(images, target, etc1s=True) if decode_flags is None else etc1s_texture_layout(images, target)
     recs = _slice_table(images, layout, firsts, alpha_firsts)
     ep_pal = np.ascontiguousarray(decoded["endpoint_palette"], np.uint8).reshape(-1, 4)
     sel_pal = np.ascontiguousarray(decoded["selector_palette"], np.uint32).reshape(-1)
@@ -502,8 +573,11 @@ def _transcode_etc1s_slices(ctx, decoded, images, firsts, alpha_firsts, target, 
             held.append(_upload_async(ctx, a))
 
         def call(d_out, out_bytes, invalid):
-            ctx.check(ctx.lib.k_transcode_etc1s_slices(ctx.h, C.c_void_p(held[0]), ep_pal.shape[0], C.c_void_p(held[1]), sel_pal.size, C.c_void_p(held[2]), C.c_void_p(held[3]),
-                                                       ep_idx.size, recs, len(images), target, d_out, out_bytes, invalid), "transcode_etc1s_slices")
+            head = (ctx.h, C.c_void_p(held[0]), ep_pal.shape[0], C.c_void_p(held[1]), sel_pal.size, C.c_void_p(held[2]), C.c_void_p(held[3]), ep_idx.size, recs, len(images), target)
+            if decode_flags is None:
+                ctx.check(ctx.lib.k_transcode_etc1s_slices(*head, d_out, out_bytes, invalid), "transcode_etc1s_slices")
+            else:
+                ctx.check(ctx.lib.k_transcode_etc1s_images(*head, int(decode_flags), d_out, out_bytes, invalid), "transcode_etc1s_images")
         return _run_slices(ctx, call, images, layout, total, out_device, "ETC1S")
     finally:
         for p in held:

@@ -470,6 +470,36 @@ BU_HIP_API int bu_hip_k_transcode_etc1s_slices(bu_hip_context*, const void* d_en
 /* bytes one record occupies from its out_offset for `target` (0 = target not supported by that codec) */
 BU_HIP_API size_t bu_hip_transcode_slice_extent(const bu_hip_transcode_slice*, uint32_t target, int etc1s);
 
+/* The ETC1S transcoder's second entry family: the three entries above with a decode_flags word, and two more targets. The first family keeps its six targets and
+ * its refusals; these take
+ *   cTFETC1_RGB (0), cTFBC1_RGB (2), cTFRGBA32 (13), cTFRGB565 (14), cTFBGR565 (15), cTFRGBA4444 (16): byte for byte what the first family writes;
+ *   cTFETC2_RGBA (1): 16 bytes per block, bytes 0-7 the EAC A8 block of the alpha slice (convert_etc1s_to_etc2_eac_a8, transcoder/basisu_transcoder.cpp:4786), bytes
+ *     8-15 the ETC1 block of the colour slice;
+ *   cTFBC7_RGBA (6): one mode-5 block (convert_etc1s_to_bc7_m5_color :4310, the chroma filter chroma_filter_bc7_mode5 :4641 with its mode-5 encoder :8102, then
+ *     convert_etc1s_to_bc7_m5_alpha :4472), bit for bit the reference's.
+ * Without an alpha slice (both alpha pointers NULL, or BU_HIP_NO_ALPHA_SLICE) the two 16-byte targets write the opaque alpha half / opaque alpha fields; with one,
+ * its indices are range-checked like the colour slice's. d_out of a 16-byte target must be 16-byte aligned.
+ * BC3_RGBA, BC4_R and BC5_RG are refused: their look-up could not be restated as a search.
+ * decode_flags: 64 (cDecodeFlagsNoETC1SChromaFiltering) turns BC7's chroma filter off; any other bit is refused by name. The filter reads the endpoint indices of
+ * the eight blocks around a block; one that is past the palette contributes the centre block's own entry (and is itself zero-filled and counted).
+ * The ETC1S -> BC7 colour look-up is built on the device by the first BC7 transcode of a context (bu_hip_etc1s_bc7_color_table copies it, 15,360 words
+ * [intensity table 8][base5 32][selector range 6][mapping 10] -> lo | hi << 8 | min(error, 65535) << 16, and the encoder's 128 float midpoints to the host; tests
+ * compare them with tools/gen_etc1s_transcode_tables.py's host computation). Everything else is as for the first family, refusals included. */
+BU_HIP_API int bu_hip_k_transcode_etc1s_image(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette, uint32_t n_selectors,
+        const void* d_endpoint_idx, const void* d_selector_idx, const void* d_alpha_endpoint_idx, const void* d_alpha_selector_idx, uint32_t num_blocks_x, uint32_t num_blocks_y,
+        uint32_t orig_width, uint32_t orig_height, uint32_t target, void* d_out, uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels, uint32_t decode_flags);
+BU_HIP_API int bu_hip_k_transcode_etc1s_image_counted(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette, uint32_t n_selectors,
+        const void* d_endpoint_idx, const void* d_selector_idx, const void* d_alpha_endpoint_idx, const void* d_alpha_selector_idx, uint32_t num_blocks_x, uint32_t num_blocks_y,
+        uint32_t orig_width, uint32_t orig_height, uint32_t target, void* d_out, uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels, uint32_t decode_flags,
+        uint32_t* out_invalid_blocks);
+BU_HIP_API int bu_hip_k_transcode_etc1s_images(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette, uint32_t n_selectors,
+        const void* d_endpoint_idx, const void* d_selector_idx, uint64_t n_indices, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target,
+        uint32_t decode_flags, void* d_out, size_t out_bytes, uint32_t* out_invalid_per_slice);
+BU_HIP_API size_t bu_hip_etc1s_image_output_bytes(uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height, uint32_t target,
+        uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
+BU_HIP_API size_t bu_hip_etc1s_image_slice_extent(const bu_hip_transcode_slice*, uint32_t target);
+BU_HIP_API int bu_hip_etc1s_bc7_color_table(bu_hip_context*, uint32_t* h_out, uint32_t* h_midpoints);
+
 /* gpu_image::unpack(encoder/basisu_gpu_texture.cpp:1218-1266) over resident blocks: what a GPU samples from a BC1 / BC3 / BC4 / BC5 / BC7 texture, as RGBA8.
  * format: the transcoder_texture_format value the transcoders above take as a target -- cTFBC1_RGB (2), cTFBC3_RGBA (3), cTFBC4_R (4), cTFBC5_RG (5), cTFBC7_RGBA (6);
  * any other fails with an error that names it. d_blocks: num_blocks_x * num_blocks_y blocks of 8 (BC1, BC4) or 16 bytes in raster order, aligned to their size;

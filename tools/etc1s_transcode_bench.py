@@ -2,7 +2,9 @@
 """Reading one ETC1S file back, timed: the 4096x4096 synthetic image compressed at quality 128 (compress(), .basis), then
   host   decode_etc1s_file: containers, tables, palettes and the slice walk (wall time, best of 3), and
   device the transcode kernel per target: palettes and indices resident in HBM, 5 warm-up + 50 timed launches, measured with the library's HIP events around the launch
-         (bu_hip_profile_*), with the algorithmic bytes (4 B of indices in + the target's bytes out per block) over time as a fraction of the 8 TB/s HBM figure.
+         (bu_hip_profile_*), with the algorithmic bytes (4 B of indices in + the target's bytes out per block) over time as a fraction of the 8 TB/s HBM figure,
+         and the whole call (launch, stream wait, read-back of the counter) on the host's clock, median of the timed calls. ETC2 RGBA and BC7 go through
+         bu_hip_k_transcode_etc1s_image_counted; BC7 is timed with and without the chroma filter.
 Also prints the RGB PSNR of the file read back (RGBA32) against the source: the figure README quotes for "the file after the backend's RDO".
 Prints one line per figure and one JSON line.   tools/etc1s_transcode_bench.py [steps] [warmup] [size]"""
 import ctypes as C
@@ -23,6 +25,7 @@ from basis_universal_amd.compress import compress  # noqa: E402
 HBM_BYTES_PER_S = 8e12
 TARGETS = [("rgba32", transcode.RGBA32, 64), ("etc1", transcode.ETC1_RGB, 8), ("bc1", transcode.BC1_RGB, 8), ("rgb565", transcode.RGB565, 32), ("bgr565", transcode.BGR565, 32),
            ("rgba4444", transcode.RGBA4444, 32)]
+TEXTURE_TARGETS = [("etc2_rgba", transcode.ETC2_RGBA, 16, 0), ("bc7_filtered", transcode.BC7_RGBA, 16, 0), ("bc7_unfiltered", transcode.BC7_RGBA, 16, transcode.DECODE_FLAGS_NO_ETC1S_CHROMA_FILTERING)]
 
 
 def main():
@@ -52,24 +55,30 @@ def main():
     d = [ctx.upload(ep), ctx.upload(sel), ctx.upload(im["endpoint_indices"]), ctx.upload(im["selector_indices"])]
     d_out = ctx.alloc(n * 64)
     rows = {}
-    for name, target, out_bytes in TARGETS:
+    for name, target, out_bytes, flags in [t + (None,) for t in TARGETS] + TEXTURE_TARGETS:
         def launch():
             invalid = C.c_uint32(0)
-            ctx.check(ctx.lib.k_transcode_etc1s_counted(ctx.h, C.c_void_p(d[0]), ep.shape[0], C.c_void_p(d[1]), sel.size, C.c_void_p(d[2]), C.c_void_p(d[3]), None, None, nbx, nby,
-                                                        size, size, target, C.c_void_p(d_out), 0, 0, C.byref(invalid)), "transcode_etc1s")
+            head = (ctx.h, C.c_void_p(d[0]), ep.shape[0], C.c_void_p(d[1]), sel.size, C.c_void_p(d[2]), C.c_void_p(d[3]), None, None, nbx, nby, size, size, target, C.c_void_p(d_out), 0, 0)
+            if flags is None:
+                ctx.check(ctx.lib.k_transcode_etc1s_counted(*head, C.byref(invalid)), "transcode_etc1s")
+            else:
+                ctx.check(ctx.lib.k_transcode_etc1s_image_counted(*head, flags, C.byref(invalid)), "transcode_etc1s_image")
             assert invalid.value == 0
         for _ in range(warmup):
             launch()
         ctx.profile_enable(True)
+        calls = []
         for _ in range(steps):
+            t0 = time.perf_counter()
             launch()
+            calls.append((time.perf_counter() - t0) * 1e3)
         ms, launches = ctx.profile_read()["etc1s_transcode"]
         ctx.profile_enable(False)
         assert launches == steps
         ms /= steps
         traffic = n * (4 + out_bytes)
-        rows[name] = {"ms": round(ms, 4), "gblocks_per_s": round(n / ms / 1e6, 2), "algorithmic_mb": round(traffic / 1e6, 1), "fraction_of_8tbps": round(traffic / (ms * 1e-3) / HBM_BYTES_PER_S, 4)}
-        print(f"{name:9s} {ms:8.4f} ms  {n / ms / 1e6:7.2f} Gblocks/s  {traffic / 1e6:6.1f} MB  {100 * traffic / (ms * 1e-3) / HBM_BYTES_PER_S:6.2f} % of 8 TB/s", flush=True)
+        rows[name] = {"ms": round(ms, 4), "call_ms": round(float(np.median(calls)), 4), "gblocks_per_s": round(n / ms / 1e6, 2), "algorithmic_mb": round(traffic / 1e6, 1), "fraction_of_8tbps": round(traffic / (ms * 1e-3) / HBM_BYTES_PER_S, 4)}
+        print(f"{name:14s} {ms:8.4f} ms  call {np.median(calls):8.4f} ms  {n / ms / 1e6:7.2f} Gblocks/s  {traffic / 1e6:6.1f} MB  {100 * traffic / (ms * 1e-3) / HBM_BYTES_PER_S:6.2f} % of 8 TB/s", flush=True)
     for p in d + [d_out]:
         ctx.free(p)
     ctx.close()

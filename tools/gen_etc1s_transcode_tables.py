@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The look-up tables of the ETC1S -> BC1 block conversion (etc1s_transcode_kernels.hip), computed from the two formats' definitions. The small ones are generated into
+"""The look-up tables of the ETC1S -> BC1, -> EAC A8 and -> BC7 mode 5 block conversions (etc1s_transcode_kernels.hip), computed from the formats' definitions. The small ones are generated into
 basis_universal_amd/csrc/etc1s_transcode_tables.inc. The two endpoint tables (15,360 entries each) are NOT committed as numbers: the library computes them on the device
 the first time a context transcodes to BC1 (etc1s_build_bc1_tables_kernel, the same search as endpoint_table() below, which the golden generator and the tests use as the
 host-side statement of it).
@@ -19,7 +19,12 @@ shows (tests/golden/etc1s_transcode_vectors.npz, whose coverage member hits ever
 Also: for solid blocks the endpoint pair whose colour 1 (2/3 hi + 1/3 lo) is nearest a value, with a small penalty on the endpoints' distance; and for two-colour
 blocks of the widest table the endpoint nearest a value.
 
+EAC A8 (the alpha half of ETC2 RGBA) and BC7 mode 5: eac_a8_table(), bc7_color_table(), bc7_alpha_table() and bc7_solid_table() below state their searches. The EAC,
+BC7 alpha and BC7 solid tables go into the .inc; the BC7 colour table (15,360 entries) is built on the device like BC1's. tests/golden/etc1s_texture_vectors.npz,
+whose coverage member reaches every entry a block can reach, decides the tie rules.
+
 usage: gen_etc1s_transcode_tables.py [--check]     (--check: regenerate in memory and compare with the committed file)"""
+import functools
 import pathlib
 import sys
 
@@ -77,6 +82,108 @@ def solid_table(bits, sel):
     return out.reshape(-1)
 
 
+ALPHA_RANGES = [(0, 3), (1, 3), (0, 2), (1, 2)]   # the selector ranges of the EAC A8 look-up; a block of one selector never gets there, any other range reads entry 0
+EAC_MODIFIERS = np.array([[-3, -6, -9, -15, 2, 5, 8, 14], [-3, -7, -10, -13, 2, 6, 9, 12], [-2, -5, -8, -13, 1, 4, 7, 12], [-2, -4, -6, -13, 1, 3, 5, 12],
+                          [-3, -6, -8, -12, 2, 5, 7, 11], [-3, -7, -9, -11, 2, 6, 8, 10], [-4, -7, -8, -11, 3, 6, 7, 10], [-3, -5, -8, -11, 2, 4, 7, 10],
+                          [-2, -6, -8, -10, 1, 5, 7, 9], [-2, -5, -8, -10, 1, 4, 7, 9], [-2, -4, -8, -10, 1, 3, 7, 9], [-2, -5, -7, -10, 1, 4, 6, 9],
+                          [-3, -4, -7, -10, 2, 3, 6, 9], [-1, -2, -3, -10, 0, 1, 2, 9], [-4, -6, -8, -9, 3, 5, 7, 8], [-3, -5, -7, -9, 2, 4, 6, 8]])   # ETC2 EAC, table 3.17.2 of the Khronos data format spec
+
+
+def eac_a8_values():
+    """(256 * 15 * 16, 8): the eight values of an EAC A8 block, row (base * 15 + multiplier - 1) * 16 + table: clamp(base + multiplier * modifier). Multiplier 0 is
+    left out of the search."""
+    base, mul, table = np.meshgrid(np.arange(256), np.arange(1, 16), np.arange(16), indexing="ij")
+    return np.clip(base.reshape(-1, 1) + mul.reshape(-1, 1) * EAC_MODIFIERS[table.reshape(-1)], 0, 255)
+
+
+def nearest_value_table(values, ranges, code_bits, ends_weighted):
+    """[inten][base5][range] -> (row of `values`, trans): the candidate row whose values are nearest the ETC1S block's in-range colours, each colour on its nearest
+    value (first minimum in code order), the squared differences summed; first minimum over the rows in their order. trans holds the code chosen for ETC1S selector
+    s at bits code_bits * s, zero for a selector outside the range. ends_weighted: the widest intensity table over the whole selector range counts the errors of
+    selectors 0 and 3 five times (there the two clamp to 0 or 255 and the block is about those)."""
+    v = values.astype(np.int16)
+    near_err = np.zeros((256, v.shape[0]), np.int32)
+    near_code = np.zeros((256, v.shape[0]), np.uint8)
+    base = expand(5)
+    blocks = np.clip(base[None, :, None] + INTEN[:, None, :], 0, 255)   # (8, 32, 4)
+    for c in np.unique(blocks):
+        d = np.abs(v - np.int16(c))
+        near_code[c] = d.argmin(1)
+        near_err[c] = d.min(1)
+    near_err *= near_err
+    rows = np.zeros((8, 32, len(ranges)), np.uint32)
+    trans = np.zeros_like(rows)
+    for t in range(8):
+        for g in range(32):
+            for r, (s0, s1) in enumerate(ranges):
+                five = ends_weighted and t == 7 and (s0, s1) == (0, 3)
+                err = sum(near_err[blocks[t, g, s]] * (5 if five and s in (0, 3) else 1) for s in range(s0, s1 + 1))
+                k = int(err.argmin())
+                rows[t, g, r] = k
+                trans[t, g, r] = sum(int(near_code[blocks[t, g, s], k]) << (code_bits * s) for s in range(s0, s1 + 1))
+    return rows, trans
+
+
+@functools.lru_cache(maxsize=None)
+def eac_a8_table():
+    """[inten][base5][range] -> base | (table | multiplier << 4) << 8 | trans << 16, the ETC1S -> EAC A8 look-up: the block's first two bytes, then the 3-bit code of
+    each ETC1S selector. Search order: base outermost, then multiplier 1..15, table innermost, first minimum -- the loop order of the reference's generator, which the
+    tool's output on the coverage file confirms."""
+    rows, trans = nearest_value_table(eac_a8_values(), ALPHA_RANGES, 3, False)
+    base, mul, table = rows // 240, (rows // 16) % 15 + 1, rows % 16
+    return (base | ((table | mul << 4) << 8) | (trans << 16)).astype(np.uint32).reshape(-1)
+
+
+def bc7_values(e):
+    """(n * n, 4): the four colours of a BC7 2-bit index between endpoints hi (outer) and lo (inner) of the expanded values e: weights 0, 21, 43, 64 of 64, rounded"""
+    hi, lo = np.meshgrid(e, e, indexing="ij")
+    hi, lo = hi.reshape(-1), lo.reshape(-1)
+    return np.stack([lo, (lo * 43 + hi * 21 + 32) // 64, (lo * 21 + hi * 43 + 32) // 64, hi], -1)
+
+
+@functools.lru_cache(maxsize=None)
+def bc7_color_table():
+    """[inten][base5][range][mapping] -> lo | hi << 8 | min(err, 65535) << 16, the ETC1S -> BC7 mode 5 colour look-up: 7-bit endpoints, expanded (c << 1) | (c >> 6).
+    As endpoint_table() (hi outermost, lo innermost, first minimum), except that the widest intensity table over the whole selector range counts the errors of
+    selectors 0 and 3 five times: there the two clamp to 0 or 255 and the block is about those."""
+    v = np.arange(128)
+    colors = bc7_values((v << 1) | (v >> 6)).astype(np.int32)
+    base = expand(5)
+    out = np.zeros((8, 32, len(RANGES), len(MAPPINGS)), np.uint32)
+    for t in range(8):
+        block = np.clip(base[:, None] + INTEN[t][None, :], 0, 255).astype(np.int32)
+        sq = {(s, k): (block[:, s][:, None] - colors[:, k][None, :]) ** 2 for s in range(4) for k in range(4)}   # (32, 16384) each
+        for r, (s0, s1) in enumerate(RANGES):
+            five = t == 7 and (s0, s1) == (0, 3)
+            for m, mapping in enumerate(MAPPINGS):
+                err = sum(sq[s, mapping[s]] * (5 if five and s in (0, 3) else 1) for s in range(s0, s1 + 1))
+                best = err.argmin(1)
+                out[t, :, r, m] = (best % 128) | ((best // 128) << 8) | (np.minimum(err[np.arange(32), best], 0xFFFF) << 16)
+    return out.reshape(-1)
+
+
+@functools.lru_cache(maxsize=None)
+def bc7_alpha_table():
+    """[inten][base5][range] -> lo | hi << 8 | trans << 16, the ETC1S -> BC7 mode 5 alpha look-up: 8-bit endpoints, hi outermost, lo innermost, first minimum; each
+    in-range selector goes to its nearest of the four values (first minimum), its 2-bit index at bits 2 s of trans; same five-fold weight as the colour table."""
+    rows, trans = nearest_value_table(bc7_values(np.arange(256)), RANGES, 2, True)
+    return ((rows % 256) | ((rows // 256) << 8) | (trans << 16)).astype(np.uint32).reshape(-1)
+
+
+@functools.lru_cache(maxsize=None)
+def bc7_solid_table():
+    """[value] {hi, lo}: the 7-bit endpoints whose index-1 colour (21/64 of the way from lo to hi) is nearest the value: lo outermost, hi innermost, first minimum"""
+    v = np.arange(128)
+    e = (v << 1) | (v >> 6)
+    lo, hi = np.meshgrid(e, e, indexing="ij")
+    c1 = ((lo * 43 + hi * 21 + 32) >> 6).reshape(-1)
+    out = np.zeros((256, 2), np.uint8)
+    for i in range(256):
+        k = int(np.abs(c1 - i).argmin())
+        out[i] = (k % 128, k // 128)
+    return out.reshape(-1)
+
+
 def emit(name, ctype, values, per_line, comment, fmt):
     lines = [f"// {comment}", f"BU_TAB {ctype} {name}[{values.size}] = {{"]
     for i in range(0, values.size, per_line):
@@ -96,6 +203,9 @@ def generate():
         for s in range(4):
             xlat[m, 0, s] = linear_to_bc1[mapping[s]]
             xlat[m, 1, s] = inverted[linear_to_bc1[mapping[s]]]
+    alpha_range_index = np.zeros((4, 4), np.uint8)
+    for i, (a, b) in enumerate(ALPHA_RANGES):
+        alpha_range_index[a, b] = i
     parts = [
         "// GENERATED by tools/gen_etc1s_transcode_tables.py from the ETC1S and BC1 format definitions -- do not edit. Tables of the ETC1S -> BC1 block conversion.",
         "// BU_TAB is defined by the includer: `static const` on the host, `static __device__ const` under hipcc.",
@@ -107,6 +217,12 @@ def generate():
         emit("ke_bc1_solid6", "unsigned char", solid_table(6, 1), 32, "the same, 6-bit", "%2u"),
         emit("ke_bc1_end5", "unsigned char", solid_table(5, 0)[0::2], 32, "[value]: the 5-bit endpoint nearest the value", "%2u"),
         emit("ke_bc1_end6", "unsigned char", solid_table(6, 0)[0::2], 32, "the same, 6-bit", "%2u"),
+        "// Tables of the ETC1S -> EAC A8 and ETC1S -> BC7 mode 5 block conversions. The selector ranges and mappings of BC7 are BC1's above. The BC7 colour look-up",
+        "// (15,360 entries) is not here: etc1s_build_bc7_tables_kernel computes it on the device, bc7_color_table() of the tool is the same search on the host.",
+        emit("ke_alpha_range_index", "unsigned char", alpha_range_index.reshape(-1), 16, "[lowest selector][highest selector] -> selector range of the EAC A8 look-up; a range it does not have reads entry 0", "%u"),
+        emit("ke_eac_a8", "unsigned int", eac_a8_table(), 8, "[inten][base5][range] -> base | (table | multiplier << 4) << 8 | 3-bit code of selector s << (16 + 3 s)", "0x%07x"),
+        emit("ke_bc7_alpha", "unsigned int", bc7_alpha_table(), 8, "[inten][base5][range] -> lo | hi << 8 | 2-bit index of selector s << (16 + 2 s)", "0x%06x"),
+        emit("ke_bc7_solid", "unsigned char", bc7_solid_table(), 32, "[value] {hi, lo}: 7-bit endpoints whose index-1 colour is nearest the value", "%3u"),
     ]
     return "\n".join(parts) + "\n"
 
