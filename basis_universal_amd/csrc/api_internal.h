@@ -141,6 +141,9 @@ inline int upload_slice_table(bu_hip_context* ctx, const bu::slice_table& t, upl
 // every refusal the two whole-file transcoders share (api_transcode_slices.cpp): nothing is touched when it returns 0
 int transcode_slices_check(bu_hip_context* ctx, bu::slice_table& t, const char* fn, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint64_t n_inputs, uint32_t target,
                            bool etc1s, const void* d_out, size_t out_bytes);
+// the same for a UASTC table under the fourteen targets of bu_hip_k_transcode_uastc_textures
+int uastc_texture_slices_check(bu_hip_context* ctx, bu::slice_table& t, const char* fn, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint64_t n_inputs,
+                               uint32_t target, const void* d_out, size_t out_bytes);
 // the same for an ETC1S table under the eight targets of bu_hip_k_transcode_etc1s_images (texture) or the six of bu_hip_k_transcode_etc1s_slices
 int etc1s_slices_check(bu_hip_context* ctx, bu::slice_table& t, const char* fn, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint64_t n_inputs, uint32_t target,
                        bool texture, const void* d_out, size_t out_bytes);

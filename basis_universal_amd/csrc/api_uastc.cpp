@@ -107,6 +107,103 @@ int bu_hip_k_transcode_uastc_slices(bu_hip_context* ctx, const void* d_blocks, u
     return out_invalid_per_slice ? read_back(ctx, out_invalid_per_slice, d.counters, (size_t)table.n * sizeof(uint32_t)) : 1;
 }
 
+// ---- the texture family: the two entries above with the further targets of uastc_transcode.h (ETC1, ETC2 RGBA, EAC R11 / RG11, the 16-bit rasters). The first
+// family keeps its seven targets and its refusals; these run the same code behind their own target list, flag check and names.
+static const char* const kUastcTextureTargets = "ETC1_RGB 0, ETC2_RGBA 1, BC1_RGB 2, BC3_RGBA 3, BC4_R 4, BC5_RG 5, BC7_RGBA 6, ASTC_4x4_RGBA 10, RGBA32 13, RGB565 14, BGR565 15, "
+                                                "RGBA4444 16, ETC2_EAC_R11 20, ETC2_EAC_RG11 21";
+
+// the refusals both texture entries share, before any pointer is looked at: the target, then every decode flag but cDecodeFlagsHighQuality, each by its name
+static int uastc_texture_ok(bu_hip_context* ctx, const char* fn, uint32_t target, uint32_t decode_flags) {
+    if (!bu::uastc_texture_unit_bytes(target)) {
+        set_error(ctx, "%s: target %u (%s) is not supported (supported: %s)", fn, target, transcoder_format_name(target), kUastcTextureTargets);
+        return 0;
+    }
+    const uint32_t refused = decode_flags & ~32u;
+    if (refused) {
+        static const struct { uint32_t bit; const char* name; } flags[] = {
+            { 2, "cDecodeFlagsPVRTCDecodeToNextPow2" }, { 4, "cDecodeFlagsTranscodeAlphaDataToOpaqueFormats" }, { 8, "cDecodeFlagsBC1ForbidThreeColorBlocks" },
+            { 16, "cDecodeFlagsOutputHasAlphaIndices" }, { 64, "cDecodeFlagsNoETC1SChromaFiltering" }, { 128, "cDecodeFlagsNoDeblockFiltering" },
+            { 512, "cDecodeFlagsForceDeblockFiltering" }, { 1024, "cDecodeFlagXUASTCLDRDisableFastBC7Transcoding" } };
+        char names[320] = "";
+        uint32_t unnamed = refused;
+        for (const auto& f : flags)
+            if (refused & f.bit) {
+                snprintf(names + strlen(names), sizeof(names) - strlen(names), "%s%s", names[0] ? ", " : "", f.name);
+                unnamed &= ~f.bit;
+            }
+        if (unnamed) snprintf(names + strlen(names), sizeof(names) - strlen(names), "%sunnamed bits 0x%x", names[0] ? ", " : "", unnamed);
+        set_error(ctx, "%s: decode_flags 0x%x: %s not supported (supported: 32, cDecodeFlagsHighQuality)", fn, decode_flags, names);
+        return 0;
+    }
+    return 1;
+}
+
+size_t bu_hip_uastc_texture_output_bytes(uint32_t nbx, uint32_t nby, uint32_t orig_width, uint32_t orig_height, uint32_t target, uint32_t out_row_pitch_pixels,
+                                         uint32_t out_rows_pixels) {
+    return bu::raster_output_bytes(bu::tile_geometry{ nbx, nby, orig_width, orig_height, out_row_pitch_pixels, out_rows_pixels }, bu::uastc_texture_unit_bytes(target),
+                                   bu::uastc_texture_is_pixel_target(target));
+}
+
+int bu_hip_k_transcode_uastc_texture(bu_hip_context* ctx, const void* d_blocks, uint32_t nbx, uint32_t nby, uint32_t orig_width, uint32_t orig_height, uint32_t target,
+                                     uint32_t decode_flags, int32_t channel0, int32_t channel1, void* d_out, uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels,
+                                     uint32_t* out_invalid_blocks) {
+    if (!ctx) return 0;
+    static const char* const fn = "transcode_uastc_texture";
+    if (out_invalid_blocks) *out_invalid_blocks = 0;
+    if (!uastc_texture_ok(ctx, fn, target, decode_flags)) return 0;
+    if (channel0 > 3 || channel1 > 3) { set_error(ctx, "%s: channel out of range", fn); return 0; }
+    bu::tile_geometry geo;
+    if (!checked(ctx, [&](bu::err_text e) {
+            return bu::resolve_geometry(fn, nbx, nby, orig_width, orig_height, out_row_pitch_pixels, out_rows_pixels, bu::kUastcOneImage, &geo, e);
+        })) return 0;
+    if (!bu::uastc_texture_is_pixel_target(target) && (out_row_pitch_pixels || out_rows_pixels)) {
+        set_error(ctx, "%s: row pitch %u / rows %u given for a block target (%s): they describe a pixel raster", fn, out_row_pitch_pixels, out_rows_pixels,
+                  transcoder_format_name(target));
+        return 0;
+    }
+    if (!nbx || !nby) return 1;   // no blocks: nothing is launched
+    if (!d_blocks || !d_out) { set_error(ctx, "%s: null device pointer", fn); return 0; }
+    const uint32_t unit = bu::uastc_texture_unit_bytes(target);
+    if (((uintptr_t)d_blocks & 15u) || ((uintptr_t)d_out & (unit - 1))) {   // a block is loaded, and a block or pixel stored, as whole words
+        set_error(ctx, "%s: the blocks must be 16-byte aligned and the output aligned to its %u-byte unit", fn, unit);
+        return 0;
+    }
+    device_guard g(ctx->device);
+    arena& counter = ctx->scratch[4];
+    BU_TRY(ctx, counter.reserve(sizeof(uint32_t)));
+    {
+        prof_scope ps(ctx, "uastc_transcode_texture");
+        BU_TRY(ctx, bu::launch_transcode_uastc(ctx->stream, d_blocks, geo, target, (decode_flags & 32u) != 0, channel0 < 0 ? 0u : (uint32_t)channel0,
+                                               channel1 < 0 ? 3u : (uint32_t)channel1, d_out, static_cast<uint32_t*>(counter.p), true));
+    }
+    uint32_t invalid = 0;
+    if (!read_back(ctx, &invalid, counter.p, sizeof(invalid))) return 0;
+    if (out_invalid_blocks) *out_invalid_blocks = invalid;
+    return 1;
+}
+
+int bu_hip_k_transcode_uastc_textures(bu_hip_context* ctx, const void* d_blocks, uint64_t n_blocks, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target,
+                                      uint32_t decode_flags, int32_t channel0, int32_t channel1, void* d_out, size_t out_bytes, uint32_t* out_invalid_per_slice) {
+    if (!ctx) return 0;
+    static const char* const fn = "transcode_uastc_textures";
+    if (!uastc_texture_ok(ctx, fn, target, decode_flags)) return 0;
+    if (!d_blocks) { set_error(ctx, "%s: null pointer", fn); return 0; }
+    if ((uintptr_t)d_blocks & 15u) { set_error(ctx, "%s: the blocks are not 16-byte aligned", fn); return 0; }
+    if (channel0 > 3 || channel1 > 3) { set_error(ctx, "%s: channel out of range", fn); return 0; }
+    bu::slice_table table;
+    if (!uastc_texture_slices_check(ctx, table, fn, slices, n_slices, n_blocks, target, d_out, out_bytes)) return 0;
+    device_guard g(ctx->device);
+    uploaded_slices d;
+    if (!upload_slice_table(ctx, table, d)) return 0;
+    {
+        prof_scope ps(ctx, fn);
+        BU_TRY(ctx, bu::launch_transcode_uastc_slices(ctx->stream, d_blocks, static_cast<const bu_hip_transcode_slice*>(d.records), d.prefix, table.n, table.total, target,
+                                                      (decode_flags & 32u) != 0, channel0 < 0 ? 0u : (uint32_t)channel0, channel1 < 0 ? 3u : (uint32_t)channel1, d_out,
+                                                      d.counters, true));
+    }
+    return out_invalid_per_slice ? read_back(ctx, out_invalid_per_slice, d.counters, (size_t)table.n * sizeof(uint32_t)) : 1;
+}
+
 void bu_hip_uastc_rdo_default_params(bu_uastc_rdo_params* p) {
     if (!p) return;
     p->m_lz_dict_size = 4096; p->m_lambda = 0.5f; p->m_max_allowed_rms_increase_ratio = 10.0f; p->m_skip_block_rms_thresh = 8.0f;

@@ -21,8 +21,6 @@ namespace bu {
 struct etc1s_entry { uint32_t r5, g5, b5, table; };
 __device__ __forceinline__ etc1s_entry unpack_entry(uint32_t e) { return etc1s_entry{ e & 31u, (e >> 8) & 31u, (e >> 16) & 31u, (e >> 24) & 7u }; }
 __device__ __forceinline__ uint32_t texel_selector(uint32_t sel, uint32_t x, uint32_t y) { return (sel >> (2u * (y * 4u + x))) & 3u; }
-// mul_8 (transcoder.cpp:269): an 8-bit value scaled to q
-__device__ __forceinline__ uint32_t mul_8(uint32_t v, uint32_t q) { v = v * q + 128u; return ((v + (v >> 8)) >> 8) & 255u; }
 
 // the four colours of an entry, r | g << 8 | b << 16 (get_block_colors5, transcoder.cpp:996-1010)
 __device__ __forceinline__ void block_colors(const etc1s_entry& e, uint32_t out[4]) {
@@ -119,9 +117,9 @@ template <uint32_t TARGET>
 __device__ __forceinline__ uint32_t pack_pixel(uint32_t c, uint32_t a) {
     const uint32_t r = c & 255u, g = (c >> 8) & 255u, b = c >> 16;
     if (TARGET == ETF_RGBA32) return c | (a << 24);
-    if (TARGET == ETF_RGB565) return (mul_8(r, 31) << 11) | (mul_8(g, 63) << 5) | mul_8(b, 31);
-    if (TARGET == ETF_BGR565) return (mul_8(b, 31) << 11) | (mul_8(g, 63) << 5) | mul_8(r, 31);
-    return (mul_8(r, 15) << 12) | (mul_8(g, 15) << 8) | (mul_8(b, 15) << 4) | mul_8(a, 15);   // RGBA4444
+    if (TARGET == ETF_RGB565) return pack_rgb565(r, g, b);   // mul_8 and the packs: tile_raster.h, shared with the UASTC transcoder
+    if (TARGET == ETF_BGR565) return pack_rgb565(b, g, r);
+    return pack_rgba4444(r, g, b, a);
 }
 
 // what every block of a launch reads besides its own indices

@@ -13,6 +13,17 @@ struct tile_geometry {
     uint32_t nbx, nby, width, height, pitch, rows;
 };
 
+// mul_8 (transcoder.cpp:269): an 8-bit value scaled to q, and on it the three 16-bit pixel formats of both transcoders' pixel targets (transcoder.cpp:9155-9332,
+// :10246-10302). Host and device: the UASTC core's host build packs the same pixels.
+#ifdef __HIPCC__
+#define BU_RASTER_FN __host__ __device__ __forceinline__
+#else
+#define BU_RASTER_FN static inline
+#endif
+BU_RASTER_FN uint32_t mul_8(uint32_t v, uint32_t q) { v = v * q + 128u; return ((v + (v >> 8)) >> 8) & 255u; }
+BU_RASTER_FN uint32_t pack_rgb565(uint32_t r, uint32_t g, uint32_t b) { return (mul_8(r, 31) << 11) | (mul_8(g, 63) << 5) | mul_8(b, 31); }
+BU_RASTER_FN uint32_t pack_rgba4444(uint32_t r, uint32_t g, uint32_t b, uint32_t a) { return (mul_8(r, 15) << 12) | (mul_8(g, 15) << 8) | (mul_8(b, 15) << 4) | mul_8(a, 15); }
+
 }  // namespace bu
 
 #ifdef __HIPCC__

@@ -8,11 +8,20 @@
 // weights, the void-extent block; BC7: mode / partition / endpoint / p-bit / index fields with the anchor convention; BC4: the 8-value ramp).
 // Same convention as uastc_core.h: hipcc compiles it for uastc_transcode_kernels.hip, g++ for the test-only host library (tests/native).
 //
-// Out of scope: ETC1 / ETC2 / EAC / PVRTC1 targets (mobile formats a CDNA GPU does not sample), the 16-bit pixel formats, ETC1S slices, UASTC HDR /
-// ASTC LDR / XUASTC blocks, Zstandard-supercompressed KTX2 levels. Callers refuse those; nothing is silently mapped to another target.
+//
+// The second half of the file is the texture family's further targets, the consumers of the encoder's ETC hints: transcode_uastc_to_etc1 (:16720) with
+// etc1_determine_selectors (:16616) and apply_etc1_bias, transcode_uastc_to_etc2_eac_a8 (:17629), transcode_uastc_to_etc2_rgba (:17706), pack_eac_solid_block /
+// pack_eac / pack_eac_high_quality (:18868-19155), transcode_uastc_to_etc2_eac_r11 / _rg11 (:19157-19214) and the three 16-bit cases of transcode_slice
+// (:10246-10302). The first family's callers (transcode_bytes_per_block) do not reach them.
+//
+// Out of scope: ETC1 from the alpha channel (cDecodeFlagsTranscodeAlphaDataToOpaqueFormats: the single-channel packer at :16925), PVRTC1 (needs neighbouring blocks
+// and power-of-two images), ATC / FXT1 / PVRTC2 (the reference refuses them for UASTC too), ETC1S slices, UASTC HDR / ASTC LDR / XUASTC blocks,
+// Zstandard-supercompressed KTX2 levels. Callers refuse those; nothing is silently mapped to another target.
 #pragma once
+#include <math.h>
 #include "uastc_rdo.h"
 #include "uastc_transcode_tables.inc"
+#include "tile_raster.h"
 
 namespace bu_uastc {
 
@@ -400,6 +409,261 @@ BU_FN_HD uint32_t transcode_bytes_per_block(uint32_t target) {   // 0: not a sup
     case TF_BC3_RGBA: case TF_BC5_RG: case TF_BC7_RGBA: case TF_ASTC_4x4_RGBA: return 16;
     case TF_RGBA32: return 64;
     default: return 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The texture family's further targets: ETC1, ETC2 RGBA, EAC R11 / RG11 and the 16-bit pixel formats. They are the consumers of the hints the encoder packs behind
+// the mode code (uastc_core.h computes them): ETC1 flip / diff / intensity tables / bias, the EAC table and multiplier, and a solid block's ETC1 colour and selector.
+// Everything is integer arithmetic but the one binary32 expression that places an EAC base value. The texels are the 16 packed dwords of transcode_bcn, every loop
+// over them is unrolled, and nothing is indexed at run time but the two constant tables (ku_eac_tables by table, the intensity values as immediates).
+// ------------------------------------------------------------------------------------------------------------------
+enum { TF_ETC1_RGB = 0, TF_ETC2_RGBA = 1, TF_RGB565 = 14, TF_BGR565 = 15, TF_RGBA4444 = 16, TF_ETC2_EAC_R11 = 20, TF_ETC2_EAC_RG11 = 21 };
+
+#if defined(__HIPCC__)
+#define BU_NOUNROLL _Pragma("nounroll")
+#else
+#define BU_NOUNROLL
+#endif
+
+// the hint fields of unpack_uastc with read_hints (transcoder.cpp:15325-15371) that the BC1 route does not read. A solid block: diff, inten0, selector and r / g / b
+// behind its colour; any other: flip, diff, the two intensity tables, the bias (modes that carry one) and the EAC byte (modes with alpha) behind the BC1 bits.
+struct etc_hints { uint32_t flip, diff, inten0, inten1, bias, etc2, selector, r, g, b; };
+BU_FN etc_hints read_etc_hints(const uint8_t* blk, uint32_t mode) {
+    etc_hints h = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    uint32_t ofs = ku_mode_code_len[mode];
+    if (mode == 8) {
+        const uint32_t v = (uint32_t)block_bits(blk, ofs + 32, 21);
+        h.diff = v & 1u; h.inten0 = (v >> 1) & 7u; h.selector = (v >> 4) & 3u; h.r = (v >> 6) & 31u; h.g = (v >> 11) & 31u; h.b = (v >> 16) & 31u;
+        return h;
+    }
+    ofs += (ku_mode_has_bc1_hint0[mode] ? 1u : 0u) + (ku_mode_has_bc1_hint1[mode] ? 1u : 0u);
+    const uint32_t v = (uint32_t)block_bits(blk, ofs, 21);
+    h.flip = v & 1u; h.diff = (v >> 1) & 1u; h.inten0 = (v >> 2) & 7u; h.inten1 = (v >> 5) & 7u;
+    uint32_t pos = 8;
+    if (ku_mode_has_etc1_bias[mode]) { h.bias = (v >> pos) & 31u; pos += 5; }
+    if (ku_mode_has_alpha[mode]) h.etc2 = (v >> pos) & 255u;
+    return h;
+}
+
+// ---- ETC1: transcode_uastc_to_etc1 (:16720-16807) with etc1_determine_selectors (:16616-16686). The block's eight bytes, byte k at bits 8 k.
+BU_FN uint32_t etc1_luma(uint32_t r, uint32_t g, uint32_t b) { return r * 54u + g * 183u + b * 19u; }
+// the three luma midpoints (sums of neighbouring block colours' luma) of a sub-block whose base colour is r, g, b (8 bits each)
+BU_FN void etc1_midpoints(int r, int g, int b, uint32_t table, uint32_t* mid) {
+    const int small = etc1_inten_small(table), large = etc1_inten_large(table);
+    const uint32_t y0 = etc1_luma((uint32_t)clampi(r - large, 0, 255), (uint32_t)clampi(g - large, 0, 255), (uint32_t)clampi(b - large, 0, 255));
+    const uint32_t y1 = etc1_luma((uint32_t)clampi(r - small, 0, 255), (uint32_t)clampi(g - small, 0, 255), (uint32_t)clampi(b - small, 0, 255));
+    const uint32_t y2 = etc1_luma((uint32_t)clampi(r + small, 0, 255), (uint32_t)clampi(g + small, 0, 255), (uint32_t)clampi(b + small, 0, 255));
+    const uint32_t y3 = etc1_luma((uint32_t)clampi(r + large, 0, 255), (uint32_t)clampi(g + large, 0, 255), (uint32_t)clampi(b + large, 0, 255));
+    mid[0] = y0 + y1; mid[1] = y1 + y2; mid[2] = y2 + y3;
+}
+BU_FN uint64_t etc1_solid(const etc_hints& h) {
+    const uint32_t b3 = (h.diff << 1) | (h.inten0 << 5) | (h.inten0 << 2);
+    const uint32_t r = h.diff ? h.r << 3 : (h.r | (h.r << 4)), g = h.diff ? h.g << 3 : (h.g | (h.g << 4)), b = h.diff ? h.b << 3 : (h.b | (h.b << 4));
+    const uint32_t sel = h.selector == 0 ? 0xFFFFFFFFu : (h.selector == 1 ? 0x0000FFFFu : (h.selector == 2 ? 0u : 0xFFFF0000u));   // s_etc1_solid_selectors
+    return (uint64_t)((r & 255u) | ((g & 255u) << 8) | ((b & 255u) << 16) | (b3 << 24)) | ((uint64_t)sel << 32);
+}
+BU_FN uint64_t etc1_from_hints(uint32_t mode, const etc_hints& h, const uint32_t* px) {
+    const bool flip = h.flip != 0, diff = h.diff != 0;
+    const uint32_t limit = diff ? 31u : 15u;
+    // sums over the four 2x2 quadrants, q[2 * (y >> 1) + (x >> 1)]: a sub-block is two of them, which two the flip bit says
+    uint32_t q[4][3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };
+    BU_UNROLL
+    for (int i = 0; i < 16; i++) {
+        BU_UNROLL
+        for (int c = 0; c < 3; c++) q[2 * (i >> 3) + ((i >> 1) & 1)][c] += (uint32_t)px_comp(px[i], c);
+    }
+    uint32_t col[2][3];
+    BU_UNROLL
+    for (int c = 0; c < 3; c++) {
+        const uint32_t s0 = q[0][c] + (flip ? q[1][c] : q[2][c]), s1 = q[3][c] + (flip ? q[2][c] : q[1][c]);
+        col[0][c] = (s0 * limit + 1020u) / 2040u;
+        col[1][c] = (s1 * limit + 1020u) / 2040u;
+        if (ku_mode_has_etc1_bias[mode]) {
+            col[0][c] = etc1_bias_apply(col[0][c], (uint32_t)c, h.bias, limit, 0);
+            col[1][c] = etc1_bias_apply(col[1][c], (uint32_t)c, h.bias, limit, 1);
+        }
+    }
+    uint32_t bytes = ((uint32_t)flip | ((uint32_t)diff << 1) | (h.inten0 << 5) | (h.inten1 << 2)) << 24;
+    int base[2][3];   // the two sub-blocks' base colours as the written block decodes them (decoder_etc_block::get_block_colors)
+    BU_UNROLL
+    for (int c = 0; c < 3; c++) {
+        if (diff) {
+            const int d = clampi((int)col[1][c] - (int)col[0][c], -4, 3);
+            bytes |= (((col[0][c] << 3) | (uint32_t)(d < 0 ? d + 8 : d)) & 255u) << (8 * c);
+            const int c1 = clampi((int)col[0][c] + d, 0, 31);
+            base[0][c] = (int)((col[0][c] << 3) | (col[0][c] >> 2));
+            base[1][c] = (c1 << 3) | (c1 >> 2);
+        } else {
+            bytes |= ((col[1][c] | (col[0][c] << 4)) & 255u) << (8 * c);
+            base[0][c] = (int)((col[0][c] << 4) | col[0][c]);
+            base[1][c] = (int)((col[1][c] << 4) | col[1][c]);
+        }
+    }
+    uint32_t mid0[3], mid1[3];
+    etc1_midpoints(base[0][0], base[0][1], base[0][2], h.inten0, mid0);
+    etc1_midpoints(base[1][0], base[1][1], base[1][2], h.inten1, mid1);
+    // texel (x, y) sits at bit x * 4 + y of both masks, whichever way the block is split; its luma is weighted twice the block colours'
+    uint32_t lmask = 0, hmask = 0;
+    BU_UNROLL
+    for (int i = 0; i < 16; i++) {
+        const int x = i & 3, y = i >> 2;
+        const bool second = flip ? y >= 2 : x >= 2;
+        const uint32_t l = (uint32_t)px_comp(px[i], 0) * 108u + (uint32_t)px_comp(px[i], 1) * 366u + (uint32_t)px_comp(px[i], 2) * 38u;
+        const uint32_t below = (l < (second ? mid1[0] : mid0[0]) ? 1u : 0u) + (l < (second ? mid1[1] : mid0[1]) ? 1u : 0u) + (l < (second ? mid1[2] : mid0[2]) ? 1u : 0u);
+        const uint32_t t = (0x3201u >> (4 * below)) & 3u;   // s_tran = { 1, 0, 2, 3 }
+        lmask |= (t & 1u) << (x * 4 + y);
+        hmask |= (t >> 1) << (x * 4 + y);
+    }
+    const uint32_t sel = (hmask >> 8) | ((hmask & 255u) << 8) | ((lmask >> 8) << 16) | ((lmask & 255u) << 24);   // bytes 4..7: h high, h low, l high, l low
+    return (uint64_t)bytes | ((uint64_t)sel << 32);
+}
+
+// ---- EAC: an eac_block (:1447-1497) as its eight bytes -- base, table | multiplier << 4, then the 48 selector bits most significant byte first. Texel (x, y) has its
+// three bits at 45 - 3 (x * 4 + y): s_etc2_eac_bit_ofs of pack_eac's raster order, and the a8 route's block_pixels[i & 3][i >> 2] at 45 - 3 i.
+BU_FN uint64_t eac_block(uint32_t base, uint32_t table, uint32_t mul, uint64_t sels48) {
+    return (uint64_t)(base & 255u) | ((uint64_t)((table & 15u) | ((mul & 15u) << 4)) << 8) | __builtin_bswap64(sels48);
+}
+BU_FN uint32_t eac_selector_shift(int i) { return 45u - 3u * (uint32_t)((i & 3) * 4 + (i >> 2)); }   // i: raster index
+enum : uint64_t { EAC_ALL_FOUR = 0x924924924924ull };   // g_etc2_eac_a8_sel4: every selector 4, the table's smallest positive step
+BU_FN void eac_table_values(uint32_t table, int* tv) {
+    const signed char* T = ku_eac_tables + (table & 15u) * 8;
+    BU_UNROLL
+    for (int s = 0; s < 8; s++) tv[s] = T[s];
+}
+// the base value that puts the table's span over [mn, mx]: (int)roundf(lerp(mn, mx, -table[3] / range)), binary32, every operation rounded on its own
+BU_FN int eac_center(const int* tv, uint32_t mn, uint32_t mx) {
+    const float range = (float)(tv[7] - tv[3]);
+    const float t = (float)(0 - tv[3]) / range;
+    const float a = (float)mn, b = (float)mx;
+    return (int)roundf(a + (b - a) * t);
+}
+// min over the eight selectors of |value - a| << 3 | selector: the nearest value, the lowest selector on a tie. clamped: the table's values clamp to 0..255 first.
+BU_FN uint32_t eac_nearest(const int* tv, int mul, int base, int a, bool clamped) {
+    uint32_t l = 0xFFFFFFFFu;
+    BU_UNROLL
+    for (int s = 0; s < 8; s++) {
+        int v = mul * tv[s] + base;
+        if (clamped) v = clampi(v, 0, 255);
+        v -= a;
+        const uint32_t e = ((uint32_t)(v < 0 ? -v : v) << 3) | (uint32_t)s;
+        l = e < l ? e : l;
+    }
+    return l;
+}
+
+// transcode_uastc_to_etc2_eac_a8 (:17629-17704) of a block that is not solid: the hint's table and multiplier (0 is computed through, as the release build does)
+BU_FN uint64_t eac_a8_from_hint(uint32_t mode, const etc_hints& h, const uint32_t* px) {
+    if (!ku_mode_has_alpha[mode]) return eac_block(255, 13, 1, EAC_ALL_FOUR);
+    uint32_t mn = 255, mx = 0;
+    BU_UNROLL
+    for (int i = 0; i < 16; i++) { const uint32_t a = px[i] >> 24; mn = a < mn ? a : mn; mx = a > mx ? a : mx; }
+    if (mn == mx) return eac_block(mn, 13, 1, EAC_ALL_FOUR);
+    const uint32_t table = h.etc2 & 15u;
+    const int mul = (int)(h.etc2 >> 4);
+    int tv[8];
+    eac_table_values(table, tv);
+    const int center = eac_center(tv, mn, mx);
+    uint64_t sels = 0;
+    BU_UNROLL
+    for (int i = 0; i < 16; i++) sels |= (uint64_t)(eac_nearest(tv, mul, center, (int)(px[i] >> 24), true) & 7u) << eac_selector_shift(i);
+    return eac_block((uint32_t)center, table, (uint32_t)mul, sels);
+}
+
+// pack_eac (:18880-19034: tables 2, 8, 11, 13; values clamp only for a texel below 7 or above 248) and pack_eac_high_quality (:19037-19155: all 16, always clamped)
+// of 16 values. Each table's squared error is accumulated first and the winner's selectors derived again, so no selector array is kept; the first table wins a tie.
+template <bool HQ>
+BU_FN uint64_t eac_pack(const int* a) {
+    int mn = 255, mx = 0;
+    BU_UNROLL
+    for (int i = 0; i < 16; i++) { mn = a[i] < mn ? a[i] : mn; mx = a[i] > mx ? a[i] : mx; }
+    if (mn == mx) return eac_block((uint32_t)mn, 13, 0, EAC_ALL_FOUR);   // pack_eac_solid_block: multiplier 0
+    if (mx - mn <= 5) {   // table 13 with multiplier 1 reaches -3..2 around its base: lossless
+        const int base = clampi(mx - 2, 0, 255);
+        uint64_t sels = 0;
+        BU_UNROLL
+        for (int i = 0; i < 16; i++) sels |= (uint64_t)((0x654012u >> (4 * (a[i] - (base - 3)))) & 7u) << eac_selector_shift(i);   // { 2, 1, 0, 4, 5, 6 }[a - (base - 3)]
+        return eac_block((uint32_t)base, 13, 1, sels);
+    }
+    uint32_t best_err = 0xFFFFFFFFu, best_table = 0;
+    int best_base = 0, best_mul = 1;
+    BU_NOUNROLL
+    for (uint32_t k = 0; k < (HQ ? 16u : 4u); k++) {
+        const uint32_t table = HQ ? k : ((0xDB82u >> (4 * k)) & 15u);
+        int tv[8];
+        eac_table_values(table, tv);
+        const int base = clampi(eac_center(tv, (uint32_t)mn, (uint32_t)mx), 0, 255);
+        const int mul = clampi((int)roundf((float)(uint32_t)(mx - mn) / (float)(tv[7] - tv[3])), 1, 15);
+        uint32_t err = 0;
+        BU_UNROLL
+        for (int i = 0; i < 16; i++) {
+            const uint32_t d = eac_nearest(tv, mul, base, a[i], HQ || a[i] < 7 || a[i] > 248) >> 3;
+            err += d * d;
+        }
+        if (err < best_err) { best_err = err; best_table = table; best_base = base; best_mul = mul; }
+    }
+    int tv[8];
+    eac_table_values(best_table, tv);
+    uint64_t sels = 0;
+    BU_UNROLL
+    for (int i = 0; i < 16; i++) sels |= (uint64_t)(eac_nearest(tv, best_mul, best_base, a[i], HQ || a[i] < 7 || a[i] > 248) & 7u) << eac_selector_shift(i);
+    return eac_block((uint32_t)best_base, best_table, (uint32_t)best_mul, sels);
+}
+template <bool HQ>
+BU_FN uint64_t eac_pack_channel(const uint32_t* px, uint32_t chan) {
+    int a[16];
+    BU_UNROLL
+    for (int i = 0; i < 16; i++) a[i] = px_comp(px[i], (int)chan);
+    return eac_pack<HQ>(a);
+}
+
+// The block targets of the texture family that the first family does not have. out[0] is the first 8 bytes, out[1] the second 8 (ETC2 RGBA: the EAC A8 block, then
+// the ETC1 block; RG11: chan0's block, then chan1's). chan0 / chan1: R11's channel, RG11's two; channel 3 of a block that is not solid goes the hint's way.
+template <uint32_t TARGET, bool HQ>
+BU_FN bool transcode_etc(const uint8_t* blk, uint32_t chan0, uint32_t chan1, uint64_t* out) {
+    cand c;
+    if (!unpack_block(blk, c)) return false;
+    const etc_hints h = read_etc_hints(blk, c.mode);
+    if (c.mode == 8) {
+        if (TARGET == TF_ETC1_RGB) out[0] = etc1_solid(h);
+        else if (TARGET == TF_ETC2_RGBA) { out[0] = eac_block(c.endpoints[3], 13, 1, EAC_ALL_FOUR); out[1] = etc1_solid(h); }
+        else {
+            out[0] = eac_block(c.endpoints[chan0], 13, 0, EAC_ALL_FOUR);
+            if (TARGET == TF_ETC2_EAC_RG11) out[1] = eac_block(c.endpoints[chan1], 13, 0, EAC_ALL_FOUR);
+        }
+        return true;
+    }
+    rgba8 dec[16];
+    decode_uastc(c, dec);
+    uint32_t px[16];
+    BU_UNROLL
+    for (int i = 0; i < 16; i++) px[i] = pack_px(dec[i].c);
+    if (TARGET == TF_ETC1_RGB) out[0] = etc1_from_hints(c.mode, h, px);
+    else if (TARGET == TF_ETC2_RGBA) { out[0] = eac_a8_from_hint(c.mode, h, px); out[1] = etc1_from_hints(c.mode, h, px); }
+    else {
+        out[0] = chan0 == 3 ? eac_a8_from_hint(c.mode, h, px) : eac_pack_channel<HQ>(px, chan0);
+        if (TARGET == TF_ETC2_EAC_RG11) out[1] = chan1 == 3 ? eac_a8_from_hint(c.mode, h, px) : eac_pack_channel<HQ>(px, chan1);
+    }
+    return true;
+}
+
+// one texel of a 16-bit pixel target (transcode_slice, :10246-10302)
+template <uint32_t TARGET>
+BU_FN uint32_t pack_pixel16(const rgba8& p) {
+    if (TARGET == TF_RGB565) return bu::pack_rgb565(p.c[0], p.c[1], p.c[2]);
+    if (TARGET == TF_BGR565) return bu::pack_rgb565(p.c[2], p.c[1], p.c[0]);
+    return bu::pack_rgba4444(p.c[0], p.c[1], p.c[2], p.c[3]);
+}
+
+// the texture family's unit: bytes per block of a block target, per pixel of a pixel target; 0: not a target of the family
+BU_FN_HD bool texture_is_pixel_target(uint32_t target) { return target == TF_RGBA32 || target == TF_RGB565 || target == TF_BGR565 || target == TF_RGBA4444; }
+BU_FN_HD uint32_t texture_unit_bytes(uint32_t target) {
+    switch (target) {
+    case TF_ETC1_RGB: case TF_ETC2_EAC_R11: return 8;
+    case TF_ETC2_RGBA: case TF_ETC2_EAC_RG11: return 16;
+    case TF_RGB565: case TF_BGR565: case TF_RGBA4444: return 2;
+    case TF_RGBA32: return 4;
+    default: return transcode_bytes_per_block(target);
     }
 }
 

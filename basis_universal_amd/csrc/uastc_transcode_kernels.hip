@@ -53,6 +53,24 @@ __device__ __forceinline__ bool transcode_uastc_block(const uint4 in, void* out,
             for (int k = 0; k < 16; k++) w[k >> 2] |= (uint32_t)o[k] << (8 * (k & 3));
         }
         ((uint4*)out)[i] = make_uint4(w[0], w[1], w[2], w[3]);
+    } else if (TARGET == TF_RGB565 || TARGET == TF_BGR565 || TARGET == TF_RGBA4444) {   // the texture family's 16-bit rasters: RGBA32's tile walk with 2-byte pixels
+        rgba8 px[16];
+        ok = transcode_rgba32(blk, px);
+        const uint32_t bx = i % g.nbx, by = i / g.nbx;
+        BU_UNROLL
+        for (uint32_t y = 0; y < 4; y++) {
+            const uint32_t row = by * 4 + y;
+            if (row >= g.height || row >= g.rows) break;
+            uint32_t v[4];
+            BU_UNROLL
+            for (uint32_t x = 0; x < 4; x++) v[x] = ok ? pack_pixel16<TARGET>(px[y * 4 + x]) : 0u;
+            store_tile_row(2, (uint16_t*)out + (size_t)row * g.pitch + bx * 4, bx, g.width, v);
+        }
+    } else if (TARGET == TF_ETC1_RGB || TARGET == TF_ETC2_RGBA || TARGET == TF_ETC2_EAC_R11 || TARGET == TF_ETC2_EAC_RG11) {   // the texture family's block targets
+        uint64_t w[2] = { 0, 0 };
+        ok = transcode_etc<TARGET, HQ>(blk, chan0, chan1, w);
+        if (!ok) w[0] = w[1] = 0;
+        store_block_words(out, i, w, TARGET == TF_ETC2_RGBA || TARGET == TF_ETC2_EAC_RG11);
     } else {
         uint64_t w[2] = { 0, 0 };
         ok = transcode_bcn(blk, TARGET, HQ, chan0, chan1, w);
@@ -113,6 +131,22 @@ static hipError_t launch_for_target(hipStream_t st, const Args& a, uint32_t targ
     }
 }
 
+// the texture family (bu_hip_k_transcode_uastc_texture / _textures): the seven targets above through the same instances, and its own -- high quality is a
+// template parameter of R11 / RG11 only, whose packers it selects
+template <class Args>
+static hipError_t launch_for_texture_target(hipStream_t st, const Args& a, uint32_t target, bool high_quality) {
+    switch (target) {
+    case TF_ETC1_RGB: return launch<TF_ETC1_RGB, false>(st, a);
+    case TF_ETC2_RGBA: return launch<TF_ETC2_RGBA, false>(st, a);
+    case TF_ETC2_EAC_R11: return high_quality ? launch<TF_ETC2_EAC_R11, true>(st, a) : launch<TF_ETC2_EAC_R11, false>(st, a);
+    case TF_ETC2_EAC_RG11: return high_quality ? launch<TF_ETC2_EAC_RG11, true>(st, a) : launch<TF_ETC2_EAC_RG11, false>(st, a);
+    case TF_RGB565: return launch<TF_RGB565, false>(st, a);
+    case TF_BGR565: return launch<TF_BGR565, false>(st, a);
+    case TF_RGBA4444: return launch<TF_RGBA4444, false>(st, a);
+    default: return launch_for_target(st, a, target, high_quality);
+    }
+}
+
 size_t transcode_output_bytes(uint32_t nbx, uint32_t nby, uint32_t width, uint32_t height, uint32_t target) {
     const uint32_t bpb = transcode_bytes_per_block(target);
     if (!bpb) return 0;
@@ -120,20 +154,24 @@ size_t transcode_output_bytes(uint32_t nbx, uint32_t nby, uint32_t width, uint32
     return raster_output_bytes(tile_geometry{ nbx, nby, width, height, 0, 0 }, pixels ? 4 : bpb, pixels);
 }
 
+uint32_t uastc_texture_unit_bytes(uint32_t target) { return texture_unit_bytes(target); }
+bool uastc_texture_is_pixel_target(uint32_t target) { return texture_is_pixel_target(target); }
+
 hipError_t launch_transcode_uastc(hipStream_t st, const void* d_blocks, const tile_geometry& g, uint32_t target, bool high_quality, uint32_t chan0, uint32_t chan1,
-                                  void* d_out, uint32_t* d_invalid) {
+                                  void* d_out, uint32_t* d_invalid, bool texture_family) {
     transcode_args a = { (const uint4*)d_blocks, d_out, d_invalid, g, chan0, chan1 };
     hipError_t e = hipMemsetAsync(d_invalid, 0, sizeof(uint32_t), st);
     if (e != hipSuccess || !g.nbx || !g.nby) return e;
-    return launch_for_target(st, a, target, high_quality);
+    return texture_family ? launch_for_texture_target(st, a, target, high_quality) : launch_for_target(st, a, target, high_quality);
 }
 
 hipError_t launch_transcode_uastc_slices(hipStream_t st, const void* d_blocks, const bu_hip_transcode_slice* d_slices, const uint32_t* d_prefix, uint32_t n_slices,
-                                         uint32_t total_blocks, uint32_t target, bool high_quality, uint32_t chan0, uint32_t chan1, void* d_out, uint32_t* d_invalid) {
+                                         uint32_t total_blocks, uint32_t target, bool high_quality, uint32_t chan0, uint32_t chan1, void* d_out, uint32_t* d_invalid,
+                                         bool texture_family) {
     transcode_slices_args a = { (const uint4*)d_blocks, (uint8_t*)d_out, d_invalid, d_slices, d_prefix, n_slices, total_blocks, chan0, chan1 };
     hipError_t e = hipMemsetAsync(d_invalid, 0, (size_t)n_slices * sizeof(uint32_t), st);
     if (e != hipSuccess || !n_slices || !total_blocks) return e;
-    return launch_for_target(st, a, target, high_quality);
+    return texture_family ? launch_for_texture_target(st, a, target, high_quality) : launch_for_target(st, a, target, high_quality);
 }
 
 } // namespace bu

@@ -1,9 +1,13 @@
 """UASTC LDR 4x4 -> GPU texture formats on the GPU: the host-side mirror of basist::basisu_lowlevel_uastc_ldr_4x4_transcoder::transcode_slice
 (transcoder/basisu_transcoder.cpp:10078) as a batch op, a reader for the two UASTC containers this package writes, and `transcode_file` on top of both.
 
-Targets are the reference's transcoder_texture_format values; only the ones below exist here. ETC1 / ETC2 / EAC / PVRTC1, the 16-bit pixel formats, ETC1S files,
-UASTC HDR / ASTC LDR / XUASTC and Zstandard-supercompressed KTX2 levels are out of scope and are refused with an error. There is no CPU implementation:
-without the HIP library and a GPU `transcode_uastc_blocks` raises.
+Targets are the reference's transcoder_texture_format values; only the ones below exist here. `transcode_uastc_blocks`, `transcode_file` and `transcode_file_images`
+take RGBA32, BC1, BC3, BC4, BC5, BC7 and ASTC 4x4 and refuse everything else. `transcode_uastc_texture_blocks`, `transcode_uastc_texture_file`, `transcode_uastc_textures`
+and `uastc_texture_layout` are a parallel UASTC family (UASTC_TEXTURE_BYTES_PER_BLOCK / UASTC_TEXTURE_BYTES_PER_PIXEL): those seven targets, byte for byte the same, plus
+the consumers of the ETC hints every UASTC block carries -- ETC1_RGB, ETC2_RGBA, ETC2_EAC_R11 / ETC2_EAC_RG11 -- and the RGB565 / BGR565 / RGBA4444 rasters, (height,
+width) u16. ETC1 from the alpha channel (cDecodeFlagsTranscodeAlphaDataToOpaqueFormats), PVRTC1, ATC / FXT1 / PVRTC2, UASTC HDR / ASTC LDR / XUASTC and
+Zstandard-supercompressed KTX2 levels are out of scope and are refused with an error. There is no CPU implementation: without the HIP library and a GPU the
+transcode functions raise.
 
 ETC1S files have their own three functions at the end of this module (`read_etc1s_file`, `decode_etc1s_file`, `transcode_etc1s_file`) and their own target list
 (ETC1S_BYTES_PER_BLOCK / ETC1S_BYTES_PER_PIXEL): the serial half -- containers, Huffman tables, palettes, the per-slice symbol walk -- is host code in
@@ -531,6 +535,129 @@ def transcode_file_images(ctx, data, target, *, high_quality=False, channels=Non
         def call(d_out, out_bytes, invalid):
             ctx.check(ctx.lib.k_transcode_uastc_slices(ctx.h, C.c_void_p(d_blocks), blocks.size // 16, recs, len(images), target, DECODE_FLAGS_HIGH_QUALITY if high_quality else 0,
                                                        c0, c1, d_out, out_bytes, invalid), "transcode_uastc_slices")
+        return _run_slices(ctx, call, images, layout, total, out_device, "UASTC LDR 4x4")
+    finally:
+        ctx.free(d_blocks)
+
+
+# ---------------------------------------------------------------- the UASTC texture family: also ETC1, ETC2 RGBA, EAC R11 / RG11 and the 16-bit rasters
+
+ETC2_EAC_R11, ETC2_EAC_RG11 = 20, 21
+UASTC_TEXTURE_BYTES_PER_BLOCK = {ETC1_RGB: 8, ETC2_RGBA: 16, BC1_RGB: 8, BC3_RGBA: 16, BC4_R: 8, BC5_RG: 16, BC7_RGBA: 16, ASTC_4x4_RGBA: 16, ETC2_EAC_R11: 8, ETC2_EAC_RG11: 16}
+UASTC_TEXTURE_BYTES_PER_PIXEL = {RGBA32: 4, RGB565: 2, BGR565: 2, RGBA4444: 2}
+
+
+def _check_uastc_texture_target(target):
+    target = int(target)
+    if target not in UASTC_TEXTURE_BYTES_PER_BLOCK and target not in UASTC_TEXTURE_BYTES_PER_PIXEL:
+        name = _TARGET_NAMES[target] if 0 <= target < len(_TARGET_NAMES) else "unknown"
+        raise ValueError(f"UASTC texture target {target} ({name}) is not supported (supported: {sorted(list(UASTC_TEXTURE_BYTES_PER_BLOCK) + list(UASTC_TEXTURE_BYTES_PER_PIXEL))})")
+    return target
+
+
+def uastc_decode_flags(*, high_quality=False, decode_flags=None):
+    """the decode_flags word of the UASTC texture entries: 32 (high quality) is the only bit there is; an explicit decode_flags with any other bit raises -- bit 4,
+    cDecodeFlagsTranscodeAlphaDataToOpaqueFormats (ETC1 from the alpha channel), among them"""
+    flags = (DECODE_FLAGS_HIGH_QUALITY if high_quality else 0) if decode_flags is None else int(decode_flags)
+    if flags & ~DECODE_FLAGS_HIGH_QUALITY:
+        raise ValueError(f"UASTC decode flags 0x{flags:x}: bits 0x{flags & ~DECODE_FLAGS_HIGH_QUALITY:x} are not supported (supported: 32, cDecodeFlagsHighQuality)")
+    return flags
+
+
+def _texture_array(ctx, d_out, target, n, width, height):
+    """the download of one image's output as the texture family returns it"""
+    if target in UASTC_TEXTURE_BYTES_PER_BLOCK:
+        unit = UASTC_TEXTURE_BYTES_PER_BLOCK[target]
+        return ctx.download(d_out, (n, unit), np.uint8) if n else np.zeros((0, unit), np.uint8)
+    if target == RGBA32:
+        return ctx.download(d_out, (height, width, 4), np.uint8) if n else np.zeros((0, 0, 4), np.uint8)
+    return ctx.download(d_out, (height, width), np.uint16) if n else np.zeros((0, 0), np.uint16)
+
+
+def transcode_uastc_texture_blocks(ctx, blocks, nbx, nby, target, *, width=None, height=None, high_quality=False, decode_flags=None, channels=None, out_device=None,
+                                   out_row_pitch=0, out_rows=0):
+    """transcode_uastc_blocks over the texture family's targets (bu_hip_k_transcode_uastc_texture): the seven of transcode_uastc_blocks, byte for byte the same, plus
+    ETC1_RGB, ETC2_RGBA (the EAC A8 block, then the ETC1 block), ETC2_EAC_R11 / ETC2_EAC_RG11 (channels: (c,) / (c0, c1), default (0,) / (0, 3); high_quality
+    selects the 16-table packer) and RGB565 / BGR565 / RGBA4444. Block targets return (nby * nbx, 8 | 16) uint8; pixel targets the cropped raster, (height, width, 4)
+    uint8 for RGBA32 and (height, width) uint16 for the 16-bit formats. With out_device (room for bu_hip_uastc_texture_output_bytes; out_row_pitch / out_rows, in
+    pixels, for a pixel target's padded raster) the output stays on the device and None is returned. Raises InvalidBlocksError when a block does not unpack."""
+    nbx, nby, target = int(nbx), int(nby), _check_uastc_texture_target(target)
+    flags = uastc_decode_flags(high_quality=high_quality, decode_flags=decode_flags)
+    c0, c1 = _channel_pair(channels)
+    n = nbx * nby
+    width, height = int(width or nbx * 4), int(height or nby * 4)
+    if not (0 < width <= nbx * 4 and 0 < height <= nby * 4) and n:
+        raise ValueError(f"{width} x {height} pixels do not fit {nbx} x {nby} blocks")
+    if target in UASTC_TEXTURE_BYTES_PER_BLOCK and (out_row_pitch or out_rows):
+        raise ValueError("out_row_pitch / out_rows describe a pixel raster: the target is a block format")
+    own = None
+    try:
+        if isinstance(blocks, np.ndarray):
+            blocks = np.ascontiguousarray(blocks, np.uint8)
+            if blocks.size != n * 16:
+                raise ValueError(f"{nbx} x {nby} blocks need {n * 16} bytes, got {blocks.size}")
+            blocks = own = ctx.upload(blocks) if n else 0
+        with _output(ctx, out_device, out_row_pitch, out_rows, lambda: ctx.lib.uastc_texture_output_bytes(nbx, nby, width, height, target, 0, 0)) as d_out:
+            invalid = C.c_uint32(0)
+            if n:
+                ctx.check(ctx.lib.k_transcode_uastc_texture(ctx.h, C.c_void_p(blocks), nbx, nby, width, height, target, flags, c0, c1, C.c_void_p(d_out), int(out_row_pitch),
+                                                            int(out_rows), C.byref(invalid)), "transcode_uastc_texture")
+            if invalid.value:
+                raise InvalidBlocksError(invalid.value, n)
+            return None if out_device is not None else _texture_array(ctx, d_out, target, n, width, height)
+    finally:
+        if own:
+            ctx.free(own)
+
+
+def transcode_uastc_texture_file(ctx, data, target, *, level=0, layer=0, face=0, high_quality=False, decode_flags=None, channels=None):
+    """One image of a UASTC .basis / .ktx2 file (read_uastc_file) as a texture of the family's targets: what transcode_uastc_texture_blocks returns for its blocks."""
+    target, flags = _check_uastc_texture_target(target), uastc_decode_flags(high_quality=high_quality, decode_flags=decode_flags)
+    _channel_pair(channels)
+    raw = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
+    for im in read_uastc_file(raw)["images"]:
+        if (im["level"], im["layer"], im["face"]) == (level, layer, face):
+            blocks = np.frombuffer(raw, np.uint8, im["length"], im["offset"]).reshape(-1, 16)
+            return transcode_uastc_texture_blocks(ctx, blocks, im["num_blocks_x"], im["num_blocks_y"], target, width=im["width"], height=im["height"], decode_flags=flags,
+                                                  channels=channels)
+    raise ValueError(f"the file has no image at level {level}, layer {layer}, face {face}")
+
+
+def uastc_texture_layout(images, target):
+    """image_layout for the UASTC texture family (transcode_uastc_textures): block targets are (blocks, 8 | 16) u8 by UASTC_TEXTURE_BYTES_PER_BLOCK, pixel targets the
+    tight raster, (height, width, 4) u8 for RGBA32 and (height, width) u16 for the 16-bit formats. Host only."""
+    target = _check_uastc_texture_target(target)
+    layout, at = [], 0
+    for im in images:
+        n, w, h = im["num_blocks_x"] * im["num_blocks_y"], im["width"], im["height"]
+        if target in UASTC_TEXTURE_BYTES_PER_PIXEL:
+            shape, dtype = ((h, w, 4), np.uint8) if target == RGBA32 else ((h, w), np.uint16)
+            nbytes = w * h * UASTC_TEXTURE_BYTES_PER_PIXEL[target]
+        else:
+            unit = UASTC_TEXTURE_BYTES_PER_BLOCK[target]
+            shape, dtype, nbytes = (n, unit), np.uint8, n * unit
+        layout.append({"offset": at, "nbytes": nbytes, "shape": shape, "dtype": dtype})
+        at += (nbytes + 15) & ~15
+    return layout, at
+
+
+def transcode_uastc_textures(ctx, data, target, *, high_quality=False, decode_flags=None, channels=None, out_device=None):
+    """transcode_file_images over the texture family's targets (bu_hip_k_transcode_uastc_textures): EVERY image of a UASTC .basis / .ktx2 file by one launch, each
+    what transcode_uastc_texture_file returns for it (views of one download). With out_device (a device pointer with room for uastc_texture_layout's total_bytes) the
+    output -- an ETC1 / ETC2 texture for a client that samples those, say -- stays there and uastc_texture_layout(images, target) is returned. Raises
+    InvalidBlocksError, with the per-slice counts and the lowest slice that has any, when a block does not unpack."""
+    target, flags = _check_uastc_texture_target(target), uastc_decode_flags(high_quality=high_quality, decode_flags=decode_flags)
+    c0, c1 = _channel_pair(channels)
+    raw = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
+    images = read_uastc_file(raw)["images"]
+    layout, total = uastc_texture_layout(images, target)
+    blocks, firsts = _uastc_block_span(raw, images)
+    recs = _slice_table(images, layout, firsts)
+    d_blocks = _upload_async(ctx, blocks)
+    try:
+        def call(d_out, out_bytes, invalid):
+            ctx.check(ctx.lib.k_transcode_uastc_textures(ctx.h, C.c_void_p(d_blocks), blocks.size // 16, recs, len(images), target, flags, c0, c1, d_out, out_bytes, invalid),
+                      "transcode_uastc_textures")
         return _run_slices(ctx, call, images, layout, total, out_device, "UASTC LDR 4x4")
     finally:
         ctx.free(d_blocks)

@@ -500,6 +500,31 @@ BU_HIP_API size_t bu_hip_etc1s_image_output_bytes(uint32_t num_blocks_x, uint32_
 BU_HIP_API size_t bu_hip_etc1s_image_slice_extent(const bu_hip_transcode_slice*, uint32_t target);
 BU_HIP_API int bu_hip_etc1s_bc7_color_table(bu_hip_context*, uint32_t* h_out, uint32_t* h_midpoints);
 
+/* The UASTC transcoder's second entry family: bu_hip_k_transcode_uastc and bu_hip_k_transcode_uastc_slices with the targets that consume the ETC1 / EAC hints every
+ * UASTC block carries, and the 16-bit rasters. The first family keeps its seven targets and its refusals; these take
+ *   cTFBC1_RGB (2), cTFBC3_RGBA (3), cTFBC4_R (4), cTFBC5_RG (5), cTFBC7_RGBA (6), cTFASTC_4x4_RGBA (10), cTFRGBA32 (13): byte for byte what the first family writes;
+ *   cTFETC1_RGB (0): 8 bytes per block (transcode_uastc_to_etc1, transcoder/basisu_transcoder.cpp:16720);
+ *   cTFETC2_RGBA (1): 16 bytes per block, bytes 0-7 the EAC A8 block from the block's EAC hint (transcode_uastc_to_etc2_eac_a8 :17629), bytes 8-15 the ETC1 block;
+ *   cTFETC2_EAC_R11 (20): 8 bytes per block, the EAC block of channel0 (-1 = 0); cTFETC2_EAC_RG11 (21): 16 bytes, channel0's block then channel1's (-1 = 0 and 3).
+ *     Channels 0-2 are packed by pack_eac (:18880), with cDecodeFlagsHighQuality by pack_eac_high_quality (:19037); channel 3 goes the hint's way, as in ETC2 RGBA;
+ *   cTFRGB565 (14), cTFBGR565 (15), cTFRGBA4444 (16): little-endian 16-bit words, exactly orig_width x orig_height pixels at out_row_pitch_pixels (0 = orig_width),
+ *     rows cut at out_rows_pixels (0 = orig_height), as RGBA32: a padded pitch stays untouched.
+ * All bit for bit the reference's. Any other target is refused with an error that names it and lists these; PVRTC1 (needs neighbouring blocks), ATC / FXT1 / PVRTC2
+ * (the reference has no UASTC route to them) are among the refused.
+ * decode_flags: 32 (cDecodeFlagsHighQuality) selects BC1 / BC3's second pass and R11 / RG11's 16-table packer; any other bit is refused by name -- with
+ * cDecodeFlagsTranscodeAlphaDataToOpaqueFormats the reference would pack ETC1 from the alpha channel, which is not built here.
+ * The blocks must be 16-byte aligned and d_out aligned to the target's unit (2 to 16 bytes; the table form: 16). The one-image entry refuses a pitch or rows for a
+ * block target, and returns 1 without a launch (nothing read, nothing written) for a grid of zero blocks. Everything else is as for the first family, refusals
+ * included: an invalid block is zero-filled and counted, per slice in the table form. */
+BU_HIP_API int bu_hip_k_transcode_uastc_texture(bu_hip_context*, const void* d_uastc_blocks, uint32_t num_blocks_x, uint32_t num_blocks_y,
+        uint32_t orig_width, uint32_t orig_height, uint32_t target, uint32_t decode_flags, int32_t channel0, int32_t channel1,
+        void* d_out, uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels, uint32_t* out_invalid_blocks);
+BU_HIP_API int bu_hip_k_transcode_uastc_textures(bu_hip_context*, const void* d_uastc_blocks, uint64_t n_blocks, const bu_hip_transcode_slice* slices, uint32_t n_slices,
+        uint32_t target, uint32_t decode_flags, int32_t channel0, int32_t channel1, void* d_out, size_t out_bytes, uint32_t* out_invalid_per_slice);
+BU_HIP_API size_t bu_hip_uastc_texture_output_bytes(uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height, uint32_t target,
+        uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
+BU_HIP_API size_t bu_hip_uastc_texture_slice_extent(const bu_hip_transcode_slice*, uint32_t target);
+
 /* gpu_image::unpack(encoder/basisu_gpu_texture.cpp:1218-1266) over resident blocks: what a GPU samples from a BC1 / BC3 / BC4 / BC5 / BC7 texture, as RGBA8.
  * format: the transcoder_texture_format value the transcoders above take as a target -- cTFBC1_RGB (2), cTFBC3_RGBA (3), cTFBC4_R (4), cTFBC5_RG (5), cTFBC7_RGBA (6);
  * any other fails with an error that names it. d_blocks: num_blocks_x * num_blocks_y blocks of 8 (BC1, BC4) or 16 bytes in raster order, aligned to their size;
