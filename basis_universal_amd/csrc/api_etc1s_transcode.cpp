@@ -4,19 +4,27 @@
 
 static const char* const kEtc1sTargets = "ETC1_RGB (0), BC1_RGB (2), RGBA32 (13), RGB565 (14), BGR565 (15), RGBA4444 (16)";
 static const char* const kEtc1sTextureTargets = "ETC1_RGB (0), ETC2_RGBA (1), BC1_RGB (2), BC7_RGBA (6), RGBA32 (13), RGB565 (14), BGR565 (15), RGBA4444 (16)";
+static const char* const kEtc1sBlockFormatTargets = "ETC1_RGB (0), ETC2_RGBA (1), BC1_RGB (2), BC7_RGBA (6), ASTC_4x4_RGBA (10), RGBA32 (13), RGB565 (14), BGR565 (15), RGBA4444 (16), "
+                                                    "ETC2_EAC_R11 (20), ETC2_EAC_RG11 (21)";
 static const uint32_t kNoChromaFiltering = 64;   // cDecodeFlagsNoETC1SChromaFiltering, the one flag of the bu_hip_k_transcode_etc1s_image* entries
 
 // Which entry family a call came through. The first (bu_hip_k_transcode_etc1s*) has six targets and no flags; the second (bu_hip_k_transcode_etc1s_image*) adds the
-// 16-byte targets and decode_flags. Both run the same code below: the family decides the target list, the flags and the name in a refusal.
-struct etc1s_family { const char* fn; bool texture; };
-static const etc1s_family kFirstFamily = { "transcode_etc1s", false }, kImageFamily = { "transcode_etc1s_image", true };
+// 16-byte targets and decode_flags; the third (bu_hip_k_transcode_etc1s_block_format*) adds ASTC 4x4 and EAC R11 / RG11. All run the same code below: the family
+// decides the target list, the flags and the name in a refusal.
+struct etc1s_family { const char* fn; const char* targets; uint32_t (*unit_bytes)(uint32_t target); };
+static const etc1s_family kFirstFamily = { "transcode_etc1s", kEtc1sTargets, bu::etc1s_transcode_unit_bytes },
+                          kImageFamily = { "transcode_etc1s_image", kEtc1sTextureTargets, bu::etc1s_texture_unit_bytes },
+                          kBlockFormatFamily = { "transcode_etc1s_block_format", kEtc1sBlockFormatTargets, bu::etc1s_block_format_unit_bytes };
 
-static uint32_t family_unit_bytes(const etc1s_family& f, uint32_t target) { return f.texture ? bu::etc1s_texture_unit_bytes(target) : bu::etc1s_transcode_unit_bytes(target); }
-static bool reads_alpha(uint32_t target) { return target == bu::ETF_RGBA32 || target == bu::ETF_RGBA4444 || target == bu::ETF_ETC2_RGBA || target == bu::ETF_BC7_RGBA; }
+static uint32_t family_unit_bytes(const etc1s_family& f, uint32_t target) { return f.unit_bytes(target); }
+static bool reads_alpha(uint32_t target) {
+    return target == bu::ETF_RGBA32 || target == bu::ETF_RGBA4444 || target == bu::ETF_ETC2_RGBA || target == bu::ETF_BC7_RGBA || target == bu::ETF_ASTC_4x4_RGBA ||
+           target == bu::ETF_ETC2_EAC_RG11;
+}
 // the target and the flags of a call; the refusal names what is wrong
 static int etc1s_target_ok(bu_hip_context* ctx, const etc1s_family& f, uint32_t target, uint32_t decode_flags) {
     if (!family_unit_bytes(f, target)) {
-        set_error(ctx, "%s: target %u (%s) is not supported (supported: %s)", f.fn, target, transcoder_format_name(target), f.texture ? kEtc1sTextureTargets : kEtc1sTargets);
+        set_error(ctx, "%s: target %u (%s) is not supported (supported: %s)", f.fn, target, transcoder_format_name(target), f.targets);
         return 0;
     }
     if (decode_flags & ~kNoChromaFiltering) {
@@ -60,8 +68,20 @@ static int ensure_bc7_tables(bu_hip_context* ctx) {
     if (e != hipSuccess) { ctx->etc1s_bc7_tables.release(); set_error(ctx, "etc1s_build_bc7_tables: %s", hipGetErrorString(e)); return 0; }
     return 1;
 }
+// the two ETC1S -> ASTC look-ups and the unquantised endpoint values, the same way: built by the first ASTC transcode
+static int ensure_astc_tables(bu_hip_context* ctx) {
+    if (ctx->etc1s_astc_tables.p) return 1;
+    BU_TRY(ctx, ctx->etc1s_astc_tables.reserve(bu::kEtc1sAstcTableWords * sizeof(uint32_t)));
+    hipError_t e = bu::launch_etc1s_build_astc_tables(ctx->stream, static_cast<uint32_t*>(ctx->etc1s_astc_tables.p));
+    if (e != hipSuccess) { ctx->etc1s_astc_tables.release(); set_error(ctx, "etc1s_build_astc_tables: %s", hipGetErrorString(e)); return 0; }
+    return 1;
+}
 // only what the target needs
-static int ensure_target_tables(bu_hip_context* ctx, uint32_t target, const uint32_t*& bc1, const uint32_t*& bc7) {
+static int ensure_target_tables(bu_hip_context* ctx, uint32_t target, const uint32_t*& bc1, const uint32_t*& bc7, const uint32_t*& astc) {
+    if (target == bu::ETF_ASTC_4x4_RGBA) {
+        if (!ensure_astc_tables(ctx)) return 0;
+        astc = static_cast<const uint32_t*>(ctx->etc1s_astc_tables.p);
+    }
     if (target == bu::ETF_BC1_RGB) {
         if (!ensure_bc1_tables(ctx)) return 0;
         bc1 = static_cast<const uint32_t*>(ctx->etc1s_bc1_tables.p);
@@ -86,7 +106,7 @@ static int transcode_image_counted(bu_hip_context* ctx, const etc1s_family& f, c
     arena& counter = ctx->scratch[4];
     BU_TRY(ctx, counter.reserve(sizeof(uint32_t)));
     a.invalid = static_cast<uint32_t*>(counter.p);
-    if (!ensure_target_tables(ctx, target, a.bc1_endpoints, a.bc7_tables)) return 0;
+    if (!ensure_target_tables(ctx, target, a.bc1_endpoints, a.bc7_tables, a.astc_tables)) return 0;
     {
         prof_scope ps(ctx, "etc1s_transcode");
         BU_TRY(ctx, bu::launch_transcode_etc1s(ctx->stream, a, target, !(decode_flags & kNoChromaFiltering)));
@@ -139,15 +159,15 @@ static int transcode_images(bu_hip_context* ctx, const etc1s_family& f, const ch
     if (!d_ep_pal || !d_sel_pal || !d_ep_idx || !d_sel_idx) { set_error(ctx, "%s: null pointer", fn); return 0; }
     if (!n_ep || !n_sel || n_ep > 65535u || n_sel > 65535u) { set_error(ctx, "%s: palettes of %u endpoints and %u selectors (1..65535 each)", fn, n_ep, n_sel); return 0; }
     bu::slice_table table;
-    if (!etc1s_slices_check(ctx, table, fn, slices, n_slices, n_indices, target, f.texture, d_out, out_bytes)) return 0;
+    if (!etc1s_slices_check(ctx, table, fn, slices, n_slices, n_indices, target, family_unit_bytes(f, target), d_out, out_bytes)) return 0;
     device_guard g(ctx->device);
-    const uint32_t *bc1 = nullptr, *bc7 = nullptr;
-    if (!ensure_target_tables(ctx, target, bc1, bc7)) return 0;
+    const uint32_t *bc1 = nullptr, *bc7 = nullptr, *astc = nullptr;
+    if (!ensure_target_tables(ctx, target, bc1, bc7, astc)) return 0;
     uploaded_slices d;
     if (!upload_slice_table(ctx, table, d)) return 0;
     const bu::etc1s_transcode_slices_args a = { static_cast<const uint32_t*>(d_ep_pal), static_cast<const uint32_t*>(d_sel_pal), static_cast<const uint16_t*>(d_ep_idx),
                                                 static_cast<const uint16_t*>(d_sel_idx), static_cast<uint8_t*>(d_out), d.counters, bc1, bc7,
-                                                static_cast<const bu_hip_transcode_slice*>(d.records), d.prefix, n_ep, n_sel, table.n, table.total };
+                                                static_cast<const bu_hip_transcode_slice*>(d.records), d.prefix, n_ep, n_sel, table.n, table.total, astc };
     {
         prof_scope ps(ctx, fn);
         BU_TRY(ctx, bu::launch_transcode_etc1s_slices(ctx->stream, a, target, !(decode_flags & kNoChromaFiltering)));
@@ -226,6 +246,42 @@ int bu_hip_k_transcode_etc1s_images(bu_hip_context* ctx, const void* d_ep_pal, u
                                     uint32_t* out_invalid_per_slice) {
     return transcode_images(ctx, kImageFamily, "transcode_etc1s_images", d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, n_indices, slices, n_slices, target, decode_flags, d_out,
                             out_bytes, out_invalid_per_slice);
+}
+
+// ---- the third family: the second one's arguments, all eleven targets
+
+size_t bu_hip_etc1s_block_format_output_bytes(uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, uint32_t pitch_px, uint32_t rows_px) {
+    return bu::raster_output_bytes(bu::tile_geometry{ nbx, nby, orig_w, orig_h, pitch_px, rows_px }, bu::etc1s_block_format_unit_bytes(target), bu::etc1s_transcode_is_pixel_target(target));
+}
+
+int bu_hip_etc1s_astc_tables(bu_hip_context* ctx, uint32_t* h_out_0_47, uint32_t* h_out_0_255, uint32_t* h_unquant48) {
+    if (!ctx || !h_out_0_47 || !h_out_0_255 || !h_unquant48) { if (ctx) set_error(ctx, "etc1s_astc_tables: null pointer"); return 0; }
+    device_guard g(ctx->device);
+    if (!ensure_astc_tables(ctx)) return 0;
+    const uint32_t* d = static_cast<const uint32_t*>(ctx->etc1s_astc_tables.p);
+    const size_t n = (bu::kEtc1sAstcTableWords - 48) / 2;
+    return fetch(ctx, h_out_0_47, d, n * sizeof(uint32_t)) && fetch(ctx, h_out_0_255, d + n, n * sizeof(uint32_t)) && fetch(ctx, h_unquant48, d + 2 * n, 48 * sizeof(uint32_t)) ? 1 : 0;
+}
+
+int bu_hip_k_transcode_etc1s_block_format_counted(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx,
+                                                  const void* d_sel_idx, const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h,
+                                                  uint32_t target, void* d_out, uint32_t pitch_px, uint32_t rows_px, uint32_t decode_flags, uint32_t* out_invalid_blocks) {
+    return transcode_image_counted(ctx, kBlockFormatFamily, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out,
+                                   pitch_px, rows_px, decode_flags, out_invalid_blocks);
+}
+
+int bu_hip_k_transcode_etc1s_block_format(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
+                                          const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, void* d_out,
+                                          uint32_t pitch_px, uint32_t rows_px, uint32_t decode_flags) {
+    return transcode_image_checked(ctx, kBlockFormatFamily, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out,
+                                   pitch_px, rows_px, decode_flags);
+}
+
+int bu_hip_k_transcode_etc1s_block_formats(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
+                                           uint64_t n_indices, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target, uint32_t decode_flags, void* d_out,
+                                           size_t out_bytes, uint32_t* out_invalid_per_slice) {
+    return transcode_images(ctx, kBlockFormatFamily, "transcode_etc1s_block_formats", d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, n_indices, slices, n_slices, target,
+                            decode_flags, d_out, out_bytes, out_invalid_per_slice);
 }
 
 } // extern "C"

@@ -26,11 +26,12 @@ __device__ __forceinline__ uint32_t red_of(const etc1s_entry& e, uint32_t s) { r
 
 // EAC A8: byte 0 base, byte 1 table | multiplier << 4, then 48 bits big endian, the 3-bit code of texel (x, y) at bit 45 - 3 (x * 4 + y). A block of one selector
 // is base = its value under table 13, multiplier 1, every code 4 (modifier 0); any other block reads base, table, multiplier and the four codes from the look-up.
-__device__ __forceinline__ uint2 to_eac_a8(const etc1s_entry& e, uint32_t sel) {
+// `lookup` is EAC A8's table or, for EAC R11 (etc1s_block_format_targets.h), the one searched on 11 bits: the two formats share the layout and the route.
+__device__ __forceinline__ uint2 eac_from_lookup(const etc1s_entry& e, uint32_t sel, const unsigned int* lookup) {
     uint32_t low, high;
     selectors_used(sel, low, high);
     uint32_t v = red_of(e, low) | ((13u | (1u << 4)) << 8) | (04444u << 16);
-    if (low != high) v = ke_eac_a8[(e.table * 32u + e.r5) * 4u + ke_alpha_range_index[low * 4u + high]];
+    if (low != high) v = lookup[(e.table * 32u + e.r5) * 4u + ke_alpha_range_index[low * 4u + high]];
     uint64_t bits = 0;
 #pragma unroll
     for (uint32_t y = 0; y < 4; y++)
@@ -38,6 +39,7 @@ __device__ __forceinline__ uint2 to_eac_a8(const etc1s_entry& e, uint32_t sel) {
         for (uint32_t x = 0; x < 4; x++) bits |= (uint64_t)((v >> (16u + 3u * texel_selector(sel, x, y))) & 7u) << (45u - 3u * (x * 4u + y));
     return make_uint2((v & 0xFFFFu) | ((uint32_t)((bits >> 40) & 255u) << 16) | ((uint32_t)((bits >> 32) & 255u) << 24), __builtin_bswap32((uint32_t)bits));
 }
+__device__ __forceinline__ uint2 to_eac_a8(const etc1s_entry& e, uint32_t sel) { return eac_from_lookup(e, sel, ke_eac_a8); }
 __device__ __forceinline__ uint2 opaque_eac_a8() { return make_uint2(255u | ((13u | (1u << 4)) << 8) | (0x92u << 16) | (0x49u << 24), 0x24499224u); }
 
 // ---- BC7 mode 5. The block as two 64-bit halves. Low: mode bit 5, rotation 0, r0 r1 g0 g1 b0 b1 (7 bits each) from bit 8, a0 at bit 50, the low 6 bits of a1 at 58.

@@ -9,8 +9,10 @@ namespace bu {
 
 enum : uint32_t { kBc1TableEntries = 8 * 32 * 6 * 10 };   // per endpoint width: intensity tables x 5-bit base values x selector ranges x selector mappings
 // the reference's transcoder_texture_format values of the targets that exist here
-enum : uint32_t { ETF_ETC1_RGB = 0, ETF_ETC2_RGBA = 1, ETF_BC1_RGB = 2, ETF_BC7_RGBA = 6, ETF_RGBA32 = 13, ETF_RGB565 = 14, ETF_BGR565 = 15, ETF_RGBA4444 = 16 };
+enum : uint32_t { ETF_ETC1_RGB = 0, ETF_ETC2_RGBA = 1, ETF_BC1_RGB = 2, ETF_BC7_RGBA = 6, ETF_ASTC_4x4_RGBA = 10, ETF_RGBA32 = 13, ETF_RGB565 = 14, ETF_BGR565 = 15, ETF_RGBA4444 = 16,
+                  ETF_ETC2_EAC_R11 = 20, ETF_ETC2_EAC_RG11 = 21 };
 enum : uint32_t { kEtc1sBc7TableWords = 8 * 32 * 6 * 10 + 128 };   // the ETC1S -> BC7 colour look-up and the mode-5 encoder's midpoints (etc1s_texture_targets.h)
+enum : uint32_t { kEtc1sAstcTableWords = 2 * 8 * 32 * 6 * 10 + 48 };   // the two ETC1S -> ASTC look-ups and the 48 unquantised endpoint values (etc1s_block_format_targets.h)
 
 struct etc1s_transcode_args {
     const uint32_t* endpoint_palette;   // r5 | g5 << 8 | b5 << 16 | intensity table << 24
@@ -22,6 +24,7 @@ struct etc1s_transcode_args {
     const uint32_t* bc7_tables;         // BC7 only: kEtc1sBc7TableWords words from launch_etc1s_build_bc7_tables
     uint32_t n_endpoints, n_selectors;
     tile_geometry g;
+    const uint32_t* astc_tables;        // ASTC only: kEtc1sAstcTableWords words from launch_etc1s_build_astc_tables
 };
 
 // every image of a file in one launch: the file's two whole index arrays, and a table that says which ranges of them are whose
@@ -34,10 +37,12 @@ struct etc1s_transcode_slices_args {
     const bu_hip_transcode_slice* slices;          // device copies of the records, every zero size replaced by what it stands for
     const uint32_t* prefix;                        // n_slices + 1 entries: where each slice's blocks begin among the total_blocks of the call
     uint32_t n_endpoints, n_selectors, n_slices, total_blocks;
+    const uint32_t* astc_tables;
 };
 
 uint32_t etc1s_transcode_unit_bytes(uint32_t target);   // per block for block targets, per pixel for pixel targets; 0 = not a target of the first six (ETC1, BC1, pixels)
 uint32_t etc1s_texture_unit_bytes(uint32_t target);     // the same over all eight targets: also 16 for ETC2 RGBA and BC7 RGBA
+uint32_t etc1s_block_format_unit_bytes(uint32_t target);   // the same over all eleven: also 16 for ASTC 4x4 and EAC RG11, 8 for EAC R11
 bool etc1s_transcode_is_pixel_target(uint32_t target);
 // one launch; d_invalid is cleared first and afterwards holds how many blocks had an index past its palette (their output is zero-filled)
 // chroma_filter: BC7 only, the reference's default
@@ -48,6 +53,8 @@ hipError_t launch_transcode_etc1s_slices(hipStream_t st, const etc1s_transcode_s
 hipError_t launch_etc1s_build_bc1_tables(hipStream_t st, uint32_t* d_tables);
 // fills d_tables[kEtc1sBc7TableWords]
 hipError_t launch_etc1s_build_bc7_tables(hipStream_t st, uint32_t* d_tables);
+// fills d_tables[kEtc1sAstcTableWords]
+hipError_t launch_etc1s_build_astc_tables(hipStream_t st, uint32_t* d_tables);
 // counts the entries of idx[n] that are >= limit into *d_count (cleared first)
 hipError_t launch_etc1s_count_indices_past(hipStream_t st, const uint16_t* idx, uint32_t n, uint32_t limit, uint32_t* d_count, bool clear);
 

@@ -6,7 +6,7 @@
 // zero-filled and counted with a vector atomic, and it does not stop the others. Two kernels share that per-block work: one image per launch, and every image of
 // a file in one launch through a slice table (tile_raster.h), counted per slice.
 // The 16-byte targets (ETC2 RGBA, BC7 mode 5) store one uint4 per block; their conversions are etc1s_texture_targets.h's. BC7's chroma filter is a second template
-// parameter, so the unfiltered instance carries none of the encoder.
+// parameter, so the unfiltered instance carries none of the encoder. ASTC 4x4 (16 bytes), EAC R11 (8) and EAC RG11 (16) are etc1s_block_format_targets.h's.
 #include <hip/hip_runtime.h>
 #include "etc1s_device.h"
 #include "etc1s_transcode_kernels.h"
@@ -14,6 +14,7 @@
 
 #define BU_TAB static __device__ const
 #include "etc1s_transcode_tables.inc"
+#include "uastc_transcode_tables.inc"   // ku_trit_encode, for ASTC's endpoints of range 0..47
 #undef BU_TAB
 
 namespace bu {
@@ -109,8 +110,10 @@ __device__ __forceinline__ uint2 to_bc1(const etc1s_entry& e, uint32_t sel, cons
 
 }  // namespace bu
 #include "etc1s_texture_targets.h"
+#include "etc1s_block_format_targets.h"
 namespace bu {
 static_assert(kBc7TableWords == kEtc1sBc7TableWords, "the header's size of the BC7 tables");
+static_assert(kAstcTableWords == kEtc1sAstcTableWords, "the header's size of the ASTC tables");
 
 // one pixel of a pixel target from the block colour (r | g << 8 | b << 16) and the alpha value (transcoder.cpp:9155-9332; the 4444 colour pass ORs onto the alpha pass)
 template <uint32_t TARGET>
@@ -124,7 +127,7 @@ __device__ __forceinline__ uint32_t pack_pixel(uint32_t c, uint32_t a) {
 
 // what every block of a launch reads besides its own indices
 struct etc1s_palettes {
-    const uint32_t *endpoint_palette, *selector_palette, *bc1_endpoints, *bc7_tables;
+    const uint32_t *endpoint_palette, *selector_palette, *bc1_endpoints, *bc7_tables, *astc_tables;
     uint32_t n_endpoints, n_selectors;
 };
 
@@ -136,7 +139,7 @@ template <uint32_t TARGET, bool FILTER>
 __device__ __forceinline__ bool transcode_etc1s_block(const etc1s_palettes& a, const uint16_t* endpoint_idx, const uint16_t* selector_idx, const uint16_t* alpha_endpoint_idx,
                                                       const uint16_t* alpha_selector_idx, void* out, uint32_t i, const tile_geometry& g) {
     constexpr bool kPixels = TARGET == ETF_RGBA32 || TARGET == ETF_RGB565 || TARGET == ETF_BGR565 || TARGET == ETF_RGBA4444;
-    constexpr bool kWide = TARGET == ETF_ETC2_RGBA || TARGET == ETF_BC7_RGBA;   // 16 bytes per block: bytes 0-7 from the alpha slice (BC7: its alpha fields)
+    constexpr bool kWide = TARGET == ETF_ETC2_RGBA || TARGET == ETF_BC7_RGBA || TARGET == ETF_ASTC_4x4_RGBA || TARGET == ETF_ETC2_EAC_RG11;   // 16 bytes per block, both slices
     constexpr bool kAlpha = TARGET == ETF_RGBA32 || TARGET == ETF_RGBA4444 || kWide;
     const uint32_t ei = endpoint_idx[i], si = selector_idx[i];
     bool ok = ei < a.n_endpoints && si < a.n_selectors;
@@ -154,6 +157,12 @@ __device__ __forceinline__ bool transcode_etc1s_block(const etc1s_palettes& a, c
             if (TARGET == ETF_ETC2_RGBA) {
                 const uint2 alpha = has_alpha ? to_eac_a8(unpack_entry(a.endpoint_palette[aei]), a.selector_palette[asi]) : opaque_eac_a8(), rgb = to_etc1(e, sel);
                 o = make_uint4(alpha.x, alpha.y, rgb.x, rgb.y);
+            } else if (TARGET == ETF_ETC2_EAC_RG11) {
+                const uint2 red = to_eac_r11(e, sel), green = has_alpha ? to_eac_r11(unpack_entry(a.endpoint_palette[aei]), a.selector_palette[asi]) : opaque_eac_a8();
+                o = make_uint4(red.x, red.y, green.x, green.y);
+            } else if (TARGET == ETF_ASTC_4x4_RGBA) {
+                const astc_block b = to_astc(e, sel, has_alpha, has_alpha ? unpack_entry(a.endpoint_palette[aei]) : e, has_alpha ? a.selector_palette[asi] : 0u, a.astc_tables);
+                o = make_uint4((uint32_t)b.lo, (uint32_t)(b.lo >> 32), (uint32_t)b.hi, (uint32_t)(b.hi >> 32));
             } else {
                 bc7_m5 b = to_bc7_m5_color(e, sel, a.bc7_tables);
                 if (FILTER)
@@ -171,7 +180,7 @@ __device__ __forceinline__ bool transcode_etc1s_block(const etc1s_palettes& a, c
         if (ok) {
             const etc1s_entry e = unpack_entry(a.endpoint_palette[ei]);
             const uint32_t sel = a.selector_palette[si];
-            o = TARGET == ETF_ETC1_RGB ? to_etc1(e, sel) : to_bc1(e, sel, a.bc1_endpoints, a.bc1_endpoints + kBc1TableEntries);
+            o = TARGET == ETF_ETC1_RGB ? to_etc1(e, sel) : (TARGET == ETF_ETC2_EAC_R11 ? to_eac_r11(e, sel) : to_bc1(e, sel, a.bc1_endpoints, a.bc1_endpoints + kBc1TableEntries));
         }
         ((uint2*)out)[i] = o;
         return ok;
@@ -211,7 +220,7 @@ template <uint32_t TARGET, bool FILTER>
 __global__ __launch_bounds__(256) void transcode_etc1s_kernel(etc1s_transcode_args a) {
     const uint32_t n = a.g.nbx * a.g.nby, i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const etc1s_palettes p = { a.endpoint_palette, a.selector_palette, a.bc1_endpoints, a.bc7_tables, a.n_endpoints, a.n_selectors };
+    const etc1s_palettes p = { a.endpoint_palette, a.selector_palette, a.bc1_endpoints, a.bc7_tables, a.astc_tables, a.n_endpoints, a.n_selectors };
     if (!transcode_etc1s_block<TARGET, FILTER>(p, a.endpoint_idx, a.selector_idx, a.alpha_endpoint_idx, a.alpha_selector_idx, a.out, i, a.g)) atomicAdd(a.invalid, 1u);
 }
 
@@ -221,7 +230,7 @@ template <uint32_t TARGET, bool FILTER>
 __global__ __launch_bounds__(256) void transcode_etc1s_slices_kernel(etc1s_transcode_slices_args a) {
     transcode_slice_view v;
     if (!find_transcode_slice(a.slices, a.prefix, a.n_slices, a.total_blocks, blockIdx.x * 256u + threadIdx.x, v)) return;
-    const etc1s_palettes p = { a.endpoint_palette, a.selector_palette, a.bc1_endpoints, a.bc7_tables, a.n_endpoints, a.n_selectors };
+    const etc1s_palettes p = { a.endpoint_palette, a.selector_palette, a.bc1_endpoints, a.bc7_tables, a.astc_tables, a.n_endpoints, a.n_selectors };
     const bool alpha = v.alpha_first_block != BU_HIP_NO_ALPHA_SLICE;
     if (!transcode_etc1s_block<TARGET, FILTER>(p, a.endpoint_idx + v.first_block, a.selector_idx + v.first_block, alpha ? a.endpoint_idx + v.alpha_first_block : nullptr,
                                                alpha ? a.selector_idx + v.alpha_first_block : nullptr, a.out + v.out_offset, v.local, v.g))
@@ -298,6 +307,56 @@ __global__ __launch_bounds__(256) void etc1s_build_bc7_tables_kernel(uint32_t* t
     tables[idx] = best_lo | (best_hi << 8) | ((best_err < 0xFFFFu ? best_err : 0xFFFFu) << 16);
 }
 
+// The two look-ups of to_astc, [intensity table][base5][range][mapping] -> lo | hi << 8 | error << 16: over the 48 BISE codes of endpoint range 0..47 in code order
+// (first kAstcEntries words), then over 8-bit endpoints; behind them the 48 unquantised values. The search is the BC7 table's (hi outermost, lo innermost, first
+// minimum) over ASTC's four values, the errors of selectors 0 and 3 counted eight times for the widest intensity table over the whole range. The ten errors of an
+// entry are stored as they are while the largest fits 16 bits; else each times 65535 over that largest, rounded to nearest. A workgroup is 25 entries of ten lanes,
+// so that the ten meet in LDS. astc_table_0_47() / astc_table_0_255() of the tool are the same on the host.
+__global__ __launch_bounds__(256) void etc1s_build_astc_tables_kernel(uint32_t* tables) {
+    __shared__ uint32_t raw[250];
+    const uint32_t idx = blockIdx.x * 250u + threadIdx.x;
+    const bool lane = threadIdx.x < 250u && idx < 2u * kAstcEntries;
+    if (blockIdx.x == 0 && threadIdx.x >= 250u) {   // the six idle lanes of the first workgroup write the unquantised values
+        for (uint32_t c = threadIdx.x - 250u; c < 48u; c += 6u) tables[2u * kAstcEntries + c] = astc_unquant48(c);
+    }
+    uint32_t best_err = 0xFFFFFFFFu, best_lo = 0, best_hi = 0;
+    if (lane) {
+        const bool wide = idx >= kAstcEntries;
+        const uint32_t e = wide ? idx - kAstcEntries : idx, m = e % 10u, r = (e / 10u) % 6u, g = (e / 60u) % 32u, t = e / 1920u;
+        const int base = scale5((int)g);
+        int block[4];
+#pragma unroll
+        for (int s = 0; s < 4; s++) block[s] = clamp255(base + inten_delta((int)t, s));
+        const uint32_t s0 = ke_bc1_ranges[r * 2], s1 = ke_bc1_ranges[r * 2 + 1];
+        const uint32_t m0 = ke_bc1_mappings[m * 4], m1 = ke_bc1_mappings[m * 4 + 1], m2 = ke_bc1_mappings[m * 4 + 2], m3 = ke_bc1_mappings[m * 4 + 3];
+        const uint32_t ends_weight = (t == 7u && s0 == 0u && s1 == 3u) ? 8u : 1u;
+        const uint32_t n = wide ? 256u : 48u;
+        for (uint32_t hi = 0; hi < n; hi++) {
+            const uint32_t vh = wide ? hi : astc_unquant48(hi);
+            for (uint32_t lo = 0; lo < n; lo++) {
+                const uint32_t vl = wide ? lo : astc_unquant48(lo);
+                const uint32_t c[4] = { astc_interp2(vl, vh, 0u), astc_interp2(vl, vh, 21u), astc_interp2(vl, vh, 43u), astc_interp2(vl, vh, 64u) };
+                const uint32_t mapped[4] = { pick4(c, m0), pick4(c, m1), pick4(c, m2), pick4(c, m3) };
+                uint32_t err = 0;
+#pragma unroll
+                for (uint32_t s = 0; s < 4; s++) {
+                    const int d = block[s] - (int)mapped[s];
+                    if (s >= s0 && s <= s1) err += (uint32_t)(d * d) * ((s == 0u || s == 3u) ? ends_weight : 1u);
+                }
+                if (err < best_err) { best_err = err; best_lo = lo; best_hi = hi; }
+            }
+        }
+        raw[threadIdx.x] = best_err;
+    }
+    __syncthreads();
+    if (!lane) return;
+    const uint32_t first = threadIdx.x - threadIdx.x % 10u;
+    uint32_t top = 0;
+    for (uint32_t k = 0; k < 10u; k++) top = raw[first + k] > top ? raw[first + k] : top;
+    if (top > 0xFFFFu) best_err = (uint32_t)((2ull * best_err * 0xFFFFull + top) / (2ull * top));
+    tables[idx] = best_lo | (best_hi << 8) | (best_err << 16);
+}
+
 __global__ __launch_bounds__(256) void etc1s_count_indices_past_kernel(const uint16_t* idx, uint32_t n, uint32_t limit, uint32_t* count) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i < n && idx[i] >= limit) atomicAdd(count, 1u);
@@ -320,7 +379,11 @@ template <class Args>
 static hipError_t launch_for_target(hipStream_t st, const Args& a, uint32_t target, bool chroma_filter) {
     if (target == ETF_BC1_RGB && !a.bc1_endpoints) return hipErrorInvalidValue;
     if (target == ETF_BC7_RGBA && !a.bc7_tables) return hipErrorInvalidValue;
+    if (target == ETF_ASTC_4x4_RGBA && !a.astc_tables) return hipErrorInvalidValue;
     switch (target) {
+    case ETF_ASTC_4x4_RGBA: return launch<ETF_ASTC_4x4_RGBA>(st, a);
+    case ETF_ETC2_EAC_R11: return launch<ETF_ETC2_EAC_R11>(st, a);
+    case ETF_ETC2_EAC_RG11: return launch<ETF_ETC2_EAC_RG11>(st, a);
     case ETF_ETC2_RGBA: return launch<ETF_ETC2_RGBA>(st, a);
     case ETF_BC7_RGBA: return chroma_filter ? launch<ETF_BC7_RGBA, true>(st, a) : launch<ETF_BC7_RGBA, false>(st, a);
     case ETF_ETC1_RGB: return launch<ETF_ETC1_RGB>(st, a);
@@ -342,6 +405,10 @@ uint32_t etc1s_transcode_unit_bytes(uint32_t target) {
     }
 }
 uint32_t etc1s_texture_unit_bytes(uint32_t target) { return target == ETF_ETC2_RGBA || target == ETF_BC7_RGBA ? 16u : etc1s_transcode_unit_bytes(target); }
+uint32_t etc1s_block_format_unit_bytes(uint32_t target) {
+    if (target == ETF_ASTC_4x4_RGBA || target == ETF_ETC2_EAC_RG11) return 16u;
+    return target == ETF_ETC2_EAC_R11 ? 8u : etc1s_texture_unit_bytes(target);
+}
 bool etc1s_transcode_is_pixel_target(uint32_t target) { return target == ETF_RGBA32 || target == ETF_RGB565 || target == ETF_BGR565 || target == ETF_RGBA4444; }
 
 hipError_t launch_transcode_etc1s(hipStream_t st, const etc1s_transcode_args& a, uint32_t target, bool chroma_filter) {
@@ -363,6 +430,11 @@ hipError_t launch_etc1s_build_bc1_tables(hipStream_t st, uint32_t* d_tables) {
 
 hipError_t launch_etc1s_build_bc7_tables(hipStream_t st, uint32_t* d_tables) {
     hipLaunchKernelGGL(etc1s_build_bc7_tables_kernel, dim3((kBc7TableWords + 255) / 256), dim3(256), 0, st, d_tables);
+    return hipGetLastError();
+}
+
+hipError_t launch_etc1s_build_astc_tables(hipStream_t st, uint32_t* d_tables) {
+    hipLaunchKernelGGL(etc1s_build_astc_tables_kernel, dim3((2u * kAstcEntries + 249) / 250), dim3(256), 0, st, d_tables);
     return hipGetLastError();
 }
 

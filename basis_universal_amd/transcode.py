@@ -15,6 +15,8 @@ libbasisu_frontend.so (csrc/host/etc1s_decode.cpp, needs no GPU), the texel half
 
 `transcode_etc1s_texture`, `transcode_etc1s_textures` and `etc1s_texture_layout` are a parallel ETC1S family with two more targets, ETC2 RGBA and BC7 RGBA (16 bytes
 per block, ETC1S_TEXTURE_BYTES_PER_BLOCK), and BC7's chroma filter as an option; the three functions above keep their six targets and their refusals.
+`transcode_etc1s_block_format`, `transcode_etc1s_block_formats` and `etc1s_block_format_layout` are a third ETC1S family with the second one's targets and three
+more: ASTC 4x4 RGBA, EAC R11 and EAC RG11 (ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK); the second family keeps its eight targets and its refusals.
 
 `transcode_file_images` and `transcode_etc1s_file_images` (the last section) are the whole-file forms: every image of a file -- levels x layers x faces -- by ONE
 launch over a slice table, into one allocation whose layout `image_layout` gives.
@@ -260,6 +262,8 @@ ETC1S_BYTES_PER_PIXEL = {RGBA32: 4, RGB565: 2, BGR565: 2, RGBA4444: 2}
 ETC2_RGBA = 1
 ETC1S_TEXTURE_BYTES_PER_BLOCK = {ETC1_RGB: 8, BC1_RGB: 8, ETC2_RGBA: 16, BC7_RGBA: 16}   # the targets of transcode_etc1s_texture*; the pixel targets are ETC1S_BYTES_PER_PIXEL's
 DECODE_FLAGS_NO_ETC1S_CHROMA_FILTERING = 64   # cDecodeFlagsNoETC1SChromaFiltering: the one decode flag of the ETC1S texture entries
+# the targets of transcode_etc1s_block_format*: the texture family's and ASTC_4x4_RGBA (10), ETC2_EAC_R11 (20), ETC2_EAC_RG11 (21)
+ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK = {**ETC1S_TEXTURE_BYTES_PER_BLOCK, 10: 16, 20: 8, 21: 16}
 _TARGET_NAMES = ["ETC1_RGB", "ETC2_RGBA", "BC1_RGB", "BC3_RGBA", "BC4_R", "BC5_RG", "BC7_RGBA", "BC7_ALT", "PVRTC1_4_RGB", "PVRTC1_4_RGBA", "ASTC_4x4_RGBA", "ATC_RGB", "ATC_RGBA",
                  "RGBA32", "RGB565", "BGR565", "RGBA4444", "FXT1_RGB", "PVRTC2_4_RGB", "PVRTC2_4_RGBA", "ETC2_EAC_R11", "ETC2_EAC_RG11"]
 
@@ -351,15 +355,16 @@ def transcode_etc1s_image(ctx, decoded, image, target, *, out_device=None, out_r
     return _transcode_etc1s_image(ctx, decoded, image, _check_etc1s_target(target), None, out_device, out_row_pitch, out_rows)
 
 
-def _transcode_etc1s_image(ctx, decoded, image, target, decode_flags, out_device, out_row_pitch, out_rows):
-    """transcode_etc1s_image (decode_flags None: bu_hip_k_transcode_etc1s_counted) and transcode_etc1s_texture_image (bu_hip_k_transcode_etc1s_image_counted)"""
+def _transcode_etc1s_image(ctx, decoded, image, target, decode_flags, out_device, out_row_pitch, out_rows, block_format=False):
+    """transcode_etc1s_image (decode_flags None: bu_hip_k_transcode_etc1s_counted), transcode_etc1s_texture_image (bu_hip_k_transcode_etc1s_image_counted) and
+    transcode_etc1s_block_format_image (block_format: bu_hip_k_transcode_etc1s_block_format_counted)"""
     texture = decode_flags is not None
     nbx, nby, w, h = image["num_blocks_x"], image["num_blocks_y"], image["width"], image["height"]
     ep_pal = np.ascontiguousarray(decoded["endpoint_palette"], np.uint8).reshape(-1, 4)
     sel_pal = np.ascontiguousarray(decoded["selector_palette"], np.uint32).reshape(-1)
-    with_alpha = image["alpha_endpoint_indices"] is not None and target in (RGBA32, RGBA4444, ETC2_RGBA, BC7_RGBA)
+    with_alpha = image["alpha_endpoint_indices"] is not None and target in (RGBA32, RGBA4444, ETC2_RGBA, BC7_RGBA, ASTC_4x4_RGBA, ETC2_EAC_RG11)
     names = ["endpoint_indices", "selector_indices"] + (["alpha_endpoint_indices", "alpha_selector_indices"] if with_alpha else [])
-    output_bytes = ctx.lib.etc1s_image_output_bytes if texture else ctx.lib.etc1s_transcode_output_bytes
+    output_bytes = ctx.lib.etc1s_block_format_output_bytes if block_format else (ctx.lib.etc1s_image_output_bytes if texture else ctx.lib.etc1s_transcode_output_bytes)
     held = []
     with _output(ctx, out_device, out_row_pitch, out_rows, lambda: output_bytes(nbx, nby, w, h, target, 0, 0)) as d_out:
         try:
@@ -369,7 +374,9 @@ def _transcode_etc1s_image(ctx, decoded, image, target, decode_flags, out_device
             invalid = C.c_uint32(0)
             args = (ctx.h, C.c_void_p(held[0]), ep_pal.shape[0], C.c_void_p(held[1]), sel_pal.size, C.c_void_p(held[2]), C.c_void_p(held[3]), C.c_void_p(d_alpha[0]),
                     C.c_void_p(d_alpha[1]), nbx, nby, w, h, target, C.c_void_p(d_out), int(out_row_pitch), int(out_rows))
-            if texture:
+            if block_format:
+                ctx.check(ctx.lib.k_transcode_etc1s_block_format_counted(*args, int(decode_flags), C.byref(invalid)), "transcode_etc1s_block_format")
+            elif texture:
                 ctx.check(ctx.lib.k_transcode_etc1s_image_counted(*args, int(decode_flags), C.byref(invalid)), "transcode_etc1s_image")
             else:
                 ctx.check(ctx.lib.k_transcode_etc1s_counted(*args, C.byref(invalid)), "transcode_etc1s")
@@ -377,8 +384,8 @@ def _transcode_etc1s_image(ctx, decoded, image, target, decode_flags, out_device
                 raise ValueError(f"{invalid.value} of {nbx * nby} blocks have an index past its palette")
             if out_device is not None:
                 return None
-            if target in ETC1S_TEXTURE_BYTES_PER_BLOCK:
-                return ctx.download(d_out, (nbx * nby, ETC1S_TEXTURE_BYTES_PER_BLOCK[target]), np.uint8)
+            if target in ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK:
+                return ctx.download(d_out, (nbx * nby, ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK[target]), np.uint8)
             return ctx.download(d_out, (h, w, 4), np.uint8) if target == RGBA32 else ctx.download(d_out, (h, w), np.uint16)
         finally:
             for p in held:
@@ -431,6 +438,36 @@ def transcode_etc1s_texture(ctx, data, target, *, level=0, layer=0, face=0, chro
     raise ValueError(f"the file has no image at level {level}, layer {layer}, face {face}")
 
 
+# ---------------------------------------------------------------- the ETC1S block-format family: also ASTC 4x4, EAC R11 and EAC RG11
+
+def _check_etc1s_block_format_target(target):
+    target = int(target)
+    if target not in ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK and target not in ETC1S_BYTES_PER_PIXEL:
+        name = _TARGET_NAMES[target] if 0 <= target < len(_TARGET_NAMES) else "unknown"
+        raise ValueError(f"ETC1S block-format target {target} ({name}) is not supported (supported: "
+                         f"{sorted(list(ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK) + list(ETC1S_BYTES_PER_PIXEL))})")
+    return target
+
+
+def transcode_etc1s_block_format_image(ctx, decoded, image, target, *, chroma_filtering=True, out_device=None, out_row_pitch=0, out_rows=0):
+    """transcode_etc1s_texture_image over the block-format family's targets: the eight of the texture family, byte for byte the same, plus ASTC_4x4_RGBA (one block of
+    whichever ASTC mode the reference picks for the ETC1S block: void extent, block truncation, luminance + alpha, RGB, or RGBA over endpoints of range 0..47),
+    ETC2_EAC_R11 (the EAC block of the colour slice's first channel) and ETC2_EAC_RG11 (that block, then the alpha slice's). Block targets return (num_blocks, 8 | 16)
+    u8; an image without an alpha slice gets alpha 255 / the opaque second half. chroma_filtering matters to BC7_RGBA alone."""
+    return _transcode_etc1s_image(ctx, decoded, image, _check_etc1s_block_format_target(target), etc1s_decode_flags(chroma_filtering=chroma_filtering), out_device, out_row_pitch,
+                                  out_rows, True)
+
+
+def transcode_etc1s_block_format(ctx, data, target, *, level=0, layer=0, face=0, chroma_filtering=True):
+    """One image of an ETC1S .basis / .ktx2 file as a texture of the block-format family's targets (transcode_etc1s_block_format_image)."""
+    target, flags = _check_etc1s_block_format_target(target), etc1s_decode_flags(chroma_filtering=chroma_filtering)
+    decoded = decode_etc1s_file(data)
+    for im in decoded["images"]:
+        if (im["level"], im["layer"], im["face"]) == (level, layer, face):
+            return _transcode_etc1s_image(ctx, decoded, im, target, flags, None, 0, 0, True)
+    raise ValueError(f"the file has no image at level {level}, layer {layer}, face {face}")
+
+
 # ---------------------------------------------------------------- every image of a file in one launch
 
 NO_ALPHA_SLICE = 2 ** 64 - 1   # BU_HIP_NO_ALPHA_SLICE
@@ -444,6 +481,12 @@ class TranscodeSlice(C.Structure):   # = bu_hip_transcode_slice, include/basisu_
 def etc1s_texture_layout(images, target):
     """image_layout for the ETC1S texture family (transcode_etc1s_textures): block targets are (blocks, 8 | 16) u8 by ETC1S_TEXTURE_BYTES_PER_BLOCK. Host only."""
     return _layout(images, _check_etc1s_texture_target(target), ETC1S_TEXTURE_BYTES_PER_BLOCK, True)
+
+
+def etc1s_block_format_layout(images, target):
+    """image_layout for the ETC1S block-format family (transcode_etc1s_block_formats): block targets are (blocks, 8 | 16) u8 by ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK; for
+    the texture family's targets it is etc1s_texture_layout. Host only."""
+    return _layout(images, _check_etc1s_block_format_target(target), ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK, True)
 
 
 def image_layout(images, target, *, etc1s):
@@ -686,10 +729,25 @@ def transcode_etc1s_textures(ctx, data, target, *, chroma_filtering=True, out_de
                                    flags)
 
 
-def _transcode_etc1s_slices(ctx, decoded, images, firsts, alpha_firsts, target, out_device, decode_flags=None):
+def transcode_etc1s_block_formats(ctx, data, target, *, chroma_filtering=True, out_device=None):
+    """transcode_etc1s_textures over the block-format family's targets (bu_hip_k_transcode_etc1s_block_formats): every image of the file in one launch, each what
+    transcode_etc1s_block_format returns for it. With out_device (room for etc1s_block_format_layout's total_bytes) the output -- an ASTC texture for a client that
+    samples it, say -- stays there and etc1s_block_format_layout(images, target) is returned."""
+    target, flags = _check_etc1s_block_format_target(target), etc1s_decode_flags(chroma_filtering=chroma_filtering)
+    decoded = _decode_etc1s(data, False, whole=True)
+    images = decoded["images"]
+    return _transcode_etc1s_slices(ctx, decoded, images, [im["_first"] for im in images], [im["_alpha_first"] if im["has_alpha"] else None for im in images], target, out_device,
+                                   flags, True)
+
+
+def _transcode_etc1s_slices(ctx, decoded, images, firsts, alpha_firsts, target, out_device, decode_flags=None, block_format=False):
     """transcode_etc1s_file_images behind the decode (_decode_etc1s with whole=True): `images` (sizes) with where each one's indices begin in the file's whole
-    arrays. stats.py decodes an alpha slice as a colour image of its own this way. decode_flags not None: the texture family's entry and layout."""
-    layout, total = image_layout(images, target, etc1s=True) if decode_flags is None else etc1s_texture_layout(images, target)
+    arrays. stats.py decodes an alpha slice as a colour image of its own this way. decode_flags not None: the texture family's entry and layout, or with
+    block_format the block-format family's."""
+    if block_format:
+        layout, total = etc1s_block_format_layout(images, target)
+    else:
+        layout, total = image_layout(images, target, etc1s=True) if decode_flags is None else etc1s_texture_layout(images, target)
     recs = _slice_table(images, layout, firsts, alpha_firsts)
     ep_pal = np.ascontiguousarray(decoded["endpoint_palette"], np.uint8).reshape(-1, 4)
     sel_pal = np.ascontiguousarray(decoded["selector_palette"], np.uint32).reshape(-1)
@@ -701,7 +759,9 @@ def _transcode_etc1s_slices(ctx, decoded, images, firsts, alpha_firsts, target, 
 
         def call(d_out, out_bytes, invalid):
             head = (ctx.h, C.c_void_p(held[0]), ep_pal.shape[0], C.c_void_p(held[1]), sel_pal.size, C.c_void_p(held[2]), C.c_void_p(held[3]), ep_idx.size, recs, len(images), target)
-            if decode_flags is None:
+            if block_format:
+                ctx.check(ctx.lib.k_transcode_etc1s_block_formats(*head, int(decode_flags), d_out, out_bytes, invalid), "transcode_etc1s_block_formats")
+            elif decode_flags is None:
                 ctx.check(ctx.lib.k_transcode_etc1s_slices(*head, d_out, out_bytes, invalid), "transcode_etc1s_slices")
             else:
                 ctx.check(ctx.lib.k_transcode_etc1s_images(*head, int(decode_flags), d_out, out_bytes, invalid), "transcode_etc1s_images")

@@ -479,7 +479,8 @@ BU_HIP_API size_t bu_hip_transcode_slice_extent(const bu_hip_transcode_slice*, u
  *     convert_etc1s_to_bc7_m5_alpha :4472), bit for bit the reference's.
  * Without an alpha slice (both alpha pointers NULL, or BU_HIP_NO_ALPHA_SLICE) the two 16-byte targets write the opaque alpha half / opaque alpha fields; with one,
  * its indices are range-checked like the colour slice's. d_out of a 16-byte target must be 16-byte aligned.
- * BC3_RGBA, BC4_R and BC5_RG are refused: their look-up could not be restated as a search.
+ * BC3_RGBA, BC4_R and BC5_RG are refused: their look-up could not be restated as a search. ASTC_4x4_RGBA, ETC2_EAC_R11 and ETC2_EAC_RG11 are refused
+ * here and taken by the third family below.
  * decode_flags: 64 (cDecodeFlagsNoETC1SChromaFiltering) turns BC7's chroma filter off; any other bit is refused by name. The filter reads the endpoint indices of
  * the eight blocks around a block; one that is past the palette contributes the centre block's own entry (and is itself zero-filled and counted).
  * The ETC1S -> BC7 colour look-up is built on the device by the first BC7 transcode of a context (bu_hip_etc1s_bc7_color_table copies it, 15,360 words
@@ -499,6 +500,36 @@ BU_HIP_API size_t bu_hip_etc1s_image_output_bytes(uint32_t num_blocks_x, uint32_
         uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
 BU_HIP_API size_t bu_hip_etc1s_image_slice_extent(const bu_hip_transcode_slice*, uint32_t target);
 BU_HIP_API int bu_hip_etc1s_bc7_color_table(bu_hip_context*, uint32_t* h_out, uint32_t* h_midpoints);
+
+/* The ETC1S transcoder's third entry family: the second family's arguments, its eight targets byte for byte, and three more. The first two families keep their
+ * targets and their refusals; these also take
+ *   cTFASTC_4x4_RGBA (10): 16 bytes per block, convert_etc1s_to_astc_4x4 (transcoder/basisu_transcoder.cpp:5747) as the native build compiles it
+ *     (BASISD_SUPPORT_ASTC_HIGHER_OPAQUE_QUALITY = 1): void extent for a constant block; block truncation (CEM 12, 8-bit endpoints, 1-bit weights) when colour
+ *     and alpha use at most two selectors each; luminance + alpha (CEM 4) for a grey base colour; RGB over 8-bit endpoints (CEM 8) for an opaque block; else
+ *     RGBA over endpoints of BISE range 0..47 in two planes (CEM 12);
+ *   cTFETC2_EAC_R11 (20): 8 bytes per block, convert_etc1s_to_etc2_eac_r11 (:5104) on the colour slice's first channel; the alpha slice is not read;
+ *   cTFETC2_EAC_RG11 (21): 16 bytes per block, bytes 0-7 that block, bytes 8-15 the same conversion of the alpha slice.
+ * Without an alpha slice ASTC's alpha is 255 and RG11's second half the opaque EAC block (base 255, table 13, multiplier 1, every code 4). d_out of a 16-byte
+ * target must be 16-byte aligned. decode_flags as in the second family: 64 alone, which only BC7 heeds.
+ * Not supported, refused by name: BC3_RGBA, BC4_R, BC5_RG (their look-up could not be restated as a search), PVRTC1, PVRTC2, ATC, FXT1, and
+ * cDecodeFlagsTranscodeAlphaDataToOpaqueFormats (R11 from the alpha slice alone).
+ * The two ETC1S -> ASTC look-ups are built on the device by the first ASTC transcode of a context. bu_hip_etc1s_astc_tables copies them to the host: twice 15,360
+ * words [intensity table 8][base5 32][selector range 6][mapping 10] -> lo | hi << 8 | error << 16, over the 48 BISE codes of range 0..47 and over 8-bit
+ * endpoints, and the 48 unquantised values of those codes; tests compare them with tools/gen_etc1s_transcode_tables.py's host computation. */
+BU_HIP_API int bu_hip_k_transcode_etc1s_block_format(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette, uint32_t n_selectors,
+        const void* d_endpoint_idx, const void* d_selector_idx, const void* d_alpha_endpoint_idx, const void* d_alpha_selector_idx, uint32_t num_blocks_x, uint32_t num_blocks_y,
+        uint32_t orig_width, uint32_t orig_height, uint32_t target, void* d_out, uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels, uint32_t decode_flags);
+BU_HIP_API int bu_hip_k_transcode_etc1s_block_format_counted(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette,
+        uint32_t n_selectors, const void* d_endpoint_idx, const void* d_selector_idx, const void* d_alpha_endpoint_idx, const void* d_alpha_selector_idx, uint32_t num_blocks_x,
+        uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height, uint32_t target, void* d_out, uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels,
+        uint32_t decode_flags, uint32_t* out_invalid_blocks);
+BU_HIP_API int bu_hip_k_transcode_etc1s_block_formats(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette, uint32_t n_selectors,
+        const void* d_endpoint_idx, const void* d_selector_idx, uint64_t n_indices, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target,
+        uint32_t decode_flags, void* d_out, size_t out_bytes, uint32_t* out_invalid_per_slice);
+BU_HIP_API size_t bu_hip_etc1s_block_format_output_bytes(uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height, uint32_t target,
+        uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
+BU_HIP_API size_t bu_hip_etc1s_block_format_slice_extent(const bu_hip_transcode_slice*, uint32_t target);
+BU_HIP_API int bu_hip_etc1s_astc_tables(bu_hip_context*, uint32_t* h_out_0_47, uint32_t* h_out_0_255, uint32_t* h_unquant48);
 
 /* The UASTC transcoder's second entry family: bu_hip_k_transcode_uastc and bu_hip_k_transcode_uastc_slices with the targets that consume the ETC1 / EAC hints every
  * UASTC block carries, and the 16-bit rasters. The first family keeps its seven targets and its refusals; these take

@@ -4,7 +4,8 @@
   device the transcode kernel per target: palettes and indices resident in HBM, 5 warm-up + 50 timed launches, measured with the library's HIP events around the launch
          (bu_hip_profile_*), with the algorithmic bytes (4 B of indices in + the target's bytes out per block) over time as a fraction of the 8 TB/s HBM figure,
          and the whole call (launch, stream wait, read-back of the counter) on the host's clock, median of the timed calls. ETC2 RGBA and BC7 go through
-         bu_hip_k_transcode_etc1s_image_counted; BC7 is timed with and without the chroma filter.
+         bu_hip_k_transcode_etc1s_image_counted; BC7 is timed with and without the chroma filter. ASTC 4x4, EAC R11 and EAC RG11 go through
+         bu_hip_k_transcode_etc1s_block_format_counted (the image has no alpha slice: ASTC takes its opaque routes, RG11 writes the opaque second half).
 Also prints the RGB PSNR of the file read back (RGBA32) against the source: the figure README quotes for "the file after the backend's RDO".
 Prints one line per figure and one JSON line.   tools/etc1s_transcode_bench.py [steps] [warmup] [size]"""
 import ctypes as C
@@ -26,6 +27,7 @@ HBM_BYTES_PER_S = 8e12
 TARGETS = [("rgba32", transcode.RGBA32, 64), ("etc1", transcode.ETC1_RGB, 8), ("bc1", transcode.BC1_RGB, 8), ("rgb565", transcode.RGB565, 32), ("bgr565", transcode.BGR565, 32),
            ("rgba4444", transcode.RGBA4444, 32)]
 TEXTURE_TARGETS = [("etc2_rgba", transcode.ETC2_RGBA, 16, 0), ("bc7_filtered", transcode.BC7_RGBA, 16, 0), ("bc7_unfiltered", transcode.BC7_RGBA, 16, transcode.DECODE_FLAGS_NO_ETC1S_CHROMA_FILTERING)]
+BLOCK_FORMAT_TARGETS = [("astc_4x4", transcode.ASTC_4x4_RGBA, 16, 0), ("eac_r11", transcode.ETC2_EAC_R11, 8, 0), ("eac_rg11", transcode.ETC2_EAC_RG11, 16, 0)]
 
 
 def main():
@@ -55,11 +57,13 @@ def main():
     d = [ctx.upload(ep), ctx.upload(sel), ctx.upload(im["endpoint_indices"]), ctx.upload(im["selector_indices"])]
     d_out = ctx.alloc(n * 64)
     rows = {}
-    for name, target, out_bytes, flags in [t + (None,) for t in TARGETS] + TEXTURE_TARGETS:
+    for name, target, out_bytes, flags, block_format in [t + (None, False) for t in TARGETS] + [t + (False,) for t in TEXTURE_TARGETS] + [t + (True,) for t in BLOCK_FORMAT_TARGETS]:
         def launch():
             invalid = C.c_uint32(0)
             head = (ctx.h, C.c_void_p(d[0]), ep.shape[0], C.c_void_p(d[1]), sel.size, C.c_void_p(d[2]), C.c_void_p(d[3]), None, None, nbx, nby, size, size, target, C.c_void_p(d_out), 0, 0)
-            if flags is None:
+            if block_format:
+                ctx.check(ctx.lib.k_transcode_etc1s_block_format_counted(*head, flags, C.byref(invalid)), "transcode_etc1s_block_format")
+            elif flags is None:
                 ctx.check(ctx.lib.k_transcode_etc1s_counted(*head, C.byref(invalid)), "transcode_etc1s")
             else:
                 ctx.check(ctx.lib.k_transcode_etc1s_image_counted(*head, flags, C.byref(invalid)), "transcode_etc1s_image")

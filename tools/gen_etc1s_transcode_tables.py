@@ -23,6 +23,10 @@ EAC A8 (the alpha half of ETC2 RGBA) and BC7 mode 5: eac_a8_table(), bc7_color_t
 BC7 alpha and BC7 solid tables go into the .inc; the BC7 colour table (15,360 entries) is built on the device like BC1's. tests/golden/etc1s_texture_vectors.npz,
 whose coverage member reaches every entry a block can reach, decides the tie rules.
 
+EAC R11 / RG11 and ASTC 4x4 (the third entry family): eac_r11_table(), astc_table_0_47(), astc_table_0_255() with astc_scaled_errors(), astc_best_grey_mapping(),
+astc_unquant48(), astc_solid_table() and astc_nearest_table() state their searches. EAC R11 and the two small ASTC tables go into the .inc; the two ASTC endpoint
+look-ups (15,360 entries each) are built on the device (etc1s_build_astc_tables_kernel). tests/golden/etc1s_block_format_vectors.npz decides the rules.
+
 usage: gen_etc1s_transcode_tables.py [--check]     (--check: regenerate in memory and compare with the committed file)"""
 import functools
 import pathlib
@@ -96,18 +100,19 @@ def eac_a8_values():
     return np.clip(base.reshape(-1, 1) + mul.reshape(-1, 1) * EAC_MODIFIERS[table.reshape(-1)], 0, 255)
 
 
-def nearest_value_table(values, ranges, code_bits, ends_weighted):
+def nearest_value_table(values, ranges, code_bits, ends_weighted, target_of=lambda c: c):
     """[inten][base5][range] -> (row of `values`, trans): the candidate row whose values are nearest the ETC1S block's in-range colours, each colour on its nearest
     value (first minimum in code order), the squared differences summed; first minimum over the rows in their order. trans holds the code chosen for ETC1S selector
     s at bits code_bits * s, zero for a selector outside the range. ends_weighted: the widest intensity table over the whole selector range counts the errors of
-    selectors 0 and 3 five times (there the two clamp to 0 or 255 and the block is about those)."""
+    selectors 0 and 3 five times (there the two clamp to 0 or 255 and the block is about those). target_of: the value an 8-bit colour stands for on the scale of
+    `values` (EAC R11 compares on 11 bits)."""
     v = values.astype(np.int16)
     near_err = np.zeros((256, v.shape[0]), np.int32)
     near_code = np.zeros((256, v.shape[0]), np.uint8)
     base = expand(5)
     blocks = np.clip(base[None, :, None] + INTEN[:, None, :], 0, 255)   # (8, 32, 4)
     for c in np.unique(blocks):
-        d = np.abs(v - np.int16(c))
+        d = np.abs(v - np.int16(target_of(int(c))))
         near_code[c] = d.argmin(1)
         near_err[c] = d.min(1)
     near_err *= near_err
@@ -184,6 +189,134 @@ def bc7_solid_table():
     return out.reshape(-1)
 
 
+# ---------------------------------------------------------------- EAC R11 and ASTC 4x4 (the third entry family, etc1s_block_format_targets.h)
+
+def eac_r11_values():
+    """(256 * 16 * 16, 8): the eight 11-bit values of an EAC R11 block, row (base * 16 + multiplier) * 16 + table: clamp(base * 8 + 4 + modifier * multiplier * 8, 0,
+    2047); multiplier 0 acts as 1/8 (the modifier itself is added)."""
+    base, mul, table = np.meshgrid(np.arange(256), np.arange(16), np.arange(16), indexing="ij")
+    step = np.where(mul == 0, 1, mul * 8).reshape(-1, 1)
+    return np.clip(base.reshape(-1, 1) * 8 + 4 + step * EAC_MODIFIERS[table.reshape(-1)], 0, 2047)
+
+
+@functools.lru_cache(maxsize=None)
+def eac_r11_table():
+    """[inten][base5][range] -> base | (table | multiplier << 4) << 8 | trans << 16, the ETC1S -> EAC R11 look-up, laid out as eac_a8_table(). An 8-bit colour p stands
+    for the 11-bit value (p * 2047 + 128) / 255. Search order: base 0..255 outermost, multiplier 0..15, table innermost; each in-range selector on its nearest of the
+    eight values (first minimum), squared 11-bit differences summed, first minimum overall -- the loop order of the reference's generator. The ranges are EAC A8's."""
+    rows, trans = nearest_value_table(eac_r11_values(), ALPHA_RANGES, 3, False, lambda c: (c * 2047 + 128) // 255)
+    base, mul, table = rows // 256, (rows // 16) % 16, rows % 16
+    return (base | ((table | mul << 4) << 8) | (trans << 16)).astype(np.uint32).reshape(-1)
+
+
+def astc_unquant48():
+    """[BISE code of range 0..47: four bits, then a trit] -> the 8-bit endpoint value, by the format's unquantisation formula for one trit and four bits
+    (A = the lowest bit replicated nine times, B = the other three bits b at b | b << 6, C = 22: ((trit * C + B) ^ A) >> 2, bit 7 from A)"""
+    out = np.zeros(48, np.int64)
+    for trit in range(3):
+        for bit in range(16):
+            a = 511 if bit & 1 else 0
+            b = (bit >> 1) | ((bit >> 1) << 6)
+            out[bit | (trit << 4)] = (a & 0x80) | (((trit * 22 + b) ^ a) >> 2)
+    return out
+
+
+def astc_values(e):
+    """(n * n, 4): the four values of an ASTC 2-bit weight between endpoints hi (outer) and lo (inner) of the unquantised 8-bit values e: both replicated to 16 bits,
+    ((c0 * (64 - w) + c1 * w + 32) / 64) >> 8 for the weights 0, 21, 43, 64"""
+    hi, lo = np.meshgrid(e, e, indexing="ij")
+    c1, c0 = (hi | (hi << 8)).reshape(-1), (lo | (lo << 8)).reshape(-1)
+    return np.stack([((c0 * (64 - w) + c1 * w + 32) // 64) >> 8 for w in (0, 21, 43, 64)], -1)
+
+
+def astc_scaled_errors(raw):
+    """(..., 10) raw errors of an entry's ten mappings -> what the table holds: as they are while the largest of the ten fits 16 bits, else each times 65535 over
+    that largest, rounded to nearest (halves up) -- so the largest becomes 65535 and the order among the ten is kept where a plain clamp would lose it"""
+    raw = np.asarray(raw, np.int64)
+    top = raw.max(-1, keepdims=True)
+    return np.where(top > 0xFFFF, (2 * raw * 0xFFFF + top) // (2 * np.maximum(top, 1)), raw)
+
+
+def astc_endpoint_table(e, scaled=True):
+    """[inten][base5][range][mapping] -> lo | hi << 8 | err << 16 over the endpoint values e, lo and hi being indices into e (BISE codes for the 0..47 table, the
+    values themselves for 0..255). The selector ranges (RANGES) and the ten mappings (MAPPINGS) are BC1's, in that order. hi outermost, lo innermost, first minimum;
+    squared error over the range's selectors, those of selectors 0 and 3 counted eight times for the widest intensity table over the range (0, 3); the ten errors
+    of an entry are stored through astc_scaled_errors() (scaled=False: each clamped to 65535 instead -- NOT what the reference's tables hold; the golden generator
+    uses it to find the blocks that tell the two rules apart)."""
+    n = e.size
+    colors = astc_values(e).astype(np.int32)
+    base = expand(5)
+    out = np.zeros((8, 32, len(RANGES), len(MAPPINGS)), np.uint32)
+    pairs = sorted({(s, mapping[s]) for mapping in MAPPINGS for s in range(4)})
+    for t in range(8):
+        block = np.clip(base[:, None] + INTEN[t][None, :], 0, 255).astype(np.int32)
+        sq = {(s, k): (block[:, s][:, None] - colors[:, k][None, :]) ** 2 for s, k in pairs}   # (32, n * n) each
+        for r, (s0, s1) in enumerate(RANGES):
+            eight = t == 7 and (s0, s1) == (0, 3)
+            raw = np.zeros((32, len(MAPPINGS)), np.int64)
+            for m, mapping in enumerate(MAPPINGS):
+                err = sum(sq[s, mapping[s]] * (8 if eight and s in (0, 3) else 1) for s in range(s0, s1 + 1))
+                best = err.argmin(1)
+                raw[:, m] = err[np.arange(32), best]
+                out[t, :, r, m] = (best % n) | ((best // n) << 8)
+            stored = astc_scaled_errors(raw) if scaled else np.minimum(raw, 0xFFFF)
+            assert stored.max() <= 0xFFFF
+            out[t, :, r, :] |= (stored << 16).astype(np.uint32)
+    return out.reshape(-1)
+
+
+@functools.lru_cache(maxsize=None)
+def astc_table_0_47():
+    """the ETC1S -> ASTC look-up over the 48 BISE codes of endpoint range 0..47, searched in code order"""
+    return astc_endpoint_table(astc_unquant48())
+
+
+@functools.lru_cache(maxsize=None)
+def astc_table_0_255():
+    """the same over 8-bit endpoints (the higher-quality opaque and grey routes); 256 x 256 pairs per entry, a few seconds"""
+    return astc_endpoint_table(np.arange(256))
+
+
+def astc_table_0_255_entries(t, base5, r):
+    """the ten entries [inten t][base5][range r][mapping] of astc_table_0_255() by the same search, for checks that cannot afford the whole table"""
+    colors = astc_values(np.arange(256)).astype(np.int64)
+    block = np.clip(int(expand(5)[base5]) + INTEN[t], 0, 255)
+    s0, s1 = RANGES[r]
+    eight = t == 7 and (s0, s1) == (0, 3)
+    best, raw = [], []
+    for mapping in MAPPINGS:
+        err = sum((int(block[s]) - colors[:, mapping[s]]) ** 2 * (8 if eight and s in (0, 3) else 1) for s in range(s0, s1 + 1))
+        best.append(int(err.argmin()))
+        raw.append(int(err[best[-1]]))
+    return np.array([(b % 256) | ((b // 256) << 8) | (int(v) << 16) for b, v in zip(best, astc_scaled_errors(raw))], np.uint32)
+
+
+def astc_best_grey_mapping(table):
+    """[inten][base5][range] -> the mapping of the ten with the least error in an endpoint table, first on ties: what a one-channel (grey or alpha) conversion uses"""
+    return (table.reshape(8, 32, len(RANGES), len(MAPPINGS)) >> 16).argmin(3).astype(np.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def astc_solid_table():
+    """[value] {lo, hi}: the BISE codes of range 0..47 whose weight-21 value is nearest the value: lo outermost, hi innermost over the codes in order, first minimum"""
+    u = astc_unquant48()
+    lo, hi = np.meshgrid(u, u, indexing="ij")
+    l16, h16 = (lo | (lo << 8)).reshape(-1), (hi | (hi << 8)).reshape(-1)
+    v = ((l16 * 43 + h16 * 21 + 32) // 64) >> 8
+    out = np.zeros((256, 2), np.uint8)
+    for i in range(256):
+        k = int(np.abs(v - i).argmin())
+        out[i] = (k // 48, k % 48)
+    return out.reshape(-1)
+
+
+@functools.lru_cache(maxsize=None)
+def astc_nearest_table():
+    """[value] -> the BISE code of range 0..47 whose unquantised value is nearest, first on ties in code order"""
+    u = astc_unquant48()
+    return np.array([int(np.abs(u - i).argmin()) for i in range(256)], np.uint8)
+
+
 def emit(name, ctype, values, per_line, comment, fmt):
     lines = [f"// {comment}", f"BU_TAB {ctype} {name}[{values.size}] = {{"]
     for i in range(0, values.size, per_line):
@@ -223,6 +356,12 @@ def generate():
         emit("ke_eac_a8", "unsigned int", eac_a8_table(), 8, "[inten][base5][range] -> base | (table | multiplier << 4) << 8 | 3-bit code of selector s << (16 + 3 s)", "0x%07x"),
         emit("ke_bc7_alpha", "unsigned int", bc7_alpha_table(), 8, "[inten][base5][range] -> lo | hi << 8 | 2-bit index of selector s << (16 + 2 s)", "0x%06x"),
         emit("ke_bc7_solid", "unsigned char", bc7_solid_table(), 32, "[value] {hi, lo}: 7-bit endpoints whose index-1 colour is nearest the value", "%3u"),
+        "// Tables of the ETC1S -> EAC R11 and ETC1S -> ASTC 4x4 block conversions. EAC R11 uses EAC A8's selector ranges, ASTC the ranges and mappings of BC1. The two ASTC",
+        "// endpoint look-ups (15,360 entries each) are not here: etc1s_build_astc_tables_kernel computes them on the device, astc_table_0_47() and astc_table_0_255() of the",
+        "// tool are the same searches on the host.",
+        emit("ke_eac_r11", "unsigned int", eac_r11_table(), 8, "[inten][base5][range] -> base | (table | multiplier << 4) << 8 | 3-bit code of selector s << (16 + 3 s)", "0x%07x"),
+        emit("ke_astc_solid", "unsigned char", astc_solid_table(), 32, "[value] {lo, hi}: BISE codes of range 0..47 whose weight-21 value is nearest the value", "%2u"),
+        emit("ke_astc_nearest", "unsigned char", astc_nearest_table(), 32, "[value]: the BISE code of range 0..47 nearest the value", "%2u"),
     ]
     return "\n".join(parts) + "\n"
 
