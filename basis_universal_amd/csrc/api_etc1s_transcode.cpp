@@ -227,6 +227,19 @@ int bu_hip_etc1s_bc7_color_table(bu_hip_context* ctx, uint32_t* h_out, uint32_t*
     return fetch(ctx, h_out, d, n * sizeof(uint32_t)) && fetch(ctx, h_midpoints, d + n, 128 * sizeof(uint32_t)) ? 1 : 0;
 }
 
+int bu_hip_k_bc7_mode5_tiles(bu_hip_context* ctx, const void* d_tiles, uint32_t n_tiles, void* d_out) {
+    if (!ctx) return 0;
+    if (!d_tiles || !d_out) { set_error(ctx, "bc7_mode5_tiles: null device pointer"); return 0; }
+    if ((reinterpret_cast<uintptr_t>(d_tiles) | reinterpret_cast<uintptr_t>(d_out)) & 15u) { set_error(ctx, "bc7_mode5_tiles: the tiles and the output must be 16-byte aligned"); return 0; }
+    if (n_tiles > (1u << 30)) { set_error(ctx, "bc7_mode5_tiles: %u tiles is too many (at most 2^30)", n_tiles); return 0; }
+    if (!n_tiles) return 1;
+    device_guard g(ctx->device);
+    if (!ensure_bc7_tables(ctx)) return 0;
+    prof_scope ps(ctx, "bc7_mode5_tiles");
+    BU_TRY(ctx, bu::launch_bc7_mode5_tiles(ctx->stream, d_tiles, n_tiles, d_out, static_cast<const uint32_t*>(ctx->etc1s_bc7_tables.p)));
+    return 1;
+}
+
 int bu_hip_k_transcode_etc1s_image_counted(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
                                            const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, void* d_out,
                                            uint32_t pitch_px, uint32_t rows_px, uint32_t decode_flags, uint32_t* out_invalid_blocks) {

@@ -53,6 +53,8 @@ hipError_t launch_transcode_etc1s_slices(hipStream_t st, const etc1s_transcode_s
 hipError_t launch_etc1s_build_bc1_tables(hipStream_t st, uint32_t* d_tables);
 // fills d_tables[kEtc1sBc7TableWords]
 hipError_t launch_etc1s_build_bc7_tables(hipStream_t st, uint32_t* d_tables);
+// diagnostic: the chroma filter's mode-5 encoder on n_tiles tiles of 16 RGBA pixels (64 bytes each, alpha ignored) -> n_tiles opaque 16-byte blocks
+hipError_t launch_bc7_mode5_tiles(hipStream_t st, const void* d_tiles, uint32_t n_tiles, void* d_out, const uint32_t* bc7_tables);
 // fills d_tables[kEtc1sAstcTableWords]
 hipError_t launch_etc1s_build_astc_tables(hipStream_t st, uint32_t* d_tables);
 // counts the entries of idx[n] that are >= limit into *d_count (cleared first)

@@ -362,6 +362,20 @@ __global__ __launch_bounds__(256) void etc1s_count_indices_past_kernel(const uin
     if (i < n && idx[i] >= limit) atomicAdd(count, 1u);
 }
 
+// A diagnostic (bu_hip_k_bc7_mode5_tiles): the filter's encoder on tiles of the caller's choosing, one lane per tile of 16 RGBA pixels, alpha ignored.
+__global__ __launch_bounds__(256) void bc7_mode5_tiles_kernel(const uint4* tiles, uint32_t n_tiles, uint4* out, const uint32_t* bc7_tables) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_tiles) return;
+    uint32_t px[16];
+#pragma unroll
+    for (uint32_t q = 0; q < 4; q++) {
+        const uint4 v = tiles[(size_t)i * 4u + q];
+        px[q * 4u] = v.x & 0xFFFFFFu; px[q * 4u + 1u] = v.y & 0xFFFFFFu; px[q * 4u + 2u] = v.z & 0xFFFFFFu; px[q * 4u + 3u] = v.w & 0xFFFFFFu;
+    }
+    const bc7_m5 b = encode_bc7_mode5(px, reinterpret_cast<const float*>(bc7_tables + kBc7ColorEntries));
+    out[i] = make_uint4((uint32_t)b.lo, (uint32_t)(b.lo >> 32), (uint32_t)b.hi, (uint32_t)(b.hi >> 32));
+}
+
 template <uint32_t TARGET, bool FILTER = false>
 static hipError_t launch(hipStream_t st, const etc1s_transcode_args& a) {
     const uint32_t n = a.g.nbx * a.g.nby;
@@ -430,6 +444,12 @@ hipError_t launch_etc1s_build_bc1_tables(hipStream_t st, uint32_t* d_tables) {
 
 hipError_t launch_etc1s_build_bc7_tables(hipStream_t st, uint32_t* d_tables) {
     hipLaunchKernelGGL(etc1s_build_bc7_tables_kernel, dim3((kBc7TableWords + 255) / 256), dim3(256), 0, st, d_tables);
+    return hipGetLastError();
+}
+
+hipError_t launch_bc7_mode5_tiles(hipStream_t st, const void* d_tiles, uint32_t n_tiles, void* d_out, const uint32_t* bc7_tables) {
+    if (!n_tiles) return hipSuccess;
+    hipLaunchKernelGGL(bc7_mode5_tiles_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st, static_cast<const uint4*>(d_tiles), n_tiles, static_cast<uint4*>(d_out), bc7_tables);
     return hipGetLastError();
 }
 

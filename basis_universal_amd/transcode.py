@@ -438,6 +438,24 @@ def transcode_etc1s_texture(ctx, data, target, *, level=0, layer=0, face=0, chro
     raise ValueError(f"the file has no image at level {level}, layer {layer}, face {face}")
 
 
+def bc7_mode5_tiles(ctx, tiles):
+    """A diagnostic (bu_hip_k_bc7_mode5_tiles): the mode-5 encoder that runs under BC7's chroma filter, on (n, 16, 4) u8 RGBA tiles (pixel y * 4 + x, alpha ignored)
+    -> (n, 16) u8 opaque blocks."""
+    tiles = np.ascontiguousarray(tiles, np.uint8)
+    if tiles.ndim != 3 or tiles.shape[1:] != (16, 4):
+        raise ValueError(f"bc7_mode5_tiles wants (n, 16, 4) u8 tiles, not {tiles.shape}")
+    n = tiles.shape[0]
+    if n == 0:
+        return np.zeros((0, 16), np.uint8)
+    d_tiles, d_out = ctx.upload(tiles), ctx.alloc(n * 16)
+    try:
+        ctx.check(ctx.lib.k_bc7_mode5_tiles(ctx.h, C.c_void_p(d_tiles), n, C.c_void_p(d_out)), "bc7_mode5_tiles")
+        return ctx.download(d_out, (n, 16), np.uint8)
+    finally:
+        ctx.free(d_tiles)
+        ctx.free(d_out)
+
+
 # ---------------------------------------------------------------- the ETC1S block-format family: also ASTC 4x4, EAC R11 and EAC RG11
 
 def _check_etc1s_block_format_target(target):

@@ -500,6 +500,11 @@ BU_HIP_API size_t bu_hip_etc1s_image_output_bytes(uint32_t num_blocks_x, uint32_
         uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
 BU_HIP_API size_t bu_hip_etc1s_image_slice_extent(const bu_hip_transcode_slice*, uint32_t target);
 BU_HIP_API int bu_hip_etc1s_bc7_color_table(bu_hip_context*, uint32_t* h_out, uint32_t* h_midpoints);
+/* A diagnostic, not a transcoding entry: the mode-5 encoder that runs under BC7's chroma filter, on tiles of the caller's choosing instead of the pixels the filter
+ * rebuilds. d_tiles: n_tiles tiles of 16 RGBA pixels (64 bytes each, pixel y * 4 + x, alpha ignored); d_out: n_tiles opaque 16-byte blocks. One lane per tile, the
+ * same device function and the same midpoint table (this context's) as the filter. Queued on the context's stream like the transcodes. Refused before any launch,
+ * d_out untouched: a null pointer, either pointer not 16-byte aligned, more than 2^30 tiles. n_tiles == 0 returns 1 and writes nothing. */
+BU_HIP_API int bu_hip_k_bc7_mode5_tiles(bu_hip_context*, const void* d_tiles, uint32_t n_tiles, void* d_out);
 
 /* The ETC1S transcoder's third entry family: the second family's arguments, its eight targets byte for byte, and three more. The first two families keep their
  * targets and their refusals; these also take

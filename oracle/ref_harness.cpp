@@ -118,7 +118,19 @@ REF_API int ref_etc1_optimize(const uint8_t* rgba, uint32_t n, int quality, int 
 // What this build of the harness offers, for tests that need more than an older build carried over in oracle/_ref/ has:
 // 2 = ref_etc1_optimize_forced, the frontend call "compute_endpoint_subblock_error_vec" and the getter "subblock_endpoint_quant_err".
 // 3 = ref_transcode_uastc: the per-block UASTC transcoders of every supported target over an array of blocks.
-REF_API int ref_harness_version() { return 3; }
+// 4 = ref_encode_bc7_mode5: the mode-5 encoder under the ETC1S -> BC7 chroma filter over an array of tiles.
+REF_API int ref_harness_version() { return 4; }
+
+// bc7_mode_5_encoder::encode_bc7_mode_5_block (transcoder.cpp:8102) as chroma_filter_bc7_mode5 calls it (:4772, hq_mode false) over n tiles of 16 RGBA pixels
+// -> n 16-byte blocks. The encoder's midpoint table is the transcoder's init's, which ref_init has run.
+REF_API int ref_encode_bc7_mode5(const uint8_t* tiles, uint32_t n, uint8_t* out) {
+	for (uint32_t i = 0; i < n; i++) {
+		basist::color32 px[16];
+		memcpy(px, tiles + (size_t)i * 64, 64);
+		basist::bc7_mode_5_encoder::encode_bc7_mode_5_block(out + (size_t)i * 16, px, false);
+	}
+	return 1;
+}
 
 // The same with m_pForce_selectors (etc.cpp:780-784): one selector (0..3) per pixel; the reference refuses qualities below slow.
 REF_API int ref_etc1_optimize_forced(const uint8_t* rgba, uint32_t n, int quality, int perceptual, const uint8_t* force_selectors,

@@ -167,11 +167,23 @@ def _midpoints():
 
 MIDPOINTS = _midpoints()
 
+# Deliberate errors in the restatement below, each behind its name in MUTATIONS (empty: the restatement as it is). tests/test_etc1s_bc7_filter_host.py switches them on
+# one at a time to show that the golden cases tell each of them from the real thing; nothing else may.
+#   chroma_ge   >= for > at the chroma gate                  var_le      <= for < at the variance gate
+#   var_fused   the variance gate's mean * mean unrounded: product and difference in binary64, rounded once (what a fused multiply-subtract computes)
+#   alt_fused   the same in the three sums of the power iteration            ls_fused    the same in the two least-squares results per channel
+#   recip       x * (1 / d) for the two divisions 2048 / k and (3 / 255) / det              axis_round  rounding for truncation in (int)(alt * m)
+#   to7_ge      >= for > in to_7                              skip_corner the gate never looks at the neighbour at (+1, +1)
+#   clamp_off   a neighbour past an edge is clamped one block short of that edge             tie_other   ties on the axis go to the other pixel
+#   thresh_161  161 for 160 as the low-variance threshold
+MUTATIONS = set()
+D = np.float64
+
 
 def to_7(c):
     """a float in 0..1 -> the 7-bit endpoint nearest it"""
     v = int(c * F(127.0))
-    return min(max(v + int(c > MIDPOINTS[v]), 0), 127)
+    return min(max(v + int(c >= MIDPOINTS[v] if "to7_ge" in MUTATIONS else c > MIDPOINTS[v]), 0), 127)
 
 
 def to_7_from_8(c8):
@@ -206,9 +218,10 @@ def pack_mode5_rgb(l, h, w):
     return _pack_lo(l, h), 3 | (_index_bits([v ^ inv for v in w]) << 2)
 
 
-def encode_mode5(t, px):
+def encode_mode5(t, px, trace=None):
     """the filter's mode-5 encoder over 16 RGB pixels ((16, 3) ints) -> ((lo, hi), route): "equal" all pixels the same, "simple" low variance: endpoints at 16/255 and
-    239/255 of the channel ranges, "pca" principal axis + one least-squares pass, "pca_det" the same when the least-squares system is singular"""
+    239/255 of the channel ranges, "pca" principal axis + one least-squares pass, "pca_det" the same when the least-squares system is singular. trace: a dict that
+    receives max_var and, on the two pca routes, default_axis (the power iteration gave nothing), the dots' tie classes (ties) and the two end pixels' numbers."""
     px = [[int(v) for v in p] for p in px]
     total = [sum(p[k] for p in px) for k in range(3)]
     mn, mx = [min(p[k] for p in px) for k in range(3)], [max(p[k] for p in px) for k in range(3)]
@@ -222,7 +235,9 @@ def encode_mode5(t, px):
         for j, v in enumerate((r * r, r * g, r * b, g * g, g * b, b * b)):
             icov[j] += v
     max_var = max(icov[0], icov[3], icov[5])
-    if max_var < 160:
+    if trace is not None:
+        trace["max_var"] = max_var
+    if max_var < (161 if "thresh_161" in MUTATIONS else 160):
         def lerp8(a, b, s):
             v = (b - a) * s + 128
             return a + ((v + (v >> 8)) >> 8)
@@ -232,17 +247,24 @@ def encode_mode5(t, px):
     sc = F(1.0) / F(max_var)
     wx, wy, wz = sc * cov[0], sc * cov[3], sc * cov[5]
     alt = [cov[0] * wx + cov[1] * wy + cov[2] * wz, cov[1] * wx + cov[3] * wy + cov[4] * wz, cov[2] * wx + cov[4] * wy + cov[5] * wz]
+    if "alt_fused" in MUTATIONS:
+        alt = [F(D(cov[a]) * D(wx) + D(cov[b]) * D(wy) + D(cov[c]) * D(wz)) for a, b, c in ((0, 1, 2), (1, 3, 4), (2, 4, 5))]
     axis = [306, 601, 117]
     k = max(abs(alt[0]), abs(alt[1]), abs(alt[2]))
     if k >= F(.0000125):
-        m = F(2048.0) / k
-        axis = [int(v * m) for v in alt]
+        m = F(2048.0) * (F(1.0) / k) if "recip" in MUTATIONS else F(2048.0) / k
+        axis = [int(np.rint(v * m)) if "axis_round" in MUTATIONS else int(v * m) for v in alt]
+    elif trace is not None:
+        trace["default_axis"] = True
     axis = [v * 16 for v in axis]
-    low_dot, high_dot = 2 ** 31 - 1, -2 ** 31
-    for i, p in enumerate(px):
-        d = ((p[0] * axis[0] + p[1] * axis[1] + p[2] * axis[2]) & ~0xF) + i
-        low_dot, high_dot = min(low_dot, d), max(high_dot, d)
-    pl, ph = px[low_dot & 15], px[high_dot & 15]
+    low_dot, high_dot, other = 2 ** 31 - 1, -2 ** 31, 15 if "tie_other" in MUTATIONS else 0
+    dots = [(p[0] * axis[0] + p[1] * axis[1] + p[2] * axis[2]) & ~0xF for p in px]
+    for i, d in enumerate(dots):
+        low_dot, high_dot = min(low_dot, d + (i ^ other)), max(high_dot, d + (i ^ other))
+    pl, ph = px[(low_dot & 15) ^ other], px[(high_dot & 15) ^ other]
+    if trace is not None:   # a tie that matters: pixels of different colours share the lowest or the highest dot
+        trace["ends"] = ((low_dot & 15) ^ other, (high_dot & 15) ^ other)
+        trace["ties"] = [len({tuple(p) for p, d in zip(px, dots) if d == e}) for e in (min(dots), max(dots))]
     l, h = [to_7_from_8(v) for v in pl], [to_7_from_8(v) for v in ph]
     w = eval_weights(px, l, h)
     # least squares for the endpoints under these weights
@@ -253,13 +275,15 @@ def encode_mode5(t, px):
     det = z00 * z11 - z10 * z10
     if abs(det) < F(1e-8):
         return pack_mode5_rgb(l, h, w), "pca_det"
-    det = (F(3.0) / F(255.0)) / det
+    det = (F(3.0) / F(255.0)) * (F(1.0) / det) if "recip" in MUTATIONS else (F(3.0) / F(255.0)) / det
     iz00, iz01, iz10, iz11 = z11 * det, -z10 * det, -z10 * det, z00 * det
 
     def clamp01(v):
         return F(0.0) if v < F(0.0) else (F(1.0) if v > F(1.0) else v)
-    h = [to_7(clamp01(iz00 * F(uq[c]) + iz01 * F(q10[c]))) for c in range(3)]
-    l = [to_7(clamp01(iz10 * F(uq[c]) + iz11 * F(q10[c]))) for c in range(3)]
+    def pair(a, b, c):
+        return F(D(a) * D(F(uq[c])) + D(b) * D(F(q10[c]))) if "ls_fused" in MUTATIONS else a * F(uq[c]) + b * F(q10[c])
+    h = [to_7(clamp01(pair(iz00, iz01, c))) for c in range(3)]
+    l = [to_7(clamp01(pair(iz10, iz11, c))) for c in range(3)]
     return pack_mode5_rgb(l, h, eval_weights(px, l, h)), "pca"
 
 
@@ -268,22 +292,28 @@ def cocg(e):
     return (r * F(0.5) + g * F(0.0)) + b * F(-0.5), (r * F(-0.25) + g * F(0.5)) + b * F(-0.25)
 
 
-def chroma_filter_block(t, lo, hi, ep, ei, bx, by, neighbour_ok=None):
+def chroma_filter_block(t, lo, hi, ep, ei, bx, by, neighbour_ok=None, trace=None):
     """The chroma filter on block (bx, by) of an image whose colour-slice endpoint indices are ei (nby, nbx): -> ((lo, hi), route). route: None no neighbour differs
     in chroma, "smooth" left alone by the variance gate, else encode_mode5's. neighbour_ok (same shape, bool): False marks an index past the palette, which
     contributes the centre's own entry (the device's documented rule)."""
     nby, nbx = ei.shape
 
+    def clamp(v, n):
+        if "clamp_off" in MUTATIONS:
+            return min(1, n - 1) if v < 0 else (max(n - 2, 0) if v >= n else v)
+        return min(max(v, 0), n - 1)
+
     def entry(x, y):
-        x, y = min(max(x, 0), nbx - 1), min(max(y, 0), nby - 1)
+        x, y = clamp(x, nbx), clamp(y, nby)
         return ep[int(ei[by, bx])] if neighbour_ok is not None and not neighbour_ok[y, x] else ep[int(ei[y, x])]
     cco, ccg = cocg(entry(bx, by))
     differs = False
     for dy in (-1, 0, 1):
         for dx in (-1, 0, 1):
-            if (dx or dy) and 0 <= bx + dx < nbx and 0 <= by + dy < nby:
+            if (dx or dy) and 0 <= bx + dx < nbx and 0 <= by + dy < nby and not ("skip_corner" in MUTATIONS and dx == 1 and dy == 1):
                 co, cg = cocg(entry(bx + dx, by + dy))
-                differs = differs or abs(co - cco) > F(10) or abs(cg - ccg) > F(10)
+                dco, dcg = abs(co - cco), abs(cg - ccg)
+                differs = differs or ((dco >= F(10) or dcg >= F(10)) if "chroma_ge" in MUTATIONS else (dco > F(10) or dcg > F(10)))
     if not differs:
         return (lo, hi), None
     l8 = [from_7((lo >> s) & 127) for s in (8, 22, 36)]
@@ -301,7 +331,8 @@ def chroma_filter_block(t, lo, hi, ep, ei, bx, by, neighbour_ok=None):
         y_sq = y_sq + y * y
     S = F(1.0) / F(16.0)
     mean = y_sum * S
-    if (y_sq * S) - mean * mean < F(3.0):
+    var = F(D(y_sq * S) - D(mean) * D(mean)) if "var_fused" in MUTATIONS else (y_sq * S) - mean * mean
+    if var <= F(3.0) if "var_le" in MUTATIONS else var < F(3.0):
         return (lo, hi), "smooth"
     px = []
     for py in range(4):
@@ -318,11 +349,14 @@ def chroma_filter_block(t, lo, hi, ep, ei, bx, by, neighbour_ok=None):
             y = ys[py * 4 + pxx]
             rgb = [(y * F(1.0) + f[0] * F(1.0)) + f[1] * F(-1.0), (y * F(1.0) + f[0] * F(0.0)) + f[1] * F(1.0), (y * F(1.0) + f[0] * F(-1.0)) + f[1] * F(-1.0)]
             px.append([int(F(.5) + min(max(v, F(0.0)), F(255.0))) for v in rgb])
-    return encode_mode5(t, px)
+    if trace is not None:
+        trace["px"] = px
+    return encode_mode5(t, px, trace)
 
 
-def bc7_blocks(decoded, image, chroma_filtering=True, routes=None, neighbour_ok=None):
-    """(n, 16) u8: what the transcoder writes for BC7_RGBA. routes: a dict that receives how many blocks took each of chroma_filter_block's routes."""
+def bc7_blocks(decoded, image, chroma_filtering=True, routes=None, neighbour_ok=None, route_of=None):
+    """(n, 16) u8: what the transcoder writes for BC7_RGBA. routes: a dict that receives how many blocks took each of chroma_filter_block's routes; route_of: a list
+    that receives every block's route, in raster order, the two pca routes with "+axis" behind them where the encoder fell back to its default axis."""
     t, ep, sel = tables(), np.asarray(decoded["endpoint_palette"]), selectors16(decoded["selector_palette"])
     ei, si = image["endpoint_indices"], image["selector_indices"]
     nby, nbx = ei.shape
@@ -331,9 +365,12 @@ def bc7_blocks(decoded, image, chroma_filtering=True, routes=None, neighbour_ok=
         for bx in range(nbx):
             lo, hi = bc7_color(t, ep[int(ei[by, bx])], sel[int(si[by, bx])])
             if chroma_filtering:
-                (lo, hi), route = chroma_filter_block(t, lo, hi, ep, ei, bx, by, neighbour_ok)
+                trace = {}
+                (lo, hi), route = chroma_filter_block(t, lo, hi, ep, ei, bx, by, neighbour_ok, trace)
                 if routes is not None:
                     routes[route] = routes.get(route, 0) + 1
+                if route_of is not None:
+                    route_of.append(route + "+axis" if trace.get("default_axis") else route)
             if image["alpha_endpoint_indices"] is not None:
                 lo, hi = bc7_alpha(t, lo, hi, ep[int(image["alpha_endpoint_indices"][by, bx])], sel[int(image["alpha_selector_indices"][by, bx])])
             out[by * nbx + bx] = np.frombuffer(int(lo).to_bytes(8, "little") + int(hi).to_bytes(8, "little"), np.uint8)
