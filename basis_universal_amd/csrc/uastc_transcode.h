@@ -14,9 +14,11 @@
 // pack_eac / pack_eac_high_quality (:18868-19155), transcode_uastc_to_etc2_eac_r11 / _rg11 (:19157-19214) and the three 16-bit cases of transcode_slice
 // (:10246-10302). The first family's callers (transcode_bytes_per_block) do not reach them.
 //
-// Out of scope: ETC1 from the alpha channel (cDecodeFlagsTranscodeAlphaDataToOpaqueFormats: the single-channel packer at :16925), PVRTC1 (needs neighbouring blocks
-// and power-of-two images), ATC / FXT1 / PVRTC2 (the reference refuses them for UASTC too), ETC1S slices, UASTC HDR / ASTC LDR / XUASTC blocks,
-// Zstandard-supercompressed KTX2 levels. Callers refuse those; nothing is silently mapped to another target.
+// PVRTC1 is not a per-block target (a block's modulation depends on the blocks around it, and images must be powers of two): it is pvrtc1.h's, in two passes over
+// transcode_rgba32 (pvrtc1_kernels.hip). The callers of this file keep refusing it.
+// Out of scope: ETC1 from the alpha channel (cDecodeFlagsTranscodeAlphaDataToOpaqueFormats: the single-channel packer at :16925), ATC / FXT1 / PVRTC2 (the reference
+// refuses them for UASTC too), ETC1S slices, UASTC HDR / ASTC LDR / XUASTC blocks, Zstandard-supercompressed KTX2 levels. Callers refuse those; nothing is silently
+// mapped to another target.
 #pragma once
 #include <math.h>
 #include "uastc_rdo.h"

@@ -5,7 +5,7 @@ Targets are the reference's transcoder_texture_format values; only the ones belo
 take RGBA32, BC1, BC3, BC4, BC5, BC7 and ASTC 4x4 and refuse everything else. `transcode_uastc_texture_blocks`, `transcode_uastc_texture_file`, `transcode_uastc_textures`
 and `uastc_texture_layout` are a parallel UASTC family (UASTC_TEXTURE_BYTES_PER_BLOCK / UASTC_TEXTURE_BYTES_PER_PIXEL): those seven targets, byte for byte the same, plus
 the consumers of the ETC hints every UASTC block carries -- ETC1_RGB, ETC2_RGBA, ETC2_EAC_R11 / ETC2_EAC_RG11 -- and the RGB565 / BGR565 / RGBA4444 rasters, (height,
-width) u16. ETC1 from the alpha channel (cDecodeFlagsTranscodeAlphaDataToOpaqueFormats), PVRTC1, ATC / FXT1 / PVRTC2, UASTC HDR / ASTC LDR / XUASTC and
+width) u16. ETC1 from the alpha channel (cDecodeFlagsTranscodeAlphaDataToOpaqueFormats), ATC / FXT1 / PVRTC2, UASTC HDR / ASTC LDR / XUASTC and
 Zstandard-supercompressed KTX2 levels are out of scope and are refused with an error. There is no CPU implementation: without the HIP library and a GPU the
 transcode functions raise.
 
@@ -18,8 +18,12 @@ per block, ETC1S_TEXTURE_BYTES_PER_BLOCK), and BC7's chroma filter as an option;
 `transcode_etc1s_block_format`, `transcode_etc1s_block_formats` and `etc1s_block_format_layout` are a third ETC1S family with the second one's targets and three
 more: ASTC 4x4 RGBA, EAC R11 and EAC RG11 (ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK); the second family keeps its eight targets and its refusals.
 
-`transcode_file_images` and `transcode_etc1s_file_images` (the last section) are the whole-file forms: every image of a file -- levels x layers x faces -- by ONE
+`transcode_file_images` and `transcode_etc1s_file_images` are the whole-file forms: every image of a file -- levels x layers x faces -- by ONE
 launch over a slice table, into one allocation whose layout `image_layout` gives.
+
+PVRTC1 4bpp RGB / RGBA (PVRTC1_4_RGB, PVRTC1_4_RGBA; power-of-two images only) is a family of its own for both codecs, the last section, because a PVRTC1 block
+depends on the blocks around it: `transcode_uastc_pvrtc1_blocks`, `transcode_uastc_pvrtc1_file`, `transcode_etc1s_pvrtc1_image`, `transcode_etc1s_pvrtc1`, and for
+every image of a file of either codec `transcode_pvrtc1_images` with `pvrtc1_layout`. Every other family keeps refusing those two targets.
 """
 import contextlib
 import ctypes as C
@@ -787,3 +791,175 @@ def _transcode_etc1s_slices(ctx, decoded, images, firsts, alpha_firsts, target, 
     finally:
         for p in held:
             ctx.free(p)
+
+
+# ---------------------------------------------------------------- PVRTC1 4bpp, both codecs: the target whose blocks depend on their neighbours
+
+PVRTC1_4_RGB, PVRTC1_4_RGBA = 8, 9
+PVRTC1_BYTES_PER_BLOCK = 8
+
+
+def _check_pvrtc1_target(target):
+    target = int(target)
+    if target not in (PVRTC1_4_RGB, PVRTC1_4_RGBA):
+        name = _TARGET_NAMES[target] if 0 <= target < len(_TARGET_NAMES) else "unknown"
+        raise ValueError(f"PVRTC1 target {target} ({name}) is not supported (supported: [{PVRTC1_4_RGB}, {PVRTC1_4_RGBA}])")
+    return target
+
+
+def _check_pvrtc1_size(width, height, what):
+    width, height = int(width), int(height)
+    if width <= 0 or height <= 0 or width & (width - 1) or height & (height - 1):
+        raise ValueError(f"{what}: {width} x {height} pixels: PVRTC1 only supports power of 2 dimensions")
+
+
+def pvrtc1_layout(images):
+    """Where transcode_pvrtc1_images puts each image: `images` is the "images" list of read_uastc_file or read_etc1s_file / decode_etc1s_file. -> ([{"offset",
+    "nbytes", "shape", "dtype"} per image, in the list's order], total_bytes): (blocks, 8) u8 each, in PVRTC1's own (Morton) block order, each image rounded up to
+    16 bytes; a level of 4x4 pixels or less is its one block, without the padding GL asks of levels under 8x8. An image that is not a power of two each way raises.
+    Host only."""
+    layout, at = [], 0
+    for im in images:
+        _check_pvrtc1_size(im["width"], im["height"], f"level {im['level']}, layer {im['layer']}, face {im['face']}")
+        n = im["num_blocks_x"] * im["num_blocks_y"]
+        layout.append({"offset": at, "nbytes": n * PVRTC1_BYTES_PER_BLOCK, "shape": (n, PVRTC1_BYTES_PER_BLOCK), "dtype": np.uint8})
+        at += (n * PVRTC1_BYTES_PER_BLOCK + 15) & ~15
+    return layout, at
+
+
+def transcode_uastc_pvrtc1_blocks(ctx, blocks, nbx, nby, target, *, out_device=None):
+    """UASTC blocks -> one PVRTC1 4bpp image (bu_hip_k_transcode_uastc_pvrtc1). blocks: (nby * nbx, 16) uint8 in raster order (uploaded once) or a device pointer to
+    that many resident blocks; nbx and nby powers of two. PVRTC1_4_RGBA keeps the pixels' alpha, PVRTC1_4_RGB ignores it (whether a FILE has alpha is its header's
+    word: transcode_uastc_pvrtc1_file reads it). Returns (nby * nbx, 8) uint8 in PVRTC1's own (Morton) block order, or None when out_device (room for
+    nbx * nby * 8 bytes, 8-byte aligned) receives it. Raises InvalidBlocksError when a block does not unpack (its eight bytes are zero)."""
+    nbx, nby, target = int(nbx), int(nby), _check_pvrtc1_target(target)
+    _check_pvrtc1_size(nbx * 4, nby * 4, "transcode_uastc_pvrtc1_blocks")
+    n = nbx * nby
+    own = None
+    try:
+        if isinstance(blocks, np.ndarray):
+            blocks = np.ascontiguousarray(blocks, np.uint8)
+            if blocks.size != n * 16:
+                raise ValueError(f"{nbx} x {nby} blocks need {n * 16} bytes, got {blocks.size}")
+            blocks = own = ctx.upload(blocks)
+        with _output(ctx, out_device, 0, 0, lambda: ctx.lib.pvrtc1_output_bytes(nbx, nby)) as d_out:
+            invalid = C.c_uint32(0)
+            ctx.check(ctx.lib.k_transcode_uastc_pvrtc1(ctx.h, C.c_void_p(blocks), nbx, nby, nbx * 4, nby * 4, target, 0, C.c_void_p(d_out), C.byref(invalid)),
+                      "transcode_uastc_pvrtc1")
+            if invalid.value:
+                raise InvalidBlocksError(invalid.value, n)
+            return None if out_device is not None else ctx.download(d_out, (n, PVRTC1_BYTES_PER_BLOCK), np.uint8)
+    finally:
+        if own:
+            ctx.free(own)
+
+
+def transcode_uastc_pvrtc1_file(ctx, data, target, *, level=0, layer=0, face=0):
+    """One image of a UASTC .basis / .ktx2 file (read_uastc_file) as PVRTC1 4bpp: what transcode_uastc_pvrtc1_blocks returns for its blocks. PVRTC1_4_RGBA asked of a
+    file whose header has no alpha flag is answered with the RGB route, as the reference does. A file whose level 0 is not a power of two each way raises before the
+    device is touched."""
+    target = _check_pvrtc1_target(target)
+    raw = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
+    info = read_uastc_file(raw)
+    _check_pvrtc1_size(info["width"], info["height"], "transcode_uastc_pvrtc1_file")
+    for im in info["images"]:
+        if (im["level"], im["layer"], im["face"]) == (level, layer, face):
+            blocks = np.frombuffer(raw, np.uint8, im["length"], im["offset"]).reshape(-1, 16)
+            return transcode_uastc_pvrtc1_blocks(ctx, blocks, im["num_blocks_x"], im["num_blocks_y"], target if info["has_alpha"] else PVRTC1_4_RGB)
+    raise ValueError(f"the file has no image at level {level}, layer {layer}, face {face}")
+
+
+def transcode_etc1s_pvrtc1_image(ctx, decoded, image, target, *, out_device=None):
+    """One image of decode_etc1s_file's result as PVRTC1 4bpp (bu_hip_k_transcode_etc1s_pvrtc1_counted): (num_blocks, 8) u8 in PVRTC1's own (Morton) block order, or
+    None when out_device receives it. PVRTC1_4_RGBA takes alpha from the image's alpha slice; an image without one gets what PVRTC1_4_RGB writes."""
+    target = _check_pvrtc1_target(target)
+    nbx, nby, w, h = image["num_blocks_x"], image["num_blocks_y"], image["width"], image["height"]
+    _check_pvrtc1_size(w, h, "transcode_etc1s_pvrtc1_image")
+    ep_pal = np.ascontiguousarray(decoded["endpoint_palette"], np.uint8).reshape(-1, 4)
+    sel_pal = np.ascontiguousarray(decoded["selector_palette"], np.uint32).reshape(-1)
+    with_alpha = image["alpha_endpoint_indices"] is not None and target == PVRTC1_4_RGBA
+    names = ["endpoint_indices", "selector_indices"] + (["alpha_endpoint_indices", "alpha_selector_indices"] if with_alpha else [])
+    held = []
+    with _output(ctx, out_device, 0, 0, lambda: ctx.lib.pvrtc1_output_bytes(nbx, nby)) as d_out:
+        try:
+            for a in [ep_pal, sel_pal] + [np.ascontiguousarray(image[k], np.uint16).reshape(-1) for k in names]:
+                held.append(ctx.upload(a))
+            d_alpha = (held[4], held[5]) if with_alpha else (None, None)
+            invalid = C.c_uint32(0)
+            ctx.check(ctx.lib.k_transcode_etc1s_pvrtc1_counted(ctx.h, C.c_void_p(held[0]), ep_pal.shape[0], C.c_void_p(held[1]), sel_pal.size, C.c_void_p(held[2]),
+                                                               C.c_void_p(held[3]), C.c_void_p(d_alpha[0]), C.c_void_p(d_alpha[1]), nbx, nby, w, h, target, C.c_void_p(d_out), 0,
+                                                               C.byref(invalid)), "transcode_etc1s_pvrtc1")
+            if invalid.value:
+                raise ValueError(f"{invalid.value} of {nbx * nby} blocks have an index past its palette")
+            return None if out_device is not None else ctx.download(d_out, (nbx * nby, PVRTC1_BYTES_PER_BLOCK), np.uint8)
+        finally:
+            for p in held:
+                ctx.free(p)
+
+
+def transcode_etc1s_pvrtc1(ctx, data, target, *, level=0, layer=0, face=0):
+    """One image of an ETC1S .basis / .ktx2 file as PVRTC1 4bpp (transcode_etc1s_pvrtc1_image): decoded on the host, transcoded on the GPU. A file whose level 0 is
+    not a power of two each way raises before the device is touched."""
+    target = _check_pvrtc1_target(target)
+    info = read_etc1s_file(data)
+    _check_pvrtc1_size(info["width"], info["height"], "transcode_etc1s_pvrtc1")
+    decoded = decode_etc1s_file(data)
+    for im in decoded["images"]:
+        if (im["level"], im["layer"], im["face"]) == (level, layer, face):
+            return transcode_etc1s_pvrtc1_image(ctx, decoded, im, target)
+    raise ValueError(f"the file has no image at level {level}, layer {layer}, face {face}")
+
+
+def _is_etc1s_file(raw):
+    """which of the two readers a .basis / .ktx2 file is for: the KTX2 header's supercompression scheme (1 = BasisLZ), the .basis header's texture format byte"""
+    if len(raw) >= 12 and raw[:12] == _KTX2_MAGIC:
+        return len(raw) >= 48 and struct.unpack_from("<I", raw, 44)[0] == 1
+    return len(raw) > 20 and raw[:2] == b"sB" and raw[20] == 0
+
+
+def transcode_pvrtc1_images(ctx, data, target, *, out_device=None):
+    """EVERY image of a UASTC or ETC1S .basis / .ktx2 file as PVRTC1 4bpp by two launches in all (bu_hip_k_transcode_uastc_pvrtc1_images /
+    bu_hip_k_transcode_etc1s_pvrtc1_images): a list of arrays, one per image in the order of the reader's "images", each what the one-image call returns for it
+    (views of one download). With out_device (room for pvrtc1_layout's total_bytes) the output stays there and pvrtc1_layout(images) is returned. PVRTC1_4_RGBA on
+    a file without alpha is answered with the RGB route. A file whose level 0 is not a power of two raises before the device is touched (a power-of-two level 0
+    gives a power-of-two chain). Raises InvalidBlocksError, with the per-slice counts, when a block is invalid."""
+    target = _check_pvrtc1_target(target)
+    raw = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
+    if _is_etc1s_file(raw):
+        info = read_etc1s_file(raw)
+        _check_pvrtc1_size(info["width"], info["height"], "transcode_pvrtc1_images")
+        decoded = _decode_etc1s(raw, False, whole=True)
+        images = decoded["images"]
+        layout, total = pvrtc1_layout(images)
+        alpha = target == PVRTC1_4_RGBA and all(im["has_alpha"] for im in images)
+        recs = _slice_table(images, layout, [im["_first"] for im in images], [im["_alpha_first"] if alpha else None for im in images])
+        ep_pal = np.ascontiguousarray(decoded["endpoint_palette"], np.uint8).reshape(-1, 4)
+        sel_pal = np.ascontiguousarray(decoded["selector_palette"], np.uint32).reshape(-1)
+        ep_idx, sel_idx = decoded["_endpoint_indices"], decoded["_selector_indices"]
+        held = []
+        try:
+            for a in (ep_pal, sel_pal, ep_idx, sel_idx):
+                held.append(_upload_async(ctx, a))
+
+            def call(d_out, out_bytes, invalid):
+                ctx.check(ctx.lib.k_transcode_etc1s_pvrtc1_images(ctx.h, C.c_void_p(held[0]), ep_pal.shape[0], C.c_void_p(held[1]), sel_pal.size, C.c_void_p(held[2]),
+                                                                  C.c_void_p(held[3]), ep_idx.size, recs, len(images), target, 0, d_out, out_bytes, invalid),
+                          "transcode_etc1s_pvrtc1_images")
+            return _run_slices(ctx, call, images, layout, total, out_device, "ETC1S")
+        finally:
+            for p in held:
+                ctx.free(p)
+    info = read_uastc_file(raw)
+    _check_pvrtc1_size(info["width"], info["height"], "transcode_pvrtc1_images")
+    images = info["images"]
+    layout, total = pvrtc1_layout(images)
+    blocks, firsts = _uastc_block_span(raw, images)
+    recs = _slice_table(images, layout, firsts)
+    d_blocks = _upload_async(ctx, blocks)
+    try:
+        def call(d_out, out_bytes, invalid):
+            ctx.check(ctx.lib.k_transcode_uastc_pvrtc1_images(ctx.h, C.c_void_p(d_blocks), blocks.size // 16, recs, len(images), target if info["has_alpha"] else PVRTC1_4_RGB,
+                                                              0, d_out, out_bytes, invalid), "transcode_uastc_pvrtc1_images")
+        return _run_slices(ctx, call, images, layout, total, out_device, "UASTC LDR 4x4")
+    finally:
+        ctx.free(d_blocks)

@@ -561,6 +561,41 @@ BU_HIP_API size_t bu_hip_uastc_texture_output_bytes(uint32_t num_blocks_x, uint3
         uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
 BU_HIP_API size_t bu_hip_uastc_texture_slice_extent(const bu_hip_transcode_slice*, uint32_t target);
 
+/* PVRTC1 4bpp, for both codecs: a family of its own, because it is the one target whose block depends on its neighbours. Every other family above keeps refusing
+ * it. target: cTFPVRTC1_4_RGB (8) or cTFPVRTC1_4_RGBA (9); 8 bytes per block, byte for byte what the reference's transcoder writes
+ * (transcode_uastc_to_pvrtc1_4_rgb / _rgba, transcoder/basisu_transcoder.cpp:19541-19643; the two PVRTC1 cases of the ETC1S transcode_slice :8901-8987 with
+ * fixup_pvrtc1_4_modulation_rgb / _rgba :3621-3977). A block's endpoints are the floor / ceil of its colour bounds; its 32 modulation bits compare each texel with
+ * the endpoints of the 3x3 blocks around it, interpolated, and the blocks around an edge block are those of the opposite edge. The blocks are stored in Morton
+ * order (for a non-square image over the shorter axis' bits, the longer axis' other bits above), num_blocks_x * num_blocks_y * 8 bytes per image, with no padding
+ * of levels under 8x8 pixels. An image is whole or nothing: there is no pitch, no rows, no channel choice.
+ * Two launches per call on the context's stream, with no host wait between them: the endpoint words go to a workspace of 4 bytes per block from the context's
+ * arenas, the second launch reads them back. The arguments are the texture family's (UASTC) and the block-format family's (ETC1S) without pitch / rows /
+ * channels; the table forms take the records of the whole-file transcoders (pitch / rows 0) and make their two launches over every image of the file.
+ * cTFPVRTC1_4_RGBA without alpha data -- an ETC1S image without an alpha slice (both alpha pointers NULL; in a table: no record has one) -- writes what
+ * cTFPVRTC1_4_RGB writes, as the reference does. Whether a UASTC file has alpha is its header's word, so that choice is the caller's (transcode.py makes it).
+ * An invalid block (an ETC1S index past its palette, a UASTC block that does not unpack) is written as eight zero bytes and counted, per slice in the table
+ * forms, and never stops the others; its neighbours read its endpoint word as 0. bu_hip_k_transcode_etc1s_pvrtc1 first counts the indices past their palette
+ * and fails without a launch if there is one; _counted skips that pass, as in the other ETC1S families.
+ * Refused by name before any launch: a target other than 8 or 9; an image whose width, height or block counts are not powers of two ("PVRTC1 only supports power
+ * of 2 dimensions"); pixels that do not fit the blocks; zero blocks; a one-image output that is not 8-byte aligned (table forms: 16, and an extent past
+ * out_bytes); any decode flag, cDecodeFlagsPVRTCDecodeToNextPow2 and cDecodeFlagsTranscodeAlphaDataToOpaqueFormats (RGB from the alpha data alone) among them;
+ * a table in which some records have an alpha slice and others none. */
+BU_HIP_API int bu_hip_k_transcode_uastc_pvrtc1(bu_hip_context*, const void* d_uastc_blocks, uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t orig_width,
+        uint32_t orig_height, uint32_t target, uint32_t decode_flags, void* d_out, uint32_t* out_invalid_blocks);
+BU_HIP_API int bu_hip_k_transcode_uastc_pvrtc1_images(bu_hip_context*, const void* d_uastc_blocks, uint64_t n_blocks, const bu_hip_transcode_slice* slices, uint32_t n_slices,
+        uint32_t target, uint32_t decode_flags, void* d_out, size_t out_bytes, uint32_t* out_invalid_per_slice);
+BU_HIP_API int bu_hip_k_transcode_etc1s_pvrtc1(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette, uint32_t n_selectors,
+        const void* d_endpoint_idx, const void* d_selector_idx, const void* d_alpha_endpoint_idx, const void* d_alpha_selector_idx, uint32_t num_blocks_x, uint32_t num_blocks_y,
+        uint32_t orig_width, uint32_t orig_height, uint32_t target, void* d_out, uint32_t decode_flags);
+BU_HIP_API int bu_hip_k_transcode_etc1s_pvrtc1_counted(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette,
+        uint32_t n_selectors, const void* d_endpoint_idx, const void* d_selector_idx, const void* d_alpha_endpoint_idx, const void* d_alpha_selector_idx, uint32_t num_blocks_x,
+        uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height, uint32_t target, void* d_out, uint32_t decode_flags, uint32_t* out_invalid_blocks);
+BU_HIP_API int bu_hip_k_transcode_etc1s_pvrtc1_images(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette, uint32_t n_selectors,
+        const void* d_endpoint_idx, const void* d_selector_idx, uint64_t n_indices, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target,
+        uint32_t decode_flags, void* d_out, size_t out_bytes, uint32_t* out_invalid_per_slice);
+BU_HIP_API size_t bu_hip_pvrtc1_output_bytes(uint32_t num_blocks_x, uint32_t num_blocks_y);
+BU_HIP_API size_t bu_hip_pvrtc1_slice_extent(const bu_hip_transcode_slice*, uint32_t target);   /* 0 = not a PVRTC1 target */
+
 /* gpu_image::unpack(encoder/basisu_gpu_texture.cpp:1218-1266) over resident blocks: what a GPU samples from a BC1 / BC3 / BC4 / BC5 / BC7 texture, as RGBA8.
  * format: the transcoder_texture_format value the transcoders above take as a target -- cTFBC1_RGB (2), cTFBC3_RGBA (3), cTFBC4_R (4), cTFBC5_RG (5), cTFBC7_RGBA (6);
  * any other fails with an error that names it. d_blocks: num_blocks_x * num_blocks_y blocks of 8 (BC1, BC4) or 16 bytes in raster order, aligned to their size;
