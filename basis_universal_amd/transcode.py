@@ -24,6 +24,9 @@ launch over a slice table, into one allocation whose layout `image_layout` gives
 PVRTC1 4bpp RGB / RGBA (PVRTC1_4_RGB, PVRTC1_4_RGBA; power-of-two images only) is a family of its own for both codecs, the last section, because a PVRTC1 block
 depends on the blocks around it: `transcode_uastc_pvrtc1_blocks`, `transcode_uastc_pvrtc1_file`, `transcode_etc1s_pvrtc1_image`, `transcode_etc1s_pvrtc1`, and for
 every image of a file of either codec `transcode_pvrtc1_images` with `pvrtc1_layout`. Every other family keeps refusing those two targets.
+
+Back to pixels: `unpack_blocks` (BC1 / BC3 / BC4 / BC5 / BC7) and, at the end of the module, `unpack_texture` (UNPACK_TEXTURE_BYTES_PER_BLOCK): those five and every other
+block target above -- ETC1, ETC2 RGBA, EAC R11 / RG11, ASTC 4x4, PVRTC1 -- as RGBA8, what the reference's gpu_image::unpack makes of them (csrc/texture_unpack_kernels.hip).
 """
 import contextlib
 import ctypes as C
@@ -39,7 +42,7 @@ DECODE_FLAGS_HIGH_QUALITY = 32   # cDecodeFlagsHighQuality
 
 
 class InvalidBlocksError(ValueError):
-    """Some blocks did not unpack as UASTC -- or, from unpack_blocks, as BC7 -- (their output was zero-filled). `count` is how many. From the whole-file calls
+    """Some blocks did not unpack as UASTC -- or, from unpack_blocks / unpack_texture, as the block format they were given as -- (their output was zero-filled). `count` is how many. From the whole-file calls
     (transcode_file_images, transcode_etc1s_file_images) `per_slice` is the count of every slice in table order and `slice` the lowest slice that has any."""
 
     def __init__(self, count, total, what="UASTC LDR 4x4", per_slice=None):
@@ -963,3 +966,51 @@ def transcode_pvrtc1_images(ctx, data, target, *, out_device=None):
         return _run_slices(ctx, call, images, layout, total, out_device, "UASTC LDR 4x4")
     finally:
         ctx.free(d_blocks)
+
+
+# ---------------------------------------------------------------- every block format back to pixels
+
+# the formats of unpack_texture: unpack_blocks' five, byte for byte, and every other block target the transcoders above write
+UNPACK_TEXTURE_BYTES_PER_BLOCK = {**UNPACK_BYTES_PER_BLOCK, ETC1_RGB: 8, ETC2_RGBA: 16, PVRTC1_4_RGB: 8, PVRTC1_4_RGBA: 8, ASTC_4x4_RGBA: 16, ETC2_EAC_R11: 8, ETC2_EAC_RG11: 16}
+
+
+def unpack_texture(ctx, blocks, nbx, nby, fmt, *, width=None, height=None, out_device=None, out_row_pitch=0, out_rows=0):
+    """gpu_image::unpack on the GPU for every block format this module's transcoders write (fmt: the transcoder's target value, UNPACK_TEXTURE_BYTES_PER_BLOCK):
+    what a GPU samples from the texture, RGBA8 (bu_hip_k_unpack_texture). The five BC formats decode as unpack_blocks decodes them; ETC1 with A = 255; ETC2 RGBA;
+    EAC R11 / RG11 into R / R, G with the 11-bit value rounded to 8 bits (the rest (0, 0, 255)); ASTC 4x4, the whole LDR format in the L8 (non-sRGB) decode profile;
+    PVRTC1 4bpp with the blocks in their own (Morton) order, as the PVRTC1 transcoders return them, power-of-two images only.
+    blocks: (nby * nbx, 8 | 16) uint8 array (uploaded once) or a device pointer (int) to that many resident blocks. Returns the (height, width, 4) raster, or None
+    when out_device (a device pointer with room for out_rows x out_row_pitch pixels, 0 = height / width) receives it; width / height default to the padded size.
+    Invalid blocks -- BC7's reserved mode, an ETC1 / ETC2 colour half whose differential base overflows (ETC2's T / H / planar encodings), an ASTC block an LDR
+    decoder refuses -- are zero-filled, and InvalidBlocksError is raised with their count. There is no CPU implementation."""
+    nbx, nby, fmt = int(nbx), int(nby), int(fmt)
+    if fmt not in UNPACK_TEXTURE_BYTES_PER_BLOCK:
+        name = _TARGET_NAMES[fmt] if 0 <= fmt < len(_TARGET_NAMES) else "unknown"
+        raise ValueError(f"texture format {fmt} ({name}) does not unpack here (supported: {sorted(UNPACK_TEXTURE_BYTES_PER_BLOCK)})")
+    n, unit = nbx * nby, UNPACK_TEXTURE_BYTES_PER_BLOCK[fmt]
+    width, height = int(width or nbx * 4), int(height or nby * 4)
+    if not (0 < width <= nbx * 4 and 0 < height <= nby * 4) and n:
+        raise ValueError(f"{width} x {height} pixels do not fit {nbx} x {nby} blocks")
+    if fmt in (PVRTC1_4_RGB, PVRTC1_4_RGBA) and n:
+        _check_pvrtc1_size(width, height, "unpack_texture")
+        _check_pvrtc1_size(nbx * 4, nby * 4, "unpack_texture")
+    with _output(ctx, out_device, out_row_pitch, out_rows, lambda: ctx.lib.unpack_output_bytes(nbx, nby, width, height, 0, 0)) as d_out:
+        own = None
+        try:
+            if isinstance(blocks, np.ndarray):
+                blocks = np.ascontiguousarray(blocks, np.uint8)
+                if blocks.size != n * unit:
+                    raise ValueError(f"{nbx} x {nby} blocks need {n * unit} bytes, got {blocks.size}")
+                blocks = own = ctx.upload(blocks) if n else 0
+            invalid = C.c_uint32(0)
+            if n:
+                ctx.check(ctx.lib.k_unpack_texture(ctx.h, C.c_void_p(blocks), nbx, nby, width, height, fmt, C.c_void_p(d_out), int(out_row_pitch), int(out_rows), C.byref(invalid)),
+                          "unpack_texture")
+            if invalid.value:
+                raise InvalidBlocksError(invalid.value, n, _TARGET_NAMES[fmt])
+            if out_device is not None:
+                return None
+            return ctx.download(d_out, (height, width, 4), np.uint8) if n else np.zeros((0, 0, 4), np.uint8)
+        finally:
+            if own:
+                ctx.free(own)

@@ -610,6 +610,28 @@ BU_HIP_API int bu_hip_k_unpack_blocks(bu_hip_context*, const void* d_blocks, uin
 BU_HIP_API size_t bu_hip_unpack_output_bytes(uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height,
         uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
 
+/* The texture unpacker: gpu_image::unpack over resident blocks of EVERY block format the transcoders above write. A family of its own: bu_hip_k_unpack_blocks keeps
+ * its five formats and its refusals. format: the transcoder_texture_format value -- the five BC formats, texel for texel what bu_hip_k_unpack_blocks writes, and
+ *   cTFETC1_RGB (0)         8 bytes   individual and differential mode, flip; A = 255
+ *   cTFETC2_RGBA (1)       16 bytes   bytes 0-7 EAC A8, bytes 8-15 ETC1
+ *   cTFETC2_EAC_R11 (20)    8 bytes   the 11-bit value to 8 bits as (v * 255 + 1023) / 2047; G = B = 0, A = 255
+ *   cTFETC2_EAC_RG11 (21)  16 bytes   two R11 blocks into R and G; B = 0, A = 255
+ *   cTFASTC_4x4_RGBA (10)  16 bytes   the whole LDR 4x4 format in the L8 (non-sRGB) decode profile -- void extent, every block mode and weight grid from 2x2 to 4x4
+ *                                     (infill), bits / trits / quints, one to four partitions, dual plane, the ten LDR endpoint modes; a channel is the top 8
+ *                                     bits of the UNORM16 result -- as basisu_astc::astc::decompress_ldr(.., isSRGB = false, 4, 4) decodes it
+ *   cTFPVRTC1_4_RGB (8), cTFPVRTC1_4_RGBA (9)   8 bytes, blocks in Morton order as bu_hip_k_transcode_*_pvrtc1 write them; both modulation modes; power-of-two
+ *                                     images only ("PVRTC1 only supports power of 2 dimensions")
+ * any other fails with an error that names it. Geometry, alignment, clipping, pitch and rows are bu_hip_k_unpack_blocks's; d_out has room for
+ * bu_hip_unpack_output_bytes. Invalid blocks are zero-filled (alpha included) and counted, and never stop the others -- the reference returns false and leaves the
+ * caller's buffer as it was: BC7's reserved mode; an ETC1 / ETC2 colour half whose differential base leaves 0..31 (ETC2's T / H / planar encodings, which the
+ * reference does not decode); an ASTC block the reference's LDR decoder refuses (reserved block modes, a weight grid past 4x4, weight or endpoint bit counts out
+ * of range, four partitions with two planes, an HDR endpoint mode in a partition that holds a texel, an HDR or malformed void extent). R11, RG11 and PVRTC1 have
+ * no invalid blocks. One launch on the context's stream; the call synchronises once to read the count. */
+BU_HIP_API int bu_hip_k_unpack_texture(bu_hip_context*, const void* d_blocks, uint32_t num_blocks_x, uint32_t num_blocks_y,
+        uint32_t orig_width, uint32_t orig_height, uint32_t format, void* d_out_rgba, uint32_t out_row_pitch_pixels,
+        uint32_t out_rows_pixels, uint32_t* out_invalid_blocks);
+BU_HIP_API uint32_t bu_hip_unpack_texture_bytes_per_block(uint32_t format);   /* 0 = not a format that unpacks */
+
 /* The payload of a DX10 .dds file from the resident tile array (64 B per tile: RGBA8, rows of four texels, borders duplicated -- what bu_hip_k_extract_slices
  * writes): pack_slice of the reference tool's `-dds` mode (encoder/basisu_dds_export.cpp:151-267). format: the tool's dds_output_format value, in the order of its
  * -dds_format tokens. BC1 is basist::encode_bc1 with cEncodeBC1HighQuality, BC4 basist::encode_bc4; BC2 = explicit 4-bit alpha + BC1, BC3 = BC4 of alpha + BC1,
