@@ -307,6 +307,7 @@ static void context_release(bu_hip_context* ctx) {   // the real teardown
     ctx->etc1s_bc1_tables.release();
     ctx->etc1s_bc7_tables.release();
     ctx->etc1s_astc_tables.release();
+    ctx->etc1s_atc_tables.release();
     if (ctx->tsvq_pinned) (void)hipHostFree(ctx->tsvq_pinned);
     for (auto& b : ctx->pool_free) (void)hipFree(b.p);
     for (auto& b : ctx->pool_live) (void)hipFree(b.p);

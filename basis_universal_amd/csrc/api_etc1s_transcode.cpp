@@ -6,25 +6,35 @@ static const char* const kEtc1sTargets = "ETC1_RGB (0), BC1_RGB (2), RGBA32 (13)
 static const char* const kEtc1sTextureTargets = "ETC1_RGB (0), ETC2_RGBA (1), BC1_RGB (2), BC7_RGBA (6), RGBA32 (13), RGB565 (14), BGR565 (15), RGBA4444 (16)";
 static const char* const kEtc1sBlockFormatTargets = "ETC1_RGB (0), ETC2_RGBA (1), BC1_RGB (2), BC7_RGBA (6), ASTC_4x4_RGBA (10), RGBA32 (13), RGB565 (14), BGR565 (15), RGBA4444 (16), "
                                                     "ETC2_EAC_R11 (20), ETC2_EAC_RG11 (21)";
+static const char* const kEtc1sVendorFormatTargets = "ETC1_RGB (0), ETC2_RGBA (1), BC1_RGB (2), BC7_RGBA (6), ASTC_4x4_RGBA (10), ATC_RGB (11), RGBA32 (13), RGB565 (14), BGR565 (15), "
+                                                     "RGBA4444 (16), FXT1_RGB (17), PVRTC2_4_RGB (18), PVRTC2_4_RGBA (19), ETC2_EAC_R11 (20), ETC2_EAC_RG11 (21)";
 static const uint32_t kNoChromaFiltering = 64;   // cDecodeFlagsNoETC1SChromaFiltering, the one flag of the bu_hip_k_transcode_etc1s_image* entries
 
 // Which entry family a call came through. The first (bu_hip_k_transcode_etc1s*) has six targets and no flags; the second (bu_hip_k_transcode_etc1s_image*) adds the
-// 16-byte targets and decode_flags; the third (bu_hip_k_transcode_etc1s_block_format*) adds ASTC 4x4 and EAC R11 / RG11. All run the same code below: the family
-// decides the target list, the flags and the name in a refusal.
-struct etc1s_family { const char* fn; const char* targets; uint32_t (*unit_bytes)(uint32_t target); };
-static const etc1s_family kFirstFamily = { "transcode_etc1s", kEtc1sTargets, bu::etc1s_transcode_unit_bytes },
-                          kImageFamily = { "transcode_etc1s_image", kEtc1sTextureTargets, bu::etc1s_texture_unit_bytes },
-                          kBlockFormatFamily = { "transcode_etc1s_block_format", kEtc1sBlockFormatTargets, bu::etc1s_block_format_unit_bytes };
+// 16-byte targets and decode_flags; the third (bu_hip_k_transcode_etc1s_block_format*) adds ASTC 4x4 and EAC R11 / RG11; the fourth (bu_hip_k_transcode_etc1s_vendor_format*)
+// adds ATC RGB, FXT1 and PVRTC2 RGB / RGBA. All run the same code below: the family decides the target list, the flags, the name in a refusal and, the fourth, why a target
+// it names is missing.
+struct etc1s_family { const char* fn; const char* targets; uint32_t (*unit_bytes)(uint32_t target); const char* (*why_not)(uint32_t target); };
+// what the fourth family says of the targets it refuses for a reason
+static const char* vendor_format_why_not(uint32_t target) {
+    if (target == 3 || target == 4 || target == 5) return ": it needs the ETC1S -> BC4 look-up, which could not be restated as a search";
+    if (target == 12) return ": its first half is a BC4 block, and the ETC1S -> BC4 look-up could not be restated as a search";
+    return "";
+}
+static const etc1s_family kFirstFamily = { "transcode_etc1s", kEtc1sTargets, bu::etc1s_transcode_unit_bytes, nullptr },
+                          kImageFamily = { "transcode_etc1s_image", kEtc1sTextureTargets, bu::etc1s_texture_unit_bytes, nullptr },
+                          kBlockFormatFamily = { "transcode_etc1s_block_format", kEtc1sBlockFormatTargets, bu::etc1s_block_format_unit_bytes, nullptr },
+                          kVendorFormatFamily = { "transcode_etc1s_vendor_format", kEtc1sVendorFormatTargets, bu::etc1s_vendor_format_unit_bytes, vendor_format_why_not };
 
 static uint32_t family_unit_bytes(const etc1s_family& f, uint32_t target) { return f.unit_bytes(target); }
 static bool reads_alpha(uint32_t target) {
     return target == bu::ETF_RGBA32 || target == bu::ETF_RGBA4444 || target == bu::ETF_ETC2_RGBA || target == bu::ETF_BC7_RGBA || target == bu::ETF_ASTC_4x4_RGBA ||
-           target == bu::ETF_ETC2_EAC_RG11;
+           target == bu::ETF_ETC2_EAC_RG11 || target == bu::ETF_PVRTC2_4_RGBA;
 }
 // the target and the flags of a call; the refusal names what is wrong
 static int etc1s_target_ok(bu_hip_context* ctx, const etc1s_family& f, uint32_t target, uint32_t decode_flags) {
     if (!family_unit_bytes(f, target)) {
-        set_error(ctx, "%s: target %u (%s) is not supported (supported: %s)", f.fn, target, transcoder_format_name(target), f.targets);
+        set_error(ctx, "%s: target %u (%s) is not supported%s (supported: %s)", f.fn, target, transcoder_format_name(target), f.why_not ? f.why_not(target) : "", f.targets);
         return 0;
     }
     if (decode_flags & ~kNoChromaFiltering) {
@@ -76,13 +86,25 @@ static int ensure_astc_tables(bu_hip_context* ctx) {
     if (e != hipSuccess) { ctx->etc1s_astc_tables.release(); set_error(ctx, "etc1s_build_astc_tables: %s", hipGetErrorString(e)); return 0; }
     return 1;
 }
-// only what the target needs
-static int ensure_target_tables(bu_hip_context* ctx, uint32_t target, const uint32_t*& bc1, const uint32_t*& bc7, const uint32_t*& astc) {
+// the three ETC1S -> ATC / PVRTC2 look-ups, the same way: built by the first ATC RGB or PVRTC2 RGB / RGBA transcode
+static int ensure_atc_tables(bu_hip_context* ctx) {
+    if (ctx->etc1s_atc_tables.p) return 1;
+    BU_TRY(ctx, ctx->etc1s_atc_tables.reserve(bu::kEtc1sAtcTableWords * sizeof(uint32_t)));
+    hipError_t e = bu::launch_etc1s_build_atc_tables(ctx->stream, static_cast<uint32_t*>(ctx->etc1s_atc_tables.p));
+    if (e != hipSuccess) { ctx->etc1s_atc_tables.release(); set_error(ctx, "etc1s_build_atc_tables: %s", hipGetErrorString(e)); return 0; }
+    return 1;
+}
+// only what the target needs; FXT1 goes through BC1's tables
+static int ensure_target_tables(bu_hip_context* ctx, uint32_t target, const uint32_t*& bc1, const uint32_t*& bc7, const uint32_t*& astc, const uint32_t*& atc) {
+    if (target == bu::ETF_ATC_RGB || target == bu::ETF_PVRTC2_4_RGB || target == bu::ETF_PVRTC2_4_RGBA) {
+        if (!ensure_atc_tables(ctx)) return 0;
+        atc = static_cast<const uint32_t*>(ctx->etc1s_atc_tables.p);
+    }
     if (target == bu::ETF_ASTC_4x4_RGBA) {
         if (!ensure_astc_tables(ctx)) return 0;
         astc = static_cast<const uint32_t*>(ctx->etc1s_astc_tables.p);
     }
-    if (target == bu::ETF_BC1_RGB) {
+    if (target == bu::ETF_BC1_RGB || target == bu::ETF_FXT1_RGB) {
         if (!ensure_bc1_tables(ctx)) return 0;
         bc1 = static_cast<const uint32_t*>(ctx->etc1s_bc1_tables.p);
     }
@@ -106,10 +128,11 @@ static int transcode_image_counted(bu_hip_context* ctx, const etc1s_family& f, c
     arena& counter = ctx->scratch[4];
     BU_TRY(ctx, counter.reserve(sizeof(uint32_t)));
     a.invalid = static_cast<uint32_t*>(counter.p);
-    if (!ensure_target_tables(ctx, target, a.bc1_endpoints, a.bc7_tables, a.astc_tables)) return 0;
+    const uint32_t* atc = nullptr;
+    if (!ensure_target_tables(ctx, target, a.bc1_endpoints, a.bc7_tables, a.astc_tables, atc)) return 0;
     {
         prof_scope ps(ctx, "etc1s_transcode");
-        BU_TRY(ctx, bu::launch_transcode_etc1s(ctx->stream, a, target, !(decode_flags & kNoChromaFiltering)));
+        BU_TRY(ctx, bu::launch_transcode_etc1s_any_target(ctx->stream, a, atc, target, !(decode_flags & kNoChromaFiltering)));
     }
     uint32_t invalid = 0;
     if (!read_back(ctx, &invalid, counter.p, sizeof(invalid))) return 0;
@@ -159,10 +182,10 @@ static int transcode_images(bu_hip_context* ctx, const etc1s_family& f, const ch
     if (!d_ep_pal || !d_sel_pal || !d_ep_idx || !d_sel_idx) { set_error(ctx, "%s: null pointer", fn); return 0; }
     if (!n_ep || !n_sel || n_ep > 65535u || n_sel > 65535u) { set_error(ctx, "%s: palettes of %u endpoints and %u selectors (1..65535 each)", fn, n_ep, n_sel); return 0; }
     bu::slice_table table;
-    if (!etc1s_slices_check(ctx, table, fn, slices, n_slices, n_indices, target, family_unit_bytes(f, target), d_out, out_bytes)) return 0;
+    if (!etc1s_slices_check(ctx, table, fn, slices, n_slices, n_indices, target, family_unit_bytes(f, target), d_out, out_bytes, target == bu::ETF_FXT1_RGB)) return 0;
     device_guard g(ctx->device);
-    const uint32_t *bc1 = nullptr, *bc7 = nullptr, *astc = nullptr;
-    if (!ensure_target_tables(ctx, target, bc1, bc7, astc)) return 0;
+    const uint32_t *bc1 = nullptr, *bc7 = nullptr, *astc = nullptr, *atc = nullptr;
+    if (!ensure_target_tables(ctx, target, bc1, bc7, astc, atc)) return 0;
     uploaded_slices d;
     if (!upload_slice_table(ctx, table, d)) return 0;
     const bu::etc1s_transcode_slices_args a = { static_cast<const uint32_t*>(d_ep_pal), static_cast<const uint32_t*>(d_sel_pal), static_cast<const uint16_t*>(d_ep_idx),
@@ -170,7 +193,7 @@ static int transcode_images(bu_hip_context* ctx, const etc1s_family& f, const ch
                                                 static_cast<const bu_hip_transcode_slice*>(d.records), d.prefix, n_ep, n_sel, table.n, table.total, astc };
     {
         prof_scope ps(ctx, fn);
-        BU_TRY(ctx, bu::launch_transcode_etc1s_slices(ctx->stream, a, target, !(decode_flags & kNoChromaFiltering)));
+        BU_TRY(ctx, bu::launch_transcode_etc1s_any_target_slices(ctx->stream, a, atc, target, !(decode_flags & kNoChromaFiltering)));
     }
     return out_invalid_per_slice ? read_back(ctx, out_invalid_per_slice, d.counters, (size_t)table.n * sizeof(uint32_t)) : 1;
 }
@@ -294,6 +317,43 @@ int bu_hip_k_transcode_etc1s_block_formats(bu_hip_context* ctx, const void* d_ep
                                            uint64_t n_indices, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target, uint32_t decode_flags, void* d_out,
                                            size_t out_bytes, uint32_t* out_invalid_per_slice) {
     return transcode_images(ctx, kBlockFormatFamily, "transcode_etc1s_block_formats", d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, n_indices, slices, n_slices, target,
+                            decode_flags, d_out, out_bytes, out_invalid_per_slice);
+}
+
+// ---- the fourth family: the third one's arguments and targets, and ATC RGB, FXT1, PVRTC2 RGB and PVRTC2 RGBA
+
+size_t bu_hip_etc1s_vendor_format_output_bytes(uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, uint32_t pitch_px, uint32_t rows_px) {
+    return bu::raster_output_bytes(bu::tile_geometry{ nbx, nby, orig_w, orig_h, pitch_px, rows_px }, bu::etc1s_vendor_format_unit_bytes(target), bu::etc1s_transcode_is_pixel_target(target),
+                                   target == bu::ETF_FXT1_RGB);
+}
+
+int bu_hip_etc1s_atc_tables(bu_hip_context* ctx, uint32_t* h_out_55, uint32_t* h_out_56, uint32_t* h_out_45) {
+    if (!ctx || !h_out_55 || !h_out_56 || !h_out_45) { if (ctx) set_error(ctx, "etc1s_atc_tables: null pointer"); return 0; }
+    device_guard g(ctx->device);
+    if (!ensure_atc_tables(ctx)) return 0;
+    const uint32_t* d = static_cast<const uint32_t*>(ctx->etc1s_atc_tables.p);
+    const size_t n = bu::kEtc1sAtcTableWords / 3;
+    return fetch(ctx, h_out_55, d, n * sizeof(uint32_t)) && fetch(ctx, h_out_56, d + n, n * sizeof(uint32_t)) && fetch(ctx, h_out_45, d + 2 * n, n * sizeof(uint32_t)) ? 1 : 0;
+}
+
+int bu_hip_k_transcode_etc1s_vendor_format_counted(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx,
+                                                   const void* d_sel_idx, const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h,
+                                                   uint32_t target, void* d_out, uint32_t pitch_px, uint32_t rows_px, uint32_t decode_flags, uint32_t* out_invalid_blocks) {
+    return transcode_image_counted(ctx, kVendorFormatFamily, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out,
+                                   pitch_px, rows_px, decode_flags, out_invalid_blocks);
+}
+
+int bu_hip_k_transcode_etc1s_vendor_format(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
+                                           const void* d_a_ep_idx, const void* d_a_sel_idx, uint32_t nbx, uint32_t nby, uint32_t orig_w, uint32_t orig_h, uint32_t target, void* d_out,
+                                           uint32_t pitch_px, uint32_t rows_px, uint32_t decode_flags) {
+    return transcode_image_checked(ctx, kVendorFormatFamily, d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, d_a_ep_idx, d_a_sel_idx, nbx, nby, orig_w, orig_h, target, d_out,
+                                   pitch_px, rows_px, decode_flags);
+}
+
+int bu_hip_k_transcode_etc1s_vendor_formats(bu_hip_context* ctx, const void* d_ep_pal, uint32_t n_ep, const void* d_sel_pal, uint32_t n_sel, const void* d_ep_idx, const void* d_sel_idx,
+                                            uint64_t n_indices, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target, uint32_t decode_flags, void* d_out,
+                                            size_t out_bytes, uint32_t* out_invalid_per_slice) {
+    return transcode_images(ctx, kVendorFormatFamily, "transcode_etc1s_vendor_formats", d_ep_pal, n_ep, d_sel_pal, n_sel, d_ep_idx, d_sel_idx, n_indices, slices, n_slices, target,
                             decode_flags, d_out, out_bytes, out_invalid_per_slice);
 }
 

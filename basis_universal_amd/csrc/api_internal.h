@@ -49,6 +49,7 @@ struct bu_hip_context {
     arena refine_lists;                   // the sorted candidate lists of refine_endpoint_clusterization (etc1s_refine_kernels.hip, k_refine_sort_lists)
     arena etc1s_bc1_tables;               // the ETC1S -> BC1 endpoint tables (api_etc1s_transcode.cpp), built by the first BC1 transcode of the context
     arena etc1s_astc_tables;              // the two ETC1S -> ASTC look-ups and the unquantised endpoint values, built by the first ASTC transcode
+    arena etc1s_atc_tables;               // the three ETC1S -> ATC / PVRTC2 look-ups 55, 56, 45, built by the first ATC RGB or PVRTC2 RGB / RGBA transcode
     arena etc1s_bc7_tables;               // the ETC1S -> BC7 colour look-up and the mode-5 encoder's midpoints, built by the first BC7 transcode
     const void* d_pixel_blocks = nullptr; // resident tiles (a1): 64 B per block
     size_t total_blocks = 0;
@@ -145,9 +146,10 @@ int transcode_slices_check(bu_hip_context* ctx, bu::slice_table& t, const char* 
 // the same for a UASTC table under the fourteen targets of bu_hip_k_transcode_uastc_textures
 int uastc_texture_slices_check(bu_hip_context* ctx, bu::slice_table& t, const char* fn, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint64_t n_inputs,
                                uint32_t target, const void* d_out, size_t out_bytes);
-// the same for an ETC1S table under the target list of one of the three ETC1S families: `unit` is what the family's unit function says of the target
+// the same for an ETC1S table under the target list of one of the ETC1S families: `unit` is what the family's unit function says of the target; two_wide: an output
+// block covers two source blocks side by side (FXT1)
 int etc1s_slices_check(bu_hip_context* ctx, bu::slice_table& t, const char* fn, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint64_t n_inputs, uint32_t target,
-                       uint32_t unit, const void* d_out, size_t out_bytes);
+                       uint32_t unit, const void* d_out, size_t out_bytes, bool two_wide = false);
 
 struct device_guard {
     int prev = -1; bool ok = false;

@@ -31,6 +31,12 @@ extern "C" size_t bu_hip_etc1s_block_format_slice_extent(const bu_hip_transcode_
     return bu::raster_output_bytes(g, bu::etc1s_block_format_unit_bytes(target), bu::etc1s_transcode_is_pixel_target(target));
 }
 
+extern "C" size_t bu_hip_etc1s_vendor_format_slice_extent(const bu_hip_transcode_slice* s, uint32_t target) {
+    if (!s) return 0;
+    const bu::tile_geometry g = { s->num_blocks_x, s->num_blocks_y, s->orig_width, s->orig_height, s->out_row_pitch_pixels, s->out_rows_pixels };
+    return bu::raster_output_bytes(g, bu::etc1s_vendor_format_unit_bytes(target), bu::etc1s_transcode_is_pixel_target(target), target == bu::ETF_FXT1_RGB);
+}
+
 extern "C" size_t bu_hip_uastc_texture_slice_extent(const bu_hip_transcode_slice* s, uint32_t target) {
     if (!s) return 0;
     const bu::tile_geometry g = { s->num_blocks_x, s->num_blocks_y, s->orig_width, s->orig_height, s->out_row_pitch_pixels, s->out_rows_pixels };
@@ -44,10 +50,11 @@ int uastc_texture_slices_check(bu_hip_context* ctx, bu::slice_table& t, const ch
     return checked(ctx, [&](bu::err_text e) { return bu::build_transcode_slices(t, fn, slices, n_slices, n_inputs, p, d_out, out_bytes, e); });
 }
 
-// the ETC1S table under any of the three families' target lists: `unit` is the family's unit for the target (0 = it does not have it)
+// the ETC1S table under any of the families' target lists: `unit` is the family's unit for the target (0 = it does not have it)
 int etc1s_slices_check(bu_hip_context* ctx, bu::slice_table& t, const char* fn, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint64_t n_inputs, uint32_t target,
-                       uint32_t unit, const void* d_out, size_t out_bytes) {
-    const bu::slice_policy p = bu::transcoder_slice_policy(true, unit, bu::etc1s_transcode_is_pixel_target(target), transcoder_format_name(target));
+                       uint32_t unit, const void* d_out, size_t out_bytes, bool two_wide) {
+    bu::slice_policy p = bu::transcoder_slice_policy(true, unit, bu::etc1s_transcode_is_pixel_target(target), transcoder_format_name(target));
+    p.two_wide = two_wide;
     return checked(ctx, [&](bu::err_text e) { return bu::build_transcode_slices(t, fn, slices, n_slices, n_inputs, p, d_out, out_bytes, e); });
 }
 

@@ -10,8 +10,9 @@ namespace bu {
 enum : uint32_t { kBc1TableEntries = 8 * 32 * 6 * 10 };   // per endpoint width: intensity tables x 5-bit base values x selector ranges x selector mappings
 // the reference's transcoder_texture_format values of the targets that exist here
 enum : uint32_t { ETF_ETC1_RGB = 0, ETF_ETC2_RGBA = 1, ETF_BC1_RGB = 2, ETF_BC7_RGBA = 6, ETF_ASTC_4x4_RGBA = 10, ETF_RGBA32 = 13, ETF_RGB565 = 14, ETF_BGR565 = 15, ETF_RGBA4444 = 16,
-                  ETF_ETC2_EAC_R11 = 20, ETF_ETC2_EAC_RG11 = 21 };
+                  ETF_ETC2_EAC_R11 = 20, ETF_ETC2_EAC_RG11 = 21, ETF_ATC_RGB = 11, ETF_FXT1_RGB = 17, ETF_PVRTC2_4_RGB = 18, ETF_PVRTC2_4_RGBA = 19 };
 enum : uint32_t { kEtc1sBc7TableWords = 8 * 32 * 6 * 10 + 128 };   // the ETC1S -> BC7 colour look-up and the mode-5 encoder's midpoints (etc1s_texture_targets.h)
+enum : uint32_t { kEtc1sAtcTableWords = 3 * 8 * 32 * 6 * 10 };   // the three ETC1S -> ATC / PVRTC2 look-ups 55, 56, 45 (etc1s_vendor_format_targets.h)
 enum : uint32_t { kEtc1sAstcTableWords = 2 * 8 * 32 * 6 * 10 + 48 };   // the two ETC1S -> ASTC look-ups and the 48 unquantised endpoint values (etc1s_block_format_targets.h)
 
 struct etc1s_transcode_args {
@@ -43,6 +44,7 @@ struct etc1s_transcode_slices_args {
 uint32_t etc1s_transcode_unit_bytes(uint32_t target);   // per block for block targets, per pixel for pixel targets; 0 = not a target of the first six (ETC1, BC1, pixels)
 uint32_t etc1s_texture_unit_bytes(uint32_t target);     // the same over all eight targets: also 16 for ETC2 RGBA and BC7 RGBA
 uint32_t etc1s_block_format_unit_bytes(uint32_t target);   // the same over all eleven: also 16 for ASTC 4x4 and EAC RG11, 8 for EAC R11
+uint32_t etc1s_vendor_format_unit_bytes(uint32_t target);  // the fourth family: also 8 for ATC RGB and PVRTC2 4bpp RGB / RGBA, 16 for FXT1 -- per 8x4 texels, two source blocks
 bool etc1s_transcode_is_pixel_target(uint32_t target);
 // one launch; d_invalid is cleared first and afterwards holds how many blocks had an index past its palette (their output is zero-filled)
 // chroma_filter: BC7 only, the reference's default
@@ -57,6 +59,12 @@ hipError_t launch_etc1s_build_bc7_tables(hipStream_t st, uint32_t* d_tables);
 hipError_t launch_bc7_mode5_tiles(hipStream_t st, const void* d_tiles, uint32_t n_tiles, void* d_out, const uint32_t* bc7_tables);
 // fills d_tables[kEtc1sAstcTableWords]
 hipError_t launch_etc1s_build_astc_tables(hipStream_t st, uint32_t* d_tables);
+// fills d_tables[kEtc1sAtcTableWords]
+hipError_t launch_etc1s_build_atc_tables(hipStream_t st, uint32_t* d_tables);
+// the launch for a target of ANY family, which every entry goes through behind its family's target check: ATC RGB, PVRTC2 RGB / RGBA (atc_tables) and FXT1
+// (a.bc1_endpoints; rows of (nbx + 1) / 2 blocks) by kernels of their own, any other target as launch_transcode_etc1s / _slices. The count is of source blocks.
+hipError_t launch_transcode_etc1s_any_target(hipStream_t st, const etc1s_transcode_args& a, const uint32_t* atc_tables, uint32_t target, bool chroma_filter = false);
+hipError_t launch_transcode_etc1s_any_target_slices(hipStream_t st, const etc1s_transcode_slices_args& a, const uint32_t* atc_tables, uint32_t target, bool chroma_filter = false);
 // counts the entries of idx[n] that are >= limit into *d_count (cleared first)
 hipError_t launch_etc1s_count_indices_past(hipStream_t st, const uint16_t* idx, uint32_t n, uint32_t limit, uint32_t* d_count, bool clear);
 

@@ -7,6 +7,7 @@
 // a file in one launch through a slice table (tile_raster.h), counted per slice.
 // The 16-byte targets (ETC2 RGBA, BC7 mode 5) store one uint4 per block; their conversions are etc1s_texture_targets.h's. BC7's chroma filter is a second template
 // parameter, so the unfiltered instance carries none of the encoder. ASTC 4x4 (16 bytes), EAC R11 (8) and EAC RG11 (16) are etc1s_block_format_targets.h's.
+// ATC RGB, PVRTC2 4bpp RGB (8 bytes) and FXT1 (16 bytes per 8x4 texels, two source blocks) are etc1s_vendor_format_targets.h's, behind kernels of their own.
 #include <hip/hip_runtime.h>
 #include "etc1s_device.h"
 #include "etc1s_transcode_kernels.h"
@@ -49,71 +50,15 @@ __device__ __forceinline__ uint2 to_etc1(const etc1s_entry& e, uint32_t sel) {
     return make_uint2(__builtin_bswap32(hi), __builtin_bswap32(lo));
 }
 
-// cBC1 with three-colour blocks allowed, which is how the reference transcodes ETC1S to plain BC1 (convert_etc1s_to_dxt1, transcoder.cpp:2271-2461, called with true
-// at :9567): a block with equal endpoints keeps them, no punch-through guard.
-__device__ __forceinline__ uint2 to_bc1(const etc1s_entry& e, uint32_t sel, const uint32_t* endpoints5, const uint32_t* endpoints6) {
-    uint32_t used = 0;
-#pragma unroll
-    for (uint32_t p = 0; p < 16; p++) used |= 1u << ((sel >> (2u * p)) & 3u);
-    const uint32_t low = (uint32_t)__ffs((int)used) - 1u, high = 31u - (uint32_t)__clz((int)used);
-    uint32_t colors[4];
-    block_colors(e, colors);
-    if (low == high) {   // one colour: the pair whose colour 1 is nearest, selectors all 2 (= colour 1 when low > high)
-        const uint32_t c = pick4(colors, low), r = c & 255u, g = (c >> 8) & 255u, b = c >> 16;
-        uint32_t max16 = ((uint32_t)ke_bc1_solid5[r * 2] << 11) | ((uint32_t)ke_bc1_solid6[g * 2] << 5) | ke_bc1_solid5[b * 2];
-        uint32_t min16 = ((uint32_t)ke_bc1_solid5[r * 2 + 1] << 11) | ((uint32_t)ke_bc1_solid6[g * 2 + 1] << 5) | ke_bc1_solid5[b * 2 + 1];
-        uint32_t mask = 0xAAu;
-        if (max16 < min16) { const uint32_t t = max16; max16 = min16; min16 = t; mask ^= 0x55u; }
-        return make_uint2(max16 | (min16 << 16), mask * 0x01010101u);
-    }
-    if (e.table >= 7 && __popc(used) == 2 && low == 0 && high == 3) {   // the widest table with only its extremes in use: the two colours become the endpoints
-        const uint32_t c0 = colors[0], c3 = colors[3];
-        uint32_t max16 = ((uint32_t)ke_bc1_end5[c0 & 255u] << 11) | ((uint32_t)ke_bc1_end6[(c0 >> 8) & 255u] << 5) | ke_bc1_end5[c0 >> 16];
-        uint32_t min16 = ((uint32_t)ke_bc1_end5[c3 & 255u] << 11) | ((uint32_t)ke_bc1_end6[(c3 >> 8) & 255u] << 5) | ke_bc1_end5[c3 >> 16];
-        uint32_t l = 0, h = 1;
-        if (min16 == max16) {
-            if (min16 > 0) { min16--; l = 0; h = 0; }
-            else { max16 = 1; min16 = 0; l = 1; h = 1; }
-        }
-        if (max16 < min16) { const uint32_t t = max16; max16 = min16; min16 = t; l = 1; h = 0; }
-        uint32_t bits = 0;
-#pragma unroll
-        for (uint32_t p = 0; p < 16; p++) bits |= ((((sel >> (2u * p)) & 3u) == 3u) ? h : l) << (2u * p);
-        return make_uint2(max16 | (min16 << 16), bits);
-    }
-    // per channel the best endpoints for each of the ten selector mappings; the mapping with the least summed error wins, first on ties
-    const uint32_t range = ke_bc1_range_index[low * 4 + high];
-    const uint32_t* tr = &endpoints5[((e.table * 32u + e.r5) * 6u + range) * 10u];
-    const uint32_t* tg = &endpoints6[((e.table * 32u + e.g5) * 6u + range) * 10u];
-    const uint32_t* tb = &endpoints5[((e.table * 32u + e.b5) * 6u + range) * 10u];
-    uint32_t best_err = 0xFFFFFFFFu, best = 0, br = 0, bg = 0, bb = 0;
-#pragma unroll
-    for (uint32_t m = 0; m < 10; m++) {
-        const uint32_t r = tr[m], g = tg[m], b = tb[m], err = (r >> 16) + (g >> 16) + (b >> 16);
-        if (err < best_err) { best_err = err; best = m; br = r; bg = g; bb = b; }
-    }
-    uint32_t l = ((br & 255u) << 11) | ((bg & 255u) << 5) | (bb & 255u);
-    uint32_t h = (((br >> 8) & 255u) << 11) | (((bg >> 8) & 255u) << 5) | ((bb >> 8) & 255u);
-    uint32_t swapped = 0;
-    if (l < h) { const uint32_t t = l; l = h; h = t; swapped = 1; }
-    if (l == h) return make_uint2(l | (h << 16), 0u);
-    const unsigned char* xl = &ke_bc1_selector_xlat[(best * 2u + swapped) * 4u];
-    const uint32_t x0 = xl[0], x1 = xl[1], x2 = xl[2], x3 = xl[3];
-    uint32_t bits = 0;
-#pragma unroll
-    for (uint32_t p = 0; p < 16; p++) {
-        const uint32_t s = (sel >> (2u * p)) & 3u;
-        bits |= ((s & 2u) ? ((s & 1u) ? x3 : x2) : ((s & 1u) ? x1 : x0)) << (2u * p);
-    }
-    return make_uint2(l | (h << 16), bits);
-}
-
 }  // namespace bu
+#include "etc1s_bc1.h"
 #include "etc1s_texture_targets.h"
 #include "etc1s_block_format_targets.h"
+#include "etc1s_vendor_format_targets.h"
 namespace bu {
 static_assert(kBc7TableWords == kEtc1sBc7TableWords, "the header's size of the BC7 tables");
 static_assert(kAstcTableWords == kEtc1sAstcTableWords, "the header's size of the ASTC tables");
+static_assert(kAtcTableWords == kEtc1sAtcTableWords, "the header's size of the ATC tables");
 
 // one pixel of a pixel target from the block colour (r | g << 8 | b << 16) and the alpha value (transcoder.cpp:9155-9332; the 4444 colour pass ORs onto the alpha pass)
 template <uint32_t TARGET>
@@ -180,7 +125,7 @@ __device__ __forceinline__ bool transcode_etc1s_block(const etc1s_palettes& a, c
         if (ok) {
             const etc1s_entry e = unpack_entry(a.endpoint_palette[ei]);
             const uint32_t sel = a.selector_palette[si];
-            o = TARGET == ETF_ETC1_RGB ? to_etc1(e, sel) : (TARGET == ETF_ETC2_EAC_R11 ? to_eac_r11(e, sel) : to_bc1(e, sel, a.bc1_endpoints, a.bc1_endpoints + kBc1TableEntries));
+            o = TARGET == ETF_ETC1_RGB ? to_etc1(e, sel) : (TARGET == ETF_ETC2_EAC_R11 ? to_eac_r11(e, sel) : to_bc1<true>(e, sel, a.bc1_endpoints, a.bc1_endpoints + kBc1TableEntries));
         }
         ((uint2*)out)[i] = o;
         return ok;
@@ -357,6 +302,67 @@ __global__ __launch_bounds__(256) void etc1s_build_astc_tables_kernel(uint32_t* 
     tables[idx] = best_lo | (best_hi << 8) | (best_err << 16);
 }
 
+// ---- the fourth family's own targets: vendor_format_block (etc1s_vendor_format_targets.h) behind the two kinds of indexing. FXT1 runs a lane per SOURCE block like the
+// others, so that the slice table's block counts hold for it too; the lanes of odd block columns have nothing to do.
+static_assert(VF_ATC_RGB == ETF_ATC_RGB && VF_FXT1_RGB == ETF_FXT1_RGB && VF_PVRTC2_4_RGB == ETF_PVRTC2_4_RGB && VF_PVRTC2_4_RGBA == ETF_PVRTC2_4_RGBA,
+              "the header's target numbers");
+template <uint32_t TARGET>
+__global__ __launch_bounds__(256) void transcode_etc1s_vendor_kernel(etc1s_transcode_args a, const uint32_t* atc_tables) {
+    const uint32_t n = a.g.nbx * a.g.nby, i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const vendor_format_inputs p = { a.endpoint_palette, a.selector_palette, a.bc1_endpoints, a.bc1_endpoints + kBc1TableEntries, atc_tables, a.n_endpoints, a.n_selectors };
+    const uint32_t bad = vendor_format_block<TARGET>(p, a.endpoint_idx, a.selector_idx, a.alpha_endpoint_idx, a.alpha_selector_idx, a.out, i, a.g.nbx);
+    if (bad) atomicAdd(a.invalid, bad);
+}
+
+template <uint32_t TARGET>
+__global__ __launch_bounds__(256) void transcode_etc1s_vendor_slices_kernel(etc1s_transcode_slices_args a, const uint32_t* atc_tables) {
+    transcode_slice_view v;
+    if (!find_transcode_slice(a.slices, a.prefix, a.n_slices, a.total_blocks, blockIdx.x * 256u + threadIdx.x, v)) return;
+    const vendor_format_inputs p = { a.endpoint_palette, a.selector_palette, a.bc1_endpoints, a.bc1_endpoints + kBc1TableEntries, atc_tables, a.n_endpoints, a.n_selectors };
+    const bool alpha = v.alpha_first_block != BU_HIP_NO_ALPHA_SLICE;
+    const uint32_t bad = vendor_format_block<TARGET>(p, a.endpoint_idx + v.first_block, a.selector_idx + v.first_block, alpha ? a.endpoint_idx + v.alpha_first_block : nullptr,
+                                                     alpha ? a.selector_idx + v.alpha_first_block : nullptr, a.out + v.out_offset, v.local, v.g.nbx);
+    if (bad) atomicAdd(a.invalid + v.slice, bad);
+}
+
+// The three look-ups of atc_solve, [intensity table][base5][range][mapping] -> lo | hi << 8 | min(error, 65535) << 16: "55" (both endpoints 5 bits), "56" (a 6-bit high
+// endpoint) and "45" (PVRTC2's 4-bit low endpoint, expanded to 5 bits and then to 8), kAtcEntries words each. One lane per entry. The search is the BC7 table's (hi
+// outermost, lo innermost, first minimum; the errors of selectors 0 and 3 counted five times for the widest intensity table over the whole range) over the values
+// lo, (5 lo + 3 hi) / 8, (3 lo + 5 hi) / 8, hi. atc_endpoint_table() of the tool is the same search on the host.
+__global__ __launch_bounds__(256) void etc1s_build_atc_tables_kernel(uint32_t* tables) {
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= kAtcTableWords) return;
+    const uint32_t which = idx / kAtcEntries, e = idx % kAtcEntries, m = e % 10u, r = (e / 10u) % 6u, g = (e / 60u) % 32u, t = e / 1920u;
+    const int base = scale5((int)g);
+    int block[4];
+#pragma unroll
+    for (int s = 0; s < 4; s++) block[s] = clamp255(base + inten_delta((int)t, s));
+    const uint32_t s0 = ke_bc1_ranges[r * 2], s1 = ke_bc1_ranges[r * 2 + 1];
+    const uint32_t m0 = ke_bc1_mappings[m * 4], m1 = ke_bc1_mappings[m * 4 + 1], m2 = ke_bc1_mappings[m * 4 + 2], m3 = ke_bc1_mappings[m * 4 + 3];
+    const uint32_t ends_weight = (t == 7u && s0 == 0u && s1 == 3u) ? 5u : 1u;
+    const uint32_t n_lo = which == 2u ? 16u : 32u, n_hi = which == 1u ? 64u : 32u;
+    uint32_t best_err = 0xFFFFFFFFu, best_lo = 0, best_hi = 0;
+    for (uint32_t hi = 0; hi < n_hi; hi++)
+        for (uint32_t lo = 0; lo < n_lo; lo++) {
+            const uint32_t lo5 = which == 2u ? ((lo << 1) | (lo >> 3)) : lo;
+            uint32_t c[4];
+            c[0] = (lo5 << 3) | (lo5 >> 2);
+            c[3] = which == 1u ? ((hi << 2) | (hi >> 4)) : ((hi << 3) | (hi >> 2));
+            c[1] = (c[0] * 5u + c[3] * 3u) / 8u;
+            c[2] = (c[3] * 5u + c[0] * 3u) / 8u;
+            const uint32_t mapped[4] = { pick4(c, m0), pick4(c, m1), pick4(c, m2), pick4(c, m3) };
+            uint32_t err = 0;
+#pragma unroll
+            for (uint32_t s = 0; s < 4; s++) {
+                const int d = block[s] - (int)mapped[s];
+                if (s >= s0 && s <= s1) err += (uint32_t)(d * d) * ((s == 0u || s == 3u) ? ends_weight : 1u);
+            }
+            if (err < best_err) { best_err = err; best_lo = lo; best_hi = hi; }
+        }
+    tables[idx] = best_lo | (best_hi << 8) | ((best_err < 0xFFFFu ? best_err : 0xFFFFu) << 16);
+}
+
 __global__ __launch_bounds__(256) void etc1s_count_indices_past_kernel(const uint16_t* idx, uint32_t n, uint32_t limit, uint32_t* count) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i < n && idx[i] >= limit) atomicAdd(count, 1u);
@@ -410,6 +416,31 @@ static hipError_t launch_for_target(hipStream_t st, const Args& a, uint32_t targ
     }
 }
 
+template <uint32_t TARGET>
+static hipError_t launch_vendor(hipStream_t st, const etc1s_transcode_args& a, const uint32_t* atc_tables) {
+    const uint32_t n = a.g.nbx * a.g.nby;
+    hipLaunchKernelGGL((transcode_etc1s_vendor_kernel<TARGET>), dim3((n + 255) / 256), dim3(256), 0, st, a, atc_tables);
+    return hipGetLastError();
+}
+template <uint32_t TARGET>
+static hipError_t launch_vendor(hipStream_t st, const etc1s_transcode_slices_args& a, const uint32_t* atc_tables) {
+    hipLaunchKernelGGL((transcode_etc1s_vendor_slices_kernel<TARGET>), dim3((a.total_blocks + 255) / 256), dim3(256), 0, st, a, atc_tables);
+    return hipGetLastError();
+}
+// any ETC1S target: the fourth family's own four here, any other through launch_for_target
+template <class Args>
+static hipError_t launch_for_any_target(hipStream_t st, const Args& a, const uint32_t* atc_tables, uint32_t target, bool chroma_filter) {
+    if ((target == ETF_ATC_RGB || target == ETF_PVRTC2_4_RGB || target == ETF_PVRTC2_4_RGBA) && !atc_tables) return hipErrorInvalidValue;
+    if (target == ETF_FXT1_RGB && !a.bc1_endpoints) return hipErrorInvalidValue;
+    switch (target) {
+    case ETF_ATC_RGB: return launch_vendor<ETF_ATC_RGB>(st, a, atc_tables);
+    case ETF_FXT1_RGB: return launch_vendor<ETF_FXT1_RGB>(st, a, atc_tables);
+    case ETF_PVRTC2_4_RGB: return launch_vendor<ETF_PVRTC2_4_RGB>(st, a, atc_tables);
+    case ETF_PVRTC2_4_RGBA: return launch_vendor<ETF_PVRTC2_4_RGBA>(st, a, atc_tables);
+    default: return launch_for_target(st, a, target, chroma_filter);
+    }
+}
+
 uint32_t etc1s_transcode_unit_bytes(uint32_t target) {
     switch (target) {
     case ETF_ETC1_RGB: case ETF_BC1_RGB: return 8;
@@ -422,6 +453,10 @@ uint32_t etc1s_texture_unit_bytes(uint32_t target) { return target == ETF_ETC2_R
 uint32_t etc1s_block_format_unit_bytes(uint32_t target) {
     if (target == ETF_ASTC_4x4_RGBA || target == ETF_ETC2_EAC_RG11) return 16u;
     return target == ETF_ETC2_EAC_R11 ? 8u : etc1s_texture_unit_bytes(target);
+}
+uint32_t etc1s_vendor_format_unit_bytes(uint32_t target) {
+    if (target == ETF_FXT1_RGB) return 16u;
+    return target == ETF_ATC_RGB || target == ETF_PVRTC2_4_RGB || target == ETF_PVRTC2_4_RGBA ? 8u : etc1s_block_format_unit_bytes(target);
 }
 bool etc1s_transcode_is_pixel_target(uint32_t target) { return target == ETF_RGBA32 || target == ETF_RGB565 || target == ETF_BGR565 || target == ETF_RGBA4444; }
 
@@ -455,6 +490,23 @@ hipError_t launch_bc7_mode5_tiles(hipStream_t st, const void* d_tiles, uint32_t 
 
 hipError_t launch_etc1s_build_astc_tables(hipStream_t st, uint32_t* d_tables) {
     hipLaunchKernelGGL(etc1s_build_astc_tables_kernel, dim3((2u * kAstcEntries + 249) / 250), dim3(256), 0, st, d_tables);
+    return hipGetLastError();
+}
+
+hipError_t launch_transcode_etc1s_any_target(hipStream_t st, const etc1s_transcode_args& a, const uint32_t* atc_tables, uint32_t target, bool chroma_filter) {
+    hipError_t e = hipMemsetAsync(a.invalid, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess || !a.g.nbx || !a.g.nby) return e;
+    return launch_for_any_target(st, a, atc_tables, target, chroma_filter);
+}
+
+hipError_t launch_transcode_etc1s_any_target_slices(hipStream_t st, const etc1s_transcode_slices_args& a, const uint32_t* atc_tables, uint32_t target, bool chroma_filter) {
+    hipError_t e = hipMemsetAsync(a.invalid, 0, (size_t)a.n_slices * sizeof(uint32_t), st);
+    if (e != hipSuccess || !a.n_slices || !a.total_blocks) return e;
+    return launch_for_any_target(st, a, atc_tables, target, chroma_filter);
+}
+
+hipError_t launch_etc1s_build_atc_tables(hipStream_t st, uint32_t* d_tables) {
+    hipLaunchKernelGGL(etc1s_build_atc_tables_kernel, dim3((kAtcTableWords + 255) / 256), dim3(256), 0, st, d_tables);
     return hipGetLastError();
 }
 

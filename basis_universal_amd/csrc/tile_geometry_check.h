@@ -50,8 +50,9 @@ inline int resolve_geometry(const char* who, uint32_t nbx, uint32_t nby, uint32_
 }
 
 // Bytes the output of one image takes; g may still hold the caller's zeros. Block targets: `unit` bytes per block; pixel targets: pitch x rows pixels of `unit` bytes.
-inline size_t raster_output_bytes(const tile_geometry& g, size_t unit, bool is_pixel_target) {
-    if (!is_pixel_target) return (size_t)g.nbx * g.nby * unit;
+// two_wide: a block target whose blocks cover two tiles side by side (FXT1): rows of (nbx + 1) / 2 blocks.
+inline size_t raster_output_bytes(const tile_geometry& g, size_t unit, bool is_pixel_target, bool two_wide = false) {
+    if (!is_pixel_target) return (two_wide ? ((size_t)g.nbx + 1) / 2 : (size_t)g.nbx) * g.nby * unit;
     const size_t width = g.width ? g.width : (size_t)g.nbx * 4, height = g.height ? g.height : (size_t)g.nby * 4;
     return (g.pitch ? g.pitch : width) * (g.rows ? g.rows : height) * unit;
 }
@@ -102,17 +103,18 @@ struct slice_policy {
     char pitch_refusal[96];       // "" = a pitch / rows may be given; else how the sentence "row pitch %u / rows %u given" goes on
     const char* alpha_refusal;    // nullptr = an alpha slice may be given; else how "alpha_first_block is set, and " goes on
     bool counters;
+    bool two_wide;                // a block target whose blocks cover two tiles side by side (FXT1)
 };
 
 // the whole-file transcoders: pitch / rows for pixel targets only, an alpha slice for ETC1S only, a counter per slice
 inline slice_policy transcoder_slice_policy(bool etc1s, uint32_t unit, bool pixels, const char* target_name) {
-    slice_policy p = { etc1s ? "indices" : "blocks", "blocks", unit, pixels, false, "", etc1s ? nullptr : "a UASTC image has no alpha slice", true };
+    slice_policy p = { etc1s ? "indices" : "blocks", "blocks", unit, pixels, false, "", etc1s ? nullptr : "a UASTC image has no alpha slice", true, false };
     if (!pixels) snprintf(p.pitch_refusal, sizeof(p.pitch_refusal), " for a block target (%s): they describe a pixel raster", target_name);
     return p;
 }
 // the DDS pixel packer: tight rows, tiles that carry their own alpha, nothing counted
 inline slice_policy dds_pixels_slice_policy(uint32_t unit) {
-    return slice_policy{ "tiles", "tiles", unit, true, true, ": the rows of a DDS subresource are tight", "a tile carries its own alpha", false };
+    return slice_policy{ "tiles", "tiles", unit, true, true, ": the rows of a DDS subresource are tight", "a tile carries its own alpha", false, false };
 }
 
 // Every refusal of a table of bu_hip_transcode_slice records, and the pack: the records with their zero sizes filled in. Nothing else is touched.
@@ -137,7 +139,7 @@ inline int build_transcode_slices(slice_table& t, const char* fn, const bu_hip_t
             return refuse(err, "%s: row pitch %u / rows %u given%s", who, s.out_row_pitch_pixels, s.out_rows_pixels, p.pitch_refusal);
         const bool alpha = s.alpha_first_block != BU_HIP_NO_ALPHA_SLICE;
         if (alpha && p.alpha_refusal) return refuse(err, "%s: alpha_first_block is set, and %s", who, p.alpha_refusal);
-        const uint64_t blocks = (uint64_t)g.nbx * g.nby, extent = raster_output_bytes(g, p.unit, p.pixels);
+        const uint64_t blocks = (uint64_t)g.nbx * g.nby, extent = raster_output_bytes(g, p.unit, p.pixels, p.two_wide);
         if (s.first_block > n_inputs || blocks > n_inputs - s.first_block)
             return refuse(err, "%s: %s %llu..%llu are past the %llu given", who, p.inputs, (ull)s.first_block, (ull)(s.first_block + blocks), (ull)n_inputs);
         if (alpha && (s.alpha_first_block > n_inputs || blocks > n_inputs - s.alpha_first_block))

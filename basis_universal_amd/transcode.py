@@ -5,7 +5,7 @@ Targets are the reference's transcoder_texture_format values; only the ones belo
 take RGBA32, BC1, BC3, BC4, BC5, BC7 and ASTC 4x4 and refuse everything else. `transcode_uastc_texture_blocks`, `transcode_uastc_texture_file`, `transcode_uastc_textures`
 and `uastc_texture_layout` are a parallel UASTC family (UASTC_TEXTURE_BYTES_PER_BLOCK / UASTC_TEXTURE_BYTES_PER_PIXEL): those seven targets, byte for byte the same, plus
 the consumers of the ETC hints every UASTC block carries -- ETC1_RGB, ETC2_RGBA, ETC2_EAC_R11 / ETC2_EAC_RG11 -- and the RGB565 / BGR565 / RGBA4444 rasters, (height,
-width) u16. ETC1 from the alpha channel (cDecodeFlagsTranscodeAlphaDataToOpaqueFormats), ATC / FXT1 / PVRTC2, UASTC HDR / ASTC LDR / XUASTC and
+width) u16. ETC1 from the alpha channel (cDecodeFlagsTranscodeAlphaDataToOpaqueFormats), ATC / FXT1 / PVRTC2 from UASTC (the reference has no such route), UASTC HDR / ASTC LDR / XUASTC and
 Zstandard-supercompressed KTX2 levels are out of scope and are refused with an error. There is no CPU implementation: without the HIP library and a GPU the
 transcode functions raise.
 
@@ -17,6 +17,9 @@ libbasisu_frontend.so (csrc/host/etc1s_decode.cpp, needs no GPU), the texel half
 per block, ETC1S_TEXTURE_BYTES_PER_BLOCK), and BC7's chroma filter as an option; the three functions above keep their six targets and their refusals.
 `transcode_etc1s_block_format`, `transcode_etc1s_block_formats` and `etc1s_block_format_layout` are a third ETC1S family with the second one's targets and three
 more: ASTC 4x4 RGBA, EAC R11 and EAC RG11 (ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK); the second family keeps its eight targets and its refusals.
+`transcode_etc1s_vendor_format`, `transcode_etc1s_vendor_formats` and `etc1s_vendor_format_layout` are a fourth ETC1S family with the third one's targets and four
+more: ATC RGB, FXT1 (16 bytes per 8x4 texels: rows of ceil(num_blocks_x / 2) blocks) and PVRTC2 4bpp RGB / RGBA (ETC1S_VENDOR_FORMAT_BYTES_PER_BLOCK). It refuses, with the
+reason, what needs the ETC1S -> BC4 look-up (BC3, BC4, BC5, ATC RGBA).
 
 `transcode_file_images` and `transcode_etc1s_file_images` are the whole-file forms: every image of a file -- levels x layers x faces -- by ONE
 launch over a slice table, into one allocation whose layout `image_layout` gives.
@@ -271,6 +274,9 @@ ETC1S_TEXTURE_BYTES_PER_BLOCK = {ETC1_RGB: 8, BC1_RGB: 8, ETC2_RGBA: 16, BC7_RGB
 DECODE_FLAGS_NO_ETC1S_CHROMA_FILTERING = 64   # cDecodeFlagsNoETC1SChromaFiltering: the one decode flag of the ETC1S texture entries
 # the targets of transcode_etc1s_block_format*: the texture family's and ASTC_4x4_RGBA (10), ETC2_EAC_R11 (20), ETC2_EAC_RG11 (21)
 ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK = {**ETC1S_TEXTURE_BYTES_PER_BLOCK, 10: 16, 20: 8, 21: 16}
+# the targets of transcode_etc1s_vendor_format*: the block-format family's and ATC_RGB (11), FXT1_RGB (17), PVRTC2_4_RGB (18), PVRTC2_4_RGBA (19). An FXT1 block is 8x4 texels
+ATC_RGB, FXT1_RGB, PVRTC2_4_RGB, PVRTC2_4_RGBA = 11, 17, 18, 19
+ETC1S_VENDOR_FORMAT_BYTES_PER_BLOCK = {**ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK, ATC_RGB: 8, FXT1_RGB: 16, PVRTC2_4_RGB: 8, PVRTC2_4_RGBA: 8}
 _TARGET_NAMES = ["ETC1_RGB", "ETC2_RGBA", "BC1_RGB", "BC3_RGBA", "BC4_R", "BC5_RG", "BC7_RGBA", "BC7_ALT", "PVRTC1_4_RGB", "PVRTC1_4_RGBA", "ASTC_4x4_RGBA", "ATC_RGB", "ATC_RGBA",
                  "RGBA32", "RGB565", "BGR565", "RGBA4444", "FXT1_RGB", "PVRTC2_4_RGB", "PVRTC2_4_RGBA", "ETC2_EAC_R11", "ETC2_EAC_RG11"]
 
@@ -362,16 +368,22 @@ def transcode_etc1s_image(ctx, decoded, image, target, *, out_device=None, out_r
     return _transcode_etc1s_image(ctx, decoded, image, _check_etc1s_target(target), None, out_device, out_row_pitch, out_rows)
 
 
-def _transcode_etc1s_image(ctx, decoded, image, target, decode_flags, out_device, out_row_pitch, out_rows, block_format=False):
-    """transcode_etc1s_image (decode_flags None: bu_hip_k_transcode_etc1s_counted), transcode_etc1s_texture_image (bu_hip_k_transcode_etc1s_image_counted) and
-    transcode_etc1s_block_format_image (block_format: bu_hip_k_transcode_etc1s_block_format_counted)"""
+def _transcode_etc1s_image(ctx, decoded, image, target, decode_flags, out_device, out_row_pitch, out_rows, block_format=False, vendor_format=False):
+    """transcode_etc1s_image (decode_flags None: bu_hip_k_transcode_etc1s_counted), transcode_etc1s_texture_image (bu_hip_k_transcode_etc1s_image_counted),
+    transcode_etc1s_block_format_image (block_format: bu_hip_k_transcode_etc1s_block_format_counted) and transcode_etc1s_vendor_format_image (vendor_format:
+    bu_hip_k_transcode_etc1s_vendor_format_counted)"""
     texture = decode_flags is not None
     nbx, nby, w, h = image["num_blocks_x"], image["num_blocks_y"], image["width"], image["height"]
     ep_pal = np.ascontiguousarray(decoded["endpoint_palette"], np.uint8).reshape(-1, 4)
     sel_pal = np.ascontiguousarray(decoded["selector_palette"], np.uint32).reshape(-1)
-    with_alpha = image["alpha_endpoint_indices"] is not None and target in (RGBA32, RGBA4444, ETC2_RGBA, BC7_RGBA, ASTC_4x4_RGBA, ETC2_EAC_RG11)
+    with_alpha = image["alpha_endpoint_indices"] is not None and target in (RGBA32, RGBA4444, ETC2_RGBA, BC7_RGBA, ASTC_4x4_RGBA, ETC2_EAC_RG11, PVRTC2_4_RGBA)
     names = ["endpoint_indices", "selector_indices"] + (["alpha_endpoint_indices", "alpha_selector_indices"] if with_alpha else [])
-    output_bytes = ctx.lib.etc1s_block_format_output_bytes if block_format else (ctx.lib.etc1s_image_output_bytes if texture else ctx.lib.etc1s_transcode_output_bytes)
+    if vendor_format:
+        output_bytes = ctx.lib.etc1s_vendor_format_output_bytes
+    elif block_format:
+        output_bytes = ctx.lib.etc1s_block_format_output_bytes
+    else:
+        output_bytes = ctx.lib.etc1s_image_output_bytes if texture else ctx.lib.etc1s_transcode_output_bytes
     held = []
     with _output(ctx, out_device, out_row_pitch, out_rows, lambda: output_bytes(nbx, nby, w, h, target, 0, 0)) as d_out:
         try:
@@ -381,7 +393,9 @@ def _transcode_etc1s_image(ctx, decoded, image, target, decode_flags, out_device
             invalid = C.c_uint32(0)
             args = (ctx.h, C.c_void_p(held[0]), ep_pal.shape[0], C.c_void_p(held[1]), sel_pal.size, C.c_void_p(held[2]), C.c_void_p(held[3]), C.c_void_p(d_alpha[0]),
                     C.c_void_p(d_alpha[1]), nbx, nby, w, h, target, C.c_void_p(d_out), int(out_row_pitch), int(out_rows))
-            if block_format:
+            if vendor_format:
+                ctx.check(ctx.lib.k_transcode_etc1s_vendor_format_counted(*args, int(decode_flags), C.byref(invalid)), "transcode_etc1s_vendor_format")
+            elif block_format:
                 ctx.check(ctx.lib.k_transcode_etc1s_block_format_counted(*args, int(decode_flags), C.byref(invalid)), "transcode_etc1s_block_format")
             elif texture:
                 ctx.check(ctx.lib.k_transcode_etc1s_image_counted(*args, int(decode_flags), C.byref(invalid)), "transcode_etc1s_image")
@@ -391,8 +405,9 @@ def _transcode_etc1s_image(ctx, decoded, image, target, decode_flags, out_device
                 raise ValueError(f"{invalid.value} of {nbx * nby} blocks have an index past its palette")
             if out_device is not None:
                 return None
-            if target in ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK:
-                return ctx.download(d_out, (nbx * nby, ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK[target]), np.uint8)
+            if target in ETC1S_VENDOR_FORMAT_BYTES_PER_BLOCK:
+                blocks = (nbx + 1) // 2 * nby if target == FXT1_RGB else nbx * nby
+                return ctx.download(d_out, (blocks, ETC1S_VENDOR_FORMAT_BYTES_PER_BLOCK[target]), np.uint8)
             return ctx.download(d_out, (h, w, 4), np.uint8) if target == RGBA32 else ctx.download(d_out, (h, w), np.uint16)
         finally:
             for p in held:
@@ -493,6 +508,43 @@ def transcode_etc1s_block_format(ctx, data, target, *, level=0, layer=0, face=0,
     raise ValueError(f"the file has no image at level {level}, layer {layer}, face {face}")
 
 
+# ---------------------------------------------------------------- the ETC1S vendor-format family: also ATC RGB, FXT1 and PVRTC2 4bpp RGB / RGBA
+
+_VENDOR_FORMAT_REFUSALS = {3: "it needs the ETC1S -> BC4 look-up, which could not be restated as a search", 12: "its first half is a BC4 block, and the ETC1S -> BC4 look-up could not be "
+                           "restated as a search"}
+_VENDOR_FORMAT_REFUSALS[4] = _VENDOR_FORMAT_REFUSALS[5] = _VENDOR_FORMAT_REFUSALS[3]
+
+
+def _check_etc1s_vendor_format_target(target):
+    target = int(target)
+    if target not in ETC1S_VENDOR_FORMAT_BYTES_PER_BLOCK and target not in ETC1S_BYTES_PER_PIXEL:
+        name = _TARGET_NAMES[target] if 0 <= target < len(_TARGET_NAMES) else "unknown"
+        why = f": {_VENDOR_FORMAT_REFUSALS[target]}" if target in _VENDOR_FORMAT_REFUSALS else ""
+        raise ValueError(f"ETC1S vendor-format target {target} ({name}) is not supported{why} (supported: "
+                         f"{sorted(list(ETC1S_VENDOR_FORMAT_BYTES_PER_BLOCK) + list(ETC1S_BYTES_PER_PIXEL))})")
+    return target
+
+
+def transcode_etc1s_vendor_format_image(ctx, decoded, image, target, *, chroma_filtering=True, out_device=None, out_row_pitch=0, out_rows=0):
+    """transcode_etc1s_block_format_image over the vendor-format family's targets: the eleven of the block-format family, byte for byte the same, plus ATC_RGB (low colour
+    555, high colour 565, 2-bit selectors), PVRTC2_4_RGB (hard opaque blocks: low colour 554, high colour 555) and FXT1_RGB (CC_MIXED blocks of 8x4 texels, each made of
+    two source blocks by way of BC1 without three-colour blocks). Block targets return (blocks, 8 | 16) u8 in raster block order; for FXT1 blocks = ceil(num_blocks_x /
+    2) * num_blocks_y, and the lone left half at the end of an odd row fills its block alone. None of the three reads the alpha slice. PVRTC2_4_RGBA re-encodes each block per pixel from
+    the colour and the alpha slice (hard translucent blocks, colours 4433 / 4443; a constant alpha of 250 or more, or an image without an alpha slice, gives the RGB block)."""
+    return _transcode_etc1s_image(ctx, decoded, image, _check_etc1s_vendor_format_target(target), etc1s_decode_flags(chroma_filtering=chroma_filtering), out_device, out_row_pitch,
+                                  out_rows, vendor_format=True)
+
+
+def transcode_etc1s_vendor_format(ctx, data, target, *, level=0, layer=0, face=0, chroma_filtering=True):
+    """One image of an ETC1S .basis / .ktx2 file as a texture of the vendor-format family's targets (transcode_etc1s_vendor_format_image)."""
+    target, flags = _check_etc1s_vendor_format_target(target), etc1s_decode_flags(chroma_filtering=chroma_filtering)
+    decoded = decode_etc1s_file(data)
+    for im in decoded["images"]:
+        if (im["level"], im["layer"], im["face"]) == (level, layer, face):
+            return _transcode_etc1s_image(ctx, decoded, im, target, flags, None, 0, 0, vendor_format=True)
+    raise ValueError(f"the file has no image at level {level}, layer {layer}, face {face}")
+
+
 # ---------------------------------------------------------------- every image of a file in one launch
 
 NO_ALPHA_SLICE = 2 ** 64 - 1   # BU_HIP_NO_ALPHA_SLICE
@@ -512,6 +564,12 @@ def etc1s_block_format_layout(images, target):
     """image_layout for the ETC1S block-format family (transcode_etc1s_block_formats): block targets are (blocks, 8 | 16) u8 by ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK; for
     the texture family's targets it is etc1s_texture_layout. Host only."""
     return _layout(images, _check_etc1s_block_format_target(target), ETC1S_BLOCK_FORMAT_BYTES_PER_BLOCK, True)
+
+
+def etc1s_vendor_format_layout(images, target):
+    """image_layout for the ETC1S vendor-format family (transcode_etc1s_vendor_formats): block targets are (blocks, 8 | 16) u8 by ETC1S_VENDOR_FORMAT_BYTES_PER_BLOCK,
+    FXT1 with ceil(num_blocks_x / 2) * num_blocks_y blocks per image; for the block-format family's targets it is etc1s_block_format_layout. Host only."""
+    return _layout(images, _check_etc1s_vendor_format_target(target), ETC1S_VENDOR_FORMAT_BYTES_PER_BLOCK, True)
 
 
 def image_layout(images, target, *, etc1s):
@@ -534,6 +592,8 @@ def _layout(images, target, bytes_per_block, etc1s):
             shape, dtype, nbytes = (h, w, 4), np.uint8, w * h * 4
         else:
             unit = bytes_per_block[target]
+            if etc1s and target == FXT1_RGB:   # a block is two source blocks side by side
+                n = (im["num_blocks_x"] + 1) // 2 * im["num_blocks_y"]
             shape, dtype, nbytes = (n, unit), np.uint8, n * unit
         layout.append({"offset": at, "nbytes": nbytes, "shape": shape, "dtype": dtype})
         at += (nbytes + 15) & ~15
@@ -765,11 +825,24 @@ def transcode_etc1s_block_formats(ctx, data, target, *, chroma_filtering=True, o
                                    flags, True)
 
 
-def _transcode_etc1s_slices(ctx, decoded, images, firsts, alpha_firsts, target, out_device, decode_flags=None, block_format=False):
+def transcode_etc1s_vendor_formats(ctx, data, target, *, chroma_filtering=True, out_device=None):
+    """transcode_etc1s_block_formats over the vendor-format family's targets (bu_hip_k_transcode_etc1s_vendor_formats): every image of the file in one launch, each what
+    transcode_etc1s_vendor_format returns for it. With out_device (room for etc1s_vendor_format_layout's total_bytes) the output stays there and
+    etc1s_vendor_format_layout(images, target) is returned."""
+    target, flags = _check_etc1s_vendor_format_target(target), etc1s_decode_flags(chroma_filtering=chroma_filtering)
+    decoded = _decode_etc1s(data, False, whole=True)
+    images = decoded["images"]
+    return _transcode_etc1s_slices(ctx, decoded, images, [im["_first"] for im in images], [im["_alpha_first"] if im["has_alpha"] else None for im in images], target, out_device,
+                                   flags, vendor_format=True)
+
+
+def _transcode_etc1s_slices(ctx, decoded, images, firsts, alpha_firsts, target, out_device, decode_flags=None, block_format=False, vendor_format=False):
     """transcode_etc1s_file_images behind the decode (_decode_etc1s with whole=True): `images` (sizes) with where each one's indices begin in the file's whole
     arrays. stats.py decodes an alpha slice as a colour image of its own this way. decode_flags not None: the texture family's entry and layout, or with
-    block_format the block-format family's."""
-    if block_format:
+    block_format the block-format family's, with vendor_format the vendor-format family's."""
+    if vendor_format:
+        layout, total = etc1s_vendor_format_layout(images, target)
+    elif block_format:
         layout, total = etc1s_block_format_layout(images, target)
     else:
         layout, total = image_layout(images, target, etc1s=True) if decode_flags is None else etc1s_texture_layout(images, target)
@@ -784,7 +857,9 @@ def _transcode_etc1s_slices(ctx, decoded, images, firsts, alpha_firsts, target, 
 
         def call(d_out, out_bytes, invalid):
             head = (ctx.h, C.c_void_p(held[0]), ep_pal.shape[0], C.c_void_p(held[1]), sel_pal.size, C.c_void_p(held[2]), C.c_void_p(held[3]), ep_idx.size, recs, len(images), target)
-            if block_format:
+            if vendor_format:
+                ctx.check(ctx.lib.k_transcode_etc1s_vendor_formats(*head, int(decode_flags), d_out, out_bytes, invalid), "transcode_etc1s_vendor_formats")
+            elif block_format:
                 ctx.check(ctx.lib.k_transcode_etc1s_block_formats(*head, int(decode_flags), d_out, out_bytes, invalid), "transcode_etc1s_block_formats")
             elif decode_flags is None:
                 ctx.check(ctx.lib.k_transcode_etc1s_slices(*head, d_out, out_bytes, invalid), "transcode_etc1s_slices")

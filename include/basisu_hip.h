@@ -516,7 +516,8 @@ BU_HIP_API int bu_hip_k_bc7_mode5_tiles(bu_hip_context*, const void* d_tiles, ui
  *   cTFETC2_EAC_RG11 (21): 16 bytes per block, bytes 0-7 that block, bytes 8-15 the same conversion of the alpha slice.
  * Without an alpha slice ASTC's alpha is 255 and RG11's second half the opaque EAC block (base 255, table 13, multiplier 1, every code 4). d_out of a 16-byte
  * target must be 16-byte aligned. decode_flags as in the second family: 64 alone, which only BC7 heeds.
- * Not supported, refused by name: BC3_RGBA, BC4_R, BC5_RG (their look-up could not be restated as a search), PVRTC1, PVRTC2, ATC, FXT1, and
+ * Not supported, refused by name: BC3_RGBA, BC4_R, BC5_RG (their look-up could not be restated as a search), PVRTC1, and PVRTC2, ATC, FXT1 (the
+ * fourth family below takes ATC RGB, FXT1 and PVRTC2 RGB / RGBA), and
  * cDecodeFlagsTranscodeAlphaDataToOpaqueFormats (R11 from the alpha slice alone).
  * The two ETC1S -> ASTC look-ups are built on the device by the first ASTC transcode of a context. bu_hip_etc1s_astc_tables copies them to the host: twice 15,360
  * words [intensity table 8][base5 32][selector range 6][mapping 10] -> lo | hi << 8 | error << 16, over the 48 BISE codes of range 0..47 and over 8-bit
@@ -535,6 +536,41 @@ BU_HIP_API size_t bu_hip_etc1s_block_format_output_bytes(uint32_t num_blocks_x, 
         uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
 BU_HIP_API size_t bu_hip_etc1s_block_format_slice_extent(const bu_hip_transcode_slice*, uint32_t target);
 BU_HIP_API int bu_hip_etc1s_astc_tables(bu_hip_context*, uint32_t* h_out_0_47, uint32_t* h_out_0_255, uint32_t* h_unquant48);
+
+/* The ETC1S transcoder's fourth entry family: the third family's arguments, its eleven targets byte for byte through the same kernels, and four more. The first
+ * three families keep their targets and their refusals; these also take
+ *   cTFATC_RGB (11): 8 bytes per block, convert_etc1s_to_atc (transcoder/basisu_transcoder.cpp:6476): the low colour 555, the high colour 565, 2-bit selectors;
+ *   cTFFXT1_RGB (17): 16 bytes per 8x4 texels, CC_MIXED without alpha: convert_etc1s_to_fxt1 (:2573) over convert_etc1s_to_dxt1 (:2271) with three-colour blocks
+ *     forbidden. An output block covers two source blocks side by side, so a row holds (num_blocks_x + 1) / 2 blocks, rows in order, and the output takes
+ *     (num_blocks_x + 1) / 2 * num_blocks_y * 16 bytes (bu_hip_etc1s_vendor_format_output_bytes, _slice_extent); the lone left half at the end of an odd row fills
+ *     both colour pairs and repeats its right column. It reads the ETC1S -> BC1 tables of the context;
+ *   cTFPVRTC2_4_RGB (18): 8 bytes per block, convert_etc1s_to_pvrtc2_rgb (:7153): hard (non-interpolated) opaque blocks, the low colour 554, the high colour 555,
+ *     the modulation bytes first. Unlike PVRTC1, any image size;
+ *   cTFPVRTC2_4_RGBA (19): 8 bytes per block, convert_etc1s_to_pvrtc2_rgba (:7285): hard translucent blocks, colour a 4433 and colour b 4443, re-encoded per pixel
+ *     from the colour and the alpha slice's block: a constant alpha >= 250 gives the RGB block; a constant colour with constant alpha the best of modulation 0, 1
+ *     and 3; any other block bounds from one of four routes (the 4D incremental PCA in binary32 among them, bit for bit the reference's), quantised, and three
+ *     integer thresholds per texel. Without an alpha slice (both alpha pointers NULL, or BU_HIP_NO_ALPHA_SLICE) it is the PVRTC2_4_RGB block. Its alpha indices are
+ *     range-checked like the colour slice's, and a bad one is the block's failure too.
+ * The alpha slice is not read by the other three. An invalid count is of SOURCE blocks; an FXT1 block with an invalid half is sixteen zero bytes.
+ * Not supported, refused by name with the reason: BC3_RGBA, BC4_R, BC5_RG and ATC_RGBA (all need the ETC1S -> BC4 look-up, which could not be restated as a
+ * search); PVRTC1 has its own family.
+ * The three ETC1S -> ATC / PVRTC2 look-ups are built on the device by the first ATC RGB or PVRTC2 transcode of a context. bu_hip_etc1s_atc_tables copies them
+ * to the host: three times 15,360 words [intensity table 8][base5 32][selector range 6][mapping 10] -> lo | hi << 8 | min(error, 65535) << 16, for endpoints of
+ * 5 and 5 bits, 5 and 6 bits, and 4 and 5 bits; tests compare them with tools/gen_etc1s_transcode_tables.py's host computation. */
+BU_HIP_API int bu_hip_k_transcode_etc1s_vendor_format(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette, uint32_t n_selectors,
+        const void* d_endpoint_idx, const void* d_selector_idx, const void* d_alpha_endpoint_idx, const void* d_alpha_selector_idx, uint32_t num_blocks_x, uint32_t num_blocks_y,
+        uint32_t orig_width, uint32_t orig_height, uint32_t target, void* d_out, uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels, uint32_t decode_flags);
+BU_HIP_API int bu_hip_k_transcode_etc1s_vendor_format_counted(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette,
+        uint32_t n_selectors, const void* d_endpoint_idx, const void* d_selector_idx, const void* d_alpha_endpoint_idx, const void* d_alpha_selector_idx, uint32_t num_blocks_x,
+        uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height, uint32_t target, void* d_out, uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels,
+        uint32_t decode_flags, uint32_t* out_invalid_blocks);
+BU_HIP_API int bu_hip_k_transcode_etc1s_vendor_formats(bu_hip_context*, const void* d_endpoint_palette, uint32_t n_endpoints, const void* d_selector_palette, uint32_t n_selectors,
+        const void* d_endpoint_idx, const void* d_selector_idx, uint64_t n_indices, const bu_hip_transcode_slice* slices, uint32_t n_slices, uint32_t target,
+        uint32_t decode_flags, void* d_out, size_t out_bytes, uint32_t* out_invalid_per_slice);
+BU_HIP_API size_t bu_hip_etc1s_vendor_format_output_bytes(uint32_t num_blocks_x, uint32_t num_blocks_y, uint32_t orig_width, uint32_t orig_height, uint32_t target,
+        uint32_t out_row_pitch_pixels, uint32_t out_rows_pixels);
+BU_HIP_API size_t bu_hip_etc1s_vendor_format_slice_extent(const bu_hip_transcode_slice*, uint32_t target);
+BU_HIP_API int bu_hip_etc1s_atc_tables(bu_hip_context*, uint32_t* h_out_55, uint32_t* h_out_56, uint32_t* h_out_45);
 
 /* The UASTC transcoder's second entry family: bu_hip_k_transcode_uastc and bu_hip_k_transcode_uastc_slices with the targets that consume the ETC1 / EAC hints every
  * UASTC block carries, and the 16-bit rasters. The first family keeps its seven targets and its refusals; these take

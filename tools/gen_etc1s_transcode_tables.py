@@ -27,6 +27,11 @@ EAC R11 / RG11 and ASTC 4x4 (the third entry family): eac_r11_table(), astc_tabl
 astc_unquant48(), astc_solid_table() and astc_nearest_table() state their searches. EAC R11 and the two small ASTC tables go into the .inc; the two ASTC endpoint
 look-ups (15,360 entries each) are built on the device (etc1s_build_astc_tables_kernel). tests/golden/etc1s_block_format_vectors.npz decides the rules.
 
+ATC RGB, PVRTC2 4bpp RGB and FXT1 (the fourth entry family): atc_endpoint_table() for the three look-ups 55 / 56 / 45 (built on the device by
+etc1s_build_atc_tables_kernel; the reference carries this generator, and every entry agrees with what it ships), atc_solid_table() and atc_nearest_table() for the six
+256-entry tables, which go into the .inc. FXT1 reads BC1's tables. PVRTC2 4bpp RGBA: pvrtc2_match_table() and atc_nearest_table() over the translucent mode's
+endpoint expansions, five 256-entry tables for its constant blocks. tests/golden/etc1s_vendor_format_vectors.npz decides the rules.
+
 usage: gen_etc1s_transcode_tables.py [--check]     (--check: regenerate in memory and compare with the committed file)"""
 import functools
 import pathlib
@@ -317,6 +322,89 @@ def astc_nearest_table():
     return np.array([int(np.abs(u - i).argmin()) for i in range(256)], np.uint8)
 
 
+# ---------------------------------------------------------------- ATC RGB, PVRTC2 4bpp and FXT1 (the fourth entry family, etc1s_vendor_format_targets.h)
+
+def expand4_via5():
+    """PVRTC2's 4-bit blue of the low colour: to 5 bits by (c << 1) | (c >> 3), then to 8 like any 5-bit value"""
+    v = np.arange(16)
+    v = (v << 1) | (v >> 3)
+    return (v << 3) | (v >> 2)
+
+
+ATC_EXPANSIONS = {"55": (expand(5), expand(5)), "56": (expand(5), expand(6)), "45": (expand4_via5(), expand(5))}   # (low endpoint, high endpoint) of the three look-ups
+
+
+@functools.lru_cache(maxsize=None)
+def atc_endpoint_table(which):
+    """[inten][base5][range][mapping] -> lo | hi << 8 | min(err, 65535) << 16, the ETC1S -> ATC / PVRTC2 look-ups "55", "56" and "45": the low and the high endpoint
+    have their own widths (ATC_EXPANSIONS). The four values are c0 = lo, c3 = hi, c1 = (5 c0 + 3 c3) / 8, c2 = (5 c3 + 3 c0) / 8 by integer division. The search is
+    endpoint_table()'s -- hi outermost, lo innermost, first minimum over the range's selectors -- with the errors of selectors 0 and 3 counted five times for the
+    widest intensity table over the range (0, 3), as in bc7_color_table()."""
+    e_lo, e_hi = ATC_EXPANSIONS[which]
+    hi, lo = np.meshgrid(e_hi, e_lo, indexing="ij")   # axis 0 = hi (outer), axis 1 = lo (inner)
+    hi, lo = hi.reshape(-1), lo.reshape(-1)
+    colors = np.stack([lo, (lo * 5 + hi * 3) // 8, (hi * 5 + lo * 3) // 8, hi], -1).astype(np.int64)
+    n_lo = e_lo.size
+    base = expand(5)
+    out = np.zeros((8, 32, len(RANGES), len(MAPPINGS)), np.uint32)
+    for t in range(8):
+        block = np.clip(base[:, None] + INTEN[t][None, :], 0, 255).astype(np.int64)
+        for r, (s0, s1) in enumerate(RANGES):
+            five = t == 7 and (s0, s1) == (0, 3)
+            for m, mapping in enumerate(MAPPINGS):
+                err = sum((block[:, s][:, None] - colors[:, mapping[s]][None, :]) ** 2 * (5 if five and s in (0, 3) else 1) for s in range(s0, s1 + 1))
+                best = err.argmin(1)
+                out[t, :, r, m] = (best % n_lo) | ((best // n_lo) << 8) | (np.minimum(err[np.arange(32), best], 0xFFFF) << 16)
+    return out.reshape(-1)
+
+
+def atc_solid_table(which):
+    """[value] {lo, hi}: the endpoints of look-up `which` whose value 1, (5 lo + 3 hi) / 8, is nearest the value: lo outermost, hi innermost, first minimum"""
+    e_lo, e_hi = ATC_EXPANSIONS[which]
+    lo, hi = np.meshgrid(e_lo, e_hi, indexing="ij")
+    c1 = ((lo * 5 + hi * 3) // 8).reshape(-1)
+    out = np.zeros((256, 2), np.uint8)
+    for i in range(256):
+        k = int(np.abs(c1 - i).argmin())
+        out[i] = (k // e_hi.size, k % e_hi.size)
+    return out.reshape(-1)
+
+
+def atc_nearest_table(e):
+    """[value] -> the endpoint of the expanded values e nearest the value, first on ties"""
+    return np.array([int(np.abs(e - i).argmin()) for i in range(256)], np.uint8)
+
+
+# PVRTC2 4bpp RGBA (translucent mode: colour a 4433 with alpha (a << 1) expanded 4 -> 8 bits by replication, colour b 4443 with alpha (a << 1) | 1)
+
+def pvrtc2_alpha_a():
+    v = np.arange(8) << 1
+    return (v << 4) | v
+
+
+def pvrtc2_alpha_b():
+    v = (np.arange(8) << 1) | 1
+    return (v << 4) | v
+
+
+def expand3_via5():
+    """the 3-bit blue of translucent colour a: to 5 bits by (c << 2) | (c >> 1), then to 8"""
+    v = np.arange(8)
+    v = (v << 2) | (v >> 1)
+    return (v << 3) | (v >> 2)
+
+
+def pvrtc2_match_table(e_lo, e_hi):
+    """[value] {l, h}: the endpoints whose value 1, (5 l + 3 h) / 8, is nearest the value: l outermost, h innermost, first minimum (transcoder_init_pvrtc2)"""
+    lo, hi = np.meshgrid(e_lo, e_hi, indexing="ij")
+    m = ((lo * 5 + hi * 3) // 8).reshape(-1)
+    out = np.zeros((256, 2), np.uint8)
+    for i in range(256):
+        k = int(np.abs(m - i).argmin())
+        out[i] = (k // e_hi.size, k % e_hi.size)
+    return out.reshape(-1)
+
+
 def emit(name, ctype, values, per_line, comment, fmt):
     lines = [f"// {comment}", f"BU_TAB {ctype} {name}[{values.size}] = {{"]
     for i in range(0, values.size, per_line):
@@ -362,6 +450,21 @@ def generate():
         emit("ke_eac_r11", "unsigned int", eac_r11_table(), 8, "[inten][base5][range] -> base | (table | multiplier << 4) << 8 | 3-bit code of selector s << (16 + 3 s)", "0x%07x"),
         emit("ke_astc_solid", "unsigned char", astc_solid_table(), 32, "[value] {lo, hi}: BISE codes of range 0..47 whose weight-21 value is nearest the value", "%2u"),
         emit("ke_astc_nearest", "unsigned char", astc_nearest_table(), 32, "[value]: the BISE code of range 0..47 nearest the value", "%2u"),
+        "// Tables of the ETC1S -> ATC RGB and ETC1S -> PVRTC2 4bpp RGB block conversions (FXT1 goes through BC1's above). The ranges and mappings are BC1's. The three",
+        "// endpoint look-ups 55 / 56 / 45 (15,360 entries each) are not here: etc1s_build_atc_tables_kernel computes them on the device, atc_endpoint_table() of the tool is",
+        "// the same search on the host.",
+        emit("ke_atc_solid55", "unsigned char", atc_solid_table("55"), 32, "[value] {lo, hi}: 5-bit endpoints whose value 1, (5 lo + 3 hi) / 8, is nearest the value", "%2u"),
+        emit("ke_atc_solid56", "unsigned char", atc_solid_table("56"), 32, "the same, 5-bit low and 6-bit high endpoint", "%2u"),
+        emit("ke_atc_solid45", "unsigned char", atc_solid_table("45"), 32, "the same, PVRTC2's 4-bit low and 5-bit high endpoint", "%2u"),
+        emit("ke_atc_end4", "unsigned char", atc_nearest_table(expand4_via5()), 32, "[value]: PVRTC2's 4-bit endpoint nearest the value", "%2u"),
+        emit("ke_atc_end5", "unsigned char", atc_nearest_table(expand(5)), 32, "the same, 5-bit", "%2u"),
+        emit("ke_atc_end6", "unsigned char", atc_nearest_table(expand(6)), 32, "the same, 6-bit", "%2u"),
+        "// Tables of the constant blocks of ETC1S -> PVRTC2 4bpp RGBA: colour a is 4433 with alpha (a << 1), colour b 4443 with alpha (a << 1) | 1, alpha to 8 bits by replication.",
+        emit("ke_pvrtc2_alpha33", "unsigned char", pvrtc2_match_table(pvrtc2_alpha_a(), pvrtc2_alpha_b()), 32, "[value] {l, h}: the 3-bit alphas whose value 1, (5 l + 3 h) / 8, is nearest the value", "%u"),
+        emit("ke_pvrtc2_alpha33_0", "unsigned char", atc_nearest_table(pvrtc2_alpha_a()), 32, "[value]: the 3-bit alpha of colour a nearest the value", "%u"),
+        emit("ke_pvrtc2_alpha33_3", "unsigned char", atc_nearest_table(pvrtc2_alpha_b()), 32, "[value]: the 3-bit alpha of colour b nearest the value", "%u"),
+        emit("ke_pvrtc2_trans34", "unsigned char", pvrtc2_match_table(expand3_via5(), expand4_via5()), 32, "[value] {l, h}: blue of 3 and 4 bits whose value 1 is nearest the value", "%2u"),
+        emit("ke_pvrtc2_trans44", "unsigned char", pvrtc2_match_table(expand4_via5(), expand4_via5()), 32, "[value] {l, h}: red / green of 4 and 4 bits whose value 1 is nearest the value", "%2u"),
     ]
     return "\n".join(parts) + "\n"
 
