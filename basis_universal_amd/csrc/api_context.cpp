@@ -446,8 +446,8 @@ int bu_hip_set_tuning(bu_hip_context* ctx, const bu_hip_tuning* t) {
     bu_hip_tuning n = default_tuning();   // fields a caller's older header does not have keep their defaults
     std::memcpy(&n, t, std::min<size_t>(t->struct_bytes, sizeof(n)));
     n.struct_bytes = (uint32_t)sizeof(n);
-    if ((n.tsvq_wide_min && n.tsvq_wide_min < 512) || (n.tsvq_wide6_min && n.tsvq_wide6_min < 512) || n.tsvq_windows > 2 || n.tsvq_poll > 2 || n.tsvq_deep_levels > bu::TSVQ_MAX_DEEP_LEVELS) {
-        set_error(ctx, "bu_hip_set_tuning: value out of range (many-workgroup thresholds are 0 or >= 512, windows / poll 0..2, deep levels 0..2)");
+    if ((n.tsvq_wide_min && n.tsvq_wide_min < 512) || (n.tsvq_wide6_min && n.tsvq_wide6_min < 512) || n.tsvq_windows > 2 || n.tsvq_poll > 2 || n.refine_unsorted > 2 || n.tsvq_deep_levels > bu::TSVQ_MAX_DEEP_LEVELS) {
+        set_error(ctx, "bu_hip_set_tuning: value out of range (many-workgroup thresholds are 0 or >= 512, windows / poll / refine_unsorted 0..2, deep levels 0..2)");
         return 0;
     }
     ctx->tuning = n;

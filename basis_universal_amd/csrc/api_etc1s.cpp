@@ -316,11 +316,18 @@ int bu_hip_k_refine_endpoint_clusterization(bu_hip_context* ctx, const void* d_p
     if (!ctx) return 0;
     device_guard g(ctx->device);
     void* work = nullptr;
-    if (const size_t wb = ctx->tuning.refine_unsorted ? 0 : bu::refine_workspace_bytes(n_clusters, n_parents)) { BU_TRY(ctx, ctx->refine_lists.reserve(wb)); work = ctx->refine_lists.p; }
+    const int path = bu_hip_refine_path(ctx, n_clusters, n_parents, perceptual);
+    if (path != 1) { BU_TRY(ctx, ctx->refine_lists.reserve(bu::refine_workspace_bytes(n_clusters, n_parents, n_blocks))); work = ctx->refine_lists.p; }
     prof_scope ps(ctx, "refine_endpoint_clusterization");
     BU_TRY(ctx, bu::launch_refine_endpoint_clusterization(ctx->stream, d_px, n_blocks, d_block_cluster, d_cluster_params, n_clusters, n_parents,
-                                                          d_cand_offsets, d_cand_indices, d_block_parent, perceptual != 0, d_out_best, work));
+                                                          d_cand_offsets, d_cand_indices, d_block_parent, perceptual != 0, d_out_best, path, work));
     return 1;
+}
+
+int bu_hip_refine_path(const bu_hip_context* ctx, uint32_t n_clusters, uint32_t n_parents, int perceptual) {
+    bu_hip_tuning t;
+    bu_hip_get_tuning(ctx, &t, sizeof(t));   // a null context: the process defaults
+    return bu::refine_path(t.refine_unsorted, n_clusters, n_parents, perceptual != 0);
 }
 
 int bu_hip_k_extract_blocks(bu_hip_context* ctx, const void* d_rgba, uint32_t width, uint32_t height, uint32_t pitch_bytes, void* d_out) {
@@ -714,11 +721,12 @@ int bu_hip_refine_endpoint_clusterization(bu_hip_context* ctx, const bu_block_in
     BU_TRY(ctx, h2d(ctx, a_idx.p, t.win.cand_indices.data(), t.win.cand_indices.size() * 4ull));
     BU_TRY(ctx, h2d(ctx, a_bp.p, t.win.block_parent.data(), n));
     void* work = nullptr;
-    if (const size_t wb = ctx->tuning.refine_unsorted ? 0 : bu::refine_workspace_bytes(total_clusters, n_parents)) { BU_TRY(ctx, ctx->refine_lists.reserve(wb)); work = ctx->refine_lists.p; }
+    const int path = bu_hip_refine_path(ctx, total_clusters, n_parents, perceptual);
+    if (path != 1) { BU_TRY(ctx, ctx->refine_lists.reserve(bu::refine_workspace_bytes(total_clusters, n_parents, n))); work = ctx->refine_lists.p; }
     BU_TRY(ctx, bu::launch_refine_endpoint_clusterization(ctx->stream, ctx->d_pixel_blocks, n, static_cast<const uint32_t*>(a_cur.p),
                                                           static_cast<const uint8_t*>(a_par.p), total_clusters, n_parents,
                                                           static_cast<const uint32_t*>(a_off.p), static_cast<const uint32_t*>(a_idx.p),
-                                                          static_cast<const uint8_t*>(a_bp.p), perceptual != 0, static_cast<uint32_t*>(a_out.p), work));
+                                                          static_cast<const uint8_t*>(a_bp.p), perceptual != 0, static_cast<uint32_t*>(a_out.p), path, work));
     std::vector<uint32_t> pos(n);
     if (!fetch(ctx, pos.data(), a_out.p, n * 4ull)) return 0;
     for (uint32_t b = 0; b < n; b++) out[b] = clusters[pos[b]].m_cluster_index; // positions -> cluster indices (.cl:1150)

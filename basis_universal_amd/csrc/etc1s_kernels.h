@@ -1,7 +1,7 @@
 // etc1s_kernels.h -- host-side launch interface of the ETC1S frontend's kernels (internal to libbasisu_hip.so). One unit per stage:
 //   etc1s_block_fit_kernels.hip    a6   the per-block etc1_optimizer                          } etc1s_fit_common.h: what the two fits share
 //   etc1s_cluster_fit_kernels.hip  a9   the cluster fit, free and with forced selectors       }   (+ etc1s_codebook_wide.inc: large clusters)
-//   etc1s_refine_kernels.hip       a10  refine_endpoint_clusterization, plain and pre-sorted lists
+//   etc1s_refine_kernels.hip       a10  refine_endpoint_clusterization: plain lists, pre-sorted lists per wave, pre-sorted lists with one block per lane
 //   etc1s_selector_kernels.hip     a11-a14  determine_selectors, selector training vectors, k_cosc_*, k_fosc_*
 //   etc1s_misc_kernels.hip         a7, sub-block errors, the backend's block errors, k_extract_blocks
 //
@@ -53,8 +53,11 @@ hipError_t launch_backend_block_errors(hipStream_t st, const void* d_pixel_block
 hipError_t launch_refine_endpoint_clusterization(hipStream_t st, const void* d_pixel_blocks, uint32_t n_blocks, const uint32_t* d_block_cluster,
                                                  const uint8_t* d_cluster_params, uint32_t n_clusters, uint32_t n_parents, const uint32_t* d_cand_offsets,
                                                  const uint32_t* d_cand_indices, const uint8_t* d_block_parent, bool perceptual, uint32_t* d_out_best,
-                                                 void* d_work /* refine_workspace_bytes(), or null: unsorted lists */);
-size_t refine_workspace_bytes(uint32_t n_clusters, uint32_t n_parents);   // 0: lists too long for the sorted form
+                                                 int path /* refine_path() */, void* d_work /* refine_workspace_bytes(); path 1 takes none */);
+// which kernels a call takes, from bu_hip_tuning::refine_unsorted and what the lists and the metric allow: 0 = sorted lists, one block per lane (k_refine_block_lanes),
+// 1 = the lists as they come (k_refine_endpoint_clusterization), 2 = sorted lists, one block per wave (k_refine_sorted)
+int refine_path(uint32_t refine_unsorted, uint32_t n_clusters, uint32_t n_parents, bool perceptual);
+size_t refine_workspace_bytes(uint32_t n_clusters, uint32_t n_parents, uint32_t n_blocks);   // sorted lists + the blocks bucketed by (parent, table); 0: lists too long for the sorted form
 hipError_t launch_determine_selectors(hipStream_t st, const void* d_pixel_blocks, uint32_t n_blocks, const uint8_t* d_color5_inten,
                                       const uint32_t* d_block_cluster, bool perceptual, void* d_out);
 // d_workspace: create_optimized_selector_codebook_workspace_bytes()

@@ -139,7 +139,7 @@ typedef struct bu_hip_tuning {
     uint32_t tsvq_zero_copy;      /* BU_TSVQ_ZEROCOPY      1      node / result records of a round in coherent pinned memory + a flag the host looks at; 0 = staged copies + synchronise */
     uint32_t tsvq_chained_only;   /* BU_TSVQ_CHAINED       0      1 = every float sum member by member in one workgroup per node (the slowest path; what the others are tested against) */
     uint32_t tsvq_poll;           /* BU_TSVQ_POLL          0      waiting for a round: 0 = spin when this is the process's only context, else yield / nap; 1 (spin) / 2 (yield) force it */
-    uint32_t refine_unsorted;     /*                       0      1 = refine_endpoint_clusterization through the unsorted kernel (the one lists beyond 65,535 entries take anyway) */
+    uint32_t refine_unsorted;     /*                       0      refine_endpoint_clusterization: 0 = sorted candidate lists, one block per lane (blocks bucketed by parent and table; the perceptual metric -- the linear metric takes 2's path); 1 = the unsorted kernel (the one lists beyond 65,535 entries take anyway); 2 = sorted lists, one block per wave. bu_hip_refine_path tells which one a call takes */
     uint32_t debug;               /* BU_TSVQ_ROUNDS = 1 | BU_TSVQ_SERIAL = 2 | BU_TSVQ_STATS = 4: developer aids (round time line on stderr, one node per round, walk statistics) */
     uint32_t tsvq_deep_levels;    /* BU_TSVQ_DEEP          0      deep rounds: generations of descendants of a round's one-workgroup nodes split in the same round trip (bu_hip_tsvq_split_deep); 0 = none, <= 2. Measured SLOWER at 4096^2 (17.4-18.0 against 16.8-17.6 ms per step: the rounds it saves cost ~50 us each, the splits nobody pops cost device time in rounds that fill the chip), hence off */
     uint32_t uastc_walk_cus;      /* BU_UASTC_WALK_CUS     0      UASTC pipeline lanes: this many CUs (every (CUs / n)-th one) carry the strip walks of uastc_rdo and nothing else -- the lanes' other kernels are masked off them; 0 = no reservation */
@@ -311,6 +311,8 @@ BU_HIP_API int bu_hip_k_generate_endpoint_codebook_part(bu_hip_context*, const v
 BU_HIP_API int bu_hip_k_refine_endpoint_clusterization(bu_hip_context*, const void* d_pixel_blocks, uint32_t n_blocks,
     const uint32_t* d_block_cluster, const uint8_t* d_cluster_params, uint32_t n_clusters, uint32_t n_parents,
     const uint32_t* d_cand_offsets, const uint32_t* d_cand_indices, const uint8_t* d_block_parent, int perceptual, uint32_t* d_out_best_cluster);
+/* The path (bu_hip_tuning::refine_unsorted: 0, 1 or 2) a refine call with these arguments takes on this context (NULL: under the process defaults). */
+BU_HIP_API int bu_hip_refine_path(const bu_hip_context*, uint32_t n_clusters, uint32_t n_parents, int perceptual);
 /* a11 create_initial_packed_texture (frontend.cpp:2014-2096): d_block_cluster may be NULL, then d_color5_inten is per block. */
 /* f4  One separable resampling step of mip generation on a resident RGBA8 raster (basis_compressor::generate_mipmaps -> image_resample ->
  *     Resampler, comp.cpp:2146-2230, enc.cpp:1022-1180, resampler.cpp:343-435). The contributor lists of both axes (CSR: first[n+1],
